@@ -13,8 +13,10 @@ ring of RESIDENT frames lives in HBM.  One "step" = 16 stereo frames in one laun
 The bundle adjustments run on their own stream and host thread beside the front end, as the reference's mapping thread
 runs beside tracking; a session's windows are solved one after the other (they depend on each other).
 value = frames/s over the whole job (all ranks); N > 1 runs one independent session per GPU (replicas, no data-path
-collective, "weak" scaling).  The JSON line carries the roofline of the kernel with the largest share of GPU time
-(every timed kernel is a candidate: HIP events on the stream the kernel runs on) and the CPU oracle on a bounded sample.
+collective, "weak" scaling).  A plain run sets up, warms up, times the K steps and prints the headline line.  With --full
+the line also carries the roofline of the kernel with the largest share of GPU time (every timed kernel is a candidate:
+HIP events on the stream the kernel runs on), the PCIe-inclusive and contiguous-track legs, the extras and the CPU oracle
+on a bounded sample.  --dump-outputs DIR writes what the timed path computed in its last step (dump_outputs below).
 """
 import argparse
 import json
@@ -55,11 +57,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=60)          # (20 steps were 72 ms of timed region: differences below 3 % drowned in it)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=FRAMES_PER_STEP, help="stereo frames per step (per launch)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything else the benchmark measures: PCIe-inclusive and "
+                    "contiguous-track legs, instrumented passes and rooflines, extras, CPU baseline, partitioned global BA (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-ba", action="store_true", help="front end only (BASELINE configs[1])")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)            # internal: an extra that needs a process of its own (tracker_multi)
     ap.add_argument("--device", type=int, default=0, help=argparse.SUPPRESS)
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed extras (latency mode, batched sessions, trackers, global BA): profiling runs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed extras (latency mode, batched sessions, trackers, global BA): profiling runs")
     return ap.parse_args()
 
 
@@ -82,18 +87,23 @@ class Workload:
         self.with_ba = with_ba
         self.frame_counter = 0          # frames fed so far (front-end thread)
         self.kf_counter = 0             # keyframes solved so far (BA thread)
+        self.last_windows = []          # (poses, landmarks, LM log) of the last windows run_steps(..., keep=n) solved
         if with_ba:
             # two kinds of window (synth.ba_problem): "random" -- every landmark keeps a random 8-9 of the ~50 keyframes that see it, the
             # reduced system is dense: the stress case and the headline of rounds 1-3 -- and "contiguous" -- a landmark is seen by a run
             # of neighbouring keyframes, as a tracker produces them: block-banded reduced system, the band path (ba_band.inl).
-            # Both at SURVEY 8(d) config 3's size: 50 KF / 5000 landmarks / 40 000 +- 2 % observations (top_up).
-            self.prob_sets = {t: [synth.ba_problem(BA_KF, BA_PTS, BA_OBS, W, H, seq_id * BA_VARIANTS + v, tracks=t, top_up=True) for v in range(BA_VARIANTS)]
-                              for t in ("random", "contiguous")}
-            self.obs_sets = {t: [hip.ba_obs_array(p) for p in ps] for t, ps in self.prob_sets.items()}
+            # Both at SURVEY 8(d) config 3's size: 50 KF / 5000 landmarks / 40 000 +- 2 % observations (top_up).  A kind is generated
+            # when it is first used: the timed loop runs "random", only --full also runs "contiguous".
+            self.seq_id = seq_id
+            self.prob_sets, self.obs_sets = {}, {}
             self.set_tracks("random")
         self.ctx.sync()
 
     def set_tracks(self, kind):
+        if kind not in self.prob_sets:
+            self.prob_sets[kind] = [self.synth.ba_problem(BA_KF, BA_PTS, BA_OBS, W, H, self.seq_id * BA_VARIANTS + v, tracks=kind, top_up=True)
+                                    for v in range(BA_VARIANTS)]
+            self.obs_sets[kind] = [self.hip.ba_obs_array(p) for p in self.prob_sets[kind]]
         self.tracks = kind
         self.probs, self.obs = self.prob_sets[kind], self.obs_sets[kind]
         self.n_obs = int(np.mean([len(o) for o in self.obs]))
@@ -132,11 +142,13 @@ class Workload:
         ba.close()
         return log
 
-    def bundle_adjust_pipelined(self, n_kf):
+    def bundle_adjust_pipelined(self, n_kf, keep=0):
         """The mapping thread as a pipeline: the structure of window k+1 (upload + device-side build, asynchronous on its own stream)
         is set up while window k is being solved; when k is done its poses / landmarks are read back and window k+1 receives its
         values (lpslam_hip_ba_set_state) -- in a tracker the observations the previous solve classified as outliers would be masked
-        with set_active at the same point.  Every window is still created, solved, read back and released inside the timed region."""
+        with set_active at the same point.  Every window is still created, solved, read back and released inside the timed region.
+        The read-back and LM log of the last `keep` windows are kept in self.last_windows."""
+        self.last_windows = []
         if n_kf <= 0:
             return
         def start(ba, v):
@@ -148,10 +160,12 @@ class Workload:
         for i in range(n_kf):
             self.kf_counter += 1
             nxt = self.new_problem(self.kf_counter) if i + 1 < n_kf else None     # builds beside the running solve
-            cur.optimize_end()
+            log = cur.optimize_end()
             if nxt is not None:
                 start(nxt, self.kf_counter)                  # the next solve is on its way before the finished one is read back
-            cur.state()
+            poses, points = cur.state()
+            if i >= n_kf - keep:
+                self.last_windows.append((poses, points, log))
             cur.close()
             cur = nxt
 
@@ -168,17 +182,19 @@ class Workload:
             self.front_end(s)
 
     def run_steps(self, first_step, k, upload=False):
-        """k steps: the front end on this thread, the keyframes' bundle adjustments on a second one (own stream)"""
+        """k steps: the front end on this thread, the keyframes' bundle adjustments on a second one (own stream); the windows of
+        the last step stay in self.last_windows"""
         if not self.with_ba:
             self.front_end_steps(first_step, k, upload)
             self.ctx.sync()
             return
         err = []
         n_kf = sum(self.keyframes_of_step(s) for s in range(first_step, first_step + k))
+        n_last = self.keyframes_of_step(first_step + k - 1) if k > 0 else 0
 
         def ba_loop():
             try:
-                self.bundle_adjust_pipelined(n_kf)
+                self.bundle_adjust_pipelined(n_kf, keep=n_last)
             except Exception as e:      # noqa: BLE001
                 err.append(e)
         th = threading.Thread(target=ba_loop)
@@ -238,6 +254,51 @@ def ba_flops(prob, dim, block_half_bandwidth=-1):
     else:
         chol = n ** 3 / 3.0 + 2.0 * n * n
     return {"linearise": 520.0 * n_obs, "schur": schur, "cholesky": chol, "backsub": 150.0 * n_obs}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, step, out_dir):
+    """What the timed path computed in its last step `step`, as a caller of it receives it, one float32 / float64 .npy file per array:
+    keypoints (x, y, size, angle, response, octave, class_id) and descriptors (32 bytes as values) of the step's 2F images, left and
+    right of every frame in turn, concatenated (`keypoint_counts`: per image); the stereo matches of its F left images (x_right,
+    depth, index of the right keypoint) and their temporal brute-force matches (best index, best and second distance); the poses,
+    landmarks and LM log (chi2_before, chi2_after, lambda, trials, status; NaN past the last iteration) of the windows solved for
+    the step's keyframes.  Over DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of its rows."""
+    c, F = wl.ctx, wl.F
+    f0 = (step * F) % wl.R
+    images = range(2 * f0, 2 * f0 + 2 * F)
+    lefts = range(2 * f0, 2 * f0 + 2 * F, 2)
+    kps, descs = zip(*[c.keypoints(i) for i in images])
+    stereo = [c.stereo(i) for i in lefts]
+    bf = [c.bf_knn2(i) for i in lefts]
+    kp_all = np.concatenate(kps)
+    out = {
+        "keypoint_counts": np.array([len(k) for k in kps], np.float64),
+        "keypoints": np.stack([kp_all[f].astype(np.float32) for f in kp_all.dtype.names], axis=1),
+        "descriptors": np.concatenate(descs).astype(np.float32),
+        "stereo_x_right": np.concatenate([s[0] for s in stereo]).astype(np.float32),
+        "stereo_depth": np.concatenate([s[1] for s in stereo]).astype(np.float32),
+        "stereo_index": np.concatenate([s[2] for s in stereo]).astype(np.float64),
+        "bf_knn2": np.stack([np.concatenate([b[j] for b in bf]) for j in range(3)], axis=1).astype(np.float64),
+    }
+    if wl.with_ba:
+        logs = np.full((len(wl.last_windows), BA_ITERS, 5), np.nan)
+        for w, (_, _, log) in enumerate(wl.last_windows):
+            logs[w, :len(log)] = np.stack([log[f].astype(np.float64) for f in log.dtype.names], axis=1)
+        out["ba_poses"] = np.array([p for p, _, _ in wl.last_windows], np.float64).reshape(-1, BA_KF, 7)
+        out["ba_points"] = np.array([x for _, x, _ in wl.last_windows], np.float64).reshape(-1, BA_PTS, 3)
+        out["ba_log"] = logs
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = DUMP_LIMIT_BYTES / total
+        for name, a in out.items():
+            m = int(len(a) * frac)
+            out[name] = a[np.sort(np.random.default_rng(0).choice(len(a), m, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -514,6 +575,33 @@ def main():
     barrier()
     if dist is not None:
         elapsed = float(sync_tensor([elapsed], dist.ReduceOp.MAX).item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(wl, args.warmup + args.steps - 1, args.dump_outputs)
+    n_kf_timed = sum(wl.keyframes_of_step(s) for s in range(args.warmup, args.warmup + args.steps)) if wl.with_ba else 0
+    kf_per_step = n_kf_timed / max(args.steps, 1)
+    frames_total = world * F * args.steps
+    value = frames_total / elapsed
+    head = {
+        "metric": "frames/sec (ORB+match+local-BA), 1280x720 stereo",
+        "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8 front end / f64 BA", "data": "synthetic",
+        "config": {"workload": "configs[1]+configs[2]: one session, 1280x720 stereo, 2000 kpts, 8 levels; step = %d stereo frames in one launch "
+                               "(extract L+R, stereo match, 2000x2000 BF temporal match; ring of %d resident frames of the 300-frame sequence) + a fresh "
+                               "50-KF/5k-landmark/%d-obs local BA (create + %d LM iterations + destroy) per keyframe (every %dth frame)"
+                               % (F, wl.R, wl.n_obs if wl.with_ba else 0, BA_ITERS, KF_INTERVAL),
+                   "frames_per_step": F, "frames_per_launch": F, "keyframes_per_step": round(kf_per_step, 3), "replicas": world, "parallelism": "replicas x%d" % world,
+                   "mapping_reserve_cus_per_xcd": MAPPING_RESERVE if wl.with_ba else 0,
+                   "ba_tracks": "random (dense reduced system; pair lists + panel-pair chain)"},
+    }
+    if not args.full:
+        # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # the same K steps once more with every frame coming over PCIe inside the loop (page-locked host frames -> copy stream): the
     # PCIe-inclusive rate, reported beside `value` (which is quoted with the inputs resident, as the bench contract says)
     wl.run_steps(max(args.warmup - 1, 0), 1, upload=True)
@@ -524,7 +612,6 @@ def main():
     barrier()
     if dist is not None:
         elapsed_pcie = float(sync_tensor([elapsed_pcie], dist.ReduceOp.MAX).item())
-    n_kf_timed = sum(wl.keyframes_of_step(s) for s in range(args.warmup, args.warmup + args.steps)) if wl.with_ba else 0
     # the same K steps with the keyframes' windows as a tracker makes them (contiguous tracks: block-banded reduced system, band path)
     elapsed_contig = None
     if wl.with_ba:
@@ -583,7 +670,6 @@ def main():
             ba_prof, ba_setup_ms, ba_total_ms, ba_iters_done, ba_dim, ba_pipe_ms, ba_solver = profile_ba()
 
         # ---- GPU time per step by kernel: the dominant one gets the roofline
-        kf_per_step = n_kf_timed / max(args.steps, 1)
         per_step = {FE_KERNEL[n]: float(ms) for n, ms in zip(FE_STAGES, fe_ms)}
         if ba_prof:
             for n, d in ba_prof.items():
@@ -649,22 +735,11 @@ def main():
         except (OSError, KeyError, ValueError, IndexError):
             pass
 
-        frames_total = world * F * args.steps
         pcie_fps = frames_total / elapsed_pcie
-        value = frames_total / elapsed
         fe_extract_ms = float(fe_ms[T_PYR] + fe_ms[T_FAST] + fe_ms[T_DIST] + fe_ms[T_DESC])
         fe_extract_free_ms = float(fe_ms_free[T_PYR] + fe_ms_free[T_FAST] + fe_ms_free[T_DIST] + fe_ms_free[T_DESC])
-        out = {
-            "metric": "frames/sec (ORB+match+local-BA), 1280x720 stereo",
-            "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8 front end / f64 BA", "data": "synthetic",
-            "config": {"workload": "configs[1]+configs[2]: one session, 1280x720 stereo, 2000 kpts, 8 levels; step = %d stereo frames in one launch "
-                                   "(extract L+R, stereo match, 2000x2000 BF temporal match; ring of %d resident frames of the 300-frame sequence) + a fresh "
-                                   "50-KF/5k-landmark/%d-obs local BA (create + %d LM iterations + destroy) per keyframe (every %dth frame)"
-                                   % (F, wl.R, wl.n_obs if wl.with_ba else 0, BA_ITERS, KF_INTERVAL),
-                       "frames_per_step": F, "frames_per_launch": F, "keyframes_per_step": round(kf_per_step, 3), "replicas": world, "parallelism": "replicas x%d" % world,
-                       "mapping_reserve_cus_per_xcd": MAPPING_RESERVE if wl.with_ba else 0},
+        out = dict(head)
+        out.update({
             "ba_ms_per_iter": round(sum(d["ms_per_solve"] for d in ba_prof.values()) / max(ba_iters_done, 1), 4) if ba_prof else None,      # event sum: every launch with the gap in front of it
             "ba_wall_ms_per_iter": round(profile_ba.wall_ms_per_iter, 4) if ba_prof else None,      # optimize(10) by graph replay, wall / 10
             "ba_setup_ms": round(ba_setup_ms, 4) if ba_setup_ms is not None else None,
@@ -690,13 +765,12 @@ def main():
                                "host_bytes_per_step": 2 * F * W * H,
                                "note": "the same K timed steps with every extracted frame copied from page-locked host memory inside the loop "
                                        "(lpslam_hip_upload_images_async: copy stream, step s+1 copied beside the kernels of step s)"},
-        }
+        })
         if flops:
             tot = sum(flops.values())
             it_ms = sum(d["ms_per_solve"] for d in ba_prof.values()) / max(ba_iters_done, 1)
             out["ba_roofline"] = {"flop_per_iteration": int(tot), "ms_per_iteration": round(it_ms, 4), "achieved_TFLOPs": round(tot / (it_ms * 1e-3) / 1e12, 4),
                                   "frac_of_fp64_peak": round(tot / (it_ms * 1e-3) / 1e12 / FP64_PEAK_TFLOPS, 5)}
-        out["config"]["ba_tracks"] = "random (dense reduced system; pair lists + panel-pair chain)"
         if wl.with_ba and elapsed_contig is not None:
             # the same workload with windows as a tracker makes them: contiguous tracks, block-banded reduced system (ba_band.inl)
             wl.set_tracks("contiguous")

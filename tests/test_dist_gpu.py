@@ -167,7 +167,7 @@ def test_partitioned_global_ba_full_size(hiplib, oracle, tmp_path):
 
 def test_bench_two_replicas(hiplib):
     """bench.py under torch.distributed.run with 2 ranks (gloo stands in for RCCL when both ranks share one GPU)."""
-    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu"], {"LPSLAM_BENCH_BACKEND": "gloo"})
+    r = _torchrun(["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu"], {"LPSLAM_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -254,7 +254,7 @@ def test_bench_distributed_path_with_rccl_one_rank(hiplib):
     reduction, and the partitioned global BA through the C++ RCCL driver (communicator id handed out over torch.distributed)."""
     env = dict(os.environ); env.update({"LPSLAM_BENCH_FORCE_DIST": "1"})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_port()), "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu"]
+           "--master-port", str(_port()), "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

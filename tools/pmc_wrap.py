@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Wraps gpurun_out/<tag>_pmc_kernels.json (tools/pmc_summary.py) into profiles/<tag>_pmc.json with the command, the units and the
-workload the counters belong to, and copies the bench line and kernel statistics of the same tag.  usage: pmc_wrap.py <tag>"""
+workload the counters belong to, and copies the bench line and kernel statistics of the same tag.
+usage: pmc_wrap.py <tag> [<output folder of tools/refresh_profiles.sh>]"""
 import json, os, shutil, sys
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "gpurun_out")
+if len(sys.argv) > 2:
+    src = sys.argv[2]
 dst = os.path.join(root, "profiles")
 k = json.load(open(os.path.join(src, tag + "_pmc_kernels.json")))
 k = {name.replace("void ", "").replace("<true>", "").replace("<false>", ""): v for name, v in k.items()}
@@ -19,7 +22,7 @@ for name, v in k.items():
                                      "fetch_correction": corr, "read_class": "16 B per lane (x2, guide)" if corr == 2.0 else "narrower than 16 B per lane (uncalibrated: as counted)"}
 bench = json.loads(open(os.path.join(src, tag + "_bench.json")).read().strip().splitlines()[-1])
 out = {
-    "command": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --no-cpu --no-extras --steps 4 --warmup 1; four separate passes: "
+    "command": "rocprofv3 --kernel-trace --pmc <set> --output-format csv -- python3 bench.py --full --no-cpu --no-extras --steps 4 --warmup 1; four separate passes: "
                "{SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES}, {FETCH_SIZE}, {WRITE_SIZE}, "
                "{SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_LDS_BANK_CONFLICT SQ_WAVES}; condensed by tools/pmc_summary.py "
                "(values summed over XCDs, mean per launch); script: tools/refresh_profiles.sh",
