@@ -245,6 +245,15 @@ int lpslam_hip_desc_store_drop(lpslam_hip_ctx* ctx, int32_t key);
 int lpslam_hip_match_bf_stored(lpslam_hip_ctx* ctx, int query, const int32_t* keys, int32_t n_keys, int32_t max_dist, float ratio,
                                int32_t cross_check, int32_t* out_q, int32_t* out_t, int32_t* out_d, int32_t capacity_per_key,
                                int32_t* counts);
+/* Per-keypoint mask of a stored set (n must equal the set's count; a set without a mask counts every keypoint).  A put clears it. */
+int lpslam_hip_desc_store_mask(lpslam_hip_ctx* ctx, int32_t key, const uint8_t* mask, int32_t n);
+/* Ranks stored sets by their votes for image slot `query`; keys == NULL ranks every stored set.  votes(k) = the number of matches
+ * lpslam_hip_match_bf_stored(query, {k}, max_dist, ratio, cross_check = 1, ...) reports whose train keypoint t has mask_k[t] != 0.
+ * Out: the top_k (1 .. 256) keys with votes >= 1, ordered by votes descending then key ascending, and their votes; *n_out of them.
+ * An unknown or duplicate key, or top_k outside 1 .. 256: LPSLAM_HIP_ERR_INVALID.  One launch pair, one wait; only the top_k pairs
+ * come back to the host. */
+int lpslam_hip_rank_stored(lpslam_hip_ctx* ctx, int query, const int32_t* keys, int32_t n_keys, int32_t max_dist, float ratio,
+                           int32_t top_k, int32_t* out_keys, int32_t* out_votes, int32_t* n_out);
 /* Batched form: pairs (query0 + i*stride, train0 + i*stride), i in [0, n_pairs), in one launch. */
 int lpslam_hip_match_bf_strided(lpslam_hip_ctx* ctx, int query0, int train0, int stride, int n_pairs);
 /* Loads a caller-provided descriptor set (host memory, n x 32 bytes) into image slot `image`, replacing the

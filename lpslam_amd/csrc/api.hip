@@ -608,7 +608,7 @@ void lpslam_hip_destroy(lpslam_hip_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->fe_stream) (void)hipStreamSynchronize(c->fe_stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    for (auto& kv : c->desc_store) if (kv.second.blk) (void)hipFree(kv.second.blk);
+    for (auto& kv : c->desc_store) { if (kv.second.blk) (void)hipFree(kv.second.blk); if (kv.second.mask) (void)hipFree(kv.second.mask); }
     c->desc_store.clear();
     for (auto& blk : c->pool) (void)hipFree(blk.second);
     c->pool.clear();

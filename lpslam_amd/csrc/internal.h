@@ -122,7 +122,8 @@ struct lpslam_hip_ctx {
     // host mirror of d_kp_count: valid after any call that fetched it, invalidated by whatever rewrites it on the device
     std::vector<int32_t> h_kp_count; std::vector<uint8_t> h_kp_valid;
     // descriptor sets kept on the device under a caller's key (lpslam_hip_desc_store_put: a tracker's keyframes), blocks of the pool
-    struct StoredDesc { void* blk = nullptr; size_t cap = 0; int n = 0; };
+    // (mask: per-descriptor byte of lpslam_hip_desc_store_mask, valid while has_mask -- a put clears it)
+    struct StoredDesc { void* blk = nullptr; size_t cap = 0; int n = 0; void* mask = nullptr; size_t mask_cap = 0; bool has_mask = false; };
     std::map<int, StoredDesc> desc_store;
     std::vector<void*> pin_free;       // page-locked 8 KB blocks handed to bundle-adjustment objects (lp_pin_alloc / lp_pin_free)
     std::vector<hipStream_t> ba_streams;   // idle high-priority streams of destroyed bundle-adjustment problems (lp_stream_acquire / release)

@@ -677,6 +677,7 @@ int lpslam_hip_desc_store_put(lpslam_hip_ctx* c, int32_t key, const uint8_t* des
         if (rc) { c->desc_store.erase(key); return rc; }
     }
     e.n = n;
+    e.has_mask = false;
     if (n) LP_HIP(hipMemcpyAsync(e.blk, desc32, (size_t)n * 32, hipMemcpyHostToDevice, aux));
     return LPSLAM_HIP_OK;
 }
@@ -686,7 +687,9 @@ int lpslam_hip_desc_store_drop(lpslam_hip_ctx* c, int32_t key)
     if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
     auto it = c->desc_store.find(key);
     if (it == c->desc_store.end()) return LPSLAM_HIP_OK;
-    if (it->second.blk) { LP_HIP(hipStreamSynchronize(lp_aux_stream(c))); lp_pool_free(c, it->second.blk, it->second.cap); }
+    if (it->second.blk || it->second.mask) LP_HIP(hipStreamSynchronize(lp_aux_stream(c)));
+    if (it->second.blk) lp_pool_free(c, it->second.blk, it->second.cap);
+    if (it->second.mask) lp_pool_free(c, it->second.mask, it->second.mask_cap);
     c->desc_store.erase(it);
     return LPSLAM_HIP_OK;
 }
@@ -1044,3 +1047,285 @@ int lp_launch_proj_batch(hipStream_t s, const LpProjReq* table, int n, int grid_
     LP_HIP(hipGetLastError());
     return LPSLAM_HIP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------
+// K7b whole-map place ranking (lpslam_hip_rank_stored): per stored set the number of cross-checked, mask-passing matches of an image
+//     slot against it -- the matches lpslam_hip_match_bf_stored(query, {key}, max_dist, ratio, cross_check = 1) reports with mask[t] != 0
+//     -- and the top K sets by (votes desc, key asc).  Workgroup = one set; lane = one query (its descriptor in 8 VGPRs), the set
+//     streams past in 1024-descriptor LDS tiles (broadcast reads).  ONE Hamming distance per pair feeds both directions: the forward
+//     2-NN stays in the lane (sequential, first minimum wins: the 2-NN of bf_knn2_body), the reverse best of a train descriptor is
+//     the wavefront minimum of (distance << 16 | query) -- the smallest distance, then the smallest query index: the first minimum of
+//     the reverse bf_knn2_body -- folded into LDS by one atomic per 64 train descriptors per wavefront.
+// ------------------------------------------------------------------------------------------------------------
+#define RK_TILE 1024
+#define RK_THREADS 256
+#define RK_TOPK_MAX 256
+
+namespace {
+struct RankSet { const uint8_t* desc; const uint8_t* mask; int32_t n, key; };
+
+// minimum over the 64 lanes of a wavefront (every lane active), shifted into the lanes' accumulator: DPP within rows of 16, then
+// row_bcast15 / row_bcast31 carry the row minima into the last row, whose lane 63 ends with the wavefront's minimum; the
+// accumulator moves down one lane (wave_shl) and takes that minimum into lane 63 -- after 64 calls lane l holds call l's minimum
+__device__ __forceinline__ uint32_t rk_wave_min_shift(uint32_t v, uint32_t acc)
+{
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false));     // quad_perm [1,0,3,2]
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));     // quad_perm [2,3,0,1]
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false));    // row_half_mirror
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false));    // row_mirror
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x142, 0xA, 0xF, false));    // row_bcast15 -> rows 1, 3
+    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x143, 0xC, 0xF, false));    // row_bcast31 -> rows 2, 3
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)acc, 0x130, 0xF, 0xF, false);  // wave_shl:1, lane 63 <- v (its own)
+}
+
+// one train descriptor (LDS broadcast) against the lane's query: the forward 2-NN update and the wavefront's reverse minimum
+// (qpack = query index, its upper half all ones on a lane without a query: above every real (distance << 16 | query))
+__device__ __forceinline__ uint32_t rk_step(const uint4& a0, const uint4& a1, const uint32_t* tile, int j, int idx, uint32_t qpack,
+                                           int& best, int& second, int& bidx, uint32_t acc)
+{
+    const uint4 b0 = *reinterpret_cast<const uint4*>(&tile[j * 8]);
+    const uint4 b1 = *reinterpret_cast<const uint4*>(&tile[j * 8 + 4]);
+    const int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
+                  __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+    if (d < best) { second = best; best = d; bidx = idx; }          // the per-lane loop of bf_knn2_body
+    else if (d < second) second = d;
+    return rk_wave_min_shift((uint32_t)d << 16 | qpack, acc);
+}
+
+// LDS: tile [RK_TILE][8 words] | reverse best (distance << 16 | query) [nt] | forward best index after the filters, -1 [nq] | vote total
+constexpr size_t rk_lds_bytes(int nt_max, int nq) { return (size_t)RK_TILE * 32 + 4 * (size_t)nt_max + 4 * (size_t)nq + 4; }
+__global__ __launch_bounds__(RK_THREADS) void k_rank_votes(const uint8_t* __restrict__ qdesc, int nq, const RankSet* __restrict__ sets,
+                                                           int max_dist, float ratio, int32_t* __restrict__ votes)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t rk_lds[];      // (the kernel's only LDS: rk_lds_bytes)
+    const RankSet S = sets[blockIdx.x];
+    const int nt = S.n;
+    if (nt == 0 || nq == 0) { if (threadIdx.x == 0) votes[blockIdx.x] = 0; return; }         // block-uniform
+    uint32_t* tile = rk_lds;
+    uint32_t* rev = rk_lds + RK_TILE * 8;
+    int* fwd = reinterpret_cast<int*>(rev + nt);
+    int& total = fwd[nq];
+    const int lane = threadIdx.x & 63;
+    if (threadIdx.x == 0) total = 0;
+    for (int i = threadIdx.x; i < nt; i += RK_THREADS) rev[i] = 0xffffffffu;
+    const uint4* td = reinterpret_cast<const uint4*>(S.desc);
+    for (int q0 = 0; q0 < nq; q0 += RK_THREADS) {
+        const int q = q0 + threadIdx.x;
+        const bool qv = q < nq;
+        const uint32_t qpack = qv ? (uint32_t)q : 0xffff0000u;
+        const uint4* qd = reinterpret_cast<const uint4*>(qdesc + (size_t)min(q, nq - 1) * 32);
+        const uint4 a0 = qd[0], a1 = qd[1];
+        int best = 257, second = 257, bidx = -1;
+        for (int base = 0; base < nt; base += RK_TILE) {
+            const int n = min(RK_TILE, nt - base);
+            if (q0 == 0 || nt > RK_TILE) {        // a set of one tile stays in LDS for every pass
+                __syncthreads();
+                for (int i = threadIdx.x; i < n * 2; i += RK_THREADS) reinterpret_cast<uint4*>(tile)[i] = td[(size_t)base * 2 + i];
+                __syncthreads();
+            }
+            for (int jc = 0; jc < n; jc += 64) {
+                const int m = min(64, n - jc);
+                uint32_t acc = 0xffffffffu;        // lane 64 - m + i: the reverse minimum of train descriptor base + jc + i
+                if (m == 64) {
+#pragma unroll
+                    for (int jj = 0; jj < 64; ++jj) acc = rk_step(a0, a1, tile, jc + jj, base + jc + jj, qpack, best, second, bidx, acc);
+                } else {
+                    for (int jj = 0; jj < m; ++jj) acc = rk_step(a0, a1, tile, jc + jj, base + jc + jj, qpack, best, second, bidx, acc);
+                }
+                if (lane >= 64 - m) atomicMin(&rev[base + jc + lane - (64 - m)], acc);
+            }
+        }
+        // the filter of lpslam_hip_get_bf_matches without the cross check (that needs every pass's reverse minimum)
+        if (qv) fwd[q] = (bidx < 0 || best > max_dist || (ratio > 0.f && ratio * (float)second < (float)best)) ? -1 : bidx;
+    }
+    __syncthreads();
+    int cnt = 0;
+    for (int q = threadIdx.x; q < nq; q += RK_THREADS) {
+        const int t = fwd[q];
+        if (t >= 0 && (!S.mask || S.mask[t]) && (int)(rev[t] & 0xffffu) == q) ++cnt;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0 && cnt) atomicAdd(&total, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0) votes[blockIdx.x] = total;
+}
+
+// count of sets with votes >= v (every thread of the 1024-thread workgroup gets it)
+__device__ int rk_count_ge(const int32_t* votes, int n, int v, int* scratch)
+{
+    int c = 0;
+    for (int i = threadIdx.x; i < n; i += 1024) c += votes[i] >= v;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    __syncthreads();
+    if (threadIdx.x == 0) *scratch = 0;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(scratch, c);
+    __syncthreads();
+    return *scratch;
+}
+
+// top K of the vote array: the sets are in key order, so "key ascending" is "index ascending".  V = the largest vote count with at
+// least K sets at or above it (1 when fewer than K sets have a vote); every set above V is taken, then the first sets AT V in index
+// order until K are taken; the <= 256 taken sets are ranked by (votes desc, index asc) and delivered into page-locked memory.
+__global__ __launch_bounds__(1024) void k_rank_topk(const int32_t* __restrict__ votes, const RankSet* __restrict__ sets, int n, int top_k,
+                                                    int32_t* out, unsigned* counter, int* flag, int seq)
+{
+    __shared__ int s_cnt, s_max, s_n;
+    __shared__ int wave_tot[16];
+    __shared__ int sel_idx[RK_TOPK_MAX], sel_v[RK_TOPK_MAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int mx = 0;
+    for (int i = tid; i < n; i += 1024) mx = max(mx, votes[i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+    if (tid == 0) { s_max = 0; s_n = 0; }
+    __syncthreads();
+    if (lane == 0) atomicMax(&s_max, mx);
+    __syncthreads();
+    const int vmax = s_max;
+    int V = 1;
+    if (vmax > 0 && rk_count_ge(votes, n, 1, &s_cnt) >= top_k) {
+        int lo = 1, hi = vmax;                        // count_ge(lo) >= top_k holds; find the largest such lo
+        while (lo < hi) {
+            const int mid = lo + (hi - lo + 1) / 2;
+            if (rk_count_ge(votes, n, mid, &s_cnt) >= top_k) lo = mid; else hi = mid - 1;
+        }
+        V = lo;
+    }
+    const int need = vmax > 0 ? top_k - rk_count_ge(votes, n, V + 1, &s_cnt) : 0;     // sets AT V still to take, in index order
+    // exclusive prefix of "votes == V" over index order: thread = contiguous chunk
+    const int per = (n + 1023) / 1024, b = min(tid * per, n), e = min(b + per, n);
+    int ties = 0;
+    for (int i = b; i < e; ++i) ties += votes[i] == V;
+    int incl = ties;
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int before = incl - ties;
+    for (int w = 0; w < wave; ++w) before += wave_tot[w];
+    if (vmax > 0)
+        for (int i = b; i < e; ++i) {
+            const int v = votes[i];
+            bool take = v > V;
+            if (v == V) { take = before < need; ++before; }
+            if (take) { const int at = atomicAdd(&s_n, 1); sel_idx[at] = i; sel_v[at] = v; }
+        }
+    __syncthreads();
+    const int ns = s_n;
+    if (tid < ns) {
+        const int v = sel_v[tid], i = sel_idx[tid];
+        int r = 0;
+        for (int j = 0; j < ns; ++j) r += sel_v[j] > v || (sel_v[j] == v && sel_idx[j] < i);
+        out[1 + r] = sets[i].key; out[1 + RK_TOPK_MAX + r] = v;
+    }
+    if (tid == 0) out[0] = ns;
+    lp_signal_done(counter, flag, seq);
+}
+}  // namespace
+
+extern "C" {
+
+int lpslam_hip_desc_store_mask(lpslam_hip_ctx* c, int32_t key, const uint8_t* mask, int32_t n)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    auto it = c->desc_store.find(key);
+    if (it == c->desc_store.end()) { set_error("descriptor set %d is not in the store", key); return LPSLAM_HIP_ERR_INVALID; }
+    lpslam_hip_ctx::StoredDesc& e = it->second;
+    if (n != e.n || (n > 0 && !mask)) { set_error("mask of %d entries for a set of %d descriptors", n, e.n); return LPSLAM_HIP_ERR_INVALID; }
+    LP_HIP(hipSetDevice(c->cfg.device));
+    hipStream_t aux = lp_aux_stream(c);
+    const size_t bytes = (size_t)std::max(n, 1);
+    if (e.mask_cap < bytes) {
+        if (e.mask) { LP_HIP(hipStreamSynchronize(aux)); lp_pool_free(c, e.mask, e.mask_cap); e.mask = nullptr; e.mask_cap = 0; }
+        const int rc = lp_pool_alloc(c, bytes, &e.mask, &e.mask_cap);
+        if (rc) return rc;
+    }
+    if (n) LP_HIP(hipMemcpyAsync(e.mask, mask, (size_t)n, hipMemcpyHostToDevice, aux));
+    e.has_mask = true;
+    return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_rank_stored(lpslam_hip_ctx* c, int query, const int32_t* keys, int32_t n_keys, int32_t max_dist, float ratio, int32_t top_k,
+                           int32_t* out_keys, int32_t* out_votes, int32_t* n_out)
+{
+    int rc = chk(c, query, query); if (rc) return rc;
+    if (!n_out || (top_k >= 1 && (!out_keys || !out_votes)) || n_keys < 0 || (n_keys > 0 && !keys)) { set_error("bad rank_stored arguments"); return LPSLAM_HIP_ERR_INVALID; }
+    *n_out = 0;
+    if (top_k < 1 || top_k > RK_TOPK_MAX) { set_error("top_k %d outside 1..%d", top_k, RK_TOPK_MAX); return LPSLAM_HIP_ERR_INVALID; }
+    // the sets in key order (votes tie -> key ascending = index ascending on the device)
+    std::vector<std::pair<int32_t, lpslam_hip_ctx::StoredDesc*>> list;
+    if (keys) {
+        list.reserve((size_t)n_keys);
+        for (int k = 0; k < n_keys; ++k) {
+            auto it = c->desc_store.find(keys[k]);
+            if (it == c->desc_store.end()) { set_error("descriptor set %d is not in the store", keys[k]); return LPSLAM_HIP_ERR_INVALID; }
+            list.emplace_back(keys[k], &it->second);
+        }
+        std::sort(list.begin(), list.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (size_t k = 1; k < list.size(); ++k)
+            if (list[k].first == list[k - 1].first) { set_error("key %d listed twice", list[k].first); return LPSLAM_HIP_ERR_INVALID; }
+    } else {
+        list.reserve(c->desc_store.size());
+        for (auto& kv : c->desc_store) list.emplace_back(kv.first, &kv.second);      // (std::map: key order)
+    }
+    int32_t nq = 0;
+    if ((rc = lpslam_hip_keypoint_count(c, query, &nq))) return rc;
+    const int n = (int)list.size();
+    if (n == 0 || nq == 0) return LPSLAM_HIP_OK;
+    int nt_max = 0;
+    for (const auto& e : list) nt_max = std::max(nt_max, e.second->n);
+    const size_t lds = rk_lds_bytes(nt_max, nq);
+    if (lds > 160 * 1024) { set_error("rank_stored: %d query and %d train descriptors exceed the workgroup's LDS", nq, nt_max); return LPSLAM_HIP_ERR_CAPACITY; }
+    hipStream_t s = lp_aux_stream(c);
+    // device block: votes [n] | set table [n] (uploaded on the stream of the launches); page-locked block of a fixed size:
+    // flag | count, keys [256], votes [256]
+    const size_t o_out = 64, h_bytes = o_out + 4 * (1 + 2 * (size_t)RK_TOPK_MAX);
+    const size_t o_tab = ((size_t)n * 4 + 63) & ~(size_t)63;
+    std::vector<RankSet> table((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const lpslam_hip_ctx::StoredDesc& e = *list[(size_t)k].second;
+        table[(size_t)k] = RankSet{(const uint8_t*)e.blk, e.has_mask ? (const uint8_t*)e.mask : nullptr, e.n, list[(size_t)k].first};
+    }
+    size_t hcap = 0;
+    uint8_t* hb = (uint8_t*)lp_pin_big_alloc(c, h_bytes, &hcap);
+    if (!hb) { set_error("page-locked memory for rank_stored"); return LPSLAM_HIP_ERR_DEVICE; }
+    void* blk = nullptr; size_t cap = 0;
+    if ((rc = lp_pool_alloc(c, o_tab + (size_t)n * sizeof(RankSet), &blk, &cap))) { lp_pin_big_free(c, hb, hcap); return rc; }
+    auto release = [&]() { lp_pool_free(c, blk, cap); lp_pin_big_free(c, hb, hcap); };
+    RankSet* sets = (RankSet*)((uint8_t*)blk + o_tab);
+    // (a pageable source: the runtime has staged the table when the call returns)
+    if (hipMemcpyAsync(sets, table.data(), (size_t)n * sizeof(RankSet), hipMemcpyHostToDevice, s) != hipSuccess) { release(); set_error("rank_stored: set table upload"); return LPSLAM_HIP_ERR_DEVICE; }
+    unsigned* done_counter = lp_done_counter(c, 2);
+    if (!done_counter) { release(); set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
+    if (lds > 64 * 1024) {
+        static std::atomic<bool> attr_set[64];
+        const int dev = c->cfg.device;
+        if (dev >= 0 && dev < 64 && !attr_set[dev].load()) {
+            if (hipFuncSetAttribute((const void*)k_rank_votes, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { release(); set_error("rank_stored: LDS attribute"); return LPSLAM_HIP_ERR_DEVICE; }
+            attr_set[dev].store(true);
+        }
+    }
+    int* flag = (int*)hb;
+    const int seq = lp_next_seq(c->done_seq);
+    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
+    const uint8_t* qdesc = c->d_desc + (size_t)query * c->slots_per_image * 32;
+    int32_t* d_votes = (int32_t*)blk;
+    int32_t* out = (int32_t*)(hb + o_out);
+    hipLaunchKernelGGL(k_rank_votes, dim3((unsigned)n), dim3(RK_THREADS), lds, s, qdesc, (int)nq, (const RankSet*)sets, (int)max_dist, ratio, d_votes);
+    hipLaunchKernelGGL(k_rank_topk, dim3(1), dim3(1024), 0, s, (const int32_t*)d_votes, (const RankSet*)sets, n, (int)top_k, out, done_counter, flag, seq);
+    if (hipGetLastError() != hipSuccess) { release(); set_error("launch failed"); return LPSLAM_HIP_ERR_DEVICE; }
+    if (!lp_wait_done(flag, seq, s)) {
+        // (a dead stream: its kernels may still read the table and write the votes -- leak both rather than hand them on)
+        if (lp_wait_recover(c, 2, s)) release();
+        set_error("lpslam_hip_rank_stored: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE;
+    }
+    const int ns = std::min(out[0], (int)top_k);
+    for (int i = 0; i < ns; ++i) { out_keys[i] = out[1 + i]; out_votes[i] = out[1 + RK_TOPK_MAX + i]; }
+    *n_out = ns;
+    release();
+    return LPSLAM_HIP_OK;
+}
+
+}  // extern "C"

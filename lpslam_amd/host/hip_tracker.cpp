@@ -1,5 +1,7 @@
 // hip_tracker.cpp -- see hip_tracker.h.  Host-side tracking glue around the HIP C ABI (the arithmetic runs on the GPU).
 #include "hip_tracker.h"
+#include "map_file.h"
+#include <cstring>
 #include <future>
 #include "rectify.h"
 #include "two_view.h"
@@ -81,7 +83,9 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_useLiveView = o.getBool("liveView"); m_useMapDb = o.getBool("useMapDb"); m_configFromFile = o.getString("configFromFile");
     m_slamKeypoints = o.getInteger("slamKeypoints"); m_cameraSetup = o.getString("cameraSetup"); m_vocabFile = o.getString("vocabFile");
     m_forwardNavState = o.getBool("forwardNavState"); m_forwardImu = o.getBool("forwardImu"); m_emitMap = o.getBool("emitMap");
-    m_enableMapping = o.getBool("enableMapping"); m_mapFilename = o.getString("mapFilename");
+    m_enableMapping = o.getBool("enableMapping");
+    if (o.given("mapFilename") || !m_mapFilenameSet) m_mapFilename = o.getString("mapFilename");
+    m_mapFilenameGiven = o.given("mapFilename");
     m_waitForNavigation = o.getBool("waitForNavigation"); m_viewerFps = o.getInteger("viewerFps");
     m_forwardHighResNav = o.getBool("forwardHighResNav"); m_loopClosure = o.getBool("loopClosure");
     m_useOpenCL = o.getBool("useOpenCL"); m_useCUDA = o.getBool("useCUDA"); m_relocWithNavigation = o.getBool("relocWithNavigation");
@@ -230,6 +234,7 @@ bool HipVslamTrackerBase::startContext(bool stereo)
     m_stats = Statistics{};
     m_kfs.clear(); m_landmarks.clear(); m_lmIndex.clear(); m_replaced.clear(); m_freshLandmarks.clear(); m_nextLandmarkId = 0; m_refKf = -1; m_segment = 0; m_segmentStart = 0;
     m_state = TrackerState::NotInitialized;
+    loadMap();
     m_started = true;
     return true;
 }
@@ -305,7 +310,12 @@ void HipVslamTrackerBase::warmUpContext(bool stereo)
 bool HipVslamTrackerBase::stop()
 {
     std::scoped_lock lock(m_slamLock);
+    // the map database is written when mapping was on and the session's file was not rejected -- after the pending window's solve
+    // has entered the map, so that the file holds what the map holds
+    const bool save = m_ctx && m_started && mapDbActive() && m_enableMapping && !m_mapRejected;
+    if (save) finishMapping();
     stopMappingThread();                               // the mapping thread uses the context
+    if (save) saveMap();
     stopPrefetchThread();
     if (m_vocab) { lpslam_hip_vocab_destroy(m_vocab); m_vocab = nullptr; }
     if (m_ctx) { logStatistics(); lpslam_hip_destroy(m_ctx); m_ctx = nullptr; }
@@ -1318,6 +1328,17 @@ bool HipVslamTrackerBase::relocalise(FrameData& cur)
     }
     std::sort(near.begin(), near.end());
     if (near.size() > 8) near.resize(8);
+    if (m_relocByRank && !m_vocab && !cur.kpts.empty()) {
+        // a loaded map: the last pose means nothing -- the frame against every keyframe on the device, the 8 with the most
+        // cross-checked matches that carry landmarks (lpslam_hip_rank_stored; max_dist 50 and ratio 0.75 as below)
+        std::vector<int32_t> keys;
+        for (size_t k = 0; k < m_kfs.size(); ++k) if (!m_kfs[k].erased && m_kfs[k].desc_on_device) keys.push_back((int32_t)k);
+        int32_t rk[8], rv[8], nr = 0;
+        if (!keys.empty() && lpslam_hip_rank_stored(m_ctx, cur.slot, keys.data(), (int32_t)keys.size(), 50, 0.75f, 8, rk, rv, &nr) == LPSLAM_HIP_OK) {
+            near.clear();
+            for (int i = 0; i < nr; ++i) near.emplace_back(-(double)rv[i], rk[i]);
+        } else if (!keys.empty()) logMessage(LpSlamLogLevel_Error, std::string("VSLAM place ranking failed: ") + lpslam_hip_last_error());
+    }
     // with a vocabulary the candidates come from the BoW database instead ([UPSTREAM] bow_database::acquire_relocalization_candidates):
     // the keyframes that share the most words with the frame, best L1 score first -- wherever they are in the map
     std::vector<int32_t> cur_node;
@@ -1760,6 +1781,133 @@ void HipVslamTrackerBase::finishMapping()
     }
 }
 
+int HipVslamTrackerBase::sharedRefKf(const FrameData& f) const
+{
+    std::unordered_map<int, int> shared;
+    for (int id : f.landmark) {
+        const Landmark* l = id >= 0 ? lm(resolve(id)) : nullptr;
+        if (l) for (const auto& o : l->obs) ++shared[o.first];
+    }
+    int best = -1, most = 0;
+    for (const auto& kv : shared) if (kv.second > most || (kv.second == most && kv.first < best)) { best = kv.first; most = kv.second; }
+    return best;
+}
+
+static bool close_to(double a, double b) { return std::fabs(a - b) <= 1e-6 * std::max(1.0, std::max(std::fabs(a), std::fabs(b))); }
+
+void HipVslamTrackerBase::loadMap()
+{
+    m_mapLoaded = false; m_mapRejected = false; m_localiseOnly = false; m_relocByRank = false; m_lostSinceUnset = false;
+    if (!mapDbActive()) return;
+    {
+        std::ifstream probe(m_mapFilename, std::ios::binary);
+        if (!probe) { logMessage(LpSlamLogLevel_Info, "Map file " + m_mapFilename + " not present: starting with an empty map"); return; }
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    MapData d; std::string err;
+    if (!read_map_file(m_mapFilename, d, &err)) {
+        m_mapRejected = true;
+        logMessage(LpSlamLogLevel_Error, "Map file " + m_mapFilename + " rejected (" + err + "): starting with an empty map; the file will not be overwritten");
+        return;
+    }
+    const MapFileCamera& c = d.cam;
+    std::string why;
+    if ((c.stereo != 0) != m_stereo) why = "camera setup";
+    else if (c.width != m_cam.resolution_x || c.height != m_cam.resolution_y) why = "resolution";
+    else if (!close_to(c.fx, m_cam.f_x) || !close_to(c.fy, m_cam.f_y) || !close_to(c.cx, m_cam.c_x) || !close_to(c.cy, m_cam.c_y)) why = "intrinsics";
+    else if (m_stereo && !close_to(c.focal_x_baseline, m_cam.focal_x_baseline)) why = "focal_x_baseline";
+    else if (c.num_levels != m_numLevels || !close_to(c.scale_factor, m_scaleFactor)) why = "numLevels / scaleFactor";
+    if (!why.empty()) {
+        m_mapRejected = true;
+        logMessage(LpSlamLogLevel_Error, "Map file " + m_mapFilename + " was made with another camera (" + why + " differs): starting with an empty map; the file will not be overwritten");
+        return;
+    }
+    m_kfs.assign(d.kfs.size(), Keyframe{});
+    int last_live = -1;
+    for (size_t k = 0; k < d.kfs.size(); ++k) {
+        const MapFileKeyframe& s = d.kfs[k];
+        Keyframe& kf = m_kfs[k];
+        kf.erased = s.erased != 0;
+        if (kf.erased) continue;
+        std::copy(s.q, s.q + 4, kf.pose.q); std::copy(s.t, s.t + 3, kf.pose.t);
+        kf.segment = s.segment; kf.kpts = s.kpts; kf.desc = s.desc; kf.x_right = s.x_right; kf.depth = s.depth; kf.landmark = s.landmark;
+        last_live = (int)k;
+    }
+    for (const MapFileLandmark& s : d.lms) {
+        Landmark l;
+        std::copy(s.p, s.p + 3, l.p); std::memcpy(l.desc, s.desc, 32); std::copy(s.normal, s.normal + 3, l.normal);
+        l.min_valid = s.min_valid; l.max_valid = s.max_valid; l.ref_kf = s.ref_kf; l.n_observable = s.n_observable; l.n_observed = s.n_observed;
+        l.obs.assign(s.obs.begin(), s.obs.end());
+        m_landmarks[s.id] = std::move(l); indexLandmark(s.id);
+    }
+    m_nextLandmarkId = d.next_landmark_id;
+    m_segment = d.segment; m_segmentStart = 0;
+    for (size_t k = 0; k < m_kfs.size(); ++k) if (!m_kfs[k].erased && m_kfs[k].segment == m_segment) { m_segmentStart = (int)k; break; }
+    for (size_t k = 0; k < m_kfs.size(); ++k) {
+        Keyframe& kf = m_kfs[k];
+        if (kf.erased) continue;
+        if (m_vocab) { computeBow(kf); m_bowDb.add((int)k, kf.bow); continue; }
+        // without a vocabulary relocalisation ranks the keyframes on the device: descriptors there, a keypoint counts when it carries a landmark
+        storeDescriptors((int)k, kf);
+        std::vector<uint8_t> mask(kf.kpts.size());
+        for (size_t i = 0; i < mask.size(); ++i) mask[i] = resolve(kf.landmark[i]) >= 0 && lm(resolve(kf.landmark[i])) ? 1 : 0;
+        if (kf.desc_on_device && lpslam_hip_desc_store_mask(m_ctx, (int32_t)k, mask.data(), (int32_t)mask.size()) != LPSLAM_HIP_OK)
+            logMessage(LpSlamLogLevel_Error, std::string("keyframe ") + std::to_string(k) + ": mask not kept on the device (" + lpslam_hip_last_error() + ")");
+    }
+    m_refKf = last_live;
+    m_mapLoaded = true;
+    m_localiseOnly = !m_enableMapping;
+    m_relocByRank = true;
+    m_state = TrackerState::Lost;                      // the first frames relocalise against the map instead of starting a new one
+    m_lostSinceUnset = true;
+    m_havePrev = false; m_haveVelocity = false;
+    const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    logMessage(LpSlamLogLevel_Info, "Map file " + m_mapFilename + " loaded: " + std::to_string(last_live < 0 ? 0 : std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; })) +
+               " keyframes, " + std::to_string(m_landmarks.size()) + " landmarks in " + std::to_string(ms) + " ms" + (m_localiseOnly ? "; localisation only" : ""));
+}
+
+void HipVslamTrackerBase::saveMap()
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    MapData d;
+    d.cam.stereo = m_stereo ? 1 : 0; d.cam.width = m_cam.resolution_x; d.cam.height = m_cam.resolution_y;
+    d.cam.fx = m_cam.f_x; d.cam.fy = m_cam.f_y; d.cam.cx = m_cam.c_x; d.cam.cy = m_cam.c_y; d.cam.focal_x_baseline = m_cam.focal_x_baseline;
+    d.cam.num_levels = m_numLevels; d.cam.scale_factor = m_scaleFactor;
+    d.next_landmark_id = m_nextLandmarkId; d.segment = m_segment;
+    d.kfs.resize(m_kfs.size());
+    long live = 0;
+    for (size_t k = 0; k < m_kfs.size(); ++k) {
+        const Keyframe& kf = m_kfs[k];
+        MapFileKeyframe& o = d.kfs[k];
+        o.erased = kf.erased ? 1 : 0;
+        if (kf.erased) continue;
+        ++live;
+        std::copy(kf.pose.q, kf.pose.q + 4, o.q); std::copy(kf.pose.t, kf.pose.t + 3, o.t);
+        o.segment = kf.segment; o.kpts = kf.kpts; o.desc = kf.desc; o.x_right = kf.x_right; o.depth = kf.depth;
+        o.landmark.resize(kf.landmark.size());
+        for (size_t i = 0; i < kf.landmark.size(); ++i) { const int id = resolve(kf.landmark[i]); o.landmark[i] = id >= 0 && lm(id) ? id : -1; }
+    }
+    std::vector<int> ids;
+    for (const auto& kv : m_landmarks) ids.push_back(kv.first);
+    std::sort(ids.begin(), ids.end());
+    for (int id : ids) {
+        const Landmark& l = m_landmarks.at(id);
+        MapFileLandmark o;
+        o.id = id;
+        std::copy(l.p, l.p + 3, o.p); std::memcpy(o.desc, l.desc, 32); std::copy(l.normal, l.normal + 3, o.normal);
+        o.min_valid = l.min_valid; o.max_valid = l.max_valid; o.ref_kf = l.ref_kf; o.n_observable = l.n_observable; o.n_observed = l.n_observed;
+        for (const auto& ob : l.obs)        // (observations of erased keyframes are not part of the map)
+            if (ob.first >= 0 && (size_t)ob.first < m_kfs.size() && !m_kfs[(size_t)ob.first].erased && ob.second >= 0 && (size_t)ob.second < m_kfs[(size_t)ob.first].kpts.size())
+                o.obs.emplace_back(ob.first, ob.second);
+        if (o.ref_kf >= (int)m_kfs.size()) o.ref_kf = -1;
+        d.lms.push_back(std::move(o));
+    }
+    std::string err;
+    if (!write_map_file(m_mapFilename, d, &err)) { logMessage(LpSlamLogLevel_Error, "Map file " + m_mapFilename + " not saved: " + err); return; }
+    const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    logMessage(LpSlamLogLevel_Info, "Map file " + m_mapFilename + " saved: " + std::to_string(live) + " keyframes, " + std::to_string(d.lms.size()) + " landmarks in " + std::to_string(ms) + " ms");
+}
+
 void HipVslamTrackerBase::storeDescriptors(int key, Keyframe& kf)
 {
     kf.desc_on_device = lpslam_hip_desc_store_put(m_ctx, key, kf.desc.data(), (int32_t)kf.kpts.size()) == LPSLAM_HIP_OK;
@@ -1964,17 +2112,21 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
         // that succeeds or time_to_relocalize has passed -- then a new map segment starts at the pose the tracker last believed
         // in, moved along by the navigation prior where there is one
         Pose nav_step;
+        if (m_lostSinceUnset) { m_lostSince = cam.timestamp; m_lostSinceUnset = false; }
         if (m_relocWithNavigation && navDelta(nav_step)) movePose(nav_step, m_lastGoodPose, m_lastGoodPose);
         if (relocalise(cur)) {
             m_state = TrackerState::Tracking;
             ++m_stats.relocalised;
-            const int c = insertKeyframe(cur);
-            startMapping(c);
+            m_relocByRank = false;
+            if (!m_localiseOnly) {
+                const int c = insertKeyframe(cur);
+                startMapping(c);
+            } else if (const int r = sharedRefKf(cur); r >= 0) m_refKf = r;
             m_haveVelocity = false;
             m_prev = std::move(cur); m_havePrev = true;
         } else {
             const double lost_for = std::chrono::duration<double>(cam.timestamp - m_lostSince).count();
-            if (lost_for > m_timeToRelocalize) {
+            if (lost_for > m_timeToRelocalize && !m_localiseOnly) {      // (localisation only: relocalise again, never re-initialise)
                 bool started = false;
                 if (stereo) { ++m_segment; started = initializeMap(cur, m_lastGoodPose); if (!started) --m_segment; }
                 else { m_state = TrackerState::Initializing; }            // monocular: the two-view initialiser takes over (scale is lost)
@@ -2015,7 +2167,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
             for (int r = 0; r < 3; ++r) m_velocity.t[r] = cur.pose.t[r] - (Rv.m[r * 3] * m_prev.pose.t[0] + Rv.m[r * 3 + 1] * m_prev.pose.t[1] + Rv.m[r * 3 + 2] * m_prev.pose.t[2]);
             m_haveVelocity = true;
             ++m_framesSinceKeyframe;
-            if (keyframeNeeded(inliers)) {
+            if (!m_localiseOnly && keyframeNeeded(inliers)) {
                 finishMapping();                    // the previous keyframe's solve enters the map before the next one is inserted
                 int c;
                 { ScopedSeconds timed(m_stats.t_kf_insert); c = insertKeyframe(cur); }
@@ -2024,6 +2176,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
                 if (!m_asyncMapping) cur.pose = m_kfs[(size_t)c].pose;
                 lap(m_stats.t_keyframe);
             }
+            if (m_localiseOnly) { if (const int r = sharedRefKf(cur); r >= 0) m_refKf = r; }      // (no keyframes: the local map follows the camera)
             m_lastGoodPose = cur.pose;
             m_prev = std::move(cur);
         } else {

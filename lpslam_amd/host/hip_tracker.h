@@ -30,7 +30,7 @@ public:
 
     // what the manager down-casts for (src/Manager/SlamManager.cpp:1316-1366)
     bool mappingSetMode(bool enableMapping) { m_enableMapping = enableMapping; return true; }
-    bool mappingSetFilename(std::string const& filename) { m_mapFilename = filename; return true; }
+    bool mappingSetFilename(std::string const& filename) { m_mapFilename = filename; m_mapFilenameSet = true; return true; }
     bool mappingExportCSV(std::string csv_filename);
     std::size_t mappingGetFeatures(LpSlamMapBoundary boundary, LpSlamFeatureEntry* entry, std::size_t entry_count, LpSlamMatrix9x9 transform);
     std::size_t mappingGetFeaturesCount(LpSlamMapBoundary boundary);
@@ -142,6 +142,17 @@ protected:
     void logStatistics();
     std::string m_lastStatistics;                       // the line logStatistics() logged last (kept past stop(): lastStatistics())
     void storeDescriptors(int key, Keyframe& kf);     // keeps the keyframe's descriptors on the device for the batched loop-candidate search
+    // map database (src/Trackers/OpenVSLAMTrackerBase.cpp:241-255,287-294): used only when useMapDb is on AND a file name was given
+    // (mapFilename in the configuration or mappingSetFilename) -- no implicit map.db in the working directory
+    bool mapDbActive() const { return m_useMapDb && (m_mapFilenameGiven || m_mapFilenameSet) && !m_mapFilename.empty(); }
+    void loadMap();                                   // startContext: restores the map, or leaves it empty (rejected file: m_mapRejected)
+    void saveMap();                                   // stop(): the map into m_mapFilename
+    bool m_mapFilenameGiven = false, m_mapFilenameSet = false;
+    bool m_mapLoaded = false, m_mapRejected = false;
+    bool m_localiseOnly = false;                      // a loaded map with enableMapping off: no keyframes, no loop closing, never re-initialise
+    bool m_relocByRank = false;                       // after a load, until the first relocalisation: candidates by lpslam_hip_rank_stored over all keyframes
+    bool m_lostSinceUnset = false;
+    int sharedRefKf(const FrameData& f) const;          // localisation only: the keyframe that sees most of the frame's landmarks (-1: none)                    // the loss started before the first frame (a loaded map): its first frame starts the clock
 
     // configuration (names as in the reference tracker)
     bool m_useLiveView = false, m_useMapDb = true, m_forwardNavState = true, m_forwardImu = true, m_emitMap = false;

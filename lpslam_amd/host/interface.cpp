@@ -5,6 +5,7 @@
 #include "../../include/lpslam_manager.h"
 #include "slam_manager.h"
 #include "jpeg.h"
+#include "map_file.h"
 #include <cstring>
 #include <vector>
 
@@ -127,6 +128,28 @@ LPS_API size_t lpslam_manager_tracker_statistics(lpslam_c_manager* m, char* out,
     return s.size();
 }
 LPS_API size_t lpslam_manager_features_count(lpslam_c_manager* m) { return m->mgr.mappingGetFeaturesCount(LpSlamMapBoundary{}); }
+LPS_API int lpslam_manager_mapping_set_mode(lpslam_c_manager* m, int enable) { return m->mgr.mappingSetMode(enable != 0) ? 1 : 0; }
+LPS_API int lpslam_manager_mapping_set_filename(lpslam_c_manager* m, const char* f) { return m->mgr.mappingSetFilename(f ? f : "") ? 1 : 0; }
+// the map database file (host/map_file.h) without a tracker: validate a file and report counts[5] = keyframe records, live keyframes,
+// landmarks, next landmark id, stereo; 1 = valid, 0 = rejected with the reason in why (at most why_cap - 1 characters)
+LPS_API int lpslam_map_file_info(const char* path, int64_t* counts, char* why, size_t why_cap) {
+    LpSlam::MapData d; std::string err;
+    const bool ok = path && LpSlam::read_map_file(path, d, &err);
+    if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
+    if (ok && counts) {
+        counts[0] = (int64_t)d.kfs.size(); counts[1] = 0;
+        for (const auto& k : d.kfs) counts[1] += k.erased ? 0 : 1;
+        counts[2] = (int64_t)d.lms.size(); counts[3] = d.next_landmark_id; counts[4] = d.cam.stereo;
+    }
+    return ok ? 1 : 0;
+}
+// reads `in` and writes it back to `out` (a valid file comes back byte for byte); 1 = done
+LPS_API int lpslam_map_file_rewrite(const char* in, const char* out, char* why, size_t why_cap) {
+    LpSlam::MapData d; std::string err;
+    const bool ok = in && out && LpSlam::read_map_file(in, d, &err) && LpSlam::write_map_file(out, d, &err);
+    if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
+    return ok ? 1 : 0;
+}
 // interface.type_conversion of the reference's tests (src/test/InterfaceTest.cpp:14-33): POD -> internal -> POD
 LPS_API void lpslam_roundtrip_state(const LpSlamGlobalStateInTime* in, LpSlamGlobalStateInTime* out) {
     *out = LpSlam::conversion::gsInTimeInternalToInterface(LpSlam::conversion::gsInTimeInterfaceToInternal(*in));

@@ -151,8 +151,10 @@ public:
             if (it == values_.end()) throw std::invalid_argument("unknown configuration option '" + kv.first + "'");
             if (it->second.kind != kv.second.kind) throw std::invalid_argument("configuration option '" + kv.first + "' has the wrong type");
             it->second = kv.second;
+            given_[kv.first] = true;
         }
     }
+    bool given(const std::string& k) const { return given_.count(k) != 0; }      // set by a parsed configuration, not only the default
     bool getBool(const std::string& k) const { return at(k).asBool(); }
     int getInteger(const std::string& k) const { return (int)std::llround(at(k).asNumber()); }
     double getDouble(const std::string& k) const { return at(k).asNumber(); }
@@ -167,6 +169,7 @@ private:
     }
     std::map<std::string, Json> values_;
     std::map<std::string, bool> ints_;
+    std::map<std::string, bool> given_;
 };
 
 }  // namespace LpSlam

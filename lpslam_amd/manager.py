@@ -248,3 +248,36 @@ class Manager:
         t = (C.c_float * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
         n = self.lib.lpslam_manager_features(self.h, buf, cap, t)
         return [(buf[i].x, buf[i].y, buf[i].z) for i in range(n)]
+
+    def features_count(self):
+        return int(self.lib.lpslam_manager_features_count(self.h))
+
+    def mapping_set_mode(self, enable):
+        """mappingSetMode: mapping on (True) or localisation only against a loaded map (False); call before start()"""
+        f = self.lib.lpslam_manager_mapping_set_mode; f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_int
+        return bool(f(self.h, 1 if enable else 0))
+
+    def mapping_set_filename(self, path):
+        """mappingSetFilename: the map database file (used when the tracker's useMapDb is on); call before start()"""
+        f = self.lib.lpslam_manager_mapping_set_filename; f.argtypes = [C.c_void_p, C.c_char_p]; f.restype = C.c_int
+        return bool(f(self.h, str(path).encode()))
+
+
+def map_file_info(path):
+    """validates a map database file: (True, counts) with counts = {keyframes, live_keyframes, landmarks, next_landmark_id, stereo},
+    or (False, reason)"""
+    lib = load()
+    f = lib.lpslam_map_file_info; f.argtypes = [C.c_char_p, C.POINTER(C.c_int64), C.c_char_p, C.c_size_t]; f.restype = C.c_int
+    counts = (C.c_int64 * 5)(); why = C.create_string_buffer(512)
+    if not f(str(path).encode(), counts, why, 512):
+        return False, why.value.decode()
+    return True, dict(zip(("keyframes", "live_keyframes", "landmarks", "next_landmark_id", "stereo"), list(counts)))
+
+
+def map_file_rewrite(src, dst):
+    """reads a map database file and writes it back: (True, "") or (False, reason)"""
+    lib = load()
+    f = lib.lpslam_map_file_rewrite; f.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]; f.restype = C.c_int
+    why = C.create_string_buffer(512)
+    ok = bool(f(str(src).encode(), str(dst).encode(), why, 512))
+    return ok, why.value.decode()
