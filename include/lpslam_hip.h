@@ -559,6 +559,37 @@ int lpslam_hip_sim3_transform_optimize(lpslam_hip_ctx* ctx, int32_t n_problems, 
                                        const int32_t* pair_start, const double* cam1, const double* cam2, double chi_sq,
                                        int32_t fix_scale, uint8_t* inlier, int32_t* n_inliers);
 
+/* ---- 2-D occupancy grid from laser scans (the reference's map_publisher occupancy_map_export, reached through
+ * src/Trackers/OpenVSLAMStereoTracker.cpp:374-400; the grid itself is defined in INTEGRATION.md, "Occupancy grid") ----------
+ * Beam directions are uploaded once per scan geometry (cos a, sin a per beam, computed by the caller in double); the ranges of each
+ * scan stay on the device under a caller's key (a tracker's keyframes); a build takes one map-plane pose per key and returns the
+ * int8 grid (-1 unknown, 0 .. 100 occupied).  All calls of a context that touch the store or build are serialised on the context and
+ * run on a stream of their own: a build may come from any thread while the context tracks. */
+typedef struct lpslam_hip_scan_pose {
+    int32_t key;
+    int32_t pad;
+    double origin[2];   /* laser position, (world lpslam y, z) */
+    double fwd[2];      /* (y, z) of R_world_laser * (0, 0, 1)  */
+    double left[2];     /* (y, z) of R_world_laser * (0, -1, 0) */
+} lpslam_hip_scan_pose;
+typedef struct lpslam_hip_grid_info {
+    int64_t x0, y0;              /* global cell of grid cell (0, 0) */
+    int32_t width, height;       /* cells; 0 x 0 when no beam counted */
+    int64_t rays;                /* beams that were not skipped */
+    int64_t cell_visits;         /* hit + miss increments inside the box */
+} lpslam_hip_grid_info;
+/* A table of n_beams (cos, sin) pairs; *id names it in scan_store_put. */
+int lpslam_hip_scan_geometry_put(lpslam_hip_ctx* ctx, const double* cos_sin, int32_t n_beams, int32_t* id);
+/* n must equal the geometry's beam count.  put replaces an existing key. */
+int lpslam_hip_scan_store_put(lpslam_hip_ctx* ctx, int32_t key, int32_t geometry_id, const float* ranges, int32_t n, float range_min,
+                              float range_max, float range_threshold);
+int lpslam_hip_scan_store_drop(lpslam_hip_ctx* ctx, int32_t key);
+/* The grid of the listed scans at the given poses; res > 0 metres per cell, max_side a positive multiple of 64.  out == NULL: sizing
+ * only (info as the full build gives it).  An unknown key, or capacity < width * height with out != NULL: LPSLAM_HIP_ERR_INVALID and
+ * nothing is written to out. */
+int lpslam_hip_occupancy_build(lpslam_hip_ctx* ctx, const lpslam_hip_scan_pose* poses, int32_t n, double res, int32_t max_side,
+                               int8_t* out, int64_t capacity, lpslam_hip_grid_info* info);
+
 #ifdef __cplusplus
 }
 #endif

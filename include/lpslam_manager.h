@@ -4,8 +4,7 @@
  * Same class name, method names, signatures and single data member as the reference's exported class
  * (/root/reference/src/Interface/LpSlamManager.h:17-121, C++ ABI, pimpl), so existing client code compiles unchanged;
  * behind it sits LpSlam::SlamManager of lpslam_amd/host/ whose trackers run on the MI355X through include/lpslam_hip.h.
- * Methods that belong to subsystems outside the accelerated path (file/replay sources, recording, laser/occupancy map,
- * live view) keep their signatures and behave as the reference does when the backing plugin is absent: they return
+ * Methods that belong to subsystems outside the accelerated path (file/replay sources, recording, live view) keep their signatures and behave as the reference does when the backing plugin is absent: they return
  * false / 0 / do nothing (cf. src/Manager/SlamManager.cpp:1311-1312,1368-1395).
  */
 #ifndef LPSLAM_AMD_MANAGER_H
@@ -57,7 +56,8 @@ public:
     std::size_t mappingGetFeatures(LpSlamMapBoundary region, LpSlamFeatureEntry* out, std::size_t capacity, LpSlamMatrix9x9 rotation);
     bool mappingExportCSV(const char* csv_path);
 
-    /* belong to subsystems outside the accelerated path; signatures kept, behaviour of the reference without the backing plugin */
+    /* the laser map (stereo tracker: INTEGRATION.md C''''); the rest belongs to subsystems outside the accelerated path: signatures
+       kept, behaviour of the reference without the backing plugin */
     void addImageFromFile(char const* image_path);  void addStereoImageFromFiles(char const* left_path, char const* right_path);
     void addMarker(LpSlamMarkerIdentifier marker, LpSlamMarkerState state);
     static bool compressImage(uint8_t* pixels, LpSlamImageDescription layout, uint8_t* jpeg_out, uint32_t* jpeg_size);

@@ -610,6 +610,7 @@ void lpslam_hip_destroy(lpslam_hip_ctx* c)
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     for (auto& kv : c->desc_store) { if (kv.second.blk) (void)hipFree(kv.second.blk); if (kv.second.mask) (void)hipFree(kv.second.mask); }
     c->desc_store.clear();
+    lp_occupancy_free(c);
     for (auto& blk : c->pool) (void)hipFree(blk.second);
     c->pool.clear();
     lpslam_hip_ctx* const pool_of = c->sess_pool;

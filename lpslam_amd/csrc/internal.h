@@ -125,6 +125,10 @@ struct lpslam_hip_ctx {
     // (mask: per-descriptor byte of lpslam_hip_desc_store_mask, valid while has_mask -- a put clears it)
     struct StoredDesc { void* blk = nullptr; size_t cap = 0; int n = 0; void* mask = nullptr; size_t mask_cap = 0; bool has_mask = false; };
     std::map<int, StoredDesc> desc_store;
+    // laser scans kept on the device and the occupancy-grid build (occupancy.hip): state, stream and buffers of their own, every
+    // call under occ_mutex (a build comes from whichever thread exports the map)
+    struct LpOccupancy* occ = nullptr;
+    std::mutex occ_mutex;
     std::vector<void*> pin_free;       // page-locked 8 KB blocks handed to bundle-adjustment objects (lp_pin_alloc / lp_pin_free)
     std::vector<hipStream_t> ba_streams;   // idle high-priority streams of destroyed bundle-adjustment problems (lp_stream_acquire / release)
     // Captured launch chains of the bundle adjustment, shared by every problem that runs on a stream: the graph's kernels read their
@@ -210,6 +214,7 @@ void* lp_pin_big_alloc(lpslam_hip_ctx* c, size_t bytes, size_t* capacity);      
 void lp_pin_big_free(lpslam_hip_ctx* c, void* p, size_t capacity);
 void* lp_pin_alloc(lpslam_hip_ctx* c);          // 8 KB of page-locked host memory, recycled through the context (nullptr on failure)
 void lp_pin_free(lpslam_hip_ctx* c, void* p);
+void lp_occupancy_free(lpslam_hip_ctx* c);      // occupancy.hip: everything the scan store and the builds hold
 int lp_launch_pyramid(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);      // list: n_images slots in any order instead of first ..
 bool lp_flat_priorities();             // several contexts live in the process: new streams at the default priority (api.hip)
 int lp_fe_calibrate(lpslam_hip_ctx* c, int reserve_cus_per_xcd);

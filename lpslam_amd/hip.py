@@ -21,6 +21,7 @@ SIM3_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("meas", "<f8", (8,))])
 SIM3_PAIR_DTYPE = np.dtype([("p1c", "<f8", (3,)), ("p2c", "<f8", (3,)), ("obs1", "<f8", (2,)), ("obs2", "<f8", (2,)),
                             ("inv_sigma2_1", "<f8"), ("inv_sigma2_2", "<f8")])
 PROJ_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("x_right", "<f4"), ("radius", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
+SCAN_POSE_DTYPE = np.dtype([("key", "<i4"), ("pad", "<i4"), ("origin", "<f8", (2,)), ("fwd", "<f8", (2,)), ("left", "<f8", (2,))])
 BA_LOG_DTYPE = np.dtype([("chi2_before", "<f8"), ("chi2_after", "<f8"), ("lambda", "<f8"),
                          ("trials", "<i4"), ("status", "<i4")])
 
@@ -41,7 +42,15 @@ SYMBOLS = [
     "lpslam_hip_ba_local", "lpslam_hip_ba_set_points_fixed", "lpslam_hip_ba_pose_optimize", "lpslam_hip_pose_optimize", "lpslam_hip_ba_reset", "lpslam_hip_ba_set_state", "lpslam_hip_prefetch_begin", "lpslam_hip_prefetch_end", "lpslam_hip_prefetch_join", "lpslam_hip_ba_get", "lpslam_hip_ba_chi2", "lpslam_hip_ba_reduced_buffer",
     "lpslam_hip_ba_step_begin", "lpslam_hip_ba_step_lambda0", "lpslam_hip_ba_step_solve", "lpslam_hip_ba_scalar_buffer", "lpslam_hip_ba_step_end", "lpslam_hip_ba_status",
     "lpslam_hip_sim3_create", "lpslam_hip_sim3_destroy", "lpslam_hip_sim3_optimize", "lpslam_hip_sim3_get", "lpslam_hip_sim3_chi2", "lpslam_hip_sim3_transform_optimize",
+    "lpslam_hip_scan_geometry_put", "lpslam_hip_scan_store_put", "lpslam_hip_scan_store_drop", "lpslam_hip_occupancy_build",
 ]
+
+
+class GridInfo(C.Structure):
+    _fields_ = [("x0", C.c_int64), ("y0", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("rays", C.c_int64), ("cell_visits", C.c_int64)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
 
 
 class LpslamHipError(RuntimeError):
@@ -452,6 +461,40 @@ class Context:
         f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         _check(f(self.h, int(query), _p(kk), 0 if kk is None else len(kk), int(max_dist), float(ratio), int(top_k), _p(ok), _p(ov), C.byref(n)))
         return ok[:n.value].copy(), ov[:n.value].copy()
+
+    def scan_geometry_put(self, cos_sin):
+        """uploads a table of beam directions ((n, 2) float64: cos a, sin a); returns its id"""
+        cs = np.ascontiguousarray(cos_sin, np.float64).reshape(-1, 2)
+        gid = C.c_int32()
+        f = self.lib.lpslam_hip_scan_geometry_put; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        _check(f(self.h, _p(cs), len(cs), C.byref(gid)))
+        return gid.value
+
+    def scan_store_put(self, key, geometry_id, ranges, range_min, range_max, range_threshold):
+        r = np.ascontiguousarray(ranges, np.float32).reshape(-1)
+        f = self.lib.lpslam_hip_scan_store_put
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float]
+        _check(f(self.h, int(key), int(geometry_id), _p(r), len(r), float(range_min), float(range_max), float(range_threshold)))
+
+    def scan_store_drop(self, key):
+        f = self.lib.lpslam_hip_scan_store_drop; f.argtypes = [C.c_void_p, C.c_int32]
+        _check(f(self.h, int(key)))
+
+    def occupancy_build(self, poses, res, max_side, out=None, sizing=False):
+        """poses: SCAN_POSE_DTYPE array.  Returns (grid (height, width) int8 or None when sizing, info dict); `out` (flat int8) is
+        the caller's buffer, its size the capacity"""
+        poses = np.ascontiguousarray(poses, SCAN_POSE_DTYPE)
+        info = GridInfo()
+        f = self.lib.lpslam_hip_occupancy_build
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+        if sizing:
+            _check(f(self.h, _p(poses), len(poses), float(res), int(max_side), None, 0, C.byref(info)))
+            return None, info.as_dict()
+        if out is None:
+            _check(f(self.h, _p(poses), len(poses), float(res), int(max_side), None, 0, C.byref(info)))
+            out = np.empty(max(info.width * info.height, 1), np.int8)
+        _check(f(self.h, _p(poses), len(poses), float(res), int(max_side), _p(out), len(out), C.byref(info)))
+        return out[:info.width * info.height].reshape(info.height, info.width), info.as_dict()
 
     def match_stereo(self, left, right, fxb, baseline):
         _check(self.lib.lpslam_hip_match_stereo(self.h, left, right, float(fxb), float(baseline)))

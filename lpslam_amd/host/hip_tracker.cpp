@@ -1,6 +1,7 @@
 // hip_tracker.cpp -- see hip_tracker.h.  Host-side tracking glue around the HIP C ABI (the arithmetic runs on the GPU).
 #include "hip_tracker.h"
 #include "map_file.h"
+#include "occupancy.h"
 #include <cstring>
 #include <future>
 #include "rectify.h"
@@ -70,6 +71,7 @@ HipVslamTrackerBase::HipVslamTrackerBase()
     o.optional("forwardHighResNav", false); o.optional("loopClosure", true); o.optional("useOpenCL", false);
     o.optional("useCUDA", false); o.optional("relocWithNavigation", true); o.optional("baselineDistThresh", 0.1);
     o.optional("mapFilename", "map.db"); o.optional("maxLaserAge", 1.0);
+    o.optional("occupancyResolution", 0.05); o.optional("occupancyMaxSide", 4096);      // the occupancy grid
     // runtime ORB parameters the reference hard-codes in its generated YAML (:193-198), plus device selection
     o.optional("numLevels", 3); o.optional("scaleFactor", 1.2); o.optional("iniFastThr", 20); o.optional("minFastThr", 7);
     o.optional("device", 0); o.optional("keyframeInterval", 6); o.optional("localWindow", 10); o.optional("asyncMapping", true); o.optional("prefetch", true); o.optional("mapCulling", true); o.optional("mappingReserve", 0);
@@ -90,6 +92,7 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_forwardHighResNav = o.getBool("forwardHighResNav"); m_loopClosure = o.getBool("loopClosure");
     m_useOpenCL = o.getBool("useOpenCL"); m_useCUDA = o.getBool("useCUDA"); m_relocWithNavigation = o.getBool("relocWithNavigation");
     m_baselineDistThresh = o.getDouble("baselineDistThresh"); m_maxLaserAge = o.getDouble("maxLaserAge");
+    m_occResolution = o.getDouble("occupancyResolution"); m_occMaxSide = o.getInteger("occupancyMaxSide");
     m_numLevels = o.getInteger("numLevels"); m_scaleFactor = o.getDouble("scaleFactor");
     m_iniFastThr = o.getInteger("iniFastThr"); m_minFastThr = o.getInteger("minFastThr"); m_device = o.getInteger("device");
     m_keyframeInterval = std::max(1, o.getInteger("keyframeInterval")); m_localWindow = std::max(2, o.getInteger("localWindow"));
@@ -233,6 +236,7 @@ bool HipVslamTrackerBase::startContext(bool stereo)
     warmUpContext(stereo);
     m_stats = Statistics{};
     m_kfs.clear(); m_landmarks.clear(); m_lmIndex.clear(); m_replaced.clear(); m_freshLandmarks.clear(); m_nextLandmarkId = 0; m_refKf = -1; m_segment = 0; m_segmentStart = 0;
+    m_scanGeometries.clear();
     m_state = TrackerState::NotInitialized;
     loadMap();
     m_started = true;
@@ -309,7 +313,7 @@ void HipVslamTrackerBase::warmUpContext(bool stereo)
 
 bool HipVslamTrackerBase::stop()
 {
-    std::scoped_lock lock(m_slamLock);
+    std::scoped_lock lock(m_occMutex, m_slamLock);
     // the map database is written when mapping was on and the session's file was not rejected -- after the pending window's solve
     // has entered the map, so that the file holds what the map holds
     const bool save = m_ctx && m_started && mapDbActive() && m_enableMapping && !m_mapRejected;
@@ -586,6 +590,7 @@ int HipVslamTrackerBase::insertKeyframe(FrameData& f)
     }
     else if (m_loopClosure) storeDescriptors(c, kf);      // without a vocabulary the loop-candidate search matches descriptors: they stay on the device
     m_kfs.push_back(std::move(kf));
+    if (f.scan) storeScan(c, *f.scan);
     if (m_mapCulling) {
         cullLandmarks(c);                                 // [UPSTREAM] mapping_module: remove_redundant_landmarks once the new keyframe is stored
         for (size_t i = 0; i < f.landmark.size(); ++i) if (f.landmark[i] >= 0 && !m_landmarks.count(f.landmark[i])) f.landmark[i] = -1;
@@ -934,6 +939,7 @@ void HipVslamTrackerBase::cullKeyframes(int cur_kf)
         }
         kf.erased = true;
         (void)lpslam_hip_desc_store_drop(m_ctx, k); kf.desc_on_device = false;
+        if (kf.has_scan) { (void)lpslam_hip_scan_store_drop(m_ctx, k); kf.has_scan = false; }
         kf.kpts.clear(); kf.kpts.shrink_to_fit(); kf.desc.clear(); kf.desc.shrink_to_fit(); kf.x_right.clear(); kf.depth.clear(); kf.landmark.clear(); kf.node.clear(); kf.bow.clear();
         m_bowDb.remove(k);
         ++m_stats.culled_keyframes;
@@ -2033,7 +2039,8 @@ void HipVslamTrackerBase::stopPrefetchThread()
     m_pfQuit = false;
 }
 
-TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry& cam, bool stereo, const std::optional<GlobalStateInTime>& navOdom)
+TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry& cam, bool stereo, const std::optional<GlobalStateInTime>& navOdom,
+                                                                std::optional<ScanAttach> scan)
 {
     ProcessImageResult res;
     std::scoped_lock lock(m_slamLock);
@@ -2096,6 +2103,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     if (stereo) { cur.x_right.assign(v_xr, v_xr + n); cur.depth.assign(v_dep, v_dep + n); }
     else { cur.x_right.assign((size_t)n, -1.0f); cur.depth.assign((size_t)n, -1.0f); }
     cur.landmark.assign((size_t)n, -1);
+    cur.scan = std::move(scan);
     dev_lap(m_stats.t_dev_get);
     ++m_imageTracked; ++m_stats.frames;
     // The next frame's upload + front end: a helper thread stages and enqueues it (0.2 ms of host time at 1280x720 stereo, mostly the
@@ -2256,7 +2264,153 @@ LpSlamStatus HipVslamTrackerBase::getSlamStatus()
 TrackerBase::ProcessImageResult HipStereoTracker::processImage(CameraQueueEntry& cam, std::optional<GlobalStateInTime> navResultOdom, std::optional<GlobalStateInTime>,
                                                                std::vector<SensorQueueEntry> const&)
 {
-    return trackFrame(cam, true, navResultOdom);
+    return trackFrame(cam, true, navResultOdom, scanForFrame(cam));      // (the transformation callback runs outside m_slamLock)
+}
+
+// ---- laser scans and the occupancy grid ----------------------------------------------------------------------------------------
+
+void HipStereoTracker::addLaserScan(GlobalStateInTime origin, float* ranges, size_t n, float range_min, float range_max, float angle_min, float,
+                                    float increment, float range_threshold)
+{
+    bufferLaserScan(ranges, n, range_min, range_max, angle_min, increment, range_threshold, origin.first.ros_timestamp);
+}
+
+void HipVslamTrackerBase::bufferLaserScan(float* ranges, size_t n, float range_min, float range_max, float angle_min, float increment,
+                                          float range_threshold, const std::optional<LpSlamROSTimestamp>& ros)
+{
+    if (!ranges || n == 0 || n > (1u << 20)) return;
+    auto s = std::make_shared<LaserScan>();
+    s->ranges.assign(ranges, ranges + n);
+    s->range_min = range_min; s->range_max = range_max; s->angle_min = angle_min; s->increment = increment; s->range_threshold = range_threshold;
+    s->ros = ros;
+    std::scoped_lock l(m_laserMutex);
+    m_laserBuffer = std::move(s);                     // one slot: the latest scan wins
+}
+
+// the buffered scan when both it and the frame have ROS times less than maxLaserAge apart (reference :232-262), with the laser's pose
+// in the camera's lpslam frame from RequestNavTransformation(Laser -> Camera) at the frame's time, or the identity (:263-285)
+std::optional<HipVslamTrackerBase::ScanAttach> HipVslamTrackerBase::scanForFrame(const CameraQueueEntry& cam)
+{
+    ScanAttach a;
+    RequestNavTransformationCallback_t cb;
+    void* ud;
+    {
+        std::scoped_lock l(m_laserMutex);
+        if (!m_laserBuffer || !m_laserBuffer->ros || !cam.ros_timestamp) return std::nullopt;
+        const LpSlamROSTimestamp& lt = *m_laserBuffer->ros;
+        const LpSlamROSTimestamp& it = *cam.ros_timestamp;
+        const double dt = double((int64_t)lt.seconds - (int64_t)it.seconds) + double(lt.nanoseconds - it.nanoseconds) * 1e-9;
+        if (!(std::abs(dt) < m_maxLaserAge)) return std::nullopt;
+        a.scan = m_laserBuffer;
+        cb = m_navTransform; ud = m_navTransformData;
+    }
+    if (cb) {
+        const LpSlamRequestNavTransformation t = cb(*cam.ros_timestamp, LpSlamNavDataFrame_Laser, LpSlamNavDataFrame_Camera, ud);
+        laserToCamera(t, a.R_cl, a.t_cl);
+    }
+    return a;
+}
+
+void HipVslamTrackerBase::storeScan(int key, const ScanAttach& a)
+{
+    const LaserScan& s = *a.scan;
+    const int n = (int)s.ranges.size();
+    const auto gkey = std::make_pair(n, std::make_pair(s.angle_min, s.increment));
+    auto it = m_scanGeometries.find(gkey);
+    if (it == m_scanGeometries.end()) {
+        std::vector<double> cs(2 * (size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const double ang = (double)s.angle_min + i * (double)s.increment;
+            cs[2 * (size_t)i] = std::cos(ang); cs[2 * (size_t)i + 1] = std::sin(ang);
+        }
+        int32_t id = -1;
+        if (lpslam_hip_scan_geometry_put(m_ctx, cs.data(), n, &id) != LPSLAM_HIP_OK) { logMessage(LpSlamLogLevel_Error, std::string("laser scan geometry: ") + lpslam_hip_last_error()); return; }
+        it = m_scanGeometries.emplace(gkey, id).first;
+    }
+    if (lpslam_hip_scan_store_put(m_ctx, key, it->second, s.ranges.data(), n, s.range_min, s.range_max, s.range_threshold) != LPSLAM_HIP_OK) {
+        logMessage(LpSlamLogLevel_Error, std::string("laser scan store: ") + lpslam_hip_last_error());
+        return;
+    }
+    Keyframe& kf = m_kfs[(size_t)key];
+    kf.has_scan = true;
+    std::copy(a.R_cl, a.R_cl + 9, kf.R_cl); std::copy(a.t_cl, a.t_cl + 3, kf.t_cl);
+    kf.scan_ros = s.ros.value_or(LpSlamROSTimestamp{});
+}
+
+std::vector<lpslam_hip_scan_pose> HipVslamTrackerBase::scanPoses(std::vector<LpSlamROSTimestamp>* stamps)
+{
+    std::vector<lpslam_hip_scan_pose> poses;
+    for (size_t k = 0; k < m_kfs.size(); ++k) {
+        const Keyframe& kf = m_kfs[k];
+        if (kf.erased || !kf.has_scan) continue;
+        lpslam_hip_scan_pose p{};
+        p.key = (int32_t)k;
+        const Mat3 R = quatToRot(kf.pose.q);
+        scanPose(R.m, kf.pose.t, kf.R_cl, kf.t_cl, p.origin, p.fwd, p.left);
+        poses.push_back(p);
+        if (stamps) stamps->push_back(kf.scan_ros);
+    }
+    return poses;
+}
+
+std::vector<std::pair<LpSlamROSTimestamp, lpslam_hip_scan_pose>> HipVslamTrackerBase::occupancyScans()
+{
+    std::scoped_lock lock(m_slamLock);
+    std::vector<LpSlamROSTimestamp> stamps;
+    const auto poses = scanPoses(&stamps);
+    std::vector<std::pair<LpSlamROSTimestamp, lpslam_hip_scan_pose>> v;
+    for (size_t i = 0; i < poses.size(); ++i) v.emplace_back(stamps[i], poses[i]);
+    return v;
+}
+
+// Every live keyframe with a scan, at its CURRENT pose: the keys and poses are copied under m_slamLock, the device work runs without
+// it on the context's occupancy stream.  A keyframe culled between the copy and the build makes the build fail (unknown key): then
+// the copy is taken again.
+bool HipVslamTrackerBase::occupancyBuild(int8_t* out, std::size_t capacity, lpslam_hip_grid_info& info)
+{
+    info = lpslam_hip_grid_info{};
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        std::vector<lpslam_hip_scan_pose> poses;
+        lpslam_hip_ctx* ctx;
+        {
+            std::scoped_lock lock(m_slamLock);
+            ctx = m_ctx;
+            if (!ctx) return false;
+            poses = scanPoses(nullptr);
+        }
+        if (poses.empty()) return false;
+        const int rc = lpslam_hip_occupancy_build(ctx, poses.data(), (int32_t)poses.size(), m_occResolution, m_occMaxSide, out, (int64_t)capacity, &info);
+        if (rc == LPSLAM_HIP_OK) return true;
+        std::string err = lpslam_hip_last_error();
+        if (rc != LPSLAM_HIP_ERR_INVALID || err.find("no scan stored") == std::string::npos) {
+            logMessage(LpSlamLogLevel_Error, "occupancy map: " + err);
+            return false;
+        }
+    }
+    return false;
+}
+
+std::optional<unsigned long> HipStereoTracker::mappingGetMapRawSize()
+{
+    std::scoped_lock lock(m_occMutex);
+    lpslam_hip_grid_info info;
+    if (!occupancyBuild(nullptr, 0, info)) return 0ul;
+    return (unsigned long)info.width * (unsigned long)info.height;
+}
+
+std::optional<LpMapInfo> HipStereoTracker::mappingGetMapRaw(int8_t* map, std::size_t capacity)
+{
+    std::scoped_lock lock(m_occMutex);
+    const auto t0 = std::chrono::steady_clock::now();
+    lpslam_hip_grid_info info;
+    if (!map || !occupancyBuild(map, capacity, info)) return LpMapInfo{};
+    const double ms = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    logMessage(LpSlamLogLevel_Info, "Occupancy map generation took " + std::to_string(ms) + " ms");      // (reference :386)
+    LpMapInfo m{};
+    m.x_cell_size = m.y_cell_size = (float)m_occResolution;
+    m.x_cell_count = (uint32_t)info.width; m.y_cell_count = (uint32_t)info.height;
+    m.x_origin = (float)((double)info.x0 * m_occResolution); m.y_origin = (float)((double)info.y0 * m_occResolution);
+    return m;
 }
 bool HipStereoTracker::start(SensorQueue&) { return startContext(true); }
 

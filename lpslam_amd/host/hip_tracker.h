@@ -38,11 +38,21 @@ public:
     LpSlamStatus getSlamStatus();
 
     TrackerState state() const { return m_state; }
+    void addRequestNavTransformationCallback(RequestNavTransformationCallback_t cb, void* user) override { std::scoped_lock l(m_laserMutex); m_navTransform = cb; m_navTransformData = user; }
     std::array<double, 16> currentCamPose();          // T_cw, row-major 4x4 (get_current_cam_pose)
 
 protected:
     struct Pose { double q[4] = {1, 0, 0, 0}; double t[3] = {0, 0, 0}; };   // world -> camera
+    // laser scans (src/Trackers/OpenVSLAMStereoTracker.cpp:232-285,344-371): the latest scan waits in a one-slot buffer; a frame
+    // whose ROS time is within maxLaserAge of it takes it along, with the laser's pose in the camera's lpslam frame
+    struct LaserScan { std::vector<float> ranges; float range_min = 0, range_max = 0, angle_min = 0, increment = 0, range_threshold = 0; std::optional<LpSlamROSTimestamp> ros; };
+    struct ScanAttach { std::shared_ptr<const LaserScan> scan; double R_cl[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}; double t_cl[3] = {0, 0, 0}; };
+public:
+    // test hook: the ROS time of every scan the grid is built from and the pose it is built at
+    std::vector<std::pair<LpSlamROSTimestamp, lpslam_hip_scan_pose>> occupancyScans();
+protected:
     struct FrameData {
+        std::optional<ScanAttach> scan;               // the laser scan attached to this frame (stereo only)
         std::vector<lpslam_hip_keypoint> kpts;
         std::vector<uint8_t> desc;                    // 32 bytes per keypoint
         std::vector<float> x_right, depth;
@@ -62,6 +72,9 @@ protected:
         bool desc_on_device = false;                  // lpslam_hip_desc_store_put succeeded: the loop-candidate search may name it in a batched comparison
         BowVector bow;                                // with a vocabulary: the keyframe's BoW vector and, per keypoint, the tree node it falls under
         std::vector<int32_t> node;
+        bool has_scan = false;                        // its scan is in the context's scan store under the keyframe index
+        double R_cl[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t_cl[3] = {0, 0, 0};      // laser pose in the camera's lpslam frame
+        LpSlamROSTimestamp scan_ros{};
     };
     struct Landmark {
         double p[3]; 
@@ -91,7 +104,8 @@ protected:
 
     bool startContext(bool stereo);
     void warmUpContext(bool stereo);                  // one frame's worth of every per-frame call on blank images: lazily created resources exist before the first frame
-    ProcessImageResult trackFrame(CameraQueueEntry& cam, bool stereo, const std::optional<GlobalStateInTime>& navOdom);
+    ProcessImageResult trackFrame(CameraQueueEntry& cam, bool stereo, const std::optional<GlobalStateInTime>& navOdom,
+                                  std::optional<ScanAttach> scan = std::nullopt);
     TrackerResult createTrackerResult(const Pose& pose_cw, TimeStamp timestamp) const;
     bool initializeMap(FrameData& f, const Pose& at);
     bool poseFromMatches(FrameData& cur, const std::vector<int>& cur_idx, const std::vector<int>& lm_ids, const Pose& init, int& n_inliers, int min_inliers = 10);
@@ -153,6 +167,20 @@ protected:
     bool m_relocByRank = false;                       // after a load, until the first relocalisation: candidates by lpslam_hip_rank_stored over all keyframes
     bool m_lostSinceUnset = false;
     int sharedRefKf(const FrameData& f) const;          // localisation only: the keyframe that sees most of the frame's landmarks (-1: none)                    // the loss started before the first frame (a loaded map): its first frame starts the clock
+
+    // occupancy grid: scans in, the keyframes' scans into the context's store, the grid out (any thread; device work without m_slamLock)
+    void bufferLaserScan(float* ranges, size_t n, float range_min, float range_max, float angle_min, float increment, float range_threshold,
+                         const std::optional<LpSlamROSTimestamp>& ros);
+    std::optional<ScanAttach> scanForFrame(const CameraQueueEntry& cam);
+    void storeScan(int key, const ScanAttach& a);     // m_slamLock held
+    bool occupancyBuild(int8_t* out, std::size_t capacity, lpslam_hip_grid_info& info);
+    std::vector<lpslam_hip_scan_pose> scanPoses(std::vector<LpSlamROSTimestamp>* stamps);      // m_slamLock held
+    std::mutex m_laserMutex;                          // the scan buffer and the transformation callback
+    std::mutex m_occMutex;                            // an export in progress (taken before m_slamLock; stop() waits for it before the context goes)
+    std::shared_ptr<const LaserScan> m_laserBuffer;
+    RequestNavTransformationCallback_t m_navTransform = nullptr; void* m_navTransformData = nullptr;
+    std::map<std::pair<int, std::pair<float, float>>, int> m_scanGeometries;      // (beams, (angle_min, increment)) -> geometry id of the context
+    double m_occResolution = 0.05; int m_occMaxSide = 4096;
 
     // configuration (names as in the reference tracker)
     bool m_useLiveView = false, m_useMapDb = true, m_forwardNavState = true, m_forwardImu = true, m_emitMap = false;
@@ -264,6 +292,10 @@ public:
                                     std::vector<SensorQueueEntry> const& sensorValues = {}) override;
     bool start(SensorQueue&) override;
     std::string type() override { return "VSLAMStereo"; }       // src/Trackers/OpenVSLAMStereoTracker.h:35-39
+    void addLaserScan(GlobalStateInTime origin, float* ranges, size_t n, float range_min, float range_max, float angle_min, float angle_max,
+                      float increment, float range_threshold) override;
+    std::optional<unsigned long> mappingGetMapRawSize() override;
+    std::optional<LpMapInfo> mappingGetMapRaw(int8_t* map, std::size_t capacity) override;
 };
 
 class HipMonoTracker : public HipVslamTrackerBase {

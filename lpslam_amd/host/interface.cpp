@@ -6,6 +6,7 @@
 #include "slam_manager.h"
 #include "jpeg.h"
 #include "map_file.h"
+#include "occupancy.h"
 #include <cstring>
 #include <vector>
 
@@ -64,9 +65,11 @@ void LpSlamManager::setRecordImages(bool) {}
 void LpSlamManager::start() { m_impl->start(); }
 void LpSlamManager::stop() { m_impl->stop(); }
 LpSlamStatus LpSlamManager::getSlamStatus() { return m_impl->getSlamStatus(); }
-void LpSlamManager::mappingAddLaserScan(LpSlamGlobalStateInTime, float*, size_t, float, float, float, float, float, float) {}
-unsigned long LpSlamManager::mappingGetMapRawSize() { return 0; }
-LpMapInfo LpSlamManager::mappingGetMapRaw(int8_t*, std::size_t) { return LpMapInfo{}; }
+void LpSlamManager::mappingAddLaserScan(LpSlamGlobalStateInTime o, float* r, size_t n, float r0, float r1, float a0, float a1, float inc, float thr) {
+    m_impl->mappingAddLaserScan(LpSlam::conversion::gsInTimeInterfaceToInternal(o), r, n, r0, r1, a0, a1, inc, thr);
+}
+unsigned long LpSlamManager::mappingGetMapRawSize() { return m_impl->mappingGetMapRawSize(); }
+LpMapInfo LpSlamManager::mappingGetMapRaw(int8_t* map, std::size_t capacity) { return m_impl->mappingGetMapRaw(map, capacity); }
 std::size_t LpSlamManager::mappingGetFeatures(LpSlamMapBoundary b, LpSlamFeatureEntry* e, std::size_t n, LpSlamMatrix9x9 t) { return m_impl->mappingGetFeatures(b, e, n, t); }
 std::size_t LpSlamManager::mappingGetFeaturesCount(LpSlamMapBoundary b) { return m_impl->mappingGetFeaturesCount(b); }
 bool LpSlamManager::mappingSetMode(bool e) { return m_impl->mappingSetMode(e); }
@@ -77,7 +80,7 @@ bool LpSlamManager::mappingExportCSV(const char* f) { return m_impl->mappingExpo
 extern "C" {
 #define LPS_API __attribute__((visibility("default")))
 typedef void (*lpslam_c_reconstruction_cb)(const LpSlamGlobalStateInTime* state, void* user);
-struct lpslam_c_manager { LpSlamManager mgr; lpslam_c_reconstruction_cb cb = nullptr; void* user = nullptr; std::atomic<uint64_t> n_results{0}, n_valid{0}; };
+struct lpslam_c_manager { LpSlamManager mgr; lpslam_c_reconstruction_cb cb = nullptr; void* user = nullptr; std::atomic<uint64_t> n_results{0}, n_valid{0}; LpSlamGlobalState laser_to_camera{}; };
 static void c_trampoline(LpSlamGlobalStateInTime const& s, void* p) { auto* m = static_cast<lpslam_c_manager*>(p); if (m->cb) m->cb(&s, m->user); }
 
 LPS_API lpslam_c_manager* lpslam_manager_create(void) { return new lpslam_c_manager(); }
@@ -149,6 +152,41 @@ LPS_API int lpslam_map_file_rewrite(const char* in, const char* out, char* why, 
     const bool ok = in && out && LpSlam::read_map_file(in, d, &err) && LpSlam::write_map_file(out, d, &err);
     if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
     return ok ? 1 : 0;
+}
+// laser scans and the occupancy grid.  ros_ts: the scan's ROS time as the frames of lpslam_manager_add_stereo_image carry it.
+LPS_API void lpslam_manager_add_laser_scan(lpslam_c_manager* m, const LpSlamROSTimestamp* ros_ts, float* ranges, size_t n, float range_min,
+                                           float range_max, float angle_min, float angle_max, float increment, float range_threshold) {
+    LpSlamGlobalStateInTime o{};
+    if (ros_ts) { o.has_ros_timestamp = 1; o.ros_timestamp = *ros_ts; }
+    o.state.orientation.w = 1.0;
+    m->mgr.mappingAddLaserScan(o, ranges, n, range_min, range_max, angle_min, angle_max, increment, range_threshold);
+}
+// a compiled RequestNavTransformationCallback_t that answers Laser -> Camera with the given state (anything else: invalid)
+static LpSlamRequestNavTransformation laser_transform(LpSlamROSTimestamp, LpSlamNavDataFrame from, LpSlamNavDataFrame to, void* p) {
+    LpSlamRequestNavTransformation r{};
+    if (from == LpSlamNavDataFrame_Laser && to == LpSlamNavDataFrame_Camera) r = static_cast<lpslam_c_manager*>(p)->laser_to_camera;
+    return r;
+}
+LPS_API void lpslam_manager_provide_laser_transform(lpslam_c_manager* m, const LpSlamGlobalState* laser_to_camera) {
+    m->laser_to_camera = *laser_to_camera;
+    m->mgr.addRequestNavTransformation(laser_transform, m);
+}
+LPS_API unsigned long lpslam_manager_map_raw_size(lpslam_c_manager* m) { return m->mgr.mappingGetMapRawSize(); }
+LPS_API void lpslam_manager_map_raw(lpslam_c_manager* m, int8_t* map, size_t capacity, LpMapInfo* info) { *info = m->mgr.mappingGetMapRaw(map, capacity); }
+// test hook: the scans the grid is built from (one per keyframe with a scan): ROS time and the pose the grid uses (key, origin, fwd,
+// left); returns their number, copies at most cap
+LPS_API size_t lpslam_manager_map_scans(lpslam_c_manager* m, LpSlamROSTimestamp* stamps, lpslam_hip_scan_pose* poses, size_t cap) {
+    LpSlam::SlamManager* impl = *reinterpret_cast<LpSlam::SlamManager**>(&m->mgr);
+    const auto v = impl ? impl->occupancyScans() : std::vector<std::pair<LpSlamROSTimestamp, lpslam_hip_scan_pose>>();
+    for (size_t i = 0; i < v.size() && i < cap; ++i) { stamps[i] = v[i].first; poses[i] = v[i].second; }
+    return v.size();
+}
+// the scan pose of a keyframe (CPU): T_cw row-major 4x4 (optical axes) and the laser -> camera state; out = origin[2], fwd[2], left[2]
+LPS_API void lpslam_occupancy_scan_pose(const double* T_cw, const LpSlamGlobalState* laser_to_camera, double* out) {
+    const double R[9] = {T_cw[0], T_cw[1], T_cw[2], T_cw[4], T_cw[5], T_cw[6], T_cw[8], T_cw[9], T_cw[10]}, t[3] = {T_cw[3], T_cw[7], T_cw[11]};
+    double Rcl[9], tcl[3];
+    LpSlam::laserToCamera(*laser_to_camera, Rcl, tcl);
+    LpSlam::scanPose(R, t, Rcl, tcl, out, out + 2, out + 4);
 }
 // interface.type_conversion of the reference's tests (src/test/InterfaceTest.cpp:14-33): POD -> internal -> POD
 LPS_API void lpslam_roundtrip_state(const LpSlamGlobalStateInTime* in, LpSlamGlobalStateInTime* out) {

@@ -510,4 +510,24 @@ bool SlamManager::mappingSetMode(bool enable) { return m_vslamTracker ? m_vslamT
 bool SlamManager::mappingSetFilename(std::string const& f) { return m_vslamTracker ? m_vslamTracker->mappingSetFilename(f) : false; }
 bool SlamManager::mappingExportCSV(std::string const& f) { return m_vslamTracker ? m_vslamTracker->mappingExportCSV(f) : false; }
 
+void SlamManager::mappingAddLaserScan(GlobalStateInTime origin, float* ranges, size_t n, float range_min, float range_max, float angle_min,
+                                      float angle_max, float increment, float range_threshold)
+{
+    for (auto& t : m_trackers) t->addLaserScan(origin, ranges, n, range_min, range_max, angle_min, angle_max, increment, range_threshold);
+}
+
+std::vector<std::pair<LpSlamROSTimestamp, lpslam_hip_scan_pose>> SlamManager::occupancyScans() { return m_vslamTracker ? m_vslamTracker->occupancyScans() : std::vector<std::pair<LpSlamROSTimestamp, lpslam_hip_scan_pose>>(); }
+
+unsigned long SlamManager::mappingGetMapRawSize()
+{
+    for (auto& t : m_trackers) if (auto r = t->mappingGetMapRawSize()) return *r;
+    return 0;
+}
+
+LpMapInfo SlamManager::mappingGetMapRaw(int8_t* map, std::size_t capacity)
+{
+    for (auto& t : m_trackers) if (auto r = t->mappingGetMapRaw(map, capacity)) return *r;
+    return LpMapInfo{};
+}
+
 }  // namespace LpSlam

@@ -43,8 +43,14 @@ public:
     bool mappingSetMode(bool enable);
     bool mappingSetFilename(std::string const& f);
     bool mappingExportCSV(std::string const& f);
+    // laser scans in, occupancy grid out (src/Manager/SlamManager.cpp:330-351,371-391): forwarded to every tracker
+    void mappingAddLaserScan(GlobalStateInTime origin, float* ranges, size_t n, float range_min, float range_max, float angle_min,
+                             float angle_max, float increment, float range_threshold);
+    unsigned long mappingGetMapRawSize();
+    LpMapInfo mappingGetMapRaw(int8_t* map, std::size_t capacity);
 
     // test hooks
+    std::vector<std::pair<LpSlamROSTimestamp, lpslam_hip_scan_pose>> occupancyScans();
     size_t trackerCount() const { return m_trackers.size(); }
     CameraRegistry& cameraRegistry() { return m_camRegistry; }
     uint64_t framesProcessed() const { return m_framesProcessed.load(); }

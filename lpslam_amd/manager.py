@@ -48,6 +48,14 @@ class FeatureEntry(C.Structure):
     _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float)]
 
 
+class MapInfo(C.Structure):
+    _fields_ = [("x_cell_size", C.c_float), ("y_cell_size", C.c_float), ("x_cell_count", C.c_uint32), ("y_cell_count", C.c_uint32),
+                ("x_origin", C.c_float), ("y_origin", C.c_float)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 RECON_CB = C.CFUNCTYPE(None, C.POINTER(GlobalStateInTime), C.c_void_p)
 IMAGE_CB = C.CFUNCTYPE(None, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint8), ImageDescription, C.c_void_p)
 NAV_CB = C.CFUNCTYPE(C.c_int, ROSTimestamp, C.POINTER(GlobalStateInTime), C.POINTER(GlobalStateInTime), C.c_void_p)
@@ -261,6 +269,75 @@ class Manager:
         """mappingSetFilename: the map database file (used when the tracker's useMapDb is on); call before start()"""
         f = self.lib.lpslam_manager_mapping_set_filename; f.argtypes = [C.c_void_p, C.c_char_p]; f.restype = C.c_int
         return bool(f(self.h, str(path).encode()))
+
+    def add_laser_scan(self, ros_ts_ns, ranges, range_min, range_max, angle_min, angle_max, increment, range_threshold):
+        """mappingAddLaserScan; the scan's ROS time is stamped as add_stereo stamps a frame's (ros_ts_ns in nanoseconds)"""
+        import numpy as np
+        r = np.ascontiguousarray(ranges, np.float32)
+        ts = ROSTimestamp(int(ros_ts_ns // 10**9), int(ros_ts_ns))
+        f = self.lib.lpslam_manager_add_laser_scan
+        f.argtypes = [C.c_void_p, C.POINTER(ROSTimestamp), C.c_void_p, C.c_size_t] + [C.c_float] * 6
+        f(self.h, C.byref(ts), r.ctypes.data, len(r), float(range_min), float(range_max), float(angle_min), float(angle_max),
+          float(increment), float(range_threshold))
+
+    def provide_laser_transform(self, R, t):
+        """answers RequestNavTransformation(Laser -> Camera) with the laser's pose in the camera's lpslam frame (rotation matrix R,
+        translation t); call before start()"""
+        f = self.lib.lpslam_manager_provide_laser_transform; f.argtypes = [C.c_void_p, C.POINTER(GlobalState)]
+        self._laser_state = laser_state(R, t)
+        f(self.h, C.byref(self._laser_state))
+
+    def map_raw_size(self):
+        f = self.lib.lpslam_manager_map_raw_size; f.argtypes = [C.c_void_p]; f.restype = C.c_ulong
+        return int(f(self.h))
+
+    def map_scans(self):
+        """test hook: the scans the grid is built from: (ROS time nanoseconds field, origin, fwd, left) each"""
+        import numpy as np
+        f = self.lib.lpslam_manager_map_scans; f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]; f.restype = C.c_size_t
+        n = f(self.h, None, None, 0)
+        st = (ROSTimestamp * max(n, 1))(); ps = np.zeros((max(n, 1), 7), np.float64)      # lpslam_hip_scan_pose: key, pad, 6 doubles
+        n = min(n, f(self.h, st, ps.ctypes.data, n))
+        return [(st[i].nanoseconds, ps[i, 1:3].copy(), ps[i, 3:5].copy(), ps[i, 5:7].copy()) for i in range(n)]
+
+    def map_raw(self, capacity=None):
+        """mappingGetMapRaw: (LpMapInfo fields, np.int8 grid of shape (height, width)); capacity: the buffer's size (default: the
+        current map_raw_size())"""
+        import numpy as np
+        cap = self.map_raw_size() if capacity is None else int(capacity)
+        buf = np.full(max(cap, 1), -1, np.int8)
+        info = MapInfo()
+        f = self.lib.lpslam_manager_map_raw; f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(MapInfo)]
+        f(self.h, buf.ctypes.data, cap, C.byref(info))
+        w, h = info.x_cell_count, info.y_cell_count
+        return info.as_dict(), buf[:w * h].reshape(h, w)
+
+
+def laser_state(R, t):
+    """LpSlamGlobalState of a rotation matrix and a translation (lpslam axes)"""
+    import numpy as np
+    R = np.asarray(R, np.float64)
+    w = np.sqrt(max(0.0, 1.0 + R[0, 0] + R[1, 1] + R[2, 2])) / 2
+    x = np.copysign(np.sqrt(max(0.0, 1.0 + R[0, 0] - R[1, 1] - R[2, 2])) / 2, R[2, 1] - R[1, 2])
+    y = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] + R[1, 1] - R[2, 2])) / 2, R[0, 2] - R[2, 0])
+    z = np.copysign(np.sqrt(max(0.0, 1.0 - R[0, 0] - R[1, 1] + R[2, 2])) / 2, R[1, 0] - R[0, 1])
+    s = GlobalState()
+    s.position.x, s.position.y, s.position.z = (float(v) for v in t)
+    s.orientation.w, s.orientation.x, s.orientation.y, s.orientation.z = w, x, y, z
+    s.valid = True
+    return s
+
+
+def scan_pose(T_cw, state):
+    """the map-plane pose of a keyframe's scan (host/occupancy.h), CPU only: T_cw 4x4 (optical axes), state the laser -> camera
+    LpSlamGlobalState (GlobalState).  Returns (origin, fwd, left), each (y, z) of the world's lpslam axes"""
+    import numpy as np
+    lib = load()
+    T = np.ascontiguousarray(T_cw, np.float64).reshape(16)
+    out = np.zeros(6, np.float64)
+    f = lib.lpslam_occupancy_scan_pose; f.argtypes = [C.c_void_p, C.POINTER(GlobalState), C.c_void_p]
+    f(T.ctypes.data, C.byref(state), out.ctypes.data)
+    return out[:2].copy(), out[2:4].copy(), out[4:].copy()
 
 
 def map_file_info(path):
