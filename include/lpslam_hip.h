@@ -590,6 +590,22 @@ int lpslam_hip_scan_store_drop(lpslam_hip_ctx* ctx, int32_t key);
 int lpslam_hip_occupancy_build(lpslam_hip_ctx* ctx, const lpslam_hip_scan_pose* poses, int32_t n, double res, int32_t max_side,
                                int8_t* out, int64_t capacity, lpslam_hip_grid_info* info);
 
+/* ---- baseline JPEG encoder (the recorder's cv::imencode(".jpg"), /root/reference/src/Manager/RecordEngine.cpp:93) ----------------
+ * A standalone object (no lpslam_hip_ctx: the reference records without a tracker) with its own stream and buffers, sized at creation
+ * for max_images images of at most max_width x max_height samples.  One encode call is one launch chain and one wait for the whole
+ * batch (both eyes of a stereo frame).  The output of every image is byte for byte what the host encoder writes
+ * (LpSlam::encode_jpeg_gray, lpslam_jpeg_encode_gray): one grey component, baseline, Annex K tables scaled for quality, libjpeg's islow
+ * FDCT and rounding, no restart markers.  Calls on one encoder are serialised. */
+typedef struct lpslam_hip_jpeg lpslam_hip_jpeg;
+int lpslam_hip_jpeg_create(int32_t max_width, int32_t max_height, int32_t max_images, lpslam_hip_jpeg** out);
+void lpslam_hip_jpeg_destroy(lpslam_hip_jpeg* enc);
+/* n images (host samples, row stride in bytes) -> n complete JPEG files in outs[i] (capacity caps[i]).  sizes[i] is always set to the
+ * exact length.  If any caps[i] is too small: LPSLAM_HIP_ERR_INVALID, and no output buffer is written.  n outside 1 .. max_images, an
+ * image larger than the encoder's maximum, a stride below the width or a quality outside 1 .. 100: LPSLAM_HIP_ERR_INVALID. */
+int lpslam_hip_jpeg_encode(lpslam_hip_jpeg* enc, int32_t n, const uint8_t* const* pixels, const int32_t* widths,
+                           const int32_t* heights, const int32_t* strides, int32_t quality,
+                           uint8_t* const* outs, const int64_t* caps, int64_t* sizes);
+
 #ifdef __cplusplus
 }
 #endif

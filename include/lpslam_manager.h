@@ -4,7 +4,8 @@
  * Same class name, method names, signatures and single data member as the reference's exported class
  * (/root/reference/src/Interface/LpSlamManager.h:17-121, C++ ABI, pimpl), so existing client code compiles unchanged;
  * behind it sits LpSlam::SlamManager of lpslam_amd/host/ whose trackers run on the MI355X through include/lpslam_hip.h.
- * Methods that belong to subsystems outside the accelerated path (file/replay sources, recording, live view) keep their signatures and behave as the reference does when the backing plugin is absent: they return
+ * Recording (setRecord, setRecordImages, setWriteImageFiles) writes the reference's recording file ("Recording file").
+ * Methods that belong to subsystems outside the accelerated path (file sources, live view) keep their signatures and behave as the reference does when the backing plugin is absent: they return
  * false / 0 / do nothing (cf. src/Manager/SlamManager.cpp:1311-1312,1368-1395).
  */
 #ifndef LPSLAM_AMD_MANAGER_H

@@ -43,6 +43,7 @@ SYMBOLS = [
     "lpslam_hip_ba_step_begin", "lpslam_hip_ba_step_lambda0", "lpslam_hip_ba_step_solve", "lpslam_hip_ba_scalar_buffer", "lpslam_hip_ba_step_end", "lpslam_hip_ba_status",
     "lpslam_hip_sim3_create", "lpslam_hip_sim3_destroy", "lpslam_hip_sim3_optimize", "lpslam_hip_sim3_get", "lpslam_hip_sim3_chi2", "lpslam_hip_sim3_transform_optimize",
     "lpslam_hip_scan_geometry_put", "lpslam_hip_scan_store_put", "lpslam_hip_scan_store_drop", "lpslam_hip_occupancy_build",
+    "lpslam_hip_jpeg_create", "lpslam_hip_jpeg_destroy", "lpslam_hip_jpeg_encode",
 ]
 
 
@@ -921,3 +922,52 @@ def pose_optimize(ctx, pose7, points, obs, cam, robust_kernel=True):
     out = np.zeros(max(len(o), 1), np.uint8); n = C.c_int32()
     _check(ctx.lib.lpslam_hip_pose_optimize(ctx.h, _p(pose), _p(pts), len(pts), _p(o), len(o), C.byref(c), _p(out), C.byref(n)))
     return pose, out[:len(o)].astype(bool), n.value
+
+
+class JpegEncoder:
+    """Baseline JPEG encoder on the device (lpslam_hip_jpeg_*): grey images in, the host encoder's streams out, byte for byte."""
+
+    def __init__(self, max_width, max_height, max_images=2):
+        self.lib = load()
+        self.lib.lpslam_hip_jpeg_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        self.lib.lpslam_hip_jpeg_destroy.argtypes = [C.c_void_p]
+        self.lib.lpslam_hip_jpeg_encode.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]
+        h = C.c_void_p()
+        _check(self.lib.lpslam_hip_jpeg_create(int(max_width), int(max_height), int(max_images), C.byref(h)))
+        self.h = h
+        self.max_width, self.max_height, self.max_images = int(max_width), int(max_height), int(max_images)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lpslam_hip_jpeg_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def encode_raw(self, images, quality=95, caps=None):
+        """one call for the list of 2-D uint8 images (row strides taken from the arrays): returns (status, sizes, outputs); outputs are
+        uint8 arrays of capacity caps[i] (default: enough), to be cut to sizes[i] when status is 0"""
+        n = len(images)
+        imgs = [np.asarray(im) for im in images]
+        if caps is None:
+            caps = [1024 + 2 * im.size + 512 for im in imgs]
+        outs = [np.full(max(int(c), 1), 0xA5, np.uint8) for c in caps]
+        px = (C.c_void_p * max(n, 1))(*[im.ctypes.data for im in imgs])
+        op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        w = np.array([im.shape[1] for im in imgs] or [0], np.int32)
+        hh = np.array([im.shape[0] for im in imgs] or [0], np.int32)
+        st = np.array([im.strides[0] for im in imgs] or [0], np.int32)
+        cp = np.array(list(caps) or [0], np.int64)
+        sz = np.full(max(n, 1), -1, np.int64)
+        rc = self.lib.lpslam_hip_jpeg_encode(self.h, n, px, _p(w), _p(hh), _p(st), int(quality), op, _p(cp), _p(sz))
+        return rc, sz[:n].copy(), outs
+
+    def encode(self, images, quality=95):
+        """list of 2-D uint8 images -> list of JPEG streams (bytes); raises on error"""
+        for im in images:
+            if np.asarray(im).dtype != np.uint8 or np.asarray(im).ndim != 2 or np.asarray(im).strides[1] != 1:
+                raise ValueError("2-D uint8 images with contiguous rows only")
+        rc, sizes, outs = self.encode_raw(images, quality)
+        _check(rc)
+        return [o[:s].tobytes() for o, s in zip(outs, sizes)]

@@ -59,9 +59,9 @@ bool LpSlamManager::addSource(char const* n, char const* c) { return m_impl->add
 bool LpSlamManager::addTracker(char const* n, char const* c) { return m_impl->addTracker(n ? n : "", c ? c : ""); }
 bool LpSlamManager::addProcessor(char const* n, char const* c) { return m_impl->addProcessor(n ? n : "", c ? c : ""); }
 void LpSlamManager::setShowLiveStream(bool) {}
-void LpSlamManager::setWriteImageFiles(bool) {}
-void LpSlamManager::setRecord(bool) {}
-void LpSlamManager::setRecordImages(bool) {}
+void LpSlamManager::setWriteImageFiles(bool on) { m_impl->setWriteImageFiles(on); }
+void LpSlamManager::setRecord(bool on) { m_impl->setRecord(on); }
+void LpSlamManager::setRecordImages(bool on) { m_impl->setRecordImages(on); }
 void LpSlamManager::start() { m_impl->start(); }
 void LpSlamManager::stop() { m_impl->stop(); }
 LpSlamStatus LpSlamManager::getSlamStatus() { return m_impl->getSlamStatus(); }
@@ -129,6 +129,16 @@ LPS_API size_t lpslam_manager_tracker_statistics(lpslam_c_manager* m, char* out,
     const std::string s = impl ? impl->trackerStatistics() : std::string();
     if (out && cap) { const size_t n = std::min(s.size(), cap - 1); memcpy(out, s.data(), n); out[n] = 0; }
     return s.size();
+}
+// recording (record.h): set before start()
+LPS_API void lpslam_manager_set_record(lpslam_c_manager* m, int on) { m->mgr.setRecord(on != 0); }
+LPS_API void lpslam_manager_set_record_images(lpslam_c_manager* m, int on) { m->mgr.setRecordImages(on != 0); }
+LPS_API void lpslam_manager_set_write_image_files(lpslam_c_manager* m, int on) { m->mgr.setWriteImageFiles(on != 0); }
+// test hook: out[4] = images encoded on the device, images encoded on the host, records written, bytes written (this manager's recorder)
+LPS_API void lpslam_manager_recorder_counters(lpslam_c_manager* m, uint64_t* out) {
+    LpSlam::SlamManager* impl = *reinterpret_cast<LpSlam::SlamManager**>(&m->mgr);
+    const LpSlam::RecorderCounters c = impl ? impl->recorderCounters() : LpSlam::RecorderCounters{};
+    out[0] = c.device_images; out[1] = c.host_images; out[2] = c.records; out[3] = c.bytes;
 }
 LPS_API size_t lpslam_manager_features_count(lpslam_c_manager* m) { return m->mgr.mappingGetFeaturesCount(LpSlamMapBoundary{}); }
 LPS_API int lpslam_manager_mapping_set_mode(lpslam_c_manager* m, int enable) { return m->mgr.mappingSetMode(enable != 0) ? 1 : 0; }

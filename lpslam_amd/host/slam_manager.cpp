@@ -103,12 +103,15 @@ bool SlamManager::readConfigurationFile(std::string const& filename)
     Json j;
     try { j = Json::parse(ss.str()); }
     catch (JsonError& e) { logMessage(LpSlamLogLevel_Error, "Cannot parse config file " + filename + " because: " + e.what()); return false; }
+    m_recorder.setWriteRawFile(false);                 // every configuration file resets record_raw first (SlamManager.cpp:642)
     try {
         if (const Json* m = j.find("manager")) {
+            if (const Json* r = m->find("record")) m_record = r->asBool();
             if (const Json* t = m->find("thread_num")) m_thread_num = (int)t->asNumber();
             if (const Json* r = m->find("require_odometry")) m_requireOdometry = r->asBool();
+            if (const Json* r = m->find("record_raw")) m_recorder.setWriteRawFile(r->asBool());
             if (const Json* c = m->find("replay_chunks")) m_replayChunk = (size_t)std::max(1.0, c->asNumber());   // SlamManager.cpp:668-671
-            // record / show_live / record_raw / replay_chunks belong to subsystems outside the accelerated path: accepted, ignored
+            // show_live belongs to a subsystem outside the accelerated path: accepted, ignored
         }
         auto plugin_list = [&](const char* section, const char* what, auto add) -> bool {
             const Json* list = j.find(section);
@@ -374,6 +377,11 @@ bool SlamManager::workerStep()
         if (r == LpSlamRequestNavDataResult_OdomOnly || r == LpSlamRequestNavDataResult_OdomAndMap) odom = conversion::gsInTimeInterfaceToInternal(lpOdom);
         if (r == LpSlamRequestNavDataResult_MapOnly || r == LpSlamRequestNavDataResult_OdomAndMap) map = conversion::gsInTimeInterfaceToInternal(lpMap);
     }
+    // the recorder gets every frame taken, before the trackers run (SlamManager.cpp:187): frames skipped for lack of odometry too
+    if (m_recorder.active()) {
+        const int64_t n = m_framesTaken++;
+        m_recorder.storeCameraImage(cam, odom, map, (m_writeImageFiles && n % 10 == 0) ? n : -1);
+    }
     bool resultSent = false;
     for (auto& tracker : m_trackers) {
         if (m_requireOdometry && !odom.has_value()) {
@@ -390,6 +398,7 @@ bool SlamManager::workerStep()
             GlobalStateInTime st;
             st.first = tr.timestamp;
             st.second.position = tr.position; st.second.orientation = tr.orientation; st.second.stateValid = true;
+            if (m_recorder.active()) m_recorder.storeResult(st);                   // SlamManager.cpp:216
             for (auto& p : m_processors) p->processSensorValuesAndResults(sensors, st);
             ResultQueueEntry re; re.globalStateInTime = st;
             m_resultQueue.push(re);
@@ -463,6 +472,10 @@ void SlamManager::start()
     // puts that expression into pushToImageCallbackQueue) and its thread calls the image callback when that one is set: images reach a
     // client that has set BOTH callbacks.  Same condition here, without queueing frames nobody will be handed.
     m_pushToImageCallbackQueue = m_onReconstruction != nullptr && m_onImage != nullptr;
+    // the recorder starts before the worker (the reference starts it after its threads, SlamManager.cpp:565-572, and may miss the
+    // first frames); with recording and image files off nothing of it is created
+    m_framesTaken = 0;
+    m_recorder.start(m_record, m_writeImageFiles);
     m_worker = std::thread([this] { while (workerStep()) {} });
     m_notifyWorker = std::thread([this] { while (notifyStep()) {} });
     m_imageCallbackWorker = std::thread([this] { while (imageCallbackStep()) {} });
@@ -487,6 +500,7 @@ void SlamManager::stop()
     m_imageCallbackQueue.push(std::move(ip));
     if (m_imageCallbackWorker.joinable()) m_imageCallbackWorker.join();
     m_imageCallbackQueue.clear();
+    m_recorder.stop();                                  // writes every entry queued before it, then closes the file (RecordEngine.cpp:330-350)
     for (auto& t : m_trackers) t->stop();
     if (const uint64_t n = m_framesProcessed.load())
         logMessage(LpSlamLogLevel_Info, "Worker statistics: frames=" + std::to_string(n) + " ms_per_frame=" + std::to_string(1e3 * m_secondsInWorker / (double)n) +

@@ -3,6 +3,7 @@
 #pragma once
 #include "core.h"
 #include "hip_tracker.h"
+#include "record.h"
 #include "replay.h"
 
 #include <atomic>
@@ -37,6 +38,11 @@ public:
     void stop();
     LpSlamStatus getSlamStatus();
 
+    // recording (src/Manager/SlamManager.cpp:565-572, RecordEngine): set before start(); a later start() opens a new file
+    void setRecord(bool on) { m_record = on; }
+    void setRecordImages(bool on) { m_recorder.setStoreImages(on); }
+    void setWriteImageFiles(bool on) { m_writeImageFiles = on; }
+
     std::size_t mappingGetFeatures(LpSlamMapBoundary b, LpSlamFeatureEntry* e, std::size_t n, LpSlamMatrix9x9 t);
     std::size_t mappingGetFeaturesCount(LpSlamMapBoundary b);
     std::string trackerStatistics();                    // the VSLAM tracker's last statistics line (empty before its first stop)
@@ -56,6 +62,7 @@ public:
     uint64_t framesProcessed() const { return m_framesProcessed.load(); }
     uint64_t framesSkipped() const { return m_framesSkipped.load(); }
     uint64_t imagesSent() const { return m_imagesSent.load(); }
+    RecorderCounters recorderCounters() const { return m_recorder.counters(); }
 
 private:
     void streamMoreReplayItems();
@@ -81,6 +88,10 @@ private:
     double m_secondsInWorker = 0, m_secondsInTrackers = 0;      // worker thread only (logged by stop()): a frame from the moment it is taken / inside processImage
     std::atomic<bool> m_stopRequested{false};
     std::optional<CameraQueueEntry> m_lookahead;       // worker thread only: the frame after the one being processed
+    Recorder m_recorder;
+    bool m_record = false;               // setRecord / "manager": {"record": true}
+    bool m_writeImageFiles = false;      // setWriteImageFiles: every 10th frame taken as <n>_left.jpg / <n>_right.jpg (SlamManager.cpp:70-85)
+    int64_t m_framesTaken = 0;           // worker thread only: frames taken since start() (the reference's numberPic)
     ReplayReader m_replay;
     std::mutex m_replayMutex;
     size_t m_replayChunk = 500;          // ReplayEngine.h:53

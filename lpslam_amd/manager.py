@@ -240,6 +240,29 @@ class Manager:
             return None
         return out[:n.value].tobytes()
 
+    def set_record(self, on):
+        """setRecord: start() writes the session to slam_<local time>.pb in the working directory ("Recording file")"""
+        f = self.lib.lpslam_manager_set_record; f.argtypes = [C.c_void_p, C.c_int]
+        f(self.h, 1 if on else 0)
+
+    def set_record_images(self, on):
+        """setRecordImages: False drops the camera records (result records are still written)"""
+        f = self.lib.lpslam_manager_set_record_images; f.argtypes = [C.c_void_p, C.c_int]
+        f(self.h, 1 if on else 0)
+
+    def set_write_image_files(self, on):
+        """setWriteImageFiles: every 10th frame the worker takes as <n>_left.jpg / <n>_right.jpg in the working directory"""
+        f = self.lib.lpslam_manager_set_write_image_files; f.argtypes = [C.c_void_p, C.c_int]
+        f(self.h, 1 if on else 0)
+
+    def recorder_counters(self):
+        """test hook: {device_images, host_images, records, bytes} of this manager's recorder"""
+        import numpy as np
+        out = np.zeros(4, np.uint64)
+        f = self.lib.lpslam_manager_recorder_counters; f.argtypes = [C.c_void_p, C.c_void_p]
+        f(self.h, out.ctypes.data)
+        return dict(zip(("device_images", "host_images", "records", "bytes"), (int(v) for v in out)))
+
     def start(self):
         self.lib.lpslam_manager_start(self.h)
 
