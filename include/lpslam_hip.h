@@ -164,6 +164,34 @@ int lpslam_hip_upload_raw_image(lpslam_hip_ctx* ctx, int image, int32_t eye, con
 /* remaps the raw frame already staged in HBM (the last upload_raw_image) into another slot: the device-side step alone */
 int lpslam_hip_remap_staged(lpslam_hip_ctx* ctx, int image, int32_t eye);
 
+/* Intensity adjustment on the device: replaces the per-frame host call of the reference's AdjustIntensity processor
+ * (src/Processor/AdjustIntensityProcessor.h:10-41 -> ImageProcessing::imadjust(image, out, nullopt, nullopt, -0.3, 1.4),
+ * src/Utils/ImageProcessing.h:258-370; run on both eyes of every frame before the trackers, src/Manager/SlamManager.cpp:114-116).
+ * Per image: the histogram of its pixels, the grey levels lo / hi that cut off low_fraction of the pixels at the dark end and
+ * 1 - high_fraction at the bright end, and the linear map that sends lo to low_out and hi to high_out (both in units of the full 8-bit
+ * range), applied through a 256-entry table in single precision, unfused, rounded half to even and saturated (DESIGN.md section 17
+ * has the arithmetic word for word; lo == hi leaves the image unchanged).  The reference's constants are {-0.3, 1.4, 0.01, 0.99}.
+ * Needs low_out < high_out (finite), 0 <= low_fraction < high_fraction <= 1 and fewer than 2^24 pixels per image; otherwise
+ * LPSLAM_HIP_ERR_INVALID / LPSLAM_HIP_ERR_CAPACITY, and nothing is enqueued.
+ *   lpslam_hip_adjust_intensity           image slots [first, first + n) in place on level 0, asynchronous, behind their uploads: two
+ *                                         launches for all n images, no host synchronisation; inside or outside a prefetch section.
+ *   lpslam_hip_upload_raw_image_adjusted  lpslam_hip_upload_raw_image with the RAW frame adjusted before it is remapped, the order of
+ *                                         the reference (SlamManager.cpp:114 runs before OpenVSLAMStereoTracker.cpp:198-213).
+ *   lpslam_hip_front_end_images_adjusted  lpslam_hip_front_end_images with the adjustment of the slot (pair) between the uploads and
+ *                                         the front end: a tracker's one call per frame stays one call.
+ *   lpslam_hip_adjust_intensity_last      test hook, synchronising: lo, hi and the 256 histogram words of the last adjustment of a slot
+ *                                         (any of the three outputs may be NULL). */
+typedef struct lpslam_hip_adjust_params {
+    double low_out, high_out;             /* where lo and hi go, in units of 255 (the reference: -0.3, 1.4) */
+    double low_fraction, high_fraction;   /* the quantiles that define lo and hi (the reference: 0.01, 0.99)  */
+} lpslam_hip_adjust_params;
+int lpslam_hip_adjust_intensity(lpslam_hip_ctx* ctx, int first, int n, const lpslam_hip_adjust_params* params);
+int lpslam_hip_upload_raw_image_adjusted(lpslam_hip_ctx* ctx, int image, int32_t eye, const uint8_t* host, int32_t stride,
+                                         const lpslam_hip_adjust_params* params);
+int lpslam_hip_front_end_images_adjusted(lpslam_hip_ctx* ctx, int image, const uint8_t* left, const uint8_t* right, int32_t stride,
+                                         float focal_x_baseline, float baseline, const lpslam_hip_adjust_params* params);
+int lpslam_hip_adjust_intensity_last(lpslam_hip_ctx* ctx, int image, int32_t* lo, int32_t* hi, uint32_t* hist256);
+
 /* Prefetch: between prefetch_begin and prefetch_end every upload / remap / extract / stereo-match call of this context is enqueued
  * on a second stream, so the front end of the NEXT frame (into image slots nothing else touches) runs on the GPU beside the
  * matching and pose optimisation of the current one; prefetch_join makes the context's main stream wait (on the device, not the

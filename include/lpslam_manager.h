@@ -5,6 +5,8 @@
  * (/root/reference/src/Interface/LpSlamManager.h:17-121, C++ ABI, pimpl), so existing client code compiles unchanged;
  * behind it sits LpSlam::SlamManager of lpslam_amd/host/ whose trackers run on the MI355X through include/lpslam_hip.h.
  * Recording (setRecord, setRecordImages, setWriteImageFiles) writes the reference's recording file ("Recording file").
+ * addProcessor knows "AdjustIntensity" (src/Processor/AdjustIntensityProcessor.h:10-41; INTEGRATION.md, "Processors"); the reference's
+ * other two processors, BlackoutImage and CameraCalibration, are not part of this library and answer false.
  * Methods that belong to subsystems outside the accelerated path (file sources, live view) keep their signatures and behave as the reference does when the backing plugin is absent: they return
  * false / 0 / do nothing (cf. src/Manager/SlamManager.cpp:1311-1312,1368-1395).
  */

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblpslam_hip.so")
-HIP_SOURCES = ["api.hip", "frontend.hip", "match.hip", "ba.hip", "bow.hip", "share.hip", "occupancy.hip", "jpeg.hip"]
+HIP_SOURCES = ["api.hip", "frontend.hip", "match.hip", "ba.hip", "bow.hip", "share.hip", "occupancy.hip", "jpeg.hip", "intensity.hip"]
 DEPS = ["internal.h", "orb_pattern.inc", os.path.join("..", "..", "include", "lpslam_hip.h"), "sim3.inl"]
 # -ffp-contract=off: parity with the CPU definition forbids FMA contraction ("Numerics").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
@@ -15,7 +15,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 
 OBJ_DIR = os.path.join(CSRC, "_obj")
 # what each translation unit includes (beyond itself): a change there recompiles only that unit
-UNIT_DEPS = {"ba.hip": ["sim3.inl", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl"], "frontend.hip": ["orb_pattern.inc"], "match.hip": [], "api.hip": [], "bow.hip": [], "share.hip": [], "occupancy.hip": [], "jpeg.hip": [os.path.join("..", "host", "jpeg_tables.h")]}
+UNIT_DEPS = {"ba.hip": ["sim3.inl", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl"], "frontend.hip": ["orb_pattern.inc"], "match.hip": [], "api.hip": [], "bow.hip": [], "share.hip": [], "occupancy.hip": [], "intensity.hip": [], "jpeg.hip": [os.path.join("..", "host", "jpeg_tables.h")]}
 COMMON_DEPS = ["internal.h", os.path.join("..", "..", "include", "lpslam_hip.h")]
 
 
@@ -30,6 +30,12 @@ def hip_library(force=False, verbose=False):
     flags_now = " ".join(compile_flags)
     if not os.path.exists(flags_file) or open(flags_file).read() != flags_now:
         force = True
+    # a tree that travelled with its library but without the per-unit objects (they are not part of a snapshot): the library stands
+    # when it is newer than everything it is made from
+    if not force and os.path.exists(LIB) and not any(os.path.exists(os.path.join(OBJ_DIR, s.replace(".hip", ".o"))) for s in srcs):
+        made_from = [os.path.join(CSRC, d) for s in srcs for d in [s] + UNIT_DEPS.get(s, []) + COMMON_DEPS] + [os.path.abspath(__file__)]
+        if all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in made_from if os.path.exists(d)):
+            return LIB
     jobs, objs = [], []
     for src in srcs:
         obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
@@ -55,19 +61,20 @@ def hip_library(force=False, verbose=False):
 
 
 HOST_LIB = os.path.join(HERE, "liblpslam.so")
-HOST_SOURCES = ["slam_manager.cpp", "hip_tracker.cpp", "interface.cpp", "rectify.cpp", "replay.cpp", "two_view.cpp", "bow.cpp", "jpeg.cpp", "map_file.cpp", "record.cpp"]
+HOST_SOURCES = ["slam_manager.cpp", "hip_tracker.cpp", "interface.cpp", "rectify.cpp", "replay.cpp", "two_view.cpp", "bow.cpp", "jpeg.cpp", "map_file.cpp", "record.cpp", "intensity.cpp"]
 
 
 def host_library(force=False, verbose=False):
     """C++ host mirror of the reference interface (g++), linked against the HIP C-ABI library next to it."""
     hdir = os.path.join(HERE, "host")
     srcs = [os.path.join(hdir, s) for s in HOST_SOURCES]
-    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "bow.h", "jpeg.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h")] + \
+    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "bow.h", "jpeg.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h")] + \
         [os.path.join(HERE, "..", "include", h) for h in ("lpslam_types.h", "lpslam_manager.h", "lpslam_hip.h")] + [LIB]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps if os.path.exists(d)):
         return HOST_LIB
     hip_library(force=False, verbose=verbose)
-    cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-Wall", "-Wextra",
+    # -ffp-contract=off: the intensity table's product and sum stay unfused on every target (DESIGN.md section 17)
+    cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-ffp-contract=off", "-Wall", "-Wextra",
            "-Wno-unused-parameter", "-pthread", "-o", HOST_LIB] + srcs + ["-L" + HERE, "-llpslam_hip", "-Wl,-rpath,$ORIGIN"]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)

@@ -632,6 +632,7 @@ void lpslam_hip_destroy(lpslam_hip_ctx* c)
     if (c->d_cu_table) (void)hipFree(c->d_cu_table);
     if (c->d_fe_counters) (void)hipFree(c->d_fe_counters);
     if (c->d_done) (void)hipFree(c->d_done);
+    lp_adjust_free(c);
     for (int i = 0; i < LPSLAM_HIP_MAX_TIMERS; ++i) { if (c->ev_begin[i]) (void)hipEventDestroy(c->ev_begin[i]); if (c->ev_end[i]) (void)hipEventDestroy(c->ev_end[i]); }
     for (void* p : c->pin_free) (void)hipHostFree(p);
     c->pin_free.clear();
@@ -1040,18 +1041,29 @@ int lpslam_hip_set_rectify_map(lpslam_hip_ctx* c, int32_t eye, const float* map_
     return LPSLAM_HIP_OK;
 }
 
-int lpslam_hip_upload_raw_image(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride)
+static int upload_raw_image_impl(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride, const lpslam_hip_adjust_params* adjust)
 {
     int rc = check_image(c, image); if (rc) return rc;
     if (eye < 0 || eye > 1 || !c->d_map_xy[eye]) { set_error("no rectify map set for eye %d", eye); return LPSLAM_HIP_ERR_INVALID; }
     if (!host || stride < c->lt.w[0]) { set_error("bad host image (stride %d < width %d)", stride, c->lt.w[0]); return LPSLAM_HIP_ERR_INVALID; }
+    if (adjust && (rc = lp_adjust_check(c, adjust))) return rc;
     LP_HIP(hipSetDevice(c->cfg.device));
     // the staging buffer is reused by every upload: copy and remap are ordered on the context stream
     const uint8_t* src = stage_upload(c, image, host, stride);
     if (!src) return LPSLAM_HIP_ERR_DEVICE;
     LP_HIP(hipMemcpy2DAsync(c->d_raw, c->lt.w[0], src, c->lt.w[0], c->lt.w[0], c->lt.h[0], hipMemcpyHostToDevice, lp_fe_stream(c)));
     LP_HIP(hipEventRecord(c->ev_upload[(size_t)image], lp_fe_stream(c)));
+    // the raw frame is adjusted, the result remapped (the order of the reference; interpolation does not commute with the table)
+    if (adjust && (rc = lp_adjust_launch(c, lp_fe_stream(c), c->d_raw, 0, c->lt.w[0], image, 1, adjust))) return rc;
     return lp_launch_remap(c, image, eye);
+}
+
+int lpslam_hip_upload_raw_image(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride) { return upload_raw_image_impl(c, image, eye, host, stride, nullptr); }
+
+int lpslam_hip_upload_raw_image_adjusted(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride, const lpslam_hip_adjust_params* adjust)
+{
+    if (!adjust) { set_error("null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    return upload_raw_image_impl(c, image, eye, host, stride, adjust);
 }
 
 int lpslam_hip_remap_staged(lpslam_hip_ctx* c, int image, int32_t eye)
@@ -1070,6 +1082,33 @@ static int check_range(lpslam_hip_ctx* c, int first, int n)
     }
     LP_HIP(hipSetDevice(c->cfg.device));
     return LPSLAM_HIP_OK;
+}
+
+// ---- intensity adjustment (intensity.hip) -----------------------------------------------------------------------------------
+// Slots [first, first + n) in place on level 0, behind their uploads, on the front-end stream of the calling thread.  Whoever reads the
+// slots next on ANOTHER stream -- a shared front-end chain waits for the slots' upload events (share.hip) -- finds those events
+// re-recorded behind the adjustment.
+static int adjust_slots(lpslam_hip_ctx* c, int first, int n, const lpslam_hip_adjust_params* p)
+{
+    hipStream_t s = lp_fe_stream(c);
+    int rc;
+    if ((rc = lp_wait_uploads(c, first, n))) return rc;
+    if ((rc = lp_wait_own_uploads(c, first, n, s))) return rc;
+    if ((rc = lp_adjust_launch(c, s, c->d_pyr + (size_t)first * c->image_slab, c->image_slab, c->lt.pitch[0], first, n, p))) return rc;
+    if (!c->up_pending.empty())
+        for (int i = first; i < first + n && (size_t)i < c->up_pending.size(); ++i) {
+            if ((size_t)i >= c->ev_upload.size() || !c->ev_upload[(size_t)i]) continue;
+            LP_HIP(hipEventRecord(c->ev_upload[(size_t)i], s));
+            c->up_pending[(size_t)i] = 1;
+        }
+    return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_adjust_intensity(lpslam_hip_ctx* c, int first, int n, const lpslam_hip_adjust_params* p)
+{
+    int rc = check_range(c, first, n); if (rc) return rc;
+    if ((rc = lp_adjust_check(c, p))) return rc;
+    return adjust_slots(c, first, n, p);
 }
 
 int lpslam_hip_stage_pyramid(lpslam_hip_ctx* c, int n) { int rc = check_batch(c, n); if (!rc) rc = lp_wait_uploads(c, 0, n); return rc ? rc : lp_launch_pyramid(c, 0, n); }
@@ -1319,25 +1358,40 @@ int lpslam_hip_front_end(lpslam_hip_ctx* c, int image, int32_t stereo, float fxb
 }
 
 // lpslam_hip_front_end with the frame itself: upload of the slot (stereo: the pair) + front end.
-int lpslam_hip_front_end_images(lpslam_hip_ctx* c, int image, const uint8_t* left, const uint8_t* right, int32_t stride, float fxb, float baseline)
+static int front_end_images_impl(lpslam_hip_ctx* c, int image, const uint8_t* left, const uint8_t* right, int32_t stride, float fxb, float baseline,
+                                const lpslam_hip_adjust_params* adjust)
 {
     int rc = check_image(c, image); if (rc) return rc;
     const bool stereo = right != nullptr;
     if (stereo && (rc = check_image(c, image + 1))) return rc;
     if (!left || stride < c->lt.w[0]) { set_error("bad host image (stride %d < width %d)", stride, c->lt.w[0]); return LPSLAM_HIP_ERR_INVALID; }
     if (stereo && (!(baseline > 0.f) || !(fxb > 0.f))) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
+    if (adjust && (rc = lp_adjust_check(c, adjust))) return rc;
     LP_HIP(hipSetDevice(c->cfg.device));
     // the uploads are enqueued at once, by the calling thread, on the context's front-end stream -- for a session that joined a pool that
     // IS the front-end role stream the shared chain will run on: the copies of the sessions' frames proceed while the gather waits for the
     // last session, and the chain's kernels queue behind them
     if ((rc = lpslam_hip_upload_image(c, image, left, stride))) return rc;
     if (stereo && (rc = lpslam_hip_upload_image(c, image + 1, right, stride))) return rc;
+    if (adjust && (rc = adjust_slots(c, image, stereo ? 2 : 1, adjust))) return rc;      // both eyes in each of its two launches, right behind the uploads
     const int shared = lp_share_front_end(c, image, stereo ? 1 : 0, fxb, baseline);
     if (shared < 0) return -shared;
     if (shared == LP_SHARE_DONE) return LPSLAM_HIP_OK;
     if ((rc = lpslam_hip_extract_range(c, image, stereo ? 2 : 1))) return rc;
     if (stereo && (rc = lpslam_hip_match_stereo(c, image, image + 1, fxb, baseline))) return rc;
     return lpslam_hip_prefetch_frame(c, image, stereo ? 1 : 0);
+}
+
+int lpslam_hip_front_end_images(lpslam_hip_ctx* c, int image, const uint8_t* left, const uint8_t* right, int32_t stride, float fxb, float baseline)
+{
+    return front_end_images_impl(c, image, left, right, stride, fxb, baseline, nullptr);
+}
+
+int lpslam_hip_front_end_images_adjusted(lpslam_hip_ctx* c, int image, const uint8_t* left, const uint8_t* right, int32_t stride, float fxb, float baseline,
+                                         const lpslam_hip_adjust_params* adjust)
+{
+    if (!adjust) { set_error("null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    return front_end_images_impl(c, image, left, right, stride, fxb, baseline, adjust);
 }
 
 // the block that holds `fields` of slot `image` once this returns (delivered ahead of time, or read back now)

@@ -189,6 +189,10 @@ struct lpslam_hip_ctx {
     short2* d_map_xy[2] = {nullptr, nullptr};      // [h][w] integer source coordinate (sx >> 5, sy >> 5)
     uint16_t* d_map_frac[2] = {nullptr, nullptr};  // [h][w] (sy & 31) * 32 + (sx & 31)
     uint8_t* d_raw = nullptr;                      // [h][w] distorted frame of the upload in flight
+    // intensity adjustment (intensity.hip): per image slot two sets of 256 histogram words and the limits (lo, hi) of its last adjustment
+    uint32_t* d_adj_hist = nullptr;                // [max_images][2][256]
+    int32_t* d_adj_lohi = nullptr;                 // [max_images][2]
+    std::vector<uint8_t> adj_set, adj_seen;        // per slot: the set its next adjustment counts into / it has been adjusted at all
     uint8_t* d_mask[2] = {nullptr, nullptr};       // camera masks (level-0 size, pitch = width, 0 = masked out), left / right eye; nullptr = none
     // cache of device blocks for the short-lived objects the tracker makes every frame / keyframe (bundle-adjustment problems, pose
     // optimiser and projection-matcher staging): hipMalloc / hipFree cost ~50-100 us each and a problem needs ~40 buffers
@@ -220,6 +224,10 @@ bool lp_flat_priorities();             // several contexts live in the process: 
 int lp_fe_calibrate(lpslam_hip_ctx* c, int reserve_cus_per_xcd);
 int lp_fe_occupy_unreserved(lpslam_hip_ctx* c, int microseconds, int* landed);
 int lp_launch_remap(lpslam_hip_ctx* c, int image, int eye);
+// intensity.hip: argument check of an adjustment; the two launches for n images in place on stream s (image k at base + k * slab, slot first + k)
+int lp_adjust_check(lpslam_hip_ctx* c, const lpslam_hip_adjust_params* p);
+int lp_adjust_launch(lpslam_hip_ctx* c, hipStream_t s, uint8_t* base, size_t slab, int pitch, int first, int n, const lpslam_hip_adjust_params* p);
+void lp_adjust_free(lpslam_hip_ctx* c);
 int lp_launch_fast(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
 int lp_launch_distribute(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
 int lp_launch_describe(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);

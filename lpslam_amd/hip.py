@@ -44,6 +44,7 @@ SYMBOLS = [
     "lpslam_hip_sim3_create", "lpslam_hip_sim3_destroy", "lpslam_hip_sim3_optimize", "lpslam_hip_sim3_get", "lpslam_hip_sim3_chi2", "lpslam_hip_sim3_transform_optimize",
     "lpslam_hip_scan_geometry_put", "lpslam_hip_scan_store_put", "lpslam_hip_scan_store_drop", "lpslam_hip_occupancy_build",
     "lpslam_hip_jpeg_create", "lpslam_hip_jpeg_destroy", "lpslam_hip_jpeg_encode",
+    "lpslam_hip_adjust_intensity", "lpslam_hip_upload_raw_image_adjusted", "lpslam_hip_front_end_images_adjusted", "lpslam_hip_adjust_intensity_last",
 ]
 
 
@@ -67,6 +68,14 @@ class FrontendConfig(C.Structure):
 class BaCamera(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("focal_x_baseline", C.c_double), ("huber_mono", C.c_double), ("huber_stereo", C.c_double)]
+
+
+class AdjustParams(C.Structure):
+    """lpslam_hip_adjust_params; the defaults are the reference's constants"""
+    _fields_ = [("low_out", C.c_double), ("high_out", C.c_double), ("low_fraction", C.c_double), ("high_fraction", C.c_double)]
+
+    def __init__(self, low_out=-0.3, high_out=1.4, low_fraction=0.01, high_fraction=0.99):
+        super().__init__(float(low_out), float(high_out), float(low_fraction), float(high_fraction))
 
 
 class BaKernelTimes(C.Structure):
@@ -190,6 +199,40 @@ class Context:
         f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float]
         left = np.ascontiguousarray(left); right = None if right is None else np.ascontiguousarray(right)
         _check(f(self.h, int(image), _p(left), None if right is None else _p(right), left.shape[1], float(fxb), float(baseline)))
+
+    def front_end_images_adjusted(self, image, left, right=None, fxb=0.0, baseline=0.0, params=None):
+        """front_end_images with the intensity adjustment of the slot (pair) between the uploads and the front end"""
+        f = self.lib.lpslam_hip_front_end_images_adjusted
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.POINTER(AdjustParams)]
+        left = np.ascontiguousarray(left); right = None if right is None else np.ascontiguousarray(right)
+        p = params if params is not None else AdjustParams()
+        _check(f(self.h, int(image), _p(left), None if right is None else _p(right), left.shape[1], float(fxb), float(baseline), C.byref(p)))
+
+    def adjust_intensity(self, first, n, params=None):
+        """image slots [first, first + n) adjusted in place on level 0 (asynchronous; AdjustParams, default: the reference's constants)"""
+        f = self.lib.lpslam_hip_adjust_intensity
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(AdjustParams)]
+        p = params if params is not None else AdjustParams()
+        _check(f(self.h, int(first), int(n), C.byref(p)))
+
+    def adjust_intensity_last(self, image):
+        """test hook (synchronising): (lo, hi, the 256 histogram words) of the last adjustment of a slot"""
+        f = self.lib.lpslam_hip_adjust_intensity_last
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+        lo, hi = C.c_int32(), C.c_int32()
+        hist = np.zeros(256, np.uint32)
+        _check(f(self.h, int(image), C.byref(lo), C.byref(hi), _p(hist)))
+        return lo.value, hi.value, hist
+
+    def upload_raw_adjusted(self, image, eye, arr, params=None):
+        """upload_raw with the raw frame adjusted before it is remapped"""
+        arr = np.ascontiguousarray(arr, np.uint8)
+        assert arr.shape == (self.cfg.height, self.cfg.width), arr.shape
+        f = self.lib.lpslam_hip_upload_raw_image_adjusted
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(AdjustParams)]
+        p = params if params is not None else AdjustParams()
+        _check(f(self.h, int(image), int(eye), _p(arr), arr.shape[1], C.byref(p)))
+        self.sync()
 
     def set_mapping_reserve(self, cus_per_xcd):
         """compute units of every XCD the front end's kernels leave to the bundle adjustments that run beside them (idle context)"""

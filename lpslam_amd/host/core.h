@@ -70,6 +70,15 @@ struct GrayImage {
     bool empty() const { return pixels.empty(); }
 };
 
+// An intensity adjustment the AdjustIntensity processor has asked for and nobody has applied yet (intensity.h): the pixels of the entry
+// are still the unadjusted ones.  Whoever reads them next applies it -- a HIP tracker on the device, inside its front end; everybody
+// else through realiseAdjust(), on the host.  The two give the same bytes.
+struct IntensityAdjust {
+    double low_out = -0.3, high_out = 1.4;            // src/Processor/AdjustIntensityProcessor.h: imadjust(.., -0.3, 1.4)
+    double low_fraction = 0.01, high_fraction = 0.99; // src/Utils/ImageProcessing.h: the tolerances of stretchlimFromHist
+    bool operator==(const IntensityAdjust& o) const { return low_out == o.low_out && high_out == o.high_out && low_fraction == o.low_fraction && high_fraction == o.high_fraction; }
+};
+
 struct CameraQueueEntry {
     bool valid = false;               // false = exit signal for the worker
     TimeStamp timestamp{};
@@ -77,6 +86,8 @@ struct CameraQueueEntry {
     GrayImage image;
     std::optional<GrayImage> image_second;
     std::optional<LpSlamROSTimestamp> ros_timestamp;
+    std::optional<IntensityAdjust> adjust;            // requested, not yet applied to `image` / `image_second`
+    bool processed = false;           // the manager's processors have seen this entry (a lookahead frame: before it became the current one)
 };
 
 struct SensorQueueEntry { TimeStamp timestamp{}; bool valid = true; };
@@ -136,6 +147,9 @@ public:
     // may start that frame's device-side front end once its own has finished, so that it runs beside the tracking of the current
     // frame; the pointer is valid during that processImage call only.
     virtual void setNextFrame(CameraQueueEntry const*) {}
+    // true: processImage applies a pending CameraQueueEntry::adjust itself (and leaves the entry as it is); false: the manager applies it
+    // on the host before the call
+    virtual bool realisesAdjust() const { return false; }
     virtual void addRequestNavTransformationCallback(RequestNavTransformationCallback_t, void*) {}
     virtual std::optional<unsigned long> mappingGetMapRawSize() { return std::nullopt; }
     virtual std::optional<LpMapInfo> mappingGetMapRaw(int8_t*, std::size_t) { return std::nullopt; }
@@ -170,7 +184,11 @@ public:
     virtual void processImage(CameraQueueEntry&) {}
     virtual void processSensorValuesAndResults(std::vector<SensorQueueEntry> const&, GlobalStateInTime const&) {}
     virtual std::string type() = 0;
-    void setConfig(std::string const&) {}
+    // false: the configuration is not acceptable (addProcessor then fails); plugins that do not override it accept everything, as the
+    // reference's ProcessorBase::setConfig does (src/Processor/ProcessorBase.h:21-22)
+    virtual bool setConfig(std::string const&) { return true; }
+    // false: processImage does not look at the pixels (a pending CameraQueueEntry::adjust may stay pending across the call)
+    virtual bool readsPixels() const { return true; }
 };
 
 }  // namespace LpSlam

@@ -1930,12 +1930,12 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
                   s.ba_failed, (long)dev[LPSLAM_HIP_BA_COUNTER_SIGNATURES], (long)dev[LPSLAM_HIP_BA_COUNTER_GRAPHS], (long)dev[LPSLAM_HIP_BA_COUNTER_REPLAYS],
-                  (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]),
+                  (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted,
                   s.t_total * per, s.t_front * per, s.t_track * per, s.t_local * per, s.t_keyframe * per,
                   s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per);
     m_lastStatistics = buf;
@@ -1948,19 +1948,29 @@ bool HipVslamTrackerBase::frontEnd(CameraQueueEntry const& cam, bool stereo, int
 {
     bool ok;
     static const bool readback_ahead_fused = std::getenv("LPSLAM_HIP_NO_PREFETCH_READBACK") == nullptr;
+    // an intensity adjustment the AdjustIntensity processor asked for and nobody applied on the host: on the device, behind the upload
+    lpslam_hip_adjust_params adj{};
+    const bool adjust = cam.adjust.has_value();
+    if (adjust) adj = lpslam_hip_adjust_params{cam.adjust->low_out, cam.adjust->high_out, cam.adjust->low_fraction, cam.adjust->high_fraction};
     if (!m_rectify && readback_ahead_fused) {
         // upload, extraction, stereo match and the read-back that rides behind them: ONE call, which the frames that other sessions of the
         // process have pending join (one upload + launch chain for all of them, share.hip)
         const float baseline = (float)(m_cam.focal_x_baseline / m_cam.f_x);
-        return lpslam_hip_front_end_images(m_ctx, slot, cam.image.pixels.data(), stereo ? cam.image_second->pixels.data() : nullptr, cam.image.width,
-                                           (float)m_cam.focal_x_baseline, baseline) == LPSLAM_HIP_OK;
+        const uint8_t* right = stereo ? cam.image_second->pixels.data() : nullptr;
+        if (adjust) return lpslam_hip_front_end_images_adjusted(m_ctx, slot, cam.image.pixels.data(), right, cam.image.width, (float)m_cam.focal_x_baseline, baseline, &adj) == LPSLAM_HIP_OK;
+        return lpslam_hip_front_end_images(m_ctx, slot, cam.image.pixels.data(), right, cam.image.width, (float)m_cam.focal_x_baseline, baseline) == LPSLAM_HIP_OK;
     }
-    if (m_rectify) {       // raw frames: undistort + rectify on the device
-        ok = lpslam_hip_upload_raw_image(m_ctx, slot, 0, cam.image.pixels.data(), cam.image.width) == LPSLAM_HIP_OK;
-        if (ok && stereo) ok = lpslam_hip_upload_raw_image(m_ctx, slot + 1, 1, cam.image_second->pixels.data(), cam.image.width) == LPSLAM_HIP_OK;
+    if (m_rectify) {       // raw frames: (adjusted, then) undistorted + rectified on the device
+        auto raw = [&](int image, int eye, const GrayImage& img) {
+            return (adjust ? lpslam_hip_upload_raw_image_adjusted(m_ctx, image, eye, img.pixels.data(), img.width, &adj)
+                           : lpslam_hip_upload_raw_image(m_ctx, image, eye, img.pixels.data(), img.width)) == LPSLAM_HIP_OK;
+        };
+        ok = raw(slot, 0, cam.image);
+        if (ok && stereo) ok = raw(slot + 1, 1, *cam.image_second);
     } else {
         ok = lpslam_hip_upload_image(m_ctx, slot, cam.image.pixels.data(), cam.image.width) == LPSLAM_HIP_OK;
         if (ok && stereo) ok = lpslam_hip_upload_image(m_ctx, slot + 1, cam.image_second->pixels.data(), cam.image.width) == LPSLAM_HIP_OK;
+        if (ok && adjust) ok = lpslam_hip_adjust_intensity(m_ctx, slot, stereo ? 2 : 1, &adj) == LPSLAM_HIP_OK;
     }
     static const bool readback_ahead = std::getenv("LPSLAM_HIP_NO_PREFETCH_READBACK") == nullptr;      // (development switch)
     const float baseline = (float)(m_cam.focal_x_baseline / m_cam.f_x);
@@ -1988,7 +1998,7 @@ void HipVslamTrackerBase::prefetchFrame(CameraQueueEntry const& cam, bool stereo
     if (!ok) logMessage(LpSlamLogLevel_Error, std::string("prefetch front end: ") + lpslam_hip_last_error());
     if (lpslam_hip_prefetch_end(m_ctx) != LPSLAM_HIP_OK || !ok) return;
     m_prefetched.valid = true; m_prefetched.data = cam.image.pixels.data(); m_prefetched.timestamp = cam.timestamp;
-    m_prefetched.slot = slot; m_prefetched.stereo = stereo;
+    m_prefetched.slot = slot; m_prefetched.stereo = stereo; m_prefetched.adjust = cam.adjust;
 }
 
 void HipVslamTrackerBase::prefetchLoop()
@@ -2077,7 +2087,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     auto t_dev = std::chrono::steady_clock::now();
     auto dev_lap = [&t_dev](double& acc) { const auto now = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(now - t_dev).count(); t_dev = now; };
     if (m_prefetched.valid && m_prefetched.data == cam.image.pixels.data() && m_prefetched.timestamp == cam.timestamp &&
-        m_prefetched.slot == cur.slot && m_prefetched.stereo == stereo) {
+        m_prefetched.slot == cur.slot && m_prefetched.stereo == stereo && m_prefetched.adjust == cam.adjust) {
         // this frame's front end was started while the previous frame was tracked: the main stream waits for it on the device
         ok = lpslam_hip_prefetch_join(m_ctx) == LPSLAM_HIP_OK;
         ++m_stats.prefetched;
@@ -2106,6 +2116,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     cur.scan = std::move(scan);
     dev_lap(m_stats.t_dev_get);
     ++m_imageTracked; ++m_stats.frames;
+    if (cam.adjust) ++m_stats.intensity_adjusted;
     // The next frame's upload + front end: a helper thread stages and enqueues it (0.2 ms of host time at 1280x720 stereo, mostly the
     // copy of the cold frame into page-locked memory) on the context's prefetch stream while this thread goes on tracking; the
     // future joins before this call returns (the frame is only valid that long) and on every early return.

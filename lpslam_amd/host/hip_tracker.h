@@ -94,6 +94,7 @@ protected:
         long culled_landmarks = 0, culled_keyframes = 0;
         long ba_failed = 0;                           // windows whose solve failed on the device (result dropped)
         long local_ba = 0, loops_closed = 0, loop_fused = 0, global_ba = 0, lost = 0, relocalised = 0, reinitialised = 0, nav_priors = 0, prefetched = 0;
+        long intensity_adjusted = 0;                  // frames whose intensity adjustment ran on the device (a request the host had applied already does not count)
         // where the frames' time went (seconds, summed): front end (upload, extraction, stereo, read-back), tracking against the
         // previous frame, local-map tracking, keyframe work on the tracking thread (insertion, fusion, loop search, BA set-up / wait)
         double t_front = 0, t_track = 0, t_local = 0, t_keyframe = 0, t_total = 0;
@@ -217,10 +218,11 @@ protected:
     BowDatabase m_bowDb;
     void computeBow(Keyframe& kf) const;
     bool frameNodes(const FrameData& f, std::vector<int32_t>& node, BowVector* bow) const;
-    struct Prefetched { bool valid = false; bool issued = false /* work may sit on the prefetch stream, valid or not */; const uint8_t* data = nullptr; TimeStamp timestamp{}; int slot = 0; bool stereo = false; } m_prefetched;
+    struct Prefetched { bool valid = false; bool issued = false /* work may sit on the prefetch stream, valid or not */; const uint8_t* data = nullptr; TimeStamp timestamp{}; int slot = 0; bool stereo = false; std::optional<IntensityAdjust> adjust /* what the prefetch applied on the device */; } m_prefetched;
     void prefetchFrame(CameraQueueEntry const& cam, bool stereo);      // m_slamLock held
     CameraQueueEntry const* m_nextFrame = nullptr;
     void setNextFrame(CameraQueueEntry const* next) override { m_nextFrame = next; }
+    bool realisesAdjust() const override { return true; }      // a pending intensity adjustment runs on the device, inside frontEnd
     bool frontEnd(CameraQueueEntry const& cam, bool stereo, int slot);
     double m_lastFrameSeconds = 0;
     int m_maxKp = 0;

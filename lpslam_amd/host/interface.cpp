@@ -4,6 +4,7 @@
 #include <atomic>
 #include "../../include/lpslam_manager.h"
 #include "slam_manager.h"
+#include "intensity.h"
 #include "jpeg.h"
 #include "map_file.h"
 #include "occupancy.h"
@@ -199,6 +200,14 @@ LPS_API void lpslam_occupancy_scan_pose(const double* T_cw, const LpSlamGlobalSt
     LpSlam::scanPose(R, t, Rcl, tcl, out, out + 2, out + 4);
 }
 // interface.type_conversion of the reference's tests (src/test/InterfaceTest.cpp:14-33): POD -> internal -> POD
+// the host implementation of the AdjustIntensity arithmetic (intensity.h), in place: params = {low_out, high_out, low_fraction,
+// high_fraction} (NULL: the reference's constants); out_lo_hi (may be NULL) receives the limits.  0: invalid arguments, nothing written.
+LPS_API int lpslam_adjust_intensity(uint8_t* pixels, int width, int height, size_t stride, const double* params, int* out_lo_hi) {
+    LpSlam::IntensityAdjust p;
+    if (params) { p.low_out = params[0]; p.high_out = params[1]; p.low_fraction = params[2]; p.high_fraction = params[3]; }
+    return LpSlam::adjust_intensity_host(pixels, width, height, stride, p, out_lo_hi) ? 1 : 0;
+}
+
 LPS_API void lpslam_roundtrip_state(const LpSlamGlobalStateInTime* in, LpSlamGlobalStateInTime* out) {
     *out = LpSlam::conversion::gsInTimeInternalToInterface(LpSlam::conversion::gsInTimeInterfaceToInternal(*in));
 }

@@ -1,5 +1,6 @@
 // slam_manager.cpp -- see slam_manager.h.
 #include "slam_manager.h"
+#include "intensity.h"
 #include "jpeg.h"
 #include "replay.h"
 
@@ -56,12 +57,35 @@ bool SlamManager::addTracker(std::string const& name, std::string const& jsonCon
     return false;
 }
 
-bool SlamManager::addProcessor(std::string const& name, std::string const&)
+bool SlamManager::addProcessor(std::string const& name, std::string const& jsonConfig)
 {
-    // the reference's processors (BlackoutImage, AdjustIntensity, CameraCalibration) are outside the accelerated path;
-    // the ProcessorBase hook is kept for client-side plugins
+    // of the reference's processors AdjustIntensity is built in (intensity.h); BlackoutImage and CameraCalibration are not part of
+    // this library, and the ProcessorBase hook is kept for client-side plugins
+    std::unique_ptr<ProcessorBase> processor;
+    if (name == "AdjustIntensity") processor = std::make_unique<AdjustIntensityProcessor>();
+    if (processor) {
+        if (!processor->setConfig(jsonConfig)) { logMessage(LpSlamLogLevel_Error, "Cannot parse config for processor " + processor->type()); return false; }
+        logMessage(LpSlamLogLevel_Info, "Processor " + processor->type() + " added");
+        m_processors.emplace_back(std::move(processor));
+        return true;
+    }
     logMessage(LpSlamLogLevel_Error, "Processor with name " + name + " not found");
     return false;
+}
+
+// The processors see every frame once, in arrival order (src/Manager/SlamManager.cpp:114-116).  One that reads the pixels gets them with
+// every earlier request applied (intensity.h).
+void SlamManager::runProcessors(CameraQueueEntry& cam)
+{
+    if (cam.processed) return;
+    cam.processed = true;
+    for (auto& p : m_processors) {
+        if (p->readsPixels()) realiseAdjust(cam);
+        p->processImage(cam);
+    }
+    // somebody will need the pixels on the host anyway (the recorder, a tracker that does not adjust on its own): now, before a tracker
+    // may prefetch the frame -- the prefetch then carries the adjusted pixels, and nobody rewrites a buffer an upload reads
+    if (cam.adjust && m_recorder.active()) realiseAdjust(cam);
 }
 
 bool SlamManager::addSource(std::string const& name, std::string const&)
@@ -340,22 +364,33 @@ bool SlamManager::workerStep()
 {
     streamMoreReplayItems();                           // SlamManager.cpp:56-57
     CameraQueueEntry cam;
-    if (m_lookahead) { cam = std::move(*m_lookahead); m_lookahead.reset(); }
+    std::optional<CameraQueueEntry> callbackCopy;
+    if (m_lookahead) { cam = std::move(*m_lookahead); m_lookahead.reset(); callbackCopy = std::move(m_lookaheadCallbackCopy); m_lookaheadCallbackCopy.reset(); }
     else m_camQueue.pop(cam);
     const auto t_taken = std::chrono::steady_clock::now();
     if (!cam.valid || m_stopRequested.load()) return false;   // exit signal; a stop abandons the backlog (SlamManager::stop)
-    // every frame the worker takes also goes to the image-callback thread (SlamManager.cpp:64-66); a copy: the tracker consumes `cam`
-    if (m_pushToImageCallbackQueue) {
+    // every frame the worker takes also goes to the image-callback thread (SlamManager.cpp:64-66); a copy: the tracker consumes `cam`.
+    // Taken before the processors run (a lookahead frame: when it was taken ahead), so the callback sees the frame as it arrived.
+    auto imageCallbackCopy = [](const CameraQueueEntry& from) {
         CameraQueueEntry copy;
-        copy.valid = true; copy.timestamp = cam.timestamp; copy.cameraNumber = cam.cameraNumber; copy.cameraNumberSecond = cam.cameraNumberSecond;
-        copy.image = cam.image; copy.image_second = cam.image_second;
-        m_imageCallbackQueue.push(std::move(copy));
-    }
+        copy.valid = true; copy.timestamp = from.timestamp; copy.cameraNumber = from.cameraNumber; copy.cameraNumberSecond = from.cameraNumberSecond;
+        copy.image = from.image; copy.image_second = from.image_second;
+        return copy;
+    };
+    if (m_pushToImageCallbackQueue) m_imageCallbackQueue.push(callbackCopy ? std::move(*callbackCopy) : imageCallbackCopy(cam));
+    runProcessors(cam);
     // one frame of lookahead, owned by this thread: if another frame is already queued the trackers learn about it, and may start
-    // its upload and extraction on the GPU beside the tracking of this frame
+    // its upload and extraction on the GPU beside the tracking of this frame.  The processors see it now, after the current frame:
+    // what they ask for (an intensity adjustment) is part of what a tracker prefetches.
     {
         CameraQueueEntry next;
-        if (m_camQueue.try_pop(next)) m_lookahead = std::move(next);
+        if (m_camQueue.try_pop(next)) {
+            if (next.valid) {
+                if (m_pushToImageCallbackQueue && !m_processors.empty()) m_lookaheadCallbackCopy = imageCallbackCopy(next);
+                runProcessors(next);
+            }
+            m_lookahead = std::move(next);
+        }
     }
     const CameraQueueEntry* next_frame = (m_lookahead && m_lookahead->valid) ? &*m_lookahead : nullptr;
     const auto now = std::chrono::steady_clock::now();
@@ -368,7 +403,6 @@ bool SlamManager::workerStep()
     std::vector<SensorQueueEntry> sensors;
     SensorQueueEntry se;
     while (m_sensorQueue.try_pop(se)) { sensors.push_back(se); if (se.timestamp > cam.timestamp) break; }
-    for (auto& p : m_processors) p->processImage(cam);
 
     std::optional<GlobalStateInTime> odom, map;
     if (m_requestNavData != nullptr && cam.ros_timestamp.has_value()) {
@@ -379,6 +413,7 @@ bool SlamManager::workerStep()
     }
     // the recorder gets every frame taken, before the trackers run (SlamManager.cpp:187): frames skipped for lack of odometry too
     if (m_recorder.active()) {
+        realiseAdjust(cam);                             // the recorder stores the frame the trackers get (SlamManager.cpp:187 comes after :114); done by runProcessors already
         const int64_t n = m_framesTaken++;
         m_recorder.storeCameraImage(cam, odom, map, (m_writeImageFiles && n % 10 == 0) ? n : -1);
     }
@@ -389,6 +424,7 @@ bool SlamManager::workerStep()
             ++m_framesSkipped;
             break;
         }
+        if (!tracker->realisesAdjust()) realiseAdjust(cam);
         tracker->setNextFrame(next_frame);
         const auto t_in = std::chrono::steady_clock::now();
         auto results = tracker->processImage(cam, odom, map, sensors);
@@ -492,6 +528,7 @@ void SlamManager::stop()
     m_camQueue.push(std::move(poison));
     if (m_worker.joinable()) m_worker.join();
     m_lookahead.reset();                                // the frame the worker had taken ahead is part of the abandoned backlog
+    m_lookaheadCallbackCopy.reset();
     m_camQueue.clear();                                 // ... and so is the exit signal if the worker left on the stop flag
     ResultQueueEntry rp; rp.exitSignal = true;
     m_resultQueue.push(rp);

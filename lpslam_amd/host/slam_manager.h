@@ -67,6 +67,7 @@ public:
 private:
     void streamMoreReplayItems();
     bool workerStep();
+    void runProcessors(CameraQueueEntry& cam);
     bool notifyStep();
     bool imageCallbackStep();
 
@@ -88,6 +89,7 @@ private:
     double m_secondsInWorker = 0, m_secondsInTrackers = 0;      // worker thread only (logged by stop()): a frame from the moment it is taken / inside processImage
     std::atomic<bool> m_stopRequested{false};
     std::optional<CameraQueueEntry> m_lookahead;       // worker thread only: the frame after the one being processed
+    std::optional<CameraQueueEntry> m_lookaheadCallbackCopy;      // ... and, with processors and an image callback, its copy for that callback, taken before the processors saw it
     Recorder m_recorder;
     bool m_record = false;               // setRecord / "manager": {"record": true}
     bool m_writeImageFiles = false;      // setWriteImageFiles: every 10th frame taken as <n>_left.jpg / <n>_right.jpg (SlamManager.cpp:70-85)

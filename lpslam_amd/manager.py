@@ -336,6 +336,28 @@ class Manager:
         return info.as_dict(), buf[:w * h].reshape(h, w)
 
 
+def adjust_intensity(img, low_out=-0.3, high_out=1.4, low_fraction=0.01, high_fraction=0.99, padding=None):
+    """the host implementation of the AdjustIntensity processor's arithmetic (lpslam_adjust_intensity), CPU only: `img` is a 2-D uint8
+    array whose rows may be strided (a view of a wider array); returns (adjusted copy of the same shape, lo, hi), or None when the
+    library rejects the arguments.  padding: a list that receives the bytes between the rows after the call (they start as 0xA5)"""
+    import numpy as np
+    assert img.dtype == np.uint8 and img.ndim == 2 and (img.shape[1] == 1 or img.strides[1] == 1)
+    h, w = img.shape
+    stride = max(int(img.strides[0]), w)
+    buf = np.full(h * stride, 0xA5, np.uint8)
+    rows = np.lib.stride_tricks.as_strided(buf, shape=(h, w), strides=(stride, 1))
+    rows[...] = img
+    params = (C.c_double * 4)(float(low_out), float(high_out), float(low_fraction), float(high_fraction))
+    lo_hi = (C.c_int * 2)(-1, -1)
+    f = load().lpslam_adjust_intensity
+    f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    if not f(buf.ctypes.data, w, h, stride, params, lo_hi):
+        return None
+    if padding is not None:
+        padding.append(buf.reshape(h, stride)[:, w:].copy())
+    return rows.copy(), int(lo_hi[0]), int(lo_hi[1])
+
+
 def laser_state(R, t):
     """LpSlamGlobalState of a rotation matrix and a translation (lpslam axes)"""
     import numpy as np
