@@ -634,6 +634,32 @@ int lpslam_hip_jpeg_encode(lpslam_hip_jpeg* enc, int32_t n, const uint8_t* const
                            const int32_t* heights, const int32_t* strides, int32_t quality,
                            uint8_t* const* outs, const int64_t* caps, int64_t* sizes);
 
+/* ---- baseline JPEG decoder: the other direction (replay of a recording, compressed frames handed in by a client) --------------------
+ * A standalone object like the encoder (no lpslam_hip_ctx, its own stream and buffers), sized at creation for max_images streams of at
+ * most max_width x max_height samples.  One decode call is one upload, one launch chain and one wait for the whole batch (both eyes
+ * of a record).  The samples of a decoded image are bit for bit those of the host decoder (LpSlam::decode_jpeg_gray,
+ * lpslam_jpeg_decode_gray), which are libjpeg's.  Calls on one decoder are serialised.  Every image gets a status: */
+#define LPSLAM_HIP_JPEG_DECODED 0      /* the samples are in outs[i] */
+#define LPSLAM_HIP_JPEG_NOT_TAKEN 1    /* a valid file of a class left to the host decoder: three components, a restart interval,
+                                          16-bit quantisation tables, larger than the decoder was made for, or more than 4 bytes per sample
+                                          + 4096 from the start of the entropy-coded data to the end of the file (a trailer counts) */
+#define LPSLAM_HIP_JPEG_IRREGULAR 2    /* the header does not parse, or the entropy-coded data does not end where the block count says
+                                          it must: the host decoder gives the verdict */
+typedef struct lpslam_hip_jpeg_dec lpslam_hip_jpeg_dec;
+int lpslam_hip_jpeg_dec_create(int32_t max_width, int32_t max_height, int32_t max_images, lpslam_hip_jpeg_dec** out);
+void lpslam_hip_jpeg_dec_destroy(lpslam_hip_jpeg_dec* dec);
+/* n complete JPEG files (host memory) -> samples in outs[i], rows out_strides[i] bytes apart, capacity out_caps[i] bytes.  widths[i] /
+ * heights[i] are always set from the frame header when there is one (0 otherwise).  If the samples of an image the device takes do
+ * not fit its out_caps[i] (or out_strides[i] is below its width): LPSLAM_HIP_ERR_INVALID, the sizes are reported and no output buffer
+ * is written.  n outside 1 .. max_images or a null argument: LPSLAM_HIP_ERR_INVALID.  Otherwise LPSLAM_HIP_OK and status[i] says what
+ * became of every image; only the buffers of DECODED images are written. */
+int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* dec, int32_t n, const uint8_t* const* streams, const int64_t* stream_sizes,
+                           uint8_t* const* outs, const int32_t* out_strides, const int64_t* out_caps,
+                           int32_t* widths, int32_t* heights, int32_t* status);
+/* test hook: per image of the last decode call (n as there) the synchronisation rounds that changed a subsequence state, the
+ * subsequences of its entropy-coded data, and the blocks they completed; zeros for an image the device did not take. */
+int lpslam_hip_jpeg_dec_last(lpslam_hip_jpeg_dec* dec, int32_t n, int32_t* rounds, int32_t* subsequences, int32_t* blocks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,8 @@ constexpr long long F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 
                     F_1_175875602 = 9633, F_1_501321110 = 12299, F_1_847759065 = 15137, F_1_961570560 = 16069, F_2_053119869 = 16819,
                     F_2_562915447 = 20995, F_3_072711026 = 25172;
 
+#include "jpeg_scan.inl"
+
 __device__ __forceinline__ int descale(long long x, int n) { return (int)((x + (1LL << (n - 1))) >> n); }
 
 // one pass of libjpeg's jpeg_fdct_islow on 8 values (host: fdct_islow in host/jpeg.cpp, the same integers); pass 0 = rows
@@ -98,18 +100,6 @@ __device__ __forceinline__ void fdct8(int d[8])
 
 __device__ __forceinline__ int category(int v) { const int a = v < 0 ? -v : v; return a ? 32 - __clz(a) : 0; }
 __device__ __forceinline__ int hlen(unsigned int e) { return (int)(e >> 16); }
-
-__device__ __forceinline__ int wave_sum(int x)
-{
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-    return x;
-}
-__device__ __forceinline__ int wave_exclusive(int x, int lane)
-{
-    int s = x;
-    for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(s, d); if (lane >= d) s += y; }
-    return s - x;
-}
 
 // the AC symbols of lane `lane` (zigzag index) of a block whose coefficient there is v; nz = ballot of the non-zero AC coefficients.
 // Returns the lane's bit count; run / eob describe the symbols for the packer.
@@ -190,25 +180,6 @@ __device__ __forceinline__ unsigned int block_bits(const JpegArgs& a, const Jpeg
     const long long b = im.blk0 + lb;
     const int s = category(a.dc[b] - (lb > 0 ? a.dc[b - 1] : 0));
     return a.acbits[b] + (unsigned int)(hlen(huff[256 + s]) + s);
-}
-
-// exclusive scan of one value per thread over the workgroup; returns the prefix, *total = the sum
-__device__ unsigned int block_exclusive(unsigned int x, unsigned int* wsum, unsigned int* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const unsigned int pre = (unsigned int)wave_exclusive((int)x, lane);
-    if (lane == 63) wsum[wave] = pre + x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned int s = 0;
-        for (int w = 0; w < nw; ++w) { const unsigned int v = wsum[w]; wsum[w] = s; s += v; }
-        wsum[nw] = s;
-    }
-    __syncthreads();
-    const unsigned int r = wsum[wave] + pre;
-    *total = wsum[nw];
-    __syncthreads();
-    return r;
 }
 
 __global__ __launch_bounds__(kScanThreads) void k_jpeg_offsets(JpegArgs a)

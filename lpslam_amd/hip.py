@@ -44,6 +44,7 @@ SYMBOLS = [
     "lpslam_hip_sim3_create", "lpslam_hip_sim3_destroy", "lpslam_hip_sim3_optimize", "lpslam_hip_sim3_get", "lpslam_hip_sim3_chi2", "lpslam_hip_sim3_transform_optimize",
     "lpslam_hip_scan_geometry_put", "lpslam_hip_scan_store_put", "lpslam_hip_scan_store_drop", "lpslam_hip_occupancy_build",
     "lpslam_hip_jpeg_create", "lpslam_hip_jpeg_destroy", "lpslam_hip_jpeg_encode",
+    "lpslam_hip_jpeg_dec_create", "lpslam_hip_jpeg_dec_destroy", "lpslam_hip_jpeg_decode", "lpslam_hip_jpeg_dec_last",
     "lpslam_hip_adjust_intensity", "lpslam_hip_upload_raw_image_adjusted", "lpslam_hip_front_end_images_adjusted", "lpslam_hip_adjust_intensity_last",
 ]
 
@@ -1014,3 +1015,67 @@ class JpegEncoder:
         rc, sizes, outs = self.encode_raw(images, quality)
         _check(rc)
         return [o[:s].tobytes() for o, s in zip(outs, sizes)]
+
+
+JPEG_DECODED, JPEG_NOT_TAKEN, JPEG_IRREGULAR = 0, 1, 2
+
+
+class JpegDecoder:
+    """Baseline JPEG decoder on the device (lpslam_hip_jpeg_dec_*): streams in, the host decoder's samples out, bit for bit.  Every
+    image gets a status: JPEG_DECODED, JPEG_NOT_TAKEN (a class left to the host decoder) or JPEG_IRREGULAR (the host decoder gives the
+    verdict)."""
+
+    def __init__(self, max_width, max_height, max_images=2):
+        self.lib = load()
+        self.lib.lpslam_hip_jpeg_dec_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        self.lib.lpslam_hip_jpeg_dec_destroy.argtypes = [C.c_void_p]
+        self.lib.lpslam_hip_jpeg_decode.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
+        self.lib.lpslam_hip_jpeg_dec_last.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        h = C.c_void_p()
+        _check(self.lib.lpslam_hip_jpeg_dec_create(int(max_width), int(max_height), int(max_images), C.byref(h)))
+        self.h = h
+        self.max_width, self.max_height, self.max_images = int(max_width), int(max_height), int(max_images)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.lpslam_hip_jpeg_dec_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def decode_raw(self, streams, caps=None, strides=None):
+        """one call for the list of streams (bytes): returns (rc, status, widths, heights, outputs); outputs are uint8 arrays of capacity
+        caps[i] (default: the decoder's maximum) filled with 0xA5 before the call, rows strides[i] apart (default: the maximum width)"""
+        n = len(streams)
+        bufs = [np.frombuffer(bytes(s), np.uint8) if len(s) else np.zeros(1, np.uint8) for s in streams]
+        if strides is None:
+            strides = [self.max_width] * n
+        if caps is None:
+            caps = [self.max_width * self.max_height] * n
+        outs = [np.full(max(int(c), 1), 0xA5, np.uint8) for c in caps]
+        sp = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        op = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+        ss = np.array([len(s) for s in streams] or [0], np.int64)
+        st = np.array(list(strides) or [0], np.int32)
+        cp = np.array(list(caps) or [0], np.int64)
+        w = np.full(max(n, 1), -1, np.int32); hh = np.full(max(n, 1), -1, np.int32); status = np.full(max(n, 1), -1, np.int32)
+        rc = self.lib.lpslam_hip_jpeg_decode(self.h, n, sp, _p(ss), op, _p(st), _p(cp), _p(w), _p(hh), _p(status))
+        return rc, status[:n].copy(), w[:n].copy(), hh[:n].copy(), outs
+
+    def decode(self, streams):
+        """list of streams -> list of (status, image or None); raises on an error of the call itself"""
+        rc, status, w, h, outs = self.decode_raw(streams)
+        _check(rc)
+        res = []
+        for s, ww, hh, o in zip(status, w, h, outs):
+            if s != JPEG_DECODED:
+                res.append((int(s), None))
+                continue
+            res.append((int(s), np.lib.stride_tricks.as_strided(o, (int(hh), int(ww)), (self.max_width, 1)).copy()))
+        return res
+
+    def last(self, n):
+        """test hook: per image of the last call (rounds, subsequences, blocks)"""
+        r = np.zeros(n, np.int32); s = np.zeros(n, np.int32); b = np.zeros(n, np.int32)
+        _check(self.lib.lpslam_hip_jpeg_dec_last(self.h, int(n), _p(r), _p(s), _p(b)))
+        return [(int(x), int(y), int(z)) for x, y, z in zip(r, s, b)]

@@ -141,6 +141,12 @@ LPS_API void lpslam_manager_recorder_counters(lpslam_c_manager* m, uint64_t* out
     const LpSlam::RecorderCounters c = impl ? impl->recorderCounters() : LpSlam::RecorderCounters{};
     out[0] = c.device_images; out[1] = c.host_images; out[2] = c.records; out[3] = c.bytes;
 }
+// test hook: out[3] = compressed images decoded on the device, decoded on the host, refused by both (this manager's replay and ingest)
+LPS_API void lpslam_manager_decoder_counters(lpslam_c_manager* m, uint64_t* out) {
+    LpSlam::SlamManager* impl = *reinterpret_cast<LpSlam::SlamManager**>(&m->mgr);
+    const LpSlam::JpegDecodeCounters c = impl ? impl->decoderCounters() : LpSlam::JpegDecodeCounters{};
+    out[0] = c.device_images; out[1] = c.host_images; out[2] = c.refused_images;
+}
 LPS_API size_t lpslam_manager_features_count(lpslam_c_manager* m) { return m->mgr.mappingGetFeaturesCount(LpSlamMapBoundary{}); }
 LPS_API int lpslam_manager_mapping_set_mode(lpslam_c_manager* m, int enable) { return m->mgr.mappingSetMode(enable != 0) ? 1 : 0; }
 LPS_API int lpslam_manager_mapping_set_filename(lpslam_c_manager* m, const char* f) { return m->mgr.mappingSetFilename(f ? f : "") ? 1 : 0; }

@@ -2,6 +2,7 @@
 // Huffman procedures of Annex F, table construction of Annex C) and the published description of libjpeg's "islow" inverse DCT
 // (Loeffler-Ligtenberg-Moschytz, 13-bit constants, two passes with 2 extra bits after the first) so that the samples are libjpeg's.
 #include "jpeg.h"
+#include "jpeg_header.h"
 #include "jpeg_tables.h"
 
 #include <algorithm>
@@ -13,36 +14,8 @@ namespace {
 
 using jpeg::kZigzag;
 
-struct HuffTable {
-    bool present = false;
-    uint8_t bits[17] = {0};          // codes of each length 1..16
-    uint8_t vals[256] = {0};
-    // decoding (T.81 F.2.2.3): smallest / largest code of every length and the index of its first value
-    int32_t mincode[17], maxcode[18], valptr[17];
-    // 9-bit look-ahead: (length << 8) | symbol, 0 = longer than 9 bits
-    uint16_t look[512];
-    bool build()
-    {
-        int code = 0, k = 0;
-        std::memset(look, 0, sizeof(look));
-        for (int l = 1; l <= 16; ++l) {
-            valptr[l] = k; mincode[l] = code;
-            for (int i = 0; i < bits[l]; ++i, ++k, ++code) {
-                if (k >= 256) return false;
-                if (l <= 9) {
-                    const int first = code << (9 - l), n = 1 << (9 - l);
-                    if (first + n > 512) return false;
-                    for (int j = 0; j < n; ++j) look[first + j] = (uint16_t)((l << 8) | vals[k]);
-                }
-            }
-            maxcode[l] = bits[l] ? code - 1 : -1;
-            if (code > (1 << l)) return false;                      // over-subscribed
-            code <<= 1;
-        }
-        maxcode[17] = 0x7FFFFFFF;
-        return true;
-    }
-};
+using jpeg::HuffTable;
+using jpeg::Component;
 
 struct BitReader {
     const uint8_t* p; const uint8_t* end;
@@ -155,8 +128,6 @@ void idct_islow(const int16_t* coef, const uint16_t* quant, uint8_t* out, int pi
     }
 }
 
-struct Component { int id = 0, h = 1, v = 1, tq = 0, td = 0, ta = 0; int pred = 0; };
-
 bool fail(std::string* why, const char* msg) { if (why) *why = msg; return false; }
 
 }  // namespace
@@ -164,93 +135,23 @@ bool fail(std::string* why, const char* msg) { if (why) *why = msg; return false
 bool decode_jpeg_gray(const uint8_t* d, size_t size, GrayImage& out, std::string* why)
 {
     if (!looks_like_jpeg(d, size)) return fail(why, "not a JPEG stream (no SOI)");
-    uint16_t quant[4][64]; bool have_q[4] = {false, false, false, false};
-    HuffTable dc[4], ac[4];
-    Component comp[4];
-    int ncomp = 0, X = 0, Y = 0, hmax = 1, vmax = 1, restart_interval = 0;
-    bool have_frame = false, decoded_luma = false;
+    jpeg::Header hd;
+    jpeg::Scan scan;
+    uint16_t (&quant)[4][64] = hd.quant;
+    HuffTable (&dc)[4] = hd.dc; HuffTable (&ac)[4] = hd.ac;
+    Component (&comp)[4] = hd.comp;
     std::vector<uint8_t> plane;            // component 0, padded to whole blocks / MCUs
-    int plane_w = 0, plane_h = 0;
     size_t pos = 2;
-    auto u16 = [&](size_t o) { return (int)((d[o] << 8) | d[o + 1]); };
     for (;;) {
-        // next marker (skip anything that is not FF, then fill FFs)
-        while (pos < size && d[pos] != 0xFF) ++pos;
-        while (pos < size && d[pos] == 0xFF) ++pos;
-        if (pos >= size) break;
-        const int m = d[pos++];
-        if (m == 0xD9) break;                                                          // EOI
-        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7) || m == 0x00) continue;               // stand-alone
-        if (pos + 2 > size) return fail(why, "truncated marker segment");
-        const int len = u16(pos);
-        if (len < 2 || pos + (size_t)len > size) return fail(why, "bad marker segment length");
-        const uint8_t* s = d + pos + 2; const int n = len - 2;
-        if (m == 0xDB) {                                                               // DQT
-            int o = 0;
-            while (o < n) {
-                const int pq = s[o] >> 4, tq = s[o] & 15; ++o;
-                if (tq > 3 || pq > 1 || o + 64 * (pq + 1) > n) return fail(why, "bad quantisation table");
-                for (int k = 0; k < 64; ++k) { quant[tq][kZigzag[k]] = pq ? (uint16_t)((s[o] << 8) | s[o + 1]) : s[o]; o += pq + 1; }
-                have_q[tq] = true;
-            }
-        } else if (m == 0xC4) {                                                        // DHT
-            int o = 0;
-            while (o < n) {
-                if (o + 17 > n) return fail(why, "bad Huffman table");
-                const int tc = s[o] >> 4, th = s[o] & 15; ++o;
-                if (tc > 1 || th > 3) return fail(why, "bad Huffman table id");
-                HuffTable& t = tc ? ac[th] : dc[th];
-                int total = 0;
-                for (int l = 1; l <= 16; ++l) { t.bits[l] = s[o + l - 1]; total += t.bits[l]; }
-                o += 16;
-                if (total > 256 || o + total > n) return fail(why, "bad Huffman table size");
-                std::memcpy(t.vals, s + o, (size_t)total); o += total;
-                if (!t.build()) return fail(why, "inconsistent Huffman table");
-                t.present = true;
-            }
-        } else if (m == 0xC0 || m == 0xC1) {                                           // SOF0 / SOF1: Huffman, sequential
-            if (have_frame) return fail(why, "second frame header");
-            if (n < 6) return fail(why, "bad frame header");
-            if (s[0] != 8) return fail(why, "only 8-bit samples are supported");
-            Y = u16(pos + 3); X = u16(pos + 5); ncomp = s[5];
-            if (X <= 0 || Y <= 0 || (ncomp != 1 && ncomp != 3) || n < 6 + 3 * ncomp) return fail(why, "unsupported frame (size / component count)");
-            if ((size_t)X * (size_t)Y > (size_t)1 << 28) return fail(why, "frame too large");
-            for (int i = 0; i < ncomp; ++i) {
-                comp[i].id = s[6 + 3 * i]; comp[i].h = s[7 + 3 * i] >> 4; comp[i].v = s[7 + 3 * i] & 15; comp[i].tq = s[8 + 3 * i];
-                if (comp[i].h < 1 || comp[i].h > 4 || comp[i].v < 1 || comp[i].v > 4 || comp[i].tq > 3) return fail(why, "bad component description");
-                hmax = std::max(hmax, comp[i].h); vmax = std::max(vmax, comp[i].v);
-            }
-            if (ncomp == 1) { comp[0].h = comp[0].v = 1; hmax = vmax = 1; }             // a single component is never interleaved
-            // the grey output is component 0's plane as it is coded: a file whose first component is SUBSAMPLED against another one
-            // (luma 1x1 beside chroma 2x2, which no camera or encoder of this code base writes) would need libjpeg's upsampling
-            if (comp[0].h != hmax || comp[0].v != vmax) return fail(why, "first component is subsampled (not supported)");
-            const int mcux = (X + 8 * hmax - 1) / (8 * hmax), mcuy = (Y + 8 * vmax - 1) / (8 * vmax);
-            plane_w = mcux * comp[0].h * 8; plane_h = mcuy * comp[0].v * 8;
-            if (plane_w < X || plane_h < Y) return fail(why, "frame geometry is inconsistent");
-            plane.assign((size_t)plane_w * plane_h, 0);
-            have_frame = true;
-        } else if (m == 0xC2 || (m >= 0xC5 && m <= 0xCF && m != 0xC8 && m != 0xCC) || m == 0xC3) {
-            return fail(why, m == 0xC2 ? "progressive JPEG is not supported (baseline only)" : "unsupported JPEG process (arithmetic / lossless / hierarchical)");
-        } else if (m == 0xDD) {                                                        // DRI
-            if (n < 2) return fail(why, "bad restart interval");
-            restart_interval = u16(pos + 2);
-        } else if (m == 0xDA) {                                                        // SOS + entropy-coded data
-            if (!have_frame) return fail(why, "scan before the frame header");
-            if (n < 1) return fail(why, "bad scan header");
-            const int ns = s[0];
-            if (ns < 1 || ns > ncomp || n < 1 + 2 * ns + 3) return fail(why, "bad scan header");
-            int idx[4];
-            for (int i = 0; i < ns; ++i) {
-                int ci = -1;
-                for (int c = 0; c < ncomp; ++c) if (comp[c].id == s[1 + 2 * i]) ci = c;
-                if (ci < 0) return fail(why, "scan names an unknown component");
-                for (int k = 0; k < i; ++k) if (idx[k] == ci) return fail(why, "scan names a component twice");
-                if (ci == 0 && decoded_luma) return fail(why, "second scan of the first component in a sequential file");
-                comp[ci].td = s[2 + 2 * i] >> 4; comp[ci].ta = s[2 + 2 * i] & 15;
-                if (comp[ci].td > 3 || comp[ci].ta > 3 || !dc[comp[ci].td].present || !ac[comp[ci].ta].present || !have_q[comp[ci].tq]) return fail(why, "scan uses a missing table");
-                idx[i] = ci;
-            }
-            BitReader br{d + pos + (size_t)len, d + size};
+        const jpeg::Walk w = jpeg::walk_to_scan(d, size, pos, hd, scan, why);         // the marker segments up to the next scan (jpeg_header.h)
+        if (w == jpeg::Walk::error) return false;
+        if (w == jpeg::Walk::end) break;
+        {
+            const int ncomp = hd.ncomp, X = hd.X, Y = hd.Y, hmax = hd.hmax, vmax = hd.vmax, restart_interval = hd.restart_interval;
+            const int plane_w = hd.plane_w, plane_h = hd.plane_h, ns = scan.ns;
+            const int* idx = scan.idx;
+            if (plane.empty()) plane.assign((size_t)plane_w * plane_h, 0);
+            BitReader br{d + scan.data, d + size};
             for (int c = 0; c < ncomp; ++c) comp[c].pred = 0;
             int16_t block[64];
             auto decode_block = [&](Component& c, bool keep, int bx, int by) -> bool {
@@ -306,16 +207,14 @@ bool decode_jpeg_gray(const uint8_t* d, size_t size, GrayImage& out, std::string
                         ++count;
                     }
             }
-            for (int i = 0; i < ns; ++i) if (idx[i] == 0) decoded_luma = true;
+            for (int i = 0; i < ns; ++i) if (idx[i] == 0) hd.decoded_luma = true;
             // continue behind the entropy-coded data: at the marker the reader stopped at, or scan for the next one
-            size_t q = (size_t)(br.p - d);
+            const size_t q = (size_t)(br.p - d);
             pos = q >= 2 ? q - 2 : q;
-            if (br.marker) { pos = q - 2; continue; }
-            continue;
         }
-        pos += (size_t)len;
     }
-    if (!have_frame || !decoded_luma) return fail(why, "no image data");
+    if (!hd.have_frame || !hd.decoded_luma) return fail(why, "no image data");
+    const int X = hd.X, Y = hd.Y, plane_w = hd.plane_w, plane_h = hd.plane_h;
     if (plane_w < X || plane_h < Y || plane.size() < (size_t)plane_w * (size_t)Y) return fail(why, "frame geometry is inconsistent");
     out.width = X; out.height = Y;
     out.pixels.resize((size_t)X * Y);

@@ -102,6 +102,37 @@ bool ReplayReader::open(const std::string& path, std::string* err)
     return true;
 }
 
+// The image(s) of one record.  JPEG payloads go to the decoder together (one device call for the two eyes); a PGM payload never
+// touches the device path.  Two JPEG payloads are handed over together, so both are looked at (and both counted as refused) even when the
+// first one cannot be decoded; the record is refused either way, as before.
+bool ReplayReader::decodeImages(const uint8_t* img, size_t img_n, const uint8_t* img2, size_t img2_n, bool stereo, ReplayFrame& fr)
+{
+    if (!img || (stereo && !img2)) return false;
+    const bool j1 = looks_like_jpeg(img, img_n), j2 = stereo && looks_like_jpeg(img2, img2_n);
+    if (!j1 && !j2) {
+        if (!decode_image(img, img_n, fr.image)) return false;
+        if (stereo) { GrayImage second; if (!decode_image(img2, img2_n, second)) return false; fr.image_second = std::move(second); }
+        return true;
+    }
+    if (!m_decoder) m_decoder = std::make_shared<JpegDecoder>();
+    GrayImage second;
+    if (j1 && j2) {
+        const uint8_t* d[2] = {img, img2}; const size_t sz[2] = {img_n, img2_n}; GrayImage* o[2] = {&fr.image, &second}; bool ok[2];
+        if (!m_decoder->decode(2, d, sz, o, ok)) return false;
+    } else {
+        // one JPEG payload beside a PGM one (no recorder writes that): each by its own decoder, the first image first
+        const uint8_t* d[1]; size_t sz[1]; GrayImage* o[1]; bool ok[1];
+        if (j1) { d[0] = img; sz[0] = img_n; o[0] = &fr.image; if (!m_decoder->decode(1, d, sz, o, ok)) return false; }
+        else if (!decode_pgm(img, img_n, fr.image)) return false;
+        if (stereo) {
+            if (j2) { d[0] = img2; sz[0] = img2_n; o[0] = &second; if (!m_decoder->decode(1, d, sz, o, ok)) return false; }
+            else if (!decode_pgm(img2, img2_n, second)) return false;
+        }
+    }
+    if (stereo) fr.image_second = std::move(second);
+    return true;
+}
+
 // The next decodable camera frame; false at the end of the stream (clean, or the first record the format does not know).
 bool ReplayReader::next(ReplayFrame& out)
 {
@@ -146,12 +177,7 @@ bool ReplayReader::next(ReplayFrame& out)
             }
         }
         if (!c.ok) { stats.truncated = true; break; }
-        if (!img || !decode_image(img, img_n, fr.image)) { ++stats.undecodable_images; continue; }
-        if (has_base2) {
-            GrayImage second;
-            if (!img2 || !decode_image(img2, img2_n, second)) { ++stats.undecodable_images; continue; }
-            fr.image_second = std::move(second);
-        }
+        if (!decodeImages(img, img_n, img2, img2_n, has_base2, fr)) { ++stats.undecodable_images; continue; }
         if (has_odom && flag_odom) fr.odom = odom;
         if (has_map && flag_map) fr.map = map;
         out = std::move(fr);

@@ -11,10 +11,12 @@
 #pragma once
 #include <cstdint>
 #include <fstream>
+#include <memory>
 #include <optional>
 #include <string>
 #include <vector>
 #include "core.h"
+#include "jpeg_device.h"
 
 namespace LpSlam {
 
@@ -45,7 +47,12 @@ public:
     bool next(ReplayFrame& out);
     bool done() const { return m_done; }
     const ReplayStats& stats() const { return m_stats; }
+    // JPEG payloads go through the reader's decoder (jpeg_device.h: the device where there is one, the host decoder otherwise; both images
+    // of a record in one call).  A manager hands its readers the decoder it counts with.
+    void setDecoder(std::shared_ptr<JpegDecoder> d) { m_decoder = std::move(d); }
 private:
+    bool decodeImages(const uint8_t* img, size_t img_n, const uint8_t* img2, size_t img2_n, bool stereo, ReplayFrame& fr);
+    std::shared_ptr<JpegDecoder> m_decoder;          // made at the first JPEG payload when nobody set one
     std::ifstream m_in;
     std::vector<uint8_t> m_buf;
     ReplayStats m_stats;

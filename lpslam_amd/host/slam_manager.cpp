@@ -134,6 +134,7 @@ bool SlamManager::readConfigurationFile(std::string const& filename)
             if (const Json* t = m->find("thread_num")) m_thread_num = (int)t->asNumber();
             if (const Json* r = m->find("require_odometry")) m_requireOdometry = r->asBool();
             if (const Json* r = m->find("record_raw")) m_recorder.setWriteRawFile(r->asBool());
+            if (const Json* r = m->find("jpeg_decode_device")) m_jpegDecoder->setUseDevice(r->asBool());
             if (const Json* c = m->find("replay_chunks")) m_replayChunk = (size_t)std::max(1.0, c->asNumber());   // SlamManager.cpp:668-671
             // show_live belongs to a subsystem outside the accelerated path: accepted, ignored
         }
@@ -286,13 +287,21 @@ bool SlamManager::addImageFromBuffer(uint32_t cameraNumber, LpSlamTimestamp time
     if (desc.hasRosTimestamp > 0) q.ros_timestamp = desc.rosTimestamp;
     if (desc.format == LpSlamImageFormat_8UC1_JPEPG) {
         // a compressed frame (LpGlobalFusion / Webots / a recording): cv::imdecode(..., IMREAD_GRAYSCALE) in the reference
-        // (SlamManager.cpp:1139-1146), only as LpSlamImageStructure_OneImage (:1138-1152)
-        if (desc.structure != LpSlamImageStructure_OneImage) { logMessage(LpSlamLogLevel_Error, "Image format not supported"); return false; }
-        std::string why;
-        if (desc.imageSize == 0 || !decode_jpeg_gray(buffer, desc.imageSize, q.image, &why)) {
-            logMessage(LpSlamLogLevel_Error, "Cannot decode the compressed frame: " + (desc.imageSize ? why : std::string("imageSize is 0")));
+        // (SlamManager.cpp:1139-1146), only as LpSlamImageStructure_OneImage (:1138-1152).  Here also what the image callback hands
+        // out (imageCallbackStep): OneImage_Compressed, and Stereo_Compressed -- the left stream, then the right one, split by
+        // imageSize / imageSizeSecond -- whose two eyes are decoded in one call.
+        const bool pair = desc.structure == LpSlamImageStructure_Stereo_Compressed;
+        if (desc.structure != LpSlamImageStructure_OneImage && desc.structure != LpSlamImageStructure_OneImage_Compressed && !pair) { logMessage(LpSlamLogLevel_Error, "Image format not supported"); return false; }
+        std::string why[2];
+        GrayImage second;
+        const uint8_t* d[2] = {buffer, buffer + desc.imageSize}; const size_t sz[2] = {desc.imageSize, desc.imageSizeSecond};
+        GrayImage* o[2] = {&q.image, &second}; bool ok[2] = {false, false};
+        const bool empty = desc.imageSize == 0 || (pair && desc.imageSizeSecond == 0);
+        if (empty || !m_jpegDecoder->decode(pair ? 2 : 1, d, sz, o, ok, why)) {
+            logMessage(LpSlamLogLevel_Error, "Cannot decode the compressed frame: " + (empty ? std::string("imageSize is 0") : (ok[0] ? why[1] : why[0])));
             return false;
         }
+        if (pair) { q.image_second = std::move(second); q.cameraNumberSecond = cameraNumber + 1; }
         m_camQueue.push(std::move(q));
         return true;
     }
@@ -331,6 +340,7 @@ bool SlamManager::loadReplayItems(std::string const& filename)
         ReplayReader r;
         std::string err;
         if (!r.open(filename, &err)) { logMessage(LpSlamLogLevel_Info, "Cannot load replay from file " + filename); return false; }
+        r.setDecoder(m_jpegDecoder);
         std::lock_guard<std::mutex> l(m_replayMutex);
         m_replay = std::move(r);
     }

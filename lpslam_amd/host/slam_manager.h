@@ -3,6 +3,7 @@
 #pragma once
 #include "core.h"
 #include "hip_tracker.h"
+#include "jpeg_device.h"
 #include "record.h"
 #include "replay.h"
 
@@ -63,6 +64,7 @@ public:
     uint64_t framesSkipped() const { return m_framesSkipped.load(); }
     uint64_t imagesSent() const { return m_imagesSent.load(); }
     RecorderCounters recorderCounters() const { return m_recorder.counters(); }
+    JpegDecodeCounters decoderCounters() const { return m_jpegDecoder->counters(); }
 
 private:
     void streamMoreReplayItems();
@@ -95,6 +97,8 @@ private:
     bool m_writeImageFiles = false;      // setWriteImageFiles: every 10th frame taken as <n>_left.jpg / <n>_right.jpg (SlamManager.cpp:70-85)
     int64_t m_framesTaken = 0;           // worker thread only: frames taken since start() (the reference's numberPic)
     ReplayReader m_replay;
+    // compressed frames (replay records and 8UC1_JPEPG frames handed in): on the device unless "manager": {"jpeg_decode_device": false}
+    std::shared_ptr<JpegDecoder> m_jpegDecoder = std::make_shared<JpegDecoder>();
     std::mutex m_replayMutex;
     size_t m_replayChunk = 500;          // ReplayEngine.h:53
     std::optional<std::chrono::steady_clock::time_point> m_lastFrame;

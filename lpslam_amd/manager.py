@@ -62,6 +62,8 @@ NAV_CB = C.CFUNCTYPE(C.c_int, ROSTimestamp, C.POINTER(GlobalStateInTime), C.POIN
 
 STEREO_TWO_BUFFER, FORMAT_8UC1, FORMAT_8UC3, NO_DISTORTION, ODOM_ONLY = 3, 1, 2, 3, 1
 PINHOLE, FISHEYE, OMNI = 0, 1, 2          # LpSlamCameraDistortionFunction
+ONE_IMAGE_COMPRESSED, STEREO_COMPRESSED = 4, 5          # LpSlamImageStructure
+JPEG_DECODE_DEVICE_KEY = "jpeg_decode_device"          # manager section of the configuration file: false = decode compressed frames on the host
 _lib = None
 
 
@@ -225,6 +227,13 @@ class Manager:
         d = ImageDescription(0, 0, 0, 0, 0, len(raw), 0, 1 if ros else 0, ROSTimestamp(int(ts_ns // 10**9), int(ts_ns)))
         return bool(self.lib.lpslam_manager_add_image(self.h, camera, int(ts_ns), C.cast(buf, C.c_void_p), C.byref(d)))
 
+    def add_jpeg_pair(self, ts_ns, left, right, camera=0, ros=True):
+        """a compressed stereo frame as the image callback hands it out (Stereo_Compressed: the left stream, then the right one)"""
+        raw = bytes(left) + bytes(right)
+        buf = C.create_string_buffer(raw, len(raw))
+        d = ImageDescription(STEREO_COMPRESSED, 0, 0, 0, 0, len(left), len(right), 1 if ros else 0, ROSTimestamp(int(ts_ns // 10**9), int(ts_ns)))
+        return bool(self.lib.lpslam_manager_add_image(self.h, camera, int(ts_ns), C.cast(buf, C.c_void_p), C.byref(d)))
+
     @staticmethod
     def compress_image(bgra):
         """LpSlamManager::compressImage: an (h, w, 4) BGRA image -> the JPEG stream of its grey version (bytes), or None"""
@@ -262,6 +271,16 @@ class Manager:
         f = self.lib.lpslam_manager_recorder_counters; f.argtypes = [C.c_void_p, C.c_void_p]
         f(self.h, out.ctypes.data)
         return dict(zip(("device_images", "host_images", "records", "bytes"), (int(v) for v in out)))
+
+    def decoder_counters(self):
+        """test hook: {device_images, host_images, refused_images}: the compressed images of this manager's replay and of add_jpeg /
+        add_jpeg_pair, by where they were decoded.  The device path is on unless the configuration file says
+        {"manager": {"jpeg_decode_device": false}} (JPEG_DECODE_DEVICE_KEY)."""
+        import numpy as np
+        out = np.zeros(3, np.uint64)
+        f = self.lib.lpslam_manager_decoder_counters; f.argtypes = [C.c_void_p, C.c_void_p]
+        f(self.h, out.ctypes.data)
+        return dict(zip(("device_images", "host_images", "refused_images"), (int(v) for v in out)))
 
     def start(self):
         self.lib.lpslam_manager_start(self.h)
