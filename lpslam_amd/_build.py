@@ -6,17 +6,30 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblpslam_hip.so")
-HIP_SOURCES = ["api.hip", "frontend.hip", "match.hip", "ba.hip", "bow.hip", "share.hip", "occupancy.hip", "jpeg.hip", "jpeg_dec.hip", "intensity.hip"]
-DEPS = ["internal.h", "orb_pattern.inc", os.path.join("..", "..", "include", "lpslam_hip.h"), "sim3.inl"]
+HIP_SOURCES = ["api.hip", "frontend.hip", "match.hip", "ba.hip", "pose_opt.hip", "sim3.hip", "bow.hip", "share.hip", "occupancy.hip", "jpeg.hip", "jpeg_dec.hip", "intensity.hip"]
 # -ffp-contract=off: parity with the CPU definition forbids FMA contraction ("Numerics").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
 
 
 OBJ_DIR = os.path.join(CSRC, "_obj")
-# what each translation unit includes (beyond itself): a change there recompiles only that unit
-UNIT_DEPS = {"ba.hip": ["sim3.inl", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl"], "frontend.hip": ["orb_pattern.inc"], "match.hip": [], "api.hip": [], "bow.hip": [], "share.hip": [], "occupancy.hip": [], "intensity.hip": [], "jpeg.hip": ["jpeg_scan.inl", os.path.join("..", "host", "jpeg_tables.h")],
-             "jpeg_dec.hip": ["jpeg_scan.inl", os.path.join("..", "host", "jpeg_header.h"), os.path.join("..", "host", "jpeg_tables.h")]}
+# What each translation unit includes, directly or through another include, beyond itself and COMMON_DEPS: a change there recompiles
+# only the units that list it.  tests/test_abi_cpu.py follows the #include lines and fails when an entry is missing.
+_HOST = os.path.join("..", "host")
+UNIT_DEPS = {
+    "api.hip": [],
+    "frontend.hip": ["orb_pattern.inc"],
+    "match.hip": [],
+    "ba.hip": ["ba_common.h", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl"],
+    "pose_opt.hip": ["ba_common.h"],
+    "sim3.hip": ["ba_common.h"],
+    "bow.hip": [],
+    "share.hip": [],
+    "occupancy.hip": [],
+    "intensity.hip": [],
+    "jpeg.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_tables.h")],
+    "jpeg_dec.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_header.h"), os.path.join(_HOST, "jpeg_tables.h")],
+}
 COMMON_DEPS = ["internal.h", os.path.join("..", "..", "include", "lpslam_hip.h")]
 
 

@@ -18,7 +18,6 @@
 
 constexpr int CW_THREADS = 512;
 constexpr int CW_UW = 7;                        // wavefronts that own tiles; wavefront 7 factors the diagonal blocks
-constexpr int CW_MAXT = 19;                     // 16-row tile rows held: dim + 1 <= 304
 constexpr int CW_SLOTS = 22;                    // tiles per owning wavefront: ceil(153 / 7)
 constexpr int CW_STRIP = 16 * 32;               // doubles of one strip (16 rows x 32 columns of a panel)
 constexpr int CW_BUF0 = CW_MAXT * CW_STRIP;     // even panels (panel 0 holds all 19 strips)
@@ -27,8 +26,6 @@ constexpr int CW_W = 32 * 32;
 constexpr int CW_VEC = 320;
 constexpr int CW_LDS_DOUBLES = CW_BUF0 + CW_BUF1 + CW_W + 2 * CW_VEC;      // strips, W / factor scratch, t and x vectors
 constexpr int CW_LDS_BYTES = CW_LDS_DOUBLES * 8 + 1024;                     // + tile table and flags
-
-__host__ __device__ inline bool cw_fits(int dim) { return dim > 0 && dim + 1 <= 16 * CW_MAXT; }
 
 // element (r, c) of a strip / of W: rows of 32 doubles, columns XOR-swizzled by the row so that the matrix-core operand reads
 // (16 rows x 2 neighbouring columns per half wavefront, ds_read_b64) hit 32 different 8-byte banks

@@ -182,10 +182,6 @@ __device__ __forceinline__ void upd_land_body(BaView& v, int bid, int robust, in
     if (tid == 0) st_sc1(&v.part[bid], (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
     // ---- 2. the trial state: chi2, and its linearisation (observation side) into the other set
     double acc = 0, acc8 = 0;
-#ifdef LPSLAM_UPD_REP2
-  for (int rep = 0; rep < 2; ++rep) {       // development: the pass a second time (hot instruction cache, same data) -- results are wrong, only the stamps count
-    if (rep == 1) { UPD_STAMP(bid == 0, 12); acc = 0; acc8 = 0; }
-#endif
     for (int chunk = s_lo; chunk < s_hi; chunk += 256) {
         const bool have = chunk + tid < s_hi;
         UpdEntry e = e0;
@@ -258,10 +254,6 @@ __device__ __forceinline__ void upd_land_body(BaView& v, int bid, int robust, in
         if (tid == 0) s_red[0] = (chunk == s_lo ? 0.0 : s_red[0]) + ((s_red[4] + s_red[5]) + (s_red[6] + s_red[7]));
         __syncthreads();
     }
-#ifdef LPSLAM_UPD_REP2
-    if (rep == 1) UPD_STAMP(bid == 0, 13);
-  }
-#endif
     {
         const int j = j0 + l;
         if (j < j1) {

@@ -251,9 +251,9 @@ struct LpProjReq {                      // one window-matcher call (k_proj_topk_
     unsigned long long* out_keys; int* out_count; unsigned* done_counter; int* done_flag;
     int nq, grid_x, done_seq; float inv_w, inv_h; LpProjGate gate;
 };
-struct LpPoseReq { uint8_t* blk; int n, seq; };        // one pose optimisation: the caller's page-locked block (ba.hip, PO_BLK_*), observation count, flag value
+struct LpPoseReq { uint8_t* blk; int n, seq; };        // one pose optimisation: the caller's page-locked block (pose_opt.hip, PO_BLK_*), observation count, flag value
 int lp_launch_proj_batch(hipStream_t s, const LpProjReq* table, int n, int grid_x_max);      // match.hip
-int lp_launch_pose_batch(hipStream_t s, const LpPoseReq* reqs, int n);                        // ba.hip (splits into launches of <= 32 requests)
+int lp_launch_pose_batch(hipStream_t s, const LpPoseReq* reqs, int n);                        // pose_opt.hip (splits into launches of <= 32 requests)
 enum { LP_SHARE_DONE = 0, LP_SHARE_DIRECT = 1 };        // (negative: minus an LPSLAM_HIP_ERR_* code)
 // Publishes the request and returns LP_SHARE_DONE when ITS flag has arrived, LP_SHARE_DIRECT when sharing does not apply to this call
 // (one session tracking alone, sharing switched off, the context's stream still has work the request must follow): the caller then

@@ -1,5 +1,6 @@
-// sim3.inl -- Sim3 pose-graph optimisation on gfx950 (FP64); included at the end of ba.hip (same translation unit: it reuses the
-// device-driven Levenberg control block, the blocked Cholesky kernels and the last-workgroup hand-over defined there).
+// sim3.hip -- Sim3 pose-graph optimisation on gfx950 (FP64).  A unit of its own: from the bundle adjuster it takes the device-driven
+// Levenberg control block and the last-workgroup hand-over (ba_common.h) and, through lp_enqueue_factor_solve, the blocked Cholesky
+// kernels of ba.hip.
 //
 // [UPSTREAM] g2o@691dc51 types/sim3 (Sim3 exp / log / inverse / product, VertexSim3Expmap::oplusImpl, EdgeSim3::computeError,
 // numeric BaseBinaryEdge::linearizeOplus with delta = 1e-9), OptimizationAlgorithmLevenberg with BlockSolver_7_3, and
@@ -16,6 +17,17 @@
 //   k_sim3_trial     chi2 of the trial state; the last workgroup runs g2o's lambda control
 // The essential graph has a few edges per keyframe, but the Cholesky of H fills in; H is kept dense (200 keyframes: 1408^2
 // doubles = 15.9 MB of 288 GB) and factored by the same 32-wide panel kernels as the reduced camera system of the BA.
+
+#include "internal.h"
+#include "ba_common.h"
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+using namespace lpslam;
 
 namespace {
 
@@ -836,7 +848,7 @@ int lpslam_hip_sim3_optimize(lpslam_hip_sim3* g, int32_t iters, lpslam_hip_ba_it
             if (v.n_edges) hipLaunchKernelGGL(k_sim3_lin, dim3(v.n_edges), dim3(64), 0, s, v);
             if (v.dim > 0) {
                 hipLaunchKernelGGL(k_sim3_assemble, dim3(v.n_blocks + v.n_free), dim3(64), 0, s, v);
-                enqueue_factor_solve(s, g->d_cv, 1, g->nb, v.dim, false, cw_fits(v.dim), !cw_fits(v.dim));
+                lp_enqueue_factor_solve(s, g->d_cv, 1, g->nb, v.dim, false, cw_fits(v.dim), !cw_fits(v.dim));
             }
             hipLaunchKernelGGL(k_sim3_update, dim3(vb + 1), dim3(256), 0, s, v, vb);
             hipLaunchKernelGGL(k_sim3_trial, dim3(g->trial_blocks), dim3(256), 0, s, v);

@@ -809,7 +809,7 @@ class RcclComm:
 
 
 def ba_factor_kernel_name(dim, band=False):
-    """name of the kernel that factors a reduced system of `dim` unknowns (rule of enqueue_solve in csrc/ba.hip)"""
+    """name of the kernel that factors a reduced system of `dim` unknowns (rule of enqueue_solve and lp_enqueue_factor_solve in csrc/ba.hip)"""
     return "k_chol_band" if band else "k_chol_pair"          # k_chol_wg takes over only in batches of 40 dense problems and more
 
 

@@ -66,3 +66,26 @@ def test_reference_header_client_links():
     have = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
     missing = [s for s in want if s not in have]
     assert not missing, missing
+
+
+def test_unit_deps_cover_every_include():
+    """Every file a translation unit reaches through its #include "..." lines (followed transitively, each resolved relative to the
+    including file) is in that unit's UNIT_DEPS or in COMMON_DEPS: an entry missing there means an edit to the file leaves the
+    unit's stale object in the library."""
+    from lpslam_amd import _build
+
+    def reached(path, seen):
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            f = os.path.normpath(os.path.join(os.path.dirname(path), inc))
+            assert os.path.exists(f), "%s includes %s, which does not exist" % (path, inc)
+            if f not in seen:
+                seen.add(f)
+                reached(f, seen)
+        return seen
+
+    assert sorted(_build.UNIT_DEPS) == sorted(_build.HIP_SOURCES)
+    for src in _build.HIP_SOURCES:
+        listed = {os.path.normpath(os.path.join(_build.CSRC, d)) for d in _build.UNIT_DEPS[src] + _build.COMMON_DEPS}
+        assert all(os.path.exists(d) for d in listed), (src, sorted(d for d in listed if not os.path.exists(d)))
+        missing = sorted(reached(os.path.join(_build.CSRC, src), set()) - listed)
+        assert not missing, "%s: not in UNIT_DEPS / COMMON_DEPS: %s" % (src, missing)
