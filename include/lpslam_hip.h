@@ -17,6 +17,30 @@
  *                       (src/Trackers/OpenVSLAMTrackerBase.cpp:239,250-255)
  * The arithmetic itself lives in absent third-party code (OpenVSLAM fork, g2o@691dc51, OpenCV); see DESIGN.md.
  */
+
+/* ---- environment switches ------------------------------------------------------------------------------
+ * Every LPSLAM_HIP_* variable the library and the host plugin read, each once per process, with its default.  This list is held to
+ * the code by tests/test_abi_cpu.py; what was measured and removed is in DESIGN.md section 20.
+ *
+ * Behaviour:
+ *   LPSLAM_HIP_FLAT_PRIORITIES      0     1: every stream at the default priority (lpslam_hip_set_flat_priorities)
+ *   LPSLAM_HIP_NO_QUEUE_SPREAD      unset set: a flat process puts no placeholder streams in front of a context's main stream
+ *   LPSLAM_HIP_POOL_SESSIONS        16    sessions a session pool holds (0 .. 64; lpslam_hip_create_session)
+ *   LPSLAM_HIP_POOL_CAP_MB          unset bound of a context's cache of released device blocks (unset: 1/32 of the device, <= 16 GB)
+ *   LPSLAM_HIP_SHARED_LAUNCHES      2     0 never, 1 always, 2 when two or more sessions are tracking (lpslam_hip_set_shared_launches)
+ *   LPSLAM_HIP_SHARE_WINDOW_US      30    a shared matcher / pose request goes out at the latest this long after the oldest one came
+ *   LPSLAM_HIP_SHARE_QUIET_US       2     ... or when no matcher request has arrived for this long (sessions without frame hints)
+ *   LPSLAM_HIP_CW_MIN_BATCH         40    windows in a batch from which on small dense systems are factored one workgroup each
+ *   LPSLAM_HIP_BA_SOLVER            unset "dense": no band plan, every window takes the dense solver
+ *   LPSLAM_HIP_BA_GROUP             32    landmarks per group of the band path's Schur kernel (4 .. 64)
+ *   LPSLAM_HIP_BA_TWO_LAUNCH_UPDATE 0     1: solve / update and trial / decision as two launches per iteration instead of one
+ *   LPSLAM_HIP_BA_GRAPH             unset 1 / 0: graph replay of the solver's launch chain forced on / off (unset: on, except under a profiler)
+ * Development traces (set to anything: lines on stderr, no change of behaviour):
+ *   LPSLAM_HIP_BA_TRACE             the solver chosen for every problem created
+ *   LPSLAM_HIP_MATCH_TRACE          timings of the window matchers' and the vocabulary (bag-of-words) calls
+ *   LPSLAM_HIP_PO_TRACE             every pose optimisation: observations, inliers, passes, time
+ *   LPSLAM_HIP_SHARE_TRACE          every shared launch, and the role streams chosen
+ */
 #ifndef LPSLAM_HIP_H
 #define LPSLAM_HIP_H
 
@@ -95,7 +119,7 @@ int lpslam_hip_set_flat_priorities(int32_t flat);
  * (blockIdx = request; per-request result blocks and completion flags as in the unshared call, same device code, same bits).
  * mode 2 (default): when two or more contexts of the device have made such calls within the last few milliseconds; 1: always, a lone
  * session too (tests); 0: never; -1: back to the environment (LPSLAM_HIP_SHARED_LAUNCHES).  LPSLAM_HIP_SHARE_WINDOW_US (30) /
- * LPSLAM_HIP_SHARE_QUIET_US (6) bound how long a request waits for the other sessions'. */
+ * LPSLAM_HIP_SHARE_QUIET_US (2) bound how long a request waits for the other sessions'. */
 int lpslam_hip_set_shared_launches(int32_t mode);
 /* How many shared launches a device has seen and how many requests they carried (measurement / test hook). */
 int lpslam_hip_shared_launch_counters(int32_t device, int64_t* batches, int64_t* requests);

@@ -28,9 +28,7 @@ std::atomic<int> g_lp_live_contexts{0};               // contexts of the process
 void lp_poll_sleep()
 {
     // 5 us between looks; 20 us once more contexts are alive than a 16-CPU quota carries polling threads for (16 managers: 5.4 k -> 6.0 k frames/s)
-    static const long sleep_env = [] { const char* e = getenv("LPSLAM_HIP_POLL_SLEEP_US"); return e ? 1000l * std::max(atoi(e), 0) : -1l; }();
-    const long sleep_ns = sleep_env >= 0 ? sleep_env : (g_lp_live_contexts.load(std::memory_order_relaxed) > 10 ? 20000l : 5000l);
-    if (sleep_ns <= 0) { sched_yield(); return; }
+    const long sleep_ns = g_lp_live_contexts.load(std::memory_order_relaxed) > 10 ? 20000l : 5000l;
     static thread_local bool slack_set = false;
     if (!slack_set) { (void)prctl(PR_SET_TIMERSLACK, 1000ul, 0ul, 0ul, 0ul); slack_set = true; }      // (the default slack of 50 us would turn a 5 us sleep into 55)
     const struct timespec ts{0, sleep_ns};
@@ -871,11 +869,9 @@ static hipStream_t lp_upload_stream(lpslam_hip_ctx* c)
 hipStream_t lp_aux_stream(lpslam_hip_ctx* c)
 {
     if (c->owns_streams) return c->stream;
-    // 0 main role stream (measured best without priorities: 8 managers 6004 / 5938 frames/s), 1 the session's copy stream (5115 / 5598),
-    // 2 the front-end role stream (5184 / 5441), 3 the auxiliary role stream (a queue of its own when the process has one to spare)
-    static const int where = [] { const char* e = getenv("LPSLAM_HIP_AUX_STREAM"); return e ? atoi(e) : 3; }();
-    if (where == 3) return c->role_aux ? c->role_aux : c->stream;
-    return where == 0 ? c->stream : (where == 1 ? lp_upload_stream(c) : c->fe_stream);
+    // the auxiliary role stream: a queue of its own when the process has one to spare, else the matchers' (share_init).  Measured, 8 managers:
+    // on the matchers' stream 6004 / 5938 frames/s, on the session's copy stream 5115 / 5598, on the front-end role stream 5184 / 5441
+    return c->role_aux ? c->role_aux : c->stream;
 }
 
 // stream `s` of the context waits (on the device) for the uploads of slots [first, first + n) that went through the copy-only stream

@@ -589,7 +589,7 @@ __device__ __forceinline__ void pose_combine_body(BaView& v, int mode, int part_
         } else {
             const double fail = v.scal[5], scale_p = v.scal[3];
             v.scal[1] = s_val[0]; v.scal[2] = s_val[1];
-            if (fused) { lm_decide(v, s_val[0], fail, s_val[1], scale_p, fused == 2); ba_sync_words(v)[2] = 0; }      // ([2]: groups of the next Schur launch that have stored their share, ba_band.inl)
+            if (fused) lm_decide(v, s_val[0], fail, s_val[1], scale_p, fused == 2);
         }
     }
 }
@@ -1646,8 +1646,6 @@ BaLaunch single_launch(lpslam_hip_ba* b)
     // a small reserve (<= 8 CUs of every XCD) cannot hold the pinned chain's workgroups on ONE XCD: spread them over all XCDs then (4 CUs:
     // 4256 against 4145 frames/s pinned); from 12 on the pinned chain is the better one again (12: 4392 against 4336, 16: 4428 against 4357)
     L.spread = b->ctx && b->ctx->reserve_cus > 0 && b->ctx->reserve_cus <= 8;
-    static const int spread_env = [] { const char* e = getenv("LPSLAM_HIP_BA_SPREAD"); return e ? atoi(e) : -1; }();      // measurements: 0 / 1 force the placement
-    if (spread_env >= 0) L.spread = spread_env != 0;
     return L;
 }
 
@@ -1670,23 +1668,19 @@ int enqueue_reduce(const BaLaunch& L, int fused)
     if (L.any_dense) hipLaunchKernelGGL(k_ba_schur, dim3(L.schur_items, L.count), dim3(64), 0, L.s, L.d_views, fused, L.robust);
     if (L.any_band) {
         if (bd_set_attributes() != hipSuccess) return LPSLAM_HIP_ERR_DEVICE;
-        // The band reduction as trailing workgroups of the group launch (LPSLAM_HIP_BA_REDUCE_IN_SCHUR=1) was measured and is OFF: the
+        // The band reduction is a launch of its own.  As trailing workgroups of the group launch it was measured and removed: the
         // groups' shares (3.1 MB per trial) then cross from workgroup to workgroup inside one launch, which on this part means
         // write-through stores and L2-bypassing loads -- 38.2 us for the one launch against 14.7 + 9.3 us for the two (MI355X, config 3).
-        static const bool reduce_in_schur_env = [] { const char* e = getenv("LPSLAM_HIP_BA_REDUCE_IN_SCHUR"); return e && atoi(e) != 0; }();
-        const int reduce_here = (fused && reduce_in_schur_env) ? 1 : 0;
         // a batch fills the chip with group workgroups: the variant that fits two of them on a compute unit (128 registers; the pose side
         // spills a few values there -- it is off the path) took a batch of 16 contiguous windows from 2.87 to 2.65 ms per 10 iterations; a single window keeps the
         // variant without spills (its pose-side workgroups are its longest).  Same arithmetic, same bytes.
-        const dim3 sg_grid(L.n_poses + std::max(L.band_groups, 1) + (reduce_here ? (L.band_blocks + 1) / 2 : 0), L.count);
+        const dim3 sg_grid(L.n_poses + std::max(L.band_groups, 1), L.count);
         const size_t sg_lds = std::max(bd_lds_bytes(L.band_gmax), (size_t)4096);
-        if (L.count >= 4) hipLaunchKernelGGL(k_schur_group<4>, sg_grid, dim3(BD_THREADS), sg_lds, L.s, L.d_views, fused, L.robust, reduce_here);
-        else hipLaunchKernelGGL(k_schur_group<1>, sg_grid, dim3(BD_THREADS), sg_lds, L.s, L.d_views, fused, L.robust, reduce_here);
+        if (L.count >= 4) hipLaunchKernelGGL(k_schur_group<4>, sg_grid, dim3(BD_THREADS), sg_lds, L.s, L.d_views, fused, L.robust);
+        else hipLaunchKernelGGL(k_schur_group<1>, sg_grid, dim3(BD_THREADS), sg_lds, L.s, L.d_views, fused, L.robust);
         L.mark(LPSLAM_HIP_BA_K_SCHUR);
-        if (!reduce_here) {
-            hipLaunchKernelGGL(k_schur_band_reduce, dim3(L.band_blocks, L.count), dim3(256), 0, L.s, L.d_views, fused);
-            L.mark(LPSLAM_HIP_BA_K_BAND_REDUCE);
-        }
+        hipLaunchKernelGGL(k_schur_band_reduce, dim3(L.band_blocks, L.count), dim3(256), 0, L.s, L.d_views, fused);
+        L.mark(LPSLAM_HIP_BA_K_BAND_REDUCE);
     } else if (L.any_dense) L.mark(LPSLAM_HIP_BA_K_SCHUR);
     LP_HIP(hipGetLastError());
     return LPSLAM_HIP_OK;
@@ -1753,7 +1747,7 @@ __global__ __launch_bounds__(64) void k_ba_arm(const BaView* __restrict__ views,
     c.ticket = 0; c.spec = 0; c.cur_launch = c.cur;
     *v.ctl = c;
     ba_sync_words(v)[3] = 0;              // the call starts with an explicit linearisation (pose side included)
-    ba_sync_words(v)[2] = 0; ba_sync_words(v)[4] = 0;      // counts of the Schur launch (groups / pose-side wavefronts that have stored)
+    ba_sync_words(v)[2] = 0; ba_sync_words(v)[4] = 0;      // [4]: pose-side wavefronts of the Schur launch that have stored; [2] is unused and cleared with its neighbours (one store)
 }
 // state given at creation back into buffer 0, every observation active, LM state cleared
 __global__ __launch_bounds__(256) void k_ba_reset(const BaView* __restrict__ views)
@@ -2127,7 +2121,6 @@ int lpslam_hip_ba_prepare(lpslam_hip_ctx* ctx, const double* poses, const uint8_
         // of the window.  Any assignment is valid (every pair is taken once); batched launches place problems, not pairs, on XCDs.
         std::vector<int> perm((size_t)nblk, 0);
         const int N = b->n_free, nb_ = b->n_blocks;
-        static const bool tiles = [] { const char* e = getenv("LPSLAM_HIP_BA_SCHUR_TILES"); return !e || atoi(e) != 0; }();
         if (nb_ > 0) {
             std::vector<std::vector<int>> of_xcd(8);
             auto grp = [N](int i) { return std::min(3, i * 4 / std::max(N, 1)); };
@@ -2136,7 +2129,7 @@ int lpslam_hip_ba_prepare(lpslam_hip_ctx* ctx, const double* poses, const uint8_
             // (every XCD's diagonal blocks first: theirs are the longest lists -- a term per observation -- and their epilogue waits for the pose side)
             for (int pass = 0; pass < 2; ++pass) {
                 blk = 0;
-                for (int i = 0; i < N; ++i) for (int k = i; k < N; ++k, ++blk) if ((i == k) == (pass == 0)) of_xcd[tiles && N >= 16 ? (size_t)tile_xcd[grp(i)][grp(k)] : (size_t)(blk & 7)].push_back(blk);
+                for (int i = 0; i < N; ++i) for (int k = i; k < N; ++k, ++blk) if ((i == k) == (pass == 0)) of_xcd[N >= 16 ? (size_t)tile_xcd[grp(i)][grp(k)] : (size_t)(blk & 7)].push_back(blk);
             }
             const int lead = n_poses * SPLIT;
             std::vector<size_t> at(8, 0);

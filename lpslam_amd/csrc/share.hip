@@ -91,12 +91,13 @@ int share_mode()
 }
 int env_us(const char* name, int dflt) { const char* e = getenv(name); return e ? std::max(atoi(e), 0) : dflt; }
 int64_t window_ns() { static const int64_t v = 1000ll * env_us("LPSLAM_HIP_SHARE_WINDOW_US", 30); return v; }
-int64_t pose_quiet_ns() { static const int64_t v = 1000ll * env_us("LPSLAM_HIP_SHARE_POSE_QUIET_US", 2); return v; }      // (a pose batch runs ~110 us: a request that just misses one waits that long)
-int64_t frame_window_ns() { static const int64_t v = 1000ll * env_us("LPSLAM_HIP_SHARE_FRAME_WINDOW_US", 25); return v; }      // how long a request waits for a session that is inside its frame and has not asked yet
 int64_t quiet_ns() { static const int64_t v = 1000ll * env_us("LPSLAM_HIP_SHARE_QUIET_US", 2); return v; }
-int64_t fe_window_ns() { static const int64_t v = 1000ll * env_us("LPSLAM_HIP_SHARE_FE_WINDOW_US", 300); return v; }
-int64_t fe_quiet_ns() { static const int64_t v = 1000ll * env_us("LPSLAM_HIP_SHARE_FE_QUIET_US", 40); return v; }
-int64_t active_ns() { static const int64_t v = 1000ll * env_us("LPSLAM_HIP_SHARE_ACTIVE_US", 3000); return v; }
+// the other gather times were tuned once and are fixed
+constexpr int64_t kPoseQuietNs = 2000;                  // (a pose batch runs ~110 us: a request that just misses one waits that long)
+constexpr int64_t kFrameWindowNs = 25000;               // how long a request waits for a session that is inside its frame and has not asked yet
+constexpr int64_t kFeWindowNs = 300000, kFeQuietNs = 40000;
+constexpr int64_t kSolveWindowNs = 200000, kSolveQuietNs = 40000;
+constexpr int64_t kActiveNs = 3000000;                  // a session that made a request this lately is expected to make the next
 
 // ---- one hardware queue per role ---------------------------------------------------------------------------------------------
 // A HIP process has four hardware queues per priority; a new stream is bound to one of them by the runtime, and streams that share a
@@ -133,44 +134,34 @@ bool share_init(Share& sh)                              // sh.m held
     constexpr int kCand = 12;
     hipStream_t cand[kCand] = {};
     int n_cand = 0;
-    // LPSLAM_HIP_SHARE_PRIO=1 (measurements): the two latency-bound roles (pose optimiser, matchers) on high-priority streams -- a
-    // process has four hardware queues PER PRIORITY, so they cannot share a queue with the chains of the front end, the solves or a
-    // session's loop-candidate search, and the dispatcher serves them first
-    static const int prio_mode = [] { const char* e = getenv("LPSLAM_HIP_SHARE_PRIO"); return e ? atoi(e) : 0; }();
-    int prio_least = 0, prio_greatest = 0;
-    if (prio_mode && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void)hipGetLastError(); prio_greatest = 0; }
-    const int n_high = (prio_mode && prio_greatest < 0) ? 5 : 0;
+    // (all of one priority: the latency-bound roles on high-priority streams measured 25 % slower)
     for (; ok && n_cand < kCand; ++n_cand)
-        if (hipStreamCreateWithPriority(&cand[n_cand], hipStreamNonBlocking, n_cand < n_high ? prio_greatest : 0) != hipSuccess) { (void)hipGetLastError(); break; }
-    ok = ok && n_cand >= 5 && n_cand > n_high + 2;
+        if (hipStreamCreateWithFlags(&cand[n_cand], hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); break; }
+    ok = ok && n_cand >= 5;
     unsigned long long* d_stamps = nullptr;
     unsigned long long h_stamps[2] = {0, 0};
     ok = ok && hipMalloc((void**)&d_stamps, 2 * sizeof(unsigned long long)) == hipSuccess;
     constexpr int kRoles = 5;                              // pose, matchers, front end, solves, auxiliary (a session's loop-candidate search)
     int picked[kRoles] = {-1, -1, -1, -1, -1}, n_picked = 0;
-    static const bool no_probe = getenv("LPSLAM_HIP_SHARE_NO_PROBE") != nullptr;      // measurements: the first candidates as they come
     auto independent = [&](int i) {
         for (int k = 0; k < n_picked; ++k)
             if (!(probe_independent(cand[picked[k]], cand[i], d_stamps, h_stamps) && probe_independent(cand[i], cand[picked[k]], d_stamps, h_stamps))) return false;
         return true;
     };
-    // roles in order; with priorities the first two come from the high-priority candidates, the others from the rest
-    for (int role = 0; ok && !no_probe && role < kRoles; ++role) {
-        const int lo = (n_high && role >= 2) ? n_high : 0, hi = (n_high && role < 2) ? n_high : n_cand;
-        for (int i = lo; i < hi; ++i) {
+    // roles in order: each takes the first candidate that is independent of those picked before it
+    for (int role = 0; ok && role < kRoles; ++role) {
+        for (int i = 0; i < n_cand; ++i) {
             if (std::find(picked, picked + n_picked, i) != picked + n_picked) continue;
             if (independent(i)) { picked[n_picked++] = i; break; }
         }
         if (n_picked != role + 1) break;
     }
     sh.distinct_queues = n_picked;
-    // fewer independent candidates than roles (four queues per priority: the fifth role shares; GPU_MAX_HW_QUEUES < 4; the probe off):
+    // fewer independent candidates than roles (four queues per priority: the fifth role shares; GPU_MAX_HW_QUEUES < 4):
     // roles share, the latency-critical ones last
     for (int next = 0; n_picked < kRoles && ok;) {
         const int role = n_picked;
         if (role == 4) { picked[n_picked++] = picked[1]; break; }      // no queue of its own: the auxiliary work stays with the matchers (measured best)
-        const int lo = (n_high && role >= 2) ? n_high : 0;
-        next = std::max(next, lo);
         while (std::find(picked, picked + n_picked, next) != picked + n_picked) ++next;
         picked[n_picked++] = next < n_cand ? next : 0;
     }
@@ -178,7 +169,7 @@ bool share_init(Share& sh)                              // sh.m held
     if (!ok) { for (int i = 0; i < n_cand; ++i) (void)hipStreamDestroy(cand[i]); (void)hipGetLastError(); sh.broken = true; return false; }
     sh.s_pose = cand[picked[0]]; sh.s_proj = cand[picked[1]]; sh.s_front = cand[picked[2]]; sh.s_solve = cand[picked[3]]; sh.s_aux = cand[picked[4]];
     for (int i = 0; i < n_cand; ++i) if (std::find(picked, picked + kRoles, i) == picked + kRoles) (void)hipStreamDestroy(cand[i]);
-    if (share_trace()) fprintf(stderr, "share: role streams from candidates %d %d %d %d %d (%d independent, %d high-priority candidates)\n", picked[0], picked[1], picked[2], picked[3], picked[4], sh.distinct_queues, n_high);
+    if (share_trace()) fprintf(stderr, "share: role streams from candidates %d %d %d %d %d (%d independent)\n", picked[0], picked[1], picked[2], picked[3], picked[4], sh.distinct_queues);
     sh.ready = true;
     return true;
 }
@@ -188,7 +179,7 @@ int active_sessions(Share& sh, int64_t now)
 {
     int n = 0;
     const int hi = sh.n_sessions.load(std::memory_order_relaxed);
-    for (int i = 0; i < hi; ++i) { const int64_t t = sh.last_ns[i].load(std::memory_order_relaxed); if (t && now - t < active_ns()) ++n; }
+    for (int i = 0; i < hi; ++i) { const int64_t t = sh.last_ns[i].load(std::memory_order_relaxed); if (t && now - t < kActiveNs) ++n; }
     return n;
 }
 
@@ -228,7 +219,7 @@ void combine(Share& sh, Ticket& mine)
             int framed = 0;
             { const int hi = sh.n_sessions.load(std::memory_order_relaxed); for (int i = 0; i < hi; ++i) framed += sh.in_frame[i].load(std::memory_order_relaxed); }
             const int expected = std::max(1, (framed ? framed : active_sessions(sh, now)) - sh.in_flight.load(std::memory_order_relaxed));
-            const int64_t pose_q = framed ? frame_window_ns() : pose_quiet_ns(), proj_q = framed ? frame_window_ns() : quiet_ns();
+            const int64_t pose_q = framed ? kFrameWindowNs : kPoseQuietNs, proj_q = framed ? kFrameWindowNs : quiet_ns();
             const bool pose_free = !sh.pose_fl[sh.pose_gen].busy();
             if (!sh.pose.empty() && pose_free &&
                 ((int)sh.pose.size() >= expected || now - sh.pose_newest_ns >= pose_q || now - sh.pose_oldest_ns >= window_ns())) pose.swap(sh.pose);
@@ -346,7 +337,7 @@ int active_fe_sessions(Share& sh, int64_t now)
 {
     int n = 0;
     const int hi = sh.n_sessions.load(std::memory_order_relaxed);
-    for (int i = 0; i < hi; ++i) { const int64_t t = sh.fe_last_ns[i].load(std::memory_order_relaxed); if (t && now - t < active_ns()) ++n; }
+    for (int i = 0; i < hi; ++i) { const int64_t t = sh.fe_last_ns[i].load(std::memory_order_relaxed); if (t && now - t < kActiveNs) ++n; }
     return n;
 }
 
@@ -371,7 +362,7 @@ void combine_front(Share& sh)
             bool busy = false;
             if (sh.fe_chain_in_flight) { busy = hipEventQuery(sh.ev_fe_chain) == hipErrorNotReady; if (!busy) sh.fe_chain_in_flight = false; (void)hipGetLastError(); }
             const int expected = std::max(1, active_fe_sessions(sh, now) - sh.fe_in_flight.load(std::memory_order_relaxed));
-            if ((!busy && (np >= expected || now - sh.fe_newest_ns >= fe_quiet_ns() || now - sh.fe_oldest_ns >= fe_window_ns())) || 2 * np >= kMaxListed) {
+            if ((!busy && (np >= expected || now - sh.fe_newest_ns >= kFeQuietNs || now - sh.fe_oldest_ns >= kFeWindowNs)) || 2 * np >= kMaxListed) {
                 reqs.swap(sh.front);
                 t_oldest = sh.fe_oldest_ns; t_taken = now;
                 sh.fe_oldest_ns = sh.fe_newest_ns = 0;
@@ -445,7 +436,7 @@ int lp_share_ba_local(lpslam_hip_ctx* c, lpslam_hip_ba* b, int first_iters, int 
         sh.solve_newest_ns = now;
         sh.solves.push_back(PendingSolve{b, first_iters, second_iters, outlier, poses, points, &state, &rc});
     }
-    static const int64_t quiet = 1000ll * env_us("LPSLAM_HIP_SHARE_SOLVE_QUIET_US", 40), window = 1000ll * env_us("LPSLAM_HIP_SHARE_SOLVE_WINDOW_US", 200), active_for = 30000000ll;
+    constexpr int64_t active_for = 30000000ll;
     for (;;) {
         if (state.load(std::memory_order_acquire) != T_PENDING) break;
         if (sh.solver.try_lock()) {
@@ -458,7 +449,7 @@ int lp_share_ba_local(lpslam_hip_ctx* c, lpslam_hip_ba* b, int first_iters, int 
                 int active = 0;
                 const int hi = sh.n_sessions.load(std::memory_order_relaxed);
                 for (int i = 0; i < hi; ++i) { const int64_t t = sh.solve_last_ns[i].load(std::memory_order_relaxed); if (t && now - t < active_for) ++active; }
-                if ((int)sh.solves.size() >= std::max(1, active) || now - sh.solve_newest_ns >= quiet || now - sh.solve_oldest_ns >= window) {
+                if ((int)sh.solves.size() >= std::max(1, active) || now - sh.solve_newest_ns >= kSolveQuietNs || now - sh.solve_oldest_ns >= kSolveWindowNs) {
                     // (windows with the same iteration counts: every tracker's are)
                     for (size_t i = 0; i < sh.solves.size();) {
                         if (sh.solves[i].first == first_iters && sh.solves[i].second == second_iters && take.size() < 64) { take.push_back(sh.solves[i]); sh.solves.erase(sh.solves.begin() + (long)i); }
@@ -579,8 +570,7 @@ void lp_share_frame(lpslam_hip_ctx* c, int inside)
     if (!c || !c->sess_pool || share_mode() == 0 || c->cfg.device < 0 || c->cfg.device >= kMaxDevices) return;
     Share& sh = g_share[c->cfg.device];
     if (c->share_slot < 0 && (!inside || !touch_session(sh, c, now_ns()))) return;
-    static const bool off = getenv("LPSLAM_HIP_SHARE_NO_FRAME_HINTS") != nullptr;      // measurements
-    if (!off) sh.in_frame[c->share_slot].store(inside ? 1 : 0, std::memory_order_relaxed);
+    sh.in_frame[c->share_slot].store(inside ? 1 : 0, std::memory_order_relaxed);
 }
 
 void lp_share_forget(lpslam_hip_ctx* c)

@@ -1946,39 +1946,26 @@ void HipVslamTrackerBase::logStatistics()
 // everything is only enqueued
 bool HipVslamTrackerBase::frontEnd(CameraQueueEntry const& cam, bool stereo, int slot)
 {
-    bool ok;
-    static const bool readback_ahead_fused = std::getenv("LPSLAM_HIP_NO_PREFETCH_READBACK") == nullptr;
     // an intensity adjustment the AdjustIntensity processor asked for and nobody applied on the host: on the device, behind the upload
     lpslam_hip_adjust_params adj{};
     const bool adjust = cam.adjust.has_value();
     if (adjust) adj = lpslam_hip_adjust_params{cam.adjust->low_out, cam.adjust->high_out, cam.adjust->low_fraction, cam.adjust->high_fraction};
-    if (!m_rectify && readback_ahead_fused) {
+    const float baseline = (float)(m_cam.focal_x_baseline / m_cam.f_x);
+    if (!m_rectify) {
         // upload, extraction, stereo match and the read-back that rides behind them: ONE call, which the frames that other sessions of the
         // process have pending join (one upload + launch chain for all of them, share.hip)
-        const float baseline = (float)(m_cam.focal_x_baseline / m_cam.f_x);
         const uint8_t* right = stereo ? cam.image_second->pixels.data() : nullptr;
         if (adjust) return lpslam_hip_front_end_images_adjusted(m_ctx, slot, cam.image.pixels.data(), right, cam.image.width, (float)m_cam.focal_x_baseline, baseline, &adj) == LPSLAM_HIP_OK;
         return lpslam_hip_front_end_images(m_ctx, slot, cam.image.pixels.data(), right, cam.image.width, (float)m_cam.focal_x_baseline, baseline) == LPSLAM_HIP_OK;
     }
-    if (m_rectify) {       // raw frames: (adjusted, then) undistorted + rectified on the device
-        auto raw = [&](int image, int eye, const GrayImage& img) {
-            return (adjust ? lpslam_hip_upload_raw_image_adjusted(m_ctx, image, eye, img.pixels.data(), img.width, &adj)
-                           : lpslam_hip_upload_raw_image(m_ctx, image, eye, img.pixels.data(), img.width)) == LPSLAM_HIP_OK;
-        };
-        ok = raw(slot, 0, cam.image);
-        if (ok && stereo) ok = raw(slot + 1, 1, *cam.image_second);
-    } else {
-        ok = lpslam_hip_upload_image(m_ctx, slot, cam.image.pixels.data(), cam.image.width) == LPSLAM_HIP_OK;
-        if (ok && stereo) ok = lpslam_hip_upload_image(m_ctx, slot + 1, cam.image_second->pixels.data(), cam.image.width) == LPSLAM_HIP_OK;
-        if (ok && adjust) ok = lpslam_hip_adjust_intensity(m_ctx, slot, stereo ? 2 : 1, &adj) == LPSLAM_HIP_OK;
-    }
-    static const bool readback_ahead = std::getenv("LPSLAM_HIP_NO_PREFETCH_READBACK") == nullptr;      // (development switch)
-    const float baseline = (float)(m_cam.focal_x_baseline / m_cam.f_x);
+    // raw frames: (adjusted, then) undistorted + rectified on the device
+    auto raw = [&](int image, int eye, const GrayImage& img) {
+        return (adjust ? lpslam_hip_upload_raw_image_adjusted(m_ctx, image, eye, img.pixels.data(), img.width, &adj)
+                       : lpslam_hip_upload_raw_image(m_ctx, image, eye, img.pixels.data(), img.width)) == LPSLAM_HIP_OK;
+    };
+    if (!raw(slot, 0, cam.image) || (stereo && !raw(slot + 1, 1, *cam.image_second))) return false;
     // extraction, stereo match and the read-back that rides behind them: one call (shared with the other sessions' pending frames when there are any)
-    if (ok && readback_ahead) return lpslam_hip_front_end(m_ctx, slot, stereo ? 1 : 0, (float)m_cam.focal_x_baseline, baseline) == LPSLAM_HIP_OK;
-    if (ok) ok = lpslam_hip_extract_range(m_ctx, slot, stereo ? 2 : 1) == LPSLAM_HIP_OK;
-    if (ok && stereo) ok = lpslam_hip_match_stereo(m_ctx, slot, slot + 1, (float)m_cam.focal_x_baseline, baseline) == LPSLAM_HIP_OK;
-    return ok;
+    return lpslam_hip_front_end(m_ctx, slot, stereo ? 1 : 0, (float)m_cam.focal_x_baseline, baseline) == LPSLAM_HIP_OK;
 }
 
 // The front end of the frame that comes next, on the context's prefetch stream: issued right after this frame's own front end has

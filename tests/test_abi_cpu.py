@@ -89,3 +89,25 @@ def test_unit_deps_cover_every_include():
         assert all(os.path.exists(d) for d in listed), (src, sorted(d for d in listed if not os.path.exists(d)))
         missing = sorted(reached(os.path.join(_build.CSRC, src), set()) - listed)
         assert not missing, "%s: not in UNIT_DEPS / COMMON_DEPS: %s" % (src, missing)
+
+
+def test_environment_switches_are_the_documented_ones():
+    """The LPSLAM_HIP_* variables the library and the host plugin read -- every name inside a getenv(...) call or given to
+    env_us(...) under lpslam_amd/csrc and lpslam_amd/host -- are exactly those of the "environment switches" block of
+    include/lpslam_hip.h, and the list stays short: at most 12 behaviour switches and 4 development traces."""
+    read = set()
+    for d in ("csrc", "host"):
+        for dp, _, files in os.walk(os.path.join(ROOT, "lpslam_amd", d)):
+            for f in files:
+                if f.endswith((".hip", ".inl", ".inc", ".h", ".cpp")):
+                    read |= set(re.findall(r'\b(?:getenv|env_us)\s*\(\s*"(LPSLAM_HIP_[A-Z0-9_]+)"', open(os.path.join(dp, f), errors="ignore").read()))
+    header = open(os.path.join(ROOT, "include", "lpslam_hip.h")).read()
+    block = re.search(r"/\* ---- environment switches -+\n(.*?)\*/", header, re.S)
+    assert block, "include/lpslam_hip.h has no environment-switch block"
+    behaviour, traces = block.group(1).split("Development traces")
+    behaviour = re.findall(r"^ \*   (LPSLAM_HIP_[A-Z0-9_]+)\s", behaviour, re.M)
+    traces = re.findall(r"^ \*   (LPSLAM_HIP_[A-Z0-9_]+)\s", traces, re.M)
+    assert len(set(behaviour + traces)) == len(behaviour + traces), "a switch is listed twice"
+    assert read == set(behaviour + traces), (sorted(read - set(behaviour + traces)), sorted(set(behaviour + traces) - read))
+    assert len(behaviour) <= 12 and len(traces) <= 4, (len(behaviour), len(traces))
+    assert all(t.endswith("_TRACE") for t in traces) and not any(b.endswith("_TRACE") for b in behaviour)
