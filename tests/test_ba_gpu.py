@@ -130,6 +130,138 @@ def test_local_ba_flow_with_outliers(hiplib, oracle, ctx):
     assert np.allclose(gchi, ochi, rtol=1e-6, atol=1e-9) and np.array_equal(gpos, opos)
 
 
+def _quat_rot(q):
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def _local_window_with_a_landmark_behind():
+    """The window of test_local_ba_flow_with_outliers with every third observation monocular and landmark 7 mirrored through the centre
+    of keyframe 0 -- behind every keyframe that observes it, its measurements those of the mirrored point: it projects where it is
+    measured (chi2 inside the bound) with negative depth, so only the depth clause of the classification can flag it."""
+    prob = synth.ba_problem(8, 300, 1800, 640, 480, seq_id=9)
+    prob["obs_uvr"][::3, 2] = -1.0
+    bad = np.arange(0, len(prob["obs_pose"]), 29)
+    prob["obs_uvr"][bad, 0] += 35.0
+    j, cam = 7, prob["cam"]
+    g0 = prob["poses_gt"][0]
+    behind = _quat_rot(g0[:4]).T @ (-(_quat_rot(g0[:4]) @ prob["points_gt"][j] + g0[4:]) - g0[4:])
+    prob["points"][j] = behind
+    of_j = np.nonzero(prob["obs_point"] == j)[0]
+    for k in of_j:
+        g = prob["poses_gt"][prob["obs_pose"][k]]
+        x, y, z = _quat_rot(g[:4]) @ behind + g[4:]
+        assert z < 0
+        u = cam["fx"] * x / z + cam["cx"]
+        prob["obs_uvr"][k, :2] = u, cam["fy"] * y / z + cam["cy"]
+        if prob["obs_uvr"][k, 2] >= 0:
+            prob["obs_uvr"][k, 2] = u - cam["fxb"] / z
+    return prob, bad, of_j
+
+
+def test_local_ba_single_and_direct_window_forms(hiplib, oracle, ctx):
+    """lpslam_hip_ba_local on a problem object and lpslam_hip_ba_local_window on a plain context (the direct, unshared path) are the
+    same flow: outlier flags, poses and points bit for bit, and the flags are the oracle's.  Monocular and stereo bounds, observations
+    beyond their bound and observations caught by the depth sign alone are all in the window."""
+    prob, bad, of_j = _local_window_with_a_landmark_behind()
+    obs = oracle.ba_obs(prob)
+    op, ox, oout = oracle.ba_local(prob["poses"], prob["fixed"], prob["points"], obs, prob["cam"], 5, 10)
+    ochi, opos = oracle.ba_chi2(op, ox, obs, prob["cam"])
+    limit = np.where(prob["obs_uvr"][:, 2] < 0, 5.99146, 7.81473)
+    assert not opos[of_j].any() and (ochi[of_j] < limit[of_j]).all() and oout[of_j].all()      # the depth clause alone
+    assert (ochi[bad] > limit[bad]).mean() > 0.9 and (prob["obs_uvr"][bad, 2] < 0).any() and (prob["obs_uvr"][bad, 2] >= 0).any()
+    hobs = hiplib.ba_obs_array(prob)
+    ba = hiplib.BundleAdjuster(ctx, prob["poses"], prob["fixed"], prob["points"], hobs, prob["cam"])
+    gout = ba.local(5, 10)
+    gp, gx = ba.state()
+    ba.close()
+    wp, wx, wout = hiplib.ba_local_window(ctx, prob["poses"], prob["fixed"], prob["points"], hobs, prob["cam"], 5, 10)
+    assert np.array_equal(gout.astype(bool), wout) and np.array_equal(gp, wp) and np.array_equal(gx, wx)
+    assert np.array_equal(gout, oout)
+
+
+def _tiny_windows():
+    """3 keyframes x 5 landmarks: 7 * 3 and 3 * 5 are both odd, so both halves of the exchange block and the points behind the poses
+    are padded to 16 bytes; and a window without landmarks or observations."""
+    odd = synth.ba_problem(3, 5, 15, 640, 480, seq_id=12)
+    none = dict(odd)
+    none["points"] = odd["points"][:0]; none["obs_pose"] = odd["obs_pose"][:0]; none["obs_point"] = odd["obs_point"][:0]
+    none["obs_uvr"] = odd["obs_uvr"][:0]; none["obs_inv_sigma2"] = odd["obs_inv_sigma2"][:0]
+    return odd, none
+
+
+def test_state_read_back_single_and_batch(hiplib, ctx):
+    """lpslam_hip_ba_get and lpslam_hip_ba_get_batch read the same bytes -- the creation values before any solve, the solved state
+    after -- whether poses, points or both are asked for."""
+    lib = hiplib.load()
+    import ctypes as C
+    probs = _tiny_windows()
+    bas = [hiplib.BundleAdjuster(ctx, p["poses"], p["fixed"], p["points"], hiplib.ba_obs_array(p), p["cam"]) for p in probs]
+
+    def single(b, want_poses, want_points):
+        po = np.full((b.n_poses, 7), np.nan); pt = np.full((b.n_points, 3), np.nan)
+        rc = lib.lpslam_hip_ba_get(b.h, po.ctypes.data_as(C.c_void_p) if want_poses else None, pt.ctypes.data_as(C.c_void_p) if want_points else None)
+        assert rc == 0
+        return po, pt
+
+    def batch(want_poses, want_points):
+        n = len(bas)
+        out = [(np.full((b.n_poses, 7), np.nan), np.full((b.n_points, 3), np.nan)) for b in bas]
+        hs = (C.c_void_p * n)(*[b.h for b in bas])
+        pa = (C.c_void_p * n)(*[o[0].ctypes.data for o in out]) if want_poses else None
+        ta = (C.c_void_p * n)(*[o[1].ctypes.data for o in out]) if want_points else None
+        f = lib.lpslam_hip_ba_get_batch
+        f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        assert f(hs, n, pa, ta) == 0
+        return out
+
+    def check(expect):
+        for want_poses, want_points in ((True, False), (False, True), (True, True)):
+            got = batch(want_poses, want_points)
+            for b, (bpo, bpt), (epo, ept) in zip(bas, got, expect):
+                spo, spt = single(b, want_poses, want_points)
+                assert np.array_equal(bpo, spo, equal_nan=True) and np.array_equal(spo, bpo, equal_nan=True)
+                assert np.array_equal(bpt, spt, equal_nan=True) and np.array_equal(spt, bpt, equal_nan=True)
+                assert np.array_equal(spo, epo) if want_poses else np.isnan(spo).all()         # what was not asked for is not written
+                assert np.array_equal(spt, ept) if want_points else np.isnan(spt).all()
+
+    check([(p["poses"], p["points"]) for p in probs])
+    bas[0].optimize(True, 3)
+    solved = [b.state() for b in bas]
+    assert not np.array_equal(solved[0][0], probs[0]["poses"]) and np.array_equal(solved[1][0], probs[1]["poses"])
+    check(solved)
+    for b in bas:
+        b.close()
+
+
+def test_activity_mask_and_chi2_are_idempotent_and_reset_by_reset(hiplib, ctx):
+    """set_active(mask) twice is set_active(mask) once; reset() re-activates every observation: chi2 and depth flags, and the solve
+    that follows, are those of a fresh problem."""
+    odd, _ = _tiny_windows()
+    make = lambda: hiplib.BundleAdjuster(ctx, odd["poses"], odd["fixed"], odd["points"], hiplib.ba_obs_array(odd), odd["cam"])
+    fresh, ba = make(), make()
+    fchi, fpos = fresh.chi2()
+    assert len(fchi) == 15 and (fchi > 0).all() and fpos.all()
+    mask = np.ones(15, np.uint8); mask[::4] = 0
+    ba.set_active(mask)
+    chi1, pos1 = ba.chi2()
+    ba.set_active(mask)
+    chi2, pos2 = ba.chi2()
+    assert np.array_equal(chi1, chi2) and np.array_equal(pos1, pos2)
+    assert np.array_equal(chi1, fchi) and np.array_equal(pos1, fpos)           # the per-observation chi2 does not look at the mask
+    masked_log = ba.optimize(True, 4)
+    ba.reset()
+    rchi, rpos = ba.chi2()
+    assert np.array_equal(rchi, fchi) and np.array_equal(rpos, fpos)
+    flog, rlog = fresh.optimize(True, 4), ba.optimize(True, 4)
+    assert rlog.tobytes() == flog.tobytes() and masked_log.tobytes() != flog.tobytes()      # every observation counts again
+    for a, b in zip(fresh.state(), ba.state()):
+        assert np.array_equal(a, b)
+    fresh.close(); ba.close()
+
+
 def test_baseline_config3_full_size(hiplib, oracle):
     """BASELINE configs[2]: 50 keyframes / 5000 landmarks / ~40k observations, 10 LM iterations."""
     c = hiplib.Context(1280, 720, 2000, 1.2, 8, max_images=1)
