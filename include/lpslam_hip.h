@@ -510,7 +510,8 @@ int lpslam_hip_ba_status(lpslam_hip_ba* ba, int32_t* outer_done, int32_t* stoppe
  * (toggled at :250-255) match keypoints with.
  * lpslam_hip_vocab_create takes the tree as DBoW2 stores it -- nodes 1 .. n_nodes in file order, each naming its parent (0 = the
  * root, which precedes every node), its 32-byte descriptor, its weight and whether it is a leaf (= a word; word ids count the
- * leaves in node order) -- and keeps it in HBM.  The file formats are read by the host mirror (lpslam_amd/host/bow.h).
+ * leaves in node order) -- and keeps it in HBM.  A node may have at most 65535 children (LPSLAM_HIP_ERR_CAPACITY otherwise): the tree
+ * itself is counted, `k` is only what the file declares.  The file formats are read by the host mirror (lpslam_amd/host/bow.h).
  * lpslam_hip_bow_transform walks the descriptors of an image slot down the tree on the device (TemplatedVocabulary::transform with
  * a FeatureVector: at every level the child at the smallest Hamming distance, the first on ties): per keypoint the word id, the
  * word's weight and the id of the node `levels_up` levels above the leaves (0 = the root when the tree is not that deep).  The

@@ -172,6 +172,10 @@ int lpslam_hip_vocab_create(lpslam_hip_ctx* c, int32_t k, int32_t L, int32_t n_n
         if (leaf) word[(size_t)i] = n_words++;          // word ids in node order (DBoW2: m_words in file order)
     }
     if (n_child[0] == 0) { set_error("the vocabulary's root has no children"); return LPSLAM_HIP_ERR_INVALID; }
+    // k_bow_transform16 keeps a child's order in the low 16 bits of its key: what counts is the widest node the tree really has, the k
+    // the file declares is only its trainer's upper bound (and nothing holds a file to it)
+    const int widest = *std::max_element(n_child.begin(), n_child.end());
+    if (widest > 65535) { set_error("vocabulary: a node has %d children (at most 65535)", widest); return LPSLAM_HIP_ERR_CAPACITY; }
     LP_HIP(hipSetDevice(c->cfg.device));
     lpslam_hip_vocab* v = new lpslam_hip_vocab();
     v->ctx = c; v->k = k; v->L = L; v->n_nodes = n_nodes; v->n_words = n_words;
@@ -215,7 +219,6 @@ static int bow_transform_device(lpslam_hip_ctx* c, lpslam_hip_vocab* v, const ui
 {
     hipStream_t s = c->stream;
     const size_t nm = (size_t)std::max(n_max, 1);
-    if (v->k > 65535) { set_error("vocabulary: more than 65535 children per node"); return LPSLAM_HIP_ERR_CAPACITY; }
     // page-locked block: done flag | count | word ids | weights | node ids -- written by the kernel itself, released by its last store
     const size_t o_word = 64, o_w = o_word + nm * 4, o_node = o_w + nm * 4, total = o_node + nm * 4;
     if (c->h_match_bytes < total) {

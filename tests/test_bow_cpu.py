@@ -8,11 +8,7 @@ import struct
 import numpy as np
 import pytest
 
-from bow_util import VOCAB, read_vocab
-
-
-def _hamming(a, b):
-    return int(np.unpackbits(np.bitwise_xor(a, b)).sum())
+from bow_util import LEVELS_UP, VOCAB, VOCAB_CASES, levels_up_of, make_vocab, read_vocab, vocab_case, walk_case, walk_numpy
 
 
 def test_tree_walk_against_brute_force(oracle):
@@ -21,21 +17,58 @@ def test_tree_walk_against_brute_force(oracle):
     rng = np.random.default_rng(5)
     desc = rng.integers(0, 256, (300, 32), dtype=np.uint8)
     desc[:50] = v["desc"][rng.integers(0, len(v["desc"]), 50)]                  # some exactly on nodes: ties between children are real
-    children = {}
-    for i, p in enumerate(v["parent"]):
-        children.setdefault(int(p), []).append(i + 1)
-    word_of = np.cumsum(v["is_leaf"]) - 1
     for lu in (0, 1, 2, 4):
         w, ww, nd = oracle.bow_transform(v, desc, lu)
-        for f in range(len(desc)):
-            cur, level, nid = 0, 0, 0
-            while cur == 0 or not v["is_leaf"][cur - 1]:
-                level += 1
-                ds = [_hamming(desc[f], v["desc"][c - 1]) for c in children[cur]]
-                cur = children[cur][int(np.argmin(ds))]                          # argmin: the first minimum
-                if level == v["L"] - lu:
-                    nid = cur
-            assert w[f] == word_of[cur - 1] and ww[f] == v["weight"][cur - 1] and nd[f] == nid
+        bw, bww, bnd = walk_numpy(v, desc, lu)
+        assert np.array_equal(w, bw) and np.array_equal(ww, bww) and np.array_equal(nd, bnd), lu
+
+
+def test_generated_vocabularies_have_the_shapes_their_cases_name():
+    """the generator itself: node counts of the balanced trees, the widest node, what `is_leaf` and the weights hold"""
+    want_nodes = {"k2_L6": 126, "k3_L6": 1092, "k16_L2": 272, "k17_L2": 306, "k33_L2": 1122, "k10_L4": 11110, "leaf_at_1": 125}
+    for name, (_, k, L, _) in VOCAB_CASES.items():
+        v, desc = vocab_case(name)
+        n = len(v["parent"])
+        n_child = np.bincount(v["parent"], minlength=n + 1)
+        assert (v["k"], v["L"]) == (k, L) and desc.shape == (300, 32)
+        assert np.all(v["parent"] < np.arange(1, n + 1)) and np.all(np.diff(v["parent"]) >= 0)          # a parent precedes its children
+        assert np.array_equal(v["is_leaf"] != 0, n_child[1:] == 0) and n_child.max() == k and n_child[0] == k
+        assert v["weight"].dtype == np.float32 and (v["weight"] == 0).any() and (v["weight"] > 0).any()
+        if name in want_nodes:
+            assert n == want_nodes[name], name
+    v, _ = vocab_case("ragged")
+    n_child = np.bincount(v["parent"], minlength=len(v["parent"]) + 1)
+    assert (n_child == 1).sum() > 100 and set(n_child[n_child > 0]) == set(range(1, 21))
+    v, _ = vocab_case("leaf_at_1")
+    assert v["is_leaf"][:5].tolist() == [0, 0, 1, 0, 0]                         # a word directly under the root
+    # the same seed gives the same tree
+    a = make_vocab(np.random.default_rng(4), 4, 3, stop=0.3, dup=0.3); b = make_vocab(np.random.default_rng(4), 4, 3, stop=0.3, dup=0.3)
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+
+
+def test_ragged_case_is_not_vacuous():
+    """conditions on the INPUT of the ragged case (tests/test_bow_gpu.py relies on them), measured with the numpy walk"""
+    v, desc = vocab_case("ragged")
+    (_, _, nid), st = walk_case("ragged", 1)
+    L, n = v["L"], len(desc)
+    assert (st["depth"] < L - 1).sum() >= n // 5                                # a word above level L - 1 ...
+    assert np.all(nid[st["depth"] < L - 1] == 0) and np.all(nid[st["depth"] >= L - 1] > 0)   # ... leaves the node id 0 at levels_up = 1
+    assert (st["depth"] == L).sum() >= n // 5
+    assert set(st["depth"]) == {1, 2, 3, 4, 5}
+    assert st["tie"].sum() >= 20 and st["single"].sum() >= 20                   # exact sibling ties; nodes with one child
+
+
+@pytest.mark.parametrize("lu", LEVELS_UP)
+@pytest.mark.parametrize("case", list(VOCAB_CASES))
+def test_oracle_walk_on_generated_vocabularies(oracle, case, lu):
+    """the oracle is what the device is held against: here it is held against the numpy walk on every generated tree, at node levels
+    below, at and above the root (levels_up >= L: the node id is 0)"""
+    v, desc = vocab_case(case)
+    levels_up = levels_up_of(lu, v["L"])
+    w, ww, nd = oracle.bow_transform(v, desc, levels_up)
+    (bw, bww, bnd), _ = walk_case(case, levels_up)
+    assert np.array_equal(w, bw) and np.array_equal(ww, bww) and np.array_equal(nd, bnd)
+    assert w.max() < v["is_leaf"].sum() and (np.all(nd == 0) if levels_up >= v["L"] else nd.max() > 0)
 
 
 def test_bow_tree_match_semantics(oracle):
