@@ -969,7 +969,9 @@ __device__ __forceinline__ void pose_oplus(const double* pose, const double* d, 
 //   4. wavefront 0 factors [D_j1; B1] -> L_j1,j1, L_i,j1.
 // D_j, X and D_j1 are factored redundantly by every panel workgroup; nobody overwrites them in S during the launch (the
 // diagonal workgroup publishes L_jj, L_j1,j1 into Ldiag; L_j1,j is needed by no later launch).  With an odd number of panels
-// the last launch is `single`: only column j.
+// the last launch is `single`: only column j, factored by wavefront 0 alone.
+// The LAST panel column of a system (step 4 of its last launch, or step 2 of a `single` one) stops after its dim - 32 (nb - 1) real
+// columns (chol_panel_trim): what follows them -- the rhs row's diagonal, the identity padding -- is read by nobody.
 constexpr int CP_BLK = NB * (NB + 1);                  // one padded 32x32 block in LDS
 constexpr int CP_LDS_BYTES = (11 * CP_BLK + 2 * (64 * 17 + 64 * 17)) * (int)sizeof(double);      // 11 blocks + the factor scratch of two wavefronts
 
@@ -1060,10 +1062,9 @@ struct PanelRegs { double dA[16], x[16], dB[16], y[16]; };
 // the two strips of a loaded panel with the block product between them; ROWS: lanes that carry rows (64, or 48 where the
 // scratch is short: 2 * ROWS * 17 doubles)
 template <int ROWS>
-__device__ __forceinline__ bool chol_panel_core(PanelRegs& p, int lane, double* scr)
+__device__ __forceinline__ void panel_between(PanelRegs& p, int lane, double* scr)
 {
     const int r = lane & 15;
-    bool fail = strip_factor(p.dA, p.x);
     double* Ls = scr; double* Us = scr + ROWS * 17;
     if (ROWS == 64 || lane < ROWS) {
 #pragma unroll
@@ -1090,10 +1091,16 @@ __device__ __forceinline__ bool chol_panel_core(PanelRegs& p, int lane, double* 
     }
 #pragma unroll
     for (int c = 0; c < 16; ++c) p.dB[c] = Ls[r * 17 + c];
+}
+template <int ROWS>
+__device__ __forceinline__ bool chol_panel_core(PanelRegs& p, int lane, double* scr)
+{
+    bool fail = strip_factor(p.dA, p.x);
+    panel_between<ROWS>(p, lane, scr);
     fail |= strip_factor(p.dB, p.y);
     return fail;
 }
-__device__ __forceinline__ bool chol_panel_dpp(PanelRegs& p, const double* Dblk, const double* Bblk, int lane, double* scr)
+__device__ __forceinline__ void panel_load(PanelRegs& p, const double* Dblk, const double* Bblk, int lane)
 {
     const int r = lane & 15;
     const double* own = lane < 16 ? Dblk + (16 + lane) * (NB + 1) : (Bblk != nullptr && lane < 48 ? Bblk + (lane - 16) * (NB + 1) : nullptr);
@@ -1103,7 +1110,54 @@ __device__ __forceinline__ bool chol_panel_dpp(PanelRegs& p, const double* Dblk,
         p.x[c] = own ? own[c] : 0.0;
         p.y[c] = own ? own[16 + c] : 0.0;
     }
+}
+__device__ __forceinline__ bool chol_panel_dpp(PanelRegs& p, const double* Dblk, const double* Bblk, int lane, double* scr)
+{
+    panel_load(p, Dblk, Bblk, lane);
     return chol_panel_core<64>(p, lane, scr);
+}
+// ---- the LAST panel column of a system: only its first `need` = dim - 32 (nb - 1) columns are real ---------------------------
+// Behind them sit the diagonal of the rhs row (1e200) and the identity padding, and nothing reads a factor column >= dim:
+// k_chol_xsolve takes Minv[i][c] and y[c] for c < dim only, and the factor leaves this file through x_p alone.  Pivot c feeds the
+// columns right of c and never one left of it, so stopping after `need` pivots leaves columns < need exactly as the full panel does;
+// the columns from `need` on keep half-updated (finite) numbers.  strip_step_n is strip_step with a uniform branch behind every
+// pivot; the common panels keep the straight-line strip.
+template <int JJ>
+__device__ __forceinline__ void strip_step_n(double (&d)[16], double (&x)[16], double piv, bool& fail, int need)
+{
+    const bool ok = piv > 0.0;
+    fail |= !ok;
+    const double pg = ok ? piv : 1.0;
+    const double y0 = __builtin_amdgcn_rsq(pg);
+    const double t = pg * y0;
+    const double e = fma(-t, y0, 1.0);
+    const double pp = fma(0.375, e, 0.5), ye = y0 * e;
+    const double rs = fma(ye, pp, y0);
+    const double l = d[JJ] * rs, lx = x[JJ] * rs;
+    d[JJ] = l; x[JJ] = lx;
+    if constexpr (JJ < 15) {
+        if (JJ + 1 < need) {
+            dpp_rank1<JJ + 1>(d, l, l);
+            const double next = dpp_bcast<JJ + 1>(d[JJ + 1]);
+            dpp_rank1<JJ + 1>(x, l, lx);
+            strip_step_n<JJ + 1>(d, x, next, fail, need);
+        }
+    }
+}
+// the first `need` (0 .. 32) columns of the panel [D; B]
+__device__ __forceinline__ bool chol_panel_trim(PanelRegs& p, const double* Dblk, const double* Bblk, int lane, double* scr, int need)
+{
+    panel_load(p, Dblk, Bblk, lane);
+    bool fail = false;
+    if (need > 0) strip_step_n<0>(p.dA, p.x, dpp_bcast<0>(p.dA[0]), fail, min(need, 16));
+    if (need > 16) {
+        panel_between<64>(p, lane, scr);
+        strip_step_n<0>(p.dB, p.y, dpp_bcast<0>(p.dB[0]), fail, need - 16);
+    } else {                                             // the second strip's columns stay as loaded
+#pragma unroll
+        for (int c = 0; c < 16; ++c) p.dB[c] = 0.0;
+    }
+    return fail;
 }
 // acc += A[tr.., :] B[tc.., :]^T over one 32-wide k-block (16x16 tile, 8 x v_mfma_f64_16x16x4)
 __device__ __forceinline__ f64x4 mfma_tile32(const double* A, const double* B, int tr, int tc, int lr, int lk, f64x4 acc)
@@ -1268,6 +1322,7 @@ __global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ vi
     }
     __syncthreads();
     bool fail = false;
+    const int need = min(max(dim - NB * (nb - 1), 0), NB);       // real columns of the system's last panel column (chol_panel_trim)
     // The factored blocks leave the registers through LDS (every lane owns a ROW there): the workgroup then stores them to memory
     // 32 lanes to a row, where a lane-per-row store touched one cache line per lane (2.4k cycles of the factoring wavefront).
     // L_jj goes into X's place (wavefront 0 alone reads X, at the start of 2a), L_j1,j1 into D_j1's, L_i,j1 into B1's.
@@ -1292,16 +1347,23 @@ __global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ vi
             dst[(size_t)r * pitch + c] = L[r * (NB + 1) + c];
         }
     };
-    if (wave == 0 && (!single || diag)) {                // 2a. [D_j; X] -> L_jj, L_j1,j   (single: the diagonal workgroup only needs L_jj)
+    if (single) {                                        // 2. the system's last panel column alone: [D_j; B0] -> L_jj / L_i,j, cut short
+        if (wave == 0) {
+            PanelRegs p;
+            fail = chol_panel_trim(p, Dj, has_b ? B0 : nullptr, lane, cp_lds + 11 * CP_BLK, need);
+            panel_to_lds(p, diag ? X : nullptr, has_b ? Ljk1 : nullptr);
+            if (diag && fail && lane == 0) scal[5] = 1.0;
+        }
+    } else if (wave == 0) {                              // 2a. [D_j; X] -> L_jj, L_j1,j
         PanelRegs p;
-        fail = chol_panel_dpp(p, Dj, single ? nullptr : X, lane, cp_lds + 11 * CP_BLK);
-        panel_to_lds(p, diag ? X : nullptr, single ? nullptr : Ljk0);                  // L_j1,j for step 3
+        fail = chol_panel_dpp(p, Dj, X, lane, cp_lds + 11 * CP_BLK);
+        panel_to_lds(p, diag ? X : nullptr, Ljk0);                                     // L_j1,j for step 3
         if (diag && fail && lane == 0) scal[5] = 1.0;
     } else if (wave == 1 && has_b) {                     // 2b. [D_j; B0] -> L_i,j
         PanelRegs p;
         chol_panel_dpp(p, Dj, B0, lane, cp_lds + 11 * CP_BLK + CH_SCR);
         panel_to_lds(p, nullptr, Ljk1);
-    } else if (prev && !single && wave >= 2) {           // 2c. the rest of the lookahead, beside the factorisations
+    } else if (prev && wave >= 2) {                      // 2c. the rest of the lookahead, beside the factorisations
         if (wave == 2) {
             for (int t4 = 0; t4 < 4; ++t4) {
                 const int r2 = (t4 >> 1) * 16, c2 = (t4 & 1) * 16;
@@ -1340,7 +1402,8 @@ __global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ vi
     __syncthreads();
     if (wave == 0) {                                     // 4. [D_j1; B1] -> L_j1,j1, L_i,j1
         PanelRegs p;
-        fail = chol_panel_dpp(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK);
+        fail = j1 == nb - 1 ? chol_panel_trim(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK, need)
+                            : chol_panel_dpp(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK);
         panel_to_lds(p, diag ? Dj1 : nullptr, has_b ? B1 : nullptr);
         if (diag && fail && lane == 0) scal[5] = 1.0;
     }
