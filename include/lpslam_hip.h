@@ -665,13 +665,24 @@ int lpslam_hip_jpeg_encode(lpslam_hip_jpeg* enc, int32_t n, const uint8_t* const
  * of a record).  The samples of a decoded image are bit for bit those of the host decoder (LpSlam::decode_jpeg_gray,
  * lpslam_jpeg_decode_gray), which are libjpeg's.  Calls on one decoder are serialised.  Every image gets a status: */
 #define LPSLAM_HIP_JPEG_DECODED 0      /* the samples are in outs[i] */
-#define LPSLAM_HIP_JPEG_NOT_TAKEN 1    /* a valid file of a class left to the host decoder: three components, a restart interval,
-                                          16-bit quantisation tables, larger than the decoder was made for, or more than 4 bytes per sample
-                                          + 4096 from the start of the entropy-coded data to the end of the file (a trailer counts) */
+#define LPSLAM_HIP_JPEG_NOT_TAKEN 1    /* a valid file of a class left to the host decoder: three components (see
+                                          lpslam_hip_jpeg_dec_create2 for the decoder that takes them), a restart interval, a 16-bit
+                                          quantisation table for the first component, larger than the decoder was made for, or more than
+                                          4 bytes per sample (12 in a decoder made for colour) + 4096 from the start of the
+                                          entropy-coded data to the end of the file (a trailer counts) */
 #define LPSLAM_HIP_JPEG_IRREGULAR 2    /* the header does not parse, or the entropy-coded data does not end where the block count says
                                           it must: the host decoder gives the verdict */
 typedef struct lpslam_hip_jpeg_dec lpslam_hip_jpeg_dec;
 int lpslam_hip_jpeg_dec_create(int32_t max_width, int32_t max_height, int32_t max_images, lpslam_hip_jpeg_dec** out);
+/* lpslam_hip_jpeg_dec_create is lpslam_hip_jpeg_dec_create2 with flags 0: such a decoder leaves every three-component stream NOT_TAKEN.
+ * With LPSLAM_HIP_JPEG_DEC_COLOR the decoder also takes three-component (YCbCr) baseline streams and gives their first component, which
+ * is what the host decoder and libjpeg's grey output give: one interleaved scan of all three components in frame order, the first
+ * sampled 1 x 1, 2 x 1 or 2 x 2 (4:4:4, 4:2:2, 4:2:0) and the other two 1 x 1, no restart interval, an 8-bit quantisation table for
+ * the first component.  Other three-component streams stay NOT_TAKEN.  Such a decoder is sized for 12 bytes of entropy-coded data per
+ * sample and for planes of whole 16 x 16 MCUs (about three times the memory of a grey one).  Unknown flag bits:
+ * LPSLAM_HIP_ERR_INVALID. */
+#define LPSLAM_HIP_JPEG_DEC_COLOR 1u
+int lpslam_hip_jpeg_dec_create2(int32_t max_width, int32_t max_height, int32_t max_images, uint32_t flags, lpslam_hip_jpeg_dec** out);
 void lpslam_hip_jpeg_dec_destroy(lpslam_hip_jpeg_dec* dec);
 /* n complete JPEG files (host memory) -> samples in outs[i], rows out_strides[i] bytes apart, capacity out_caps[i] bytes.  widths[i] /
  * heights[i] are always set from the frame header when there is one (0 otherwise).  If the samples of an image the device takes do
@@ -682,7 +693,8 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* dec, int32_t n, const uint8_t* c
                            uint8_t* const* outs, const int32_t* out_strides, const int64_t* out_caps,
                            int32_t* widths, int32_t* heights, int32_t* status);
 /* test hook: per image of the last decode call (n as there) the synchronisation rounds that changed a subsequence state, the
- * subsequences of its entropy-coded data, and the blocks they completed; zeros for an image the device did not take. */
+ * subsequences of its entropy-coded data, and the blocks they completed (of all components); zeros for an image the device did not
+ * take. */
 int lpslam_hip_jpeg_dec_last(lpslam_hip_jpeg_dec* dec, int32_t n, int32_t* rounds, int32_t* subsequences, int32_t* blocks);
 
 #ifdef __cplusplus

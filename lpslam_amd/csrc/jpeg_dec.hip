@@ -1,5 +1,6 @@
-// jpeg_dec.hip -- baseline JPEG decoder (one grey component, no restart interval) on gfx950: the direction jpeg.hip lacks.  The samples
-// are bit for bit those of the host decoder LpSlam::decode_jpeg_gray (lpslam_amd/host/jpeg.cpp), which are libjpeg's.  The header is
+// jpeg_dec.hip -- baseline JPEG decoder (no restart interval; one grey component, or -- a decoder made with LPSLAM_HIP_JPEG_DEC_COLOR
+// -- component 0 of a three-component 4:4:4 / 4:2:2 / 4:2:0 stream) on gfx950: the direction jpeg.hip lacks.  The samples are bit for bit
+// those of the host decoder LpSlam::decode_jpeg_gray (lpslam_amd/host/jpeg.cpp), which are libjpeg's.  The header is
 // parsed on the host by the routine the host decoder uses (host/jpeg_header.h); the entropy-coded data of one scan has no restart
 // markers, so it is decoded in parallel with the self-synchronising scheme of Weissenberger and Schmidt ("Accelerating JPEG
 // decompression on GPUs"): a Huffman decoder started in a wrong state falls into step with the true one after a few symbols.
@@ -10,21 +11,26 @@
 //                   without its stuffed zeros; the first real marker (an FF that no 00 follows) ends the data
 //   k_jdec_unstuff  a wave per piece, lane per word: every byte but the stuffed zeros to its place -> the clean bit string
 //   k_jdec_sync     one launch per round, lane = subsequence of kSubBits bits: decodes its subsequence from the exit state of its
-//                   predecessor (bit overhang, zigzag index; subsequence 0 from the true state, every other one from (0, DC next) at
-//                   first) whenever that state changed, and records its own exit state and the blocks it completed.  States are read
+//                   predecessor (bit overhang, zigzag index, and in a batch with a three-component image the place of the block in its
+//                   MCU; subsequence 0 from the true state, every other one from (0, DC next, place 0) at first) whenever that state changed, and records its own exit state and the blocks it completed.  States are read
 //                   from the previous round's array and written to this round's (two arrays in turn), so no workgroup waits for
 //                   another one and a round does not depend on scheduling.  A round that changes nothing ends the iteration: at most
 //                   as many rounds as subsequences, since subsequence s is final after round s.
 //   k_jdec_blocks   one workgroup per image: exclusive scan of the completed-block counts -> first block of every subsequence; the
-//                   total has to be the block count of the frame header
-//   k_jdec_write    as k_jdec_sync, from the final entry states: coefficients to int16[blocks][64] (natural order, zeroed before),
-//                   DC differences in place 0; flags what the host decoder refuses (undecodable code, index past 63, DC category > 11)
-//   k_jdec_dc       one workgroup per image: running sum of the DC differences (integers, predictor 0 at the first block)
+//                   total has to be the block count of the frame header, all components counted
+//   k_jdec_write    as k_jdec_sync, from the final entry states: coefficients of component 0 to int16[its blocks][64] (natural order,
+//                   zeroed before), DC differences in place 0, the symbols of the other components decoded and dropped; flags what the host decoder refuses (undecodable code, index past 63, DC category > 11)
+//   k_jdec_dc       one workgroup per image: running sum of component 0's DC differences in decode order (integers, predictor 0 at the
+//                   first block; the predictors of the other components are never needed)
 //   k_jdec_idct     one workgroup per chunk of 32 blocks: dequantisation and libjpeg's islow IDCT, lane = (block, column) for the first
-//                   pass, lane = (block, row) for the second one through LDS, range limit, 8 samples per store
+//                   pass, lane = (block, row) for the second one through LDS, range limit, 8 samples per store; a block's place in
+//                   the plane follows from its MCU and its place inside it (decode order is MCU by MCU, not the plane's raster)
 //   k_jdec_out      the planes and the per-image results to page-locked host memory with 16-byte stores
-// Every write is a plain store to a place of its own, an integer sum or an OR / MIN / MAX of integers: the output does not depend on
-// scheduling.  Every decode loop consumes at least one bit per turn and ends at its subsequence's last bit.
+// k_jdec_sync and k_jdec_write exist twice: <false> for a batch of one-component images (state without the MCU place, one table pair
+// in LDS -- the code of the grey-only decoder), <true> for a batch that holds a three-component image (a grey image in it is an MCU of
+// one block).  Every write is a plain store to a place of its own, an integer sum or an OR / MIN / MAX of integers: the output does
+// not depend on scheduling.  Every decode loop consumes at least one bit per turn and ends at its subsequence's last bit.  Plain C++
+// throughout: no inline assembly and no builtins beyond byte swap, shuffles and ballots.
 #include "internal.h"
 #include "../host/jpeg_header.h"
 
@@ -62,17 +68,27 @@ static_assert(kSubBits >= 32 && kSubBits % 32 == 0, "a symbol must not span more
 static_assert(kSyncThreads >= 64 && kSyncThreads <= 1024 && kSyncThreads % 64 == 0, "whole waves");
 static_assert(kRoundsPerCheck >= 1 && kRoundsPerCheck <= kRing / 2, "a batch of rounds must not lap the ring of changed words");
 
-struct DecTab {             // decoding tables of one image (T.81 F.2.2.3, as jpeg::HuffTable): [0] = DC, [1] = AC
+constexpr int kMaxPairs = 3;                                  // distinct (DC, AC) table pairs of one scan: one per component at most
+struct DecPair {            // decoding tables of one component (T.81 F.2.2.3, as jpeg::HuffTable): [0] = DC, [1] = AC
     unsigned short look[2][512];
     int mincode[2][17], maxcode[2][18], valptr[2][17];
     unsigned char vals[2][256];
-    unsigned short quant[64];   // natural order
+};
+struct DecTab {             // of one image: pair[0] is component 0's; a grey image uses no other
+    DecPair pair[kMaxPairs];
+    unsigned short quant[64];   // component 0's, natural order
 };
 struct DecImg {             // one image of a batch (device table)
     long long raw0;         // its entropy-coded data in the raw / clean buffers (a multiple of kPieceBytes)
     long long plane0;       // its plane (pitch x 8 * block rows) in the plane buffers
     unsigned int raw_n;     // bytes from the start of the data to the end of the file
-    int w, h, bw, nblk;
+    int w, h;
+    int bw;                 // blocks in a row of its plane (whole MCUs)
+    int nblk;               // blocks of all components in its scan: what the subsequences have to complete
+    int nluma;              // blocks of component 0: the coefficient array, k_jdec_dc and k_jdec_idct see no others
+    int h0, v0, mcux;       // component 0's blocks in an MCU (h0 x v0, in this order inside the MCU) and MCUs in a row
+    int mcu;                // blocks in an MCU: h0 * v0 of component 0, then one each of the others (grey: 1)
+    unsigned int pairs;     // 4 bits per place in the MCU: the table pair of the block there
     int blk0;               // first block in the coefficient array
     int piece0;             // first entry of its piece offsets
     int sub0;               // first entry of its subsequence arrays
@@ -245,50 +261,67 @@ __global__ __launch_bounds__(kThreads) void k_jdec_unstuff(DecArgs a)
     }
 }
 
-struct DecLds {
-    unsigned short look[2][512];
-    int mincode[2][17], maxcode[2][18], valptr[2][17];
-    unsigned char vals[2][256];
+template <int NP>
+struct DecLds {             // NP = 1: a batch of grey images (3040 B); NP = kMaxPairs: a batch that holds a three-component one (8992 B)
+    DecPair pair[NP];
     unsigned char nat[64];
 };
 
-__device__ __forceinline__ void load_tables(DecLds& t, const DecTab& g, const unsigned char* nat)
+template <int NP>
+__device__ __forceinline__ void load_tables(DecLds<NP>& t, const DecTab& g, const unsigned char* nat)
 {
-    for (int k = threadIdx.x; k < 1024; k += kSyncThreads) (&t.look[0][0])[k] = (&g.look[0][0])[k];
-    for (int k = threadIdx.x; k < 34; k += kSyncThreads) { (&t.mincode[0][0])[k] = (&g.mincode[0][0])[k]; (&t.valptr[0][0])[k] = (&g.valptr[0][0])[k]; }
-    for (int k = threadIdx.x; k < 36; k += kSyncThreads) (&t.maxcode[0][0])[k] = (&g.maxcode[0][0])[k];
-    for (int k = threadIdx.x; k < 512; k += kSyncThreads) (&t.vals[0][0])[k] = (&g.vals[0][0])[k];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) {
+        DecPair& tp = t.pair[q]; const DecPair& gp = g.pair[q];
+        for (int k = threadIdx.x; k < 1024; k += kSyncThreads) (&tp.look[0][0])[k] = (&gp.look[0][0])[k];
+        for (int k = threadIdx.x; k < 34; k += kSyncThreads) { (&tp.mincode[0][0])[k] = (&gp.mincode[0][0])[k]; (&tp.valptr[0][0])[k] = (&gp.valptr[0][0])[k]; }
+        for (int k = threadIdx.x; k < 36; k += kSyncThreads) (&tp.maxcode[0][0])[k] = (&gp.maxcode[0][0])[k];
+        for (int k = threadIdx.x; k < 512; k += kSyncThreads) (&tp.vals[0][0])[k] = (&gp.vals[0][0])[k];
+    }
     for (int k = threadIdx.x; k < 64; k += kSyncThreads) t.nat[k] = nat[k];
 }
 
 __device__ __forceinline__ int extend(int v, int s) { return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
 
-// Decodes the symbols that START in the subsequence [start, start + kSubBits) of the clean bit string (total bits) from the entry state
-// (bit overhang << 8 | zigzag index, 0 = DC next).  Returns the exit state; nb = blocks completed.  A block is complete at an EOB, at a
-// coefficient in place 63, and where a run leaves the block (a ZRL as in the host decoder; any other run is flagged in err, as are an
-// undecodable code and a DC category above 11 -- the host decoder refuses those, this one goes on so that the state it reaches is a
-// function of the entry state alone).  WRITE: coefficients of block first + nb to coef (DC: the difference), inside [0, nblk).
-template <bool WRITE>
-__device__ __forceinline__ unsigned int decode_sub(const DecLds& t, const unsigned int* words, unsigned int start, unsigned int total,
-                                                   unsigned int entry, unsigned int& nb, int16_t* coef, unsigned int first, unsigned int nblk,
-                                                   unsigned int& err)
+// Decodes the symbols that START in the subsequence [start, start + kSubBits) of the clean bit string (total bits) from the entry state.
+// COLOR = false (every image of the batch has one component): the state is (bit overhang << 8 | zigzag index, 0 = DC next).  COLOR =
+// true: (bit overhang << 12 | j << 8 | zigzag index) with j the place of the block inside its MCU, 0 .. mcu - 1; places below hv hold
+// component 0, the table pair of every place is in `pairs`.  Two states are equal only if all parts are; kStop (zigzag index 255) and
+// kNoEntry are no state of either kind.  Returns the exit state; nb = blocks completed, of all components.  A block is complete at an
+// EOB, at a coefficient in place 63, and where a run leaves the block (a ZRL as in the host decoder; any other run is flagged in err,
+// as are an undecodable code and a DC category above 11 -- the host decoder refuses those, this one goes on so that the state it
+// reaches is a function of the entry state alone).  WRITE: the coefficients (DC: the difference) of component 0's blocks to coef,
+// inside [0, nluma): block first + nb of the scan is a block of component 0 iff (first + nb) % mcu < hv, and then its number
+// (first + nb) / mcu * hv + (first + nb) % mcu; the symbols of the other components are decoded and dropped.
+struct DecMcu { unsigned int mcu, hv, pairs; };
+template <bool WRITE, bool COLOR>
+__device__ __forceinline__ unsigned int decode_sub(const DecLds<COLOR ? kMaxPairs : 1>& t, const unsigned int* words, unsigned int start, unsigned int total,
+                                                   unsigned int entry, unsigned int& nb, int16_t* coef, unsigned int first, unsigned int nluma,
+                                                   unsigned int& err, const DecMcu mc)
 {
     nb = 0;
     if (entry == kStop) return kStop;
     const unsigned int end = start + kSubBits;
-    unsigned int p = start + (entry >> 8);
+    unsigned int p = start + (entry >> (COLOR ? 12 : 8));
     int k = (int)(entry & 0xFFu);
+    unsigned int j = 0, q = 0, lb = first;                    // COLOR: place in the MCU by the state / by the running index, next block of component 0
+    const DecPair* tp = &t.pair[0];
+    if constexpr (COLOR) {
+        j = (entry >> 8) & 15u;
+        tp = &t.pair[(mc.pairs >> (4u * j)) & 3u];
+        if (WRITE) { const unsigned int m = first / mc.mcu; q = first - m * mc.mcu; lb = m * mc.hv + min(q, mc.hv); }
+    }
     unsigned int wi = 0xFFFFFFFFu, w0 = 0, w1 = 0;
     while (p < end && p < total) {                            // at least one bit per turn
         if ((p >> 5) != wi) { wi = p >> 5; w0 = __builtin_bswap32(words[wi]); w1 = __builtin_bswap32(words[wi + 1]); }
         const unsigned int bits = (unsigned int)(((((unsigned long long)w0) << 32) | w1) >> (32 - (p & 31)));
         const int tc = k ? 1 : 0;
-        const unsigned int e = t.look[tc][bits >> 23];
+        const unsigned int e = tp->look[tc][bits >> 23];
         int len = (int)(e >> 8), sym = (int)(e & 0xFFu);
         if (!e) {                                             // longer than 9 bits: F.2.2.3
             for (int l = 10; l <= 16; ++l) {
                 const int code = (int)(bits >> (32 - l));
-                if (t.maxcode[tc][l] >= 0 && code <= t.maxcode[tc][l] && code >= t.mincode[tc][l]) { len = l; sym = t.vals[tc][t.valptr[tc][l] + code - t.mincode[tc][l]]; break; }
+                if (tp->maxcode[tc][l] >= 0 && code <= tp->maxcode[tc][l] && code >= tp->mincode[tc][l]) { len = l; sym = tp->vals[tc][tp->valptr[tc][l] + code - tp->mincode[tc][l]]; break; }
             }
             if (!len) {
                 if (p + 16 > total) return kStop;             // the data ends inside what may be a code
@@ -300,7 +333,8 @@ __device__ __forceinline__ unsigned int decode_sub(const DecLds& t, const unsign
             const int s = sym & 15;
             if (p + len + s > total) return kStop;            // before the verdict: behind the last block the window holds leftovers
             if (sym > 11) err = 1u;
-            if (WRITE && s && first + nb < nblk) coef[(long long)(first + nb) * 64] = (int16_t)extend((int)((bits << len) >> (32 - s)), s);
+            if constexpr (COLOR) { if (WRITE && s && q < mc.hv && lb < nluma) coef[(long long)lb * 64] = (int16_t)extend((int)((bits << len) >> (32 - s)), s); }
+            else { if (WRITE && s && first + nb < nluma) coef[(long long)(first + nb) * 64] = (int16_t)extend((int)((bits << len) >> (32 - s)), s); }
             p += len + s; k = 1;
         } else {
             const int r = sym >> 4, s = sym & 15;
@@ -312,20 +346,29 @@ __device__ __forceinline__ unsigned int decode_sub(const DecLds& t, const unsign
                 k += r;
                 if (k > 63) { err = 1u; complete = true; }
                 else {
-                    if (WRITE && first + nb < nblk) coef[(long long)(first + nb) * 64 + t.nat[k]] = (int16_t)extend((int)((bits << len) >> (32 - s)), s);
+                    if constexpr (COLOR) { if (WRITE && q < mc.hv && lb < nluma) coef[(long long)lb * 64 + t.nat[k]] = (int16_t)extend((int)((bits << len) >> (32 - s)), s); }
+                    else { if (WRITE && first + nb < nluma) coef[(long long)(first + nb) * 64 + t.nat[k]] = (int16_t)extend((int)((bits << len) >> (32 - s)), s); }
                     ++k; complete = k == 64;
                 }
             }
             p += len + s;
         }
-        if (complete) { ++nb; k = 0; }
+        if (complete) {
+            ++nb; k = 0;
+            if constexpr (COLOR) {
+                j = j + 1u == mc.mcu ? 0u : j + 1u;
+                tp = &t.pair[(mc.pairs >> (4u * j)) & 3u];
+                if (WRITE) { if (q < mc.hv) ++lb; q = q + 1u == mc.mcu ? 0u : q + 1u; }
+            }
+        }
     }
-    return p >= end ? (((p - end) << 8) | (unsigned int)k) : kStop;
+    return p >= end ? (((p - end) << (COLOR ? 12 : 8)) | (COLOR ? j << 8 : 0u) | (unsigned int)k) : kStop;
 }
 
+template <bool COLOR>
 __global__ __launch_bounds__(kSyncThreads) void k_jdec_sync(DecArgs a, int round)
 {
-    __shared__ DecLds t;
+    __shared__ DecLds<COLOR ? kMaxPairs : 1> t;
     if (blockIdx.x == 0 && threadIdx.x == 0) a.changed[(round + 1) % kRing] = 0u;
     if (round > 0 && a.changed[(round - 1) % kRing] == 0u) return;           // the iteration has ended: nothing to do, for everyone
     const int i = image_of(a.imgs, a.n, blockIdx.x, false);
@@ -349,7 +392,8 @@ __global__ __launch_bounds__(kSyncThreads) void k_jdec_sync(DecArgs a, int round
     bool changed = false;
     if (need) {
         unsigned int nb, err = 0;
-        const unsigned int ex = decode_sub<false>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, total, entry, nb, nullptr, 0, 0, err);
+        const unsigned int ex = decode_sub<false, COLOR>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, total, entry, nb, nullptr, 0, 0, err,
+                                                         DecMcu{(unsigned int)im.mcu, (unsigned int)(im.h0 * im.v0), im.pairs});
         a.entry[g] = entry; a.nblk[g] = nb; cur[g] = ex;
         changed = ex != old_exit;
     }
@@ -374,9 +418,10 @@ __global__ __launch_bounds__(kScanThreads) void k_jdec_blocks(DecArgs a)
     if (threadIdx.x == 0) a.stat[i].blocks = carry;
 }
 
+template <bool COLOR>
 __global__ __launch_bounds__(kSyncThreads) void k_jdec_write(DecArgs a)
 {
-    __shared__ DecLds t;
+    __shared__ DecLds<COLOR ? kMaxPairs : 1> t;
     const int i = image_of(a.imgs, a.n, blockIdx.x, false);
     const DecImg im = a.imgs[i];
     const DecStat st = a.stat[i];
@@ -389,8 +434,9 @@ __global__ __launch_bounds__(kSyncThreads) void k_jdec_write(DecArgs a)
     if (s < st.nsub) {
         const long long g = im.sub0 + (long long)s;
         unsigned int nb;
-        decode_sub<true>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, st.nbytes * 8u, a.entry[g], nb,
-                         a.coef + (long long)im.blk0 * 64, a.bfirst[g], (unsigned int)im.nblk, err);
+        decode_sub<true, COLOR>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, st.nbytes * 8u, a.entry[g], nb,
+                                a.coef + (long long)im.blk0 * 64, a.bfirst[g], (unsigned int)im.nluma, err,
+                                DecMcu{(unsigned int)im.mcu, (unsigned int)(im.h0 * im.v0), im.pairs});
     }
     if (__ballot(err != 0u) && (threadIdx.x & 63) == 0) atomicOr(&a.stat[i].err, 1u);
 }
@@ -402,8 +448,8 @@ __global__ __launch_bounds__(kScanThreads) void k_jdec_dc(DecArgs a)
     const DecImg im = a.imgs[i];
     if (a.stat[i].blocks != (unsigned int)im.nblk) return;
     int16_t* coef = a.coef + (long long)im.blk0 * 64;
-    const int per = (im.nblk + kScanThreads - 1) / kScanThreads;
-    const int b0 = min(im.nblk, (int)threadIdx.x * per), b1 = min(im.nblk, b0 + per);
+    const int per = (im.nluma + kScanThreads - 1) / kScanThreads;
+    const int b0 = min(im.nluma, (int)threadIdx.x * per), b1 = min(im.nluma, b0 + per);
     int sum = 0;
     for (int b = b0; b < b1; ++b) sum += coef[(long long)b * 64];
     unsigned int total;
@@ -427,7 +473,7 @@ __global__ __launch_bounds__(kThreads) void k_jdec_idct(DecArgs a)
     const int j = lane >> 3, c = lane & 7;
     const int lb = (chunk - im.chunk0) * kChunkBlocks + wave * 8 + j;
     int* t = tile[wave] + 8 * j;
-    if (lb < im.nblk) {                               // columns: lane = (block j, column c)
+    if (lb < im.nluma) {                              // columns: lane = (block j, column c)
         const int16_t* in = a.coef + ((long long)im.blk0 + lb) * 64;
         int d[8], o[8];
 #pragma unroll
@@ -437,12 +483,14 @@ __global__ __launch_bounds__(kThreads) void k_jdec_idct(DecArgs a)
         for (int r = 0; r < 8; ++r) t[64 * r + ((r + c) & 7)] = o[r];
     }
     __syncthreads();
-    if (lb < im.nblk) {                               // rows: lane = (block j, row c)
+    if (lb < im.nluma) {                              // rows: lane = (block j, row c)
         int d[8], o[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) d[k] = t[64 * c + ((c + k) & 7)];
         idct8<18>(d, o);
-        const int by = lb / im.bw, bx = lb - by * im.bw;
+        const int hv = im.h0 * im.v0, m = lb / hv, q = lb - m * hv;               // decode order: MCU m, place q inside it (h0 x v0, rows first)
+        const int my = m / im.mcux, qy = q / im.h0;
+        const int by = my * im.v0 + qy, bx = (m - my * im.mcux) * im.h0 + (q - qy * im.h0);
         uint2 v;
         v.x = range_limit(o[0]) | (range_limit(o[1]) << 8) | (range_limit(o[2]) << 16) | (range_limit(o[3]) << 24);
         v.y = range_limit(o[4]) | (range_limit(o[5]) << 8) | (range_limit(o[6]) << 16) | (range_limit(o[7]) << 24);
@@ -471,6 +519,7 @@ long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 struct lpslam_hip_jpeg_dec {
     int device = 0;
     int max_w = 0, max_h = 0, max_images = 0;
+    bool color = false;                // made with LPSLAM_HIP_JPEG_DEC_COLOR: takes three-component streams too
     long long max_blocks = 0;          // per image
     long long raw_cap = 0;             // entropy-coded bytes per image
     long long plane_cap = 0;           // per image
@@ -518,21 +567,30 @@ extern "C" {
 
 int lpslam_hip_jpeg_dec_create(int32_t max_width, int32_t max_height, int32_t max_images, lpslam_hip_jpeg_dec** out)
 {
+    return lpslam_hip_jpeg_dec_create2(max_width, max_height, max_images, 0u, out);
+}
+
+int lpslam_hip_jpeg_dec_create2(int32_t max_width, int32_t max_height, int32_t max_images, uint32_t flags, lpslam_hip_jpeg_dec** out)
+{
     if (!out) { set_error("jpeg_dec_create: null argument"); return LPSLAM_HIP_ERR_INVALID; }
     *out = nullptr;
     if (max_width < 1 || max_height < 1 || max_width > 65535 || max_height > 65535 || max_images < 1 || max_images > 256) {
         set_error("jpeg_dec_create: sizes out of range (1 .. 65535 samples, 1 .. 256 images)");
         return LPSLAM_HIP_ERR_INVALID;
     }
-    const long long bw = (max_width + 7) / 8, bh = (max_height + 7) / 8, blocks = bw * bh;
-    // entropy-coded data the decoder takes: 4 bytes per sample (a coefficient has at most 26 bits; twice that with every byte stuffed)
-    const long long raw_cap = align_up(blocks * 64 * 4 + 4096, kPieceBytes);
+    if (flags & ~(uint32_t)LPSLAM_HIP_JPEG_DEC_COLOR) { set_error("jpeg_dec_create: unknown flag bits 0x%x", flags & ~(uint32_t)LPSLAM_HIP_JPEG_DEC_COLOR); return LPSLAM_HIP_ERR_INVALID; }
+    const bool color = (flags & LPSLAM_HIP_JPEG_DEC_COLOR) != 0;
+    // component 0's blocks: whole 8 x 8 blocks of a grey image; whole 16 x 16 MCUs (the largest of the class, 2 x 2) of a colour one
+    const long long bw = color ? (max_width + 15) / 16 * 2 : (max_width + 7) / 8, bh = color ? (max_height + 15) / 16 * 2 : (max_height + 7) / 8, blocks = bw * bh;
+    // entropy-coded data the decoder takes: 4 bytes per sample (a coefficient has at most 26 bits; twice that with every byte stuffed),
+    // and three coefficients per sample of component 0 in a 4:4:4 stream
+    const long long raw_cap = align_up(blocks * 64 * (color ? 12 : 4) + 4096, kPieceBytes);
     if (raw_cap * 8 >= (1LL << 31)) { set_error("jpeg_dec_create: image too large for 32-bit bit offsets"); return LPSLAM_HIP_ERR_INVALID; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_error("jpeg_dec_create: no HIP device (the host decoder is LpSlam::decode_jpeg_gray)"); return LPSLAM_HIP_ERR_DEVICE; }
     lpslam_hip_jpeg_dec* e = new (std::nothrow) lpslam_hip_jpeg_dec();
     if (!e) { set_error("jpeg_dec_create: out of host memory"); return LPSLAM_HIP_ERR_INVALID; }
-    e->max_w = max_width; e->max_h = max_height; e->max_images = max_images; e->max_blocks = blocks;
+    e->max_w = max_width; e->max_h = max_height; e->max_images = max_images; e->max_blocks = blocks; e->color = color;
     e->raw_cap = raw_cap; e->plane_cap = blocks * 64;
     e->head_bytes = align_up((long long)(sizeof(DecImg) + sizeof(DecStat) + sizeof(DecTab)) * max_images, kPieceBytes);
     e->raw_total = (raw_cap + kPieceBytes) * max_images + kPieceBytes;            // every image: its bytes and a piece of slack for the readers
@@ -586,6 +644,7 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
     DecTab* tabs = reinterpret_cast<DecTab*>(e->h_up + (sizeof(DecImg) + sizeof(DecStat)) * e->max_images);
     uint8_t* h_raw = e->h_up + e->head_bytes;
     int nd = 0, blk = 0, piece = 0, sub = 0, wg = 0, chunks = 0;
+    bool any_color = false;                                   // the batch holds a three-component image: the kernels that know the MCU
     long long raw = 0, plane = 0;
     unsigned int max_sub = 0;
     bool fits = true;
@@ -601,7 +660,9 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
         const jpeg::Header& hd = p.hd;
         const long long raw_n = (long long)(size - p.scan.data);
         if (raw_n < 1) continue;
-        if (hd.ncomp != 1 || hd.restart_interval != 0 || hd.q16[hd.comp[0].tq] || hd.X > e->max_w || hd.Y > e->max_h || raw_n > e->raw_cap) {
+        const bool grey = hd.ncomp == 1 && hd.restart_interval == 0 && !hd.q16[hd.comp[0].tq];
+        const bool ycc = e->color && jpeg::interleaved_ycc_scan(hd, p.scan);
+        if (!(grey || ycc) || hd.X > e->max_w || hd.Y > e->max_h || raw_n > e->raw_cap) {
             p.status = status[i] = LPSLAM_HIP_JPEG_NOT_TAKEN;
             continue;
         }
@@ -609,24 +670,41 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
         p.dev = nd;
         DecImg& im = imgs[nd];
         im.raw0 = raw; im.plane0 = plane; im.raw_n = (unsigned int)raw_n;
-        im.w = hd.X; im.h = hd.Y; im.bw = (hd.X + 7) / 8; im.nblk = im.bw * ((hd.Y + 7) / 8);
+        // the plane of component 0 is whole MCUs (hd.plane_w x hd.plane_h; whole blocks for one component, whose h and v the walk sets to 1)
+        im.w = hd.X; im.h = hd.Y; im.bw = hd.plane_w / 8; im.nluma = im.bw * (hd.plane_h / 8);
+        im.h0 = hd.comp[0].h; im.v0 = hd.comp[0].v; im.mcux = im.bw / im.h0;
+        im.mcu = im.h0 * im.v0 + (ycc ? 2 : 0); im.nblk = im.nluma / (im.h0 * im.v0) * im.mcu;
+        im.pairs = 0u;
+        any_color = any_color || ycc;
         im.blk0 = blk; im.piece0 = piece; im.sub0 = sub;
         const unsigned int nsub_cap = (unsigned int)((raw_n * 8 + kSubBits - 1) / kSubBits);
         im.wg0 = wg; im.nwg = (int)((nsub_cap + kSyncThreads - 1) / kSyncThreads);
-        im.chunk0 = chunks; im.nchunks = (im.nblk + kChunkBlocks - 1) / kChunkBlocks;
+        im.chunk0 = chunks; im.nchunks = (im.nluma + kChunkBlocks - 1) / kChunkBlocks;
         DecStat& st = stats[nd];
         st = DecStat{}; st.marker = im.raw_n; st.last_changed = -1;
         DecTab& t = tabs[nd];
-        const jpeg::HuffTable* ht[2] = {&hd.dc[hd.comp[0].td], &hd.ac[hd.comp[0].ta]};
-        for (int c = 0; c < 2; ++c) {
-            std::memcpy(t.look[c], ht[c]->look, sizeof(t.look[c]));
-            std::memcpy(t.mincode[c], ht[c]->mincode, sizeof(t.mincode[c])); std::memcpy(t.maxcode[c], ht[c]->maxcode, sizeof(t.maxcode[c]));
-            std::memcpy(t.valptr[c], ht[c]->valptr, sizeof(t.valptr[c])); std::memcpy(t.vals[c], ht[c]->vals, sizeof(t.vals[c]));
+        // the distinct (DC, AC) pairs of the scan's components, component 0's first; every place of the MCU names its pair
+        int npairs = 0, pair_td[kMaxPairs], pair_ta[kMaxPairs];
+        for (int ci = 0; ci < hd.ncomp; ++ci) {
+            int q = 0;
+            while (q < npairs && (pair_td[q] != hd.comp[ci].td || pair_ta[q] != hd.comp[ci].ta)) ++q;
+            if (q == npairs) {
+                pair_td[q] = hd.comp[ci].td; pair_ta[q] = hd.comp[ci].ta; ++npairs;
+                const jpeg::HuffTable* ht[2] = {&hd.dc[pair_td[q]], &hd.ac[pair_ta[q]]};
+                DecPair& tp = t.pair[q];
+                for (int c = 0; c < 2; ++c) {
+                    std::memcpy(tp.look[c], ht[c]->look, sizeof(tp.look[c]));
+                    std::memcpy(tp.mincode[c], ht[c]->mincode, sizeof(tp.mincode[c])); std::memcpy(tp.maxcode[c], ht[c]->maxcode, sizeof(tp.maxcode[c]));
+                    std::memcpy(tp.valptr[c], ht[c]->valptr, sizeof(tp.valptr[c])); std::memcpy(tp.vals[c], ht[c]->vals, sizeof(tp.vals[c]));
+                }
+            }
+            if (ci > 0) im.pairs |= (unsigned int)q << (4 * (im.h0 * im.v0 + ci - 1));
         }
+        for (int q = npairs; q < kMaxPairs; ++q) t.pair[q] = t.pair[0];              // staged in LDS with the others: defined bytes
         std::memcpy(t.quant, hd.quant[hd.comp[0].tq], sizeof(t.quant));
         std::memcpy(h_raw + raw, d + p.scan.data, (size_t)raw_n);
-        raw += align_up(raw_n + 32, kPieceBytes); plane += (long long)im.nblk * 64;
-        blk += im.nblk; piece += (int)((raw_n + kPieceBytes - 1) / kPieceBytes) + 1; sub += (int)nsub_cap + 1;
+        raw += align_up(raw_n + 32, kPieceBytes); plane += (long long)im.nluma * 64;
+        blk += im.nluma; piece += (int)((raw_n + kPieceBytes - 1) / kPieceBytes) + 1; sub += (int)nsub_cap + 1;
         wg += im.nwg; chunks += im.nchunks;
         max_sub = std::max(max_sub, nsub_cap);
         ++nd;
@@ -653,14 +731,18 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
     int round = 0;
     bool converged = false;
     for (int batch = kRoundsPerCheck; !converged && round <= (int)max_sub + 1; batch = std::min(2 * batch, kRing / 2)) {
-        for (int b = 0; b < batch; ++b, ++round) hipLaunchKernelGGL(k_jdec_sync, dim3(wg), dim3(kSyncThreads), 0, s, a, round);
+        for (int b = 0; b < batch; ++b, ++round) {
+            if (any_color) hipLaunchKernelGGL(k_jdec_sync<true>, dim3(wg), dim3(kSyncThreads), 0, s, a, round);
+            else hipLaunchKernelGGL(k_jdec_sync<false>, dim3(wg), dim3(kSyncThreads), 0, s, a, round);
+        }
         LP_HIP(hipGetLastError());
         LP_HIP(hipMemcpyAsync(e->h_changed, e->d_changed + (round - 1) % kRing, 4, hipMemcpyDeviceToHost, s));
         LP_HIP(hipStreamSynchronize(s));
         converged = *e->h_changed == 0u;
     }
     hipLaunchKernelGGL(k_jdec_blocks, dim3(nd), dim3(kScanThreads), 0, s, a);
-    hipLaunchKernelGGL(k_jdec_write, dim3(wg), dim3(kSyncThreads), 0, s, a);
+    if (any_color) hipLaunchKernelGGL(k_jdec_write<true>, dim3(wg), dim3(kSyncThreads), 0, s, a);
+    else hipLaunchKernelGGL(k_jdec_write<false>, dim3(wg), dim3(kSyncThreads), 0, s, a);
     hipLaunchKernelGGL(k_jdec_dc, dim3(nd), dim3(kScanThreads), 0, s, a);
     hipLaunchKernelGGL(k_jdec_idct, dim3(chunks), dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(k_jdec_out, dim3(kCopyGrid), dim3(kThreads), 0, s, a);

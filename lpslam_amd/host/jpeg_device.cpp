@@ -16,6 +16,15 @@ void JpegDecoder::setUseDevice(bool on)
     if (!on && m_dec) { lpslam_hip_jpeg_dec_destroy(m_dec); m_dec = nullptr; }
 }
 
+void JpegDecoder::setUseDeviceForColor(bool on)
+{
+    std::lock_guard<std::mutex> l(m_mutex);
+    m_useDeviceForColor = on;
+    // a device object made for colour would still take such a stream: the next one is made for grey
+    if (!on && m_dec && m_decColor) { lpslam_hip_jpeg_dec_destroy(m_dec); m_dec = nullptr; }
+    if (!on) m_decColor = false;
+}
+
 JpegDecodeCounters JpegDecoder::counters() const
 {
     JpegDecodeCounters c;
@@ -31,18 +40,22 @@ bool JpegDecoder::decode(int n, const uint8_t* const* data, const size_t* sizes,
     if (m_useDevice) {
         // the frame sizes, from the headers: the decoder is sized by the first record and regrown when a larger frame comes
         int w = 0, h = 0, X[2] = {0, 0}, Y[2] = {0, 0};
+        bool color = false;
         for (int i = 0; i < n; ++i) {
             if (!looks_like_jpeg(data[i], sizes[i])) continue;
             jpeg::Header hd; jpeg::Scan sc; size_t pos = 2;
-            if (jpeg::walk_to_scan(data[i], sizes[i], pos, hd, sc, nullptr) != jpeg::Walk::scan || hd.ncomp != 1) continue;
+            if (jpeg::walk_to_scan(data[i], sizes[i], pos, hd, sc, nullptr) != jpeg::Walk::scan) continue;
+            const bool ycc = m_useDeviceForColor && jpeg::interleaved_ycc_scan(hd, sc);
+            if (hd.ncomp != 1 && !ycc) continue;
+            color = color || ycc;
             X[i] = hd.X; Y[i] = hd.Y;
             w = std::max(w, hd.X); h = std::max(h, hd.Y);
         }
-        if (w > 0 && (!m_dec || w > m_decW || h > m_decH)) {
+        if (w > 0 && (!m_dec || w > m_decW || h > m_decH || (color && !m_decColor))) {
             if (m_dec) lpslam_hip_jpeg_dec_destroy(m_dec);
             m_dec = nullptr;
-            m_decW = std::max(w, m_decW); m_decH = std::max(h, m_decH);
-            if (lpslam_hip_jpeg_dec_create(m_decW, m_decH, 2, &m_dec) != LPSLAM_HIP_OK) {
+            m_decW = std::max(w, m_decW); m_decH = std::max(h, m_decH); m_decColor = m_decColor || color;
+            if (lpslam_hip_jpeg_dec_create2(m_decW, m_decH, 2, m_decColor ? LPSLAM_HIP_JPEG_DEC_COLOR : 0u, &m_dec) != LPSLAM_HIP_OK) {
                 logMessage(LpSlamLogLevel_Info, std::string("The device JPEG decoder cannot be created, decoding on the host: ") + lpslam_hip_last_error());
                 m_dec = nullptr; m_useDevice = false;
             }

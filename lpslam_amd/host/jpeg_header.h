@@ -164,5 +164,18 @@ inline Walk walk_to_scan(const uint8_t* d, size_t size, size_t& pos, Header& hd,
     }
 }
 
+// The three-component class the device decoder takes when it was made for colour (csrc/jpeg_dec.hip; DESIGN.md, the section on colour
+// streams): one interleaved scan of all three components in frame order, component 0 sampled 1 x 1, 2 x 1 or 2 x 2 (h x v), the other
+// two 1 x 1, no restart interval, an 8-bit quantisation table for component 0 (the chroma tables are never used).  Asked by the device
+// decoder and by the host layer that offers streams to it, so the two cannot disagree.
+inline bool interleaved_ycc_scan(const Header& hd, const Scan& scan)
+{
+    if (hd.ncomp != 3 || scan.ns != 3 || scan.idx[0] != 0 || scan.idx[1] != 1 || scan.idx[2] != 2) return false;
+    const Component& y = hd.comp[0];
+    if (!((y.h == 1 && y.v == 1) || (y.h == 2 && y.v == 1) || (y.h == 2 && y.v == 2))) return false;
+    if (hd.comp[1].h != 1 || hd.comp[1].v != 1 || hd.comp[2].h != 1 || hd.comp[2].v != 1) return false;
+    return hd.restart_interval == 0 && !hd.q16[y.tq];
+}
+
 }  // namespace jpeg
 }  // namespace LpSlam

@@ -64,6 +64,7 @@ STEREO_TWO_BUFFER, FORMAT_8UC1, FORMAT_8UC3, NO_DISTORTION, ODOM_ONLY = 3, 1, 2,
 PINHOLE, FISHEYE, OMNI = 0, 1, 2          # LpSlamCameraDistortionFunction
 ONE_IMAGE_COMPRESSED, STEREO_COMPRESSED = 4, 5          # LpSlamImageStructure
 JPEG_DECODE_DEVICE_KEY = "jpeg_decode_device"          # manager section of the configuration file: false = decode compressed frames on the host
+JPEG_DECODE_COLOR_DEVICE_KEY = "jpeg_decode_color_device"    # the same for three-component (YCbCr) streams alone; default true
 _lib = None
 
 
