@@ -1,9 +1,10 @@
 """Seeded random parity cases shared by tests/test_fuzz_gpu.py (bounded slices inside `-m gpu`) and the open-ended sweeps
-tools/fuzz_parity.py / fuzz_ba.py / fuzz_pose.py.  Every case is a function of (seed, case index) alone: a failing case can be
+tools/fuzz_parity.py / fuzz_ba.py / fuzz_pose.py / fuzz_sim3.py.  Every case is a function of (seed, case index) alone: a failing case can be
 re-run by its number.  Each `*_case` returns (ok, tag): the HIP path through the C ABI against the CPU oracle, bit for bit for
-the front end and the matchers, within the tolerances of tests/test_ba_gpu.py for the optimisers."""
+the front end and the matchers, within the tolerances of tests/test_ba_gpu.py for the optimisers (tests/sim3_cases.py for Sim3)."""
 import numpy as np
 
+import sim3_cases
 from lpslam_amd import hip, synth
 
 ROT_TOL, TRANS_TOL, CHI_RTOL = 1e-4, 1e-3, 1e-9
@@ -153,3 +154,25 @@ def pose_case(O, ctx, seed, case):
     ok = (same or flips <= max(1, n // 200)) and dr < 1e-6 and dt < 1e-5
     tag = "case %d: n %d stereo %s inliers %d / %d flips %d |dq| %.2e |dt| %.2e passes %d" % (case, n, cam_stereo, kin, oin, flips, dr, dt, ctx.pose_optimize_passes())
     return ok, tag, dr, dt
+
+
+def sim3_case(O, ctx, seed, case):
+    """lpslam_hip_sim3_* on an irregular pose graph (sim3_cases.irregular_graph: reversed and duplicated edges, a hub, fixed vertices
+    anywhere in the numbering): 2 ... 70 vertices, 1 ... 3 of them fixed, the scale fixed or free, with or without scale drift; 12
+    iterations on both sides, per-edge chi2, the logs over the oracle's converging prefix, final vertices, fixed vertices and fixed
+    scales bit for bit.  The prefix is as long as the draw makes it: small graphs converge in two steps.  Where the oracle itself is
+    not steady under a one-ulp change of its input (sim3_cases.oracle_wobble: most large graphs with the scale free), the logs are
+    compared over the first iteration only and the final vertices not at all; the tag says so."""
+    rng = _rng(seed, case)
+    n = int(rng.integers(2, 71)); n_fixed = int(rng.integers(1, min(3, n - 1) + 1))
+    fix_scale = bool(rng.integers(0, 2)); drift_scale = float(rng.choice([0.0, 0.01]))
+    p = sim3_cases.irregular_graph(n, int(rng.integers(1 << 30)), n_fixed, fix_scale, drift_scale)
+    steady = sim3_cases.oracle_is_steady(O, p, 12, trials=8)
+    checks, info = sim3_cases.compare_graph(hip, O, ctx, p, 12, min_prefix=0, first_step_only=not steady)
+    n_free = n - n_fixed
+    nb, need = sim3_cases.panel_shape(n_free)
+    tag = "case %d: n %d n_free %d nb %d need %d edges %d fix_scale %d drift_scale %g prefix %d%s" % (case, n, n_free, nb, need, info["n_edges"], fix_scale, drift_scale, info["prefix"], "" if steady else " (oracle unsteady)")
+    ok = all(checks.values())
+    if not ok:
+        tag += "  failed: " + ",".join(k for k, v in checks.items() if not v)
+    return ok, tag + "  |dq| %.1e |dt| %.1e trials %s" % (info["rot_dev"], info["trans_dev"], list(info["lg"]["trials"]))

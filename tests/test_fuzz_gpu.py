@@ -1,4 +1,4 @@
-"""Seeded, bounded slices of the randomised parity sweeps (tools/fuzz_parity.py, fuzz_ba.py, fuzz_pose.py) inside `-m gpu`, so that
+"""Seeded, bounded slices of the randomised parity sweeps (tools/fuzz_parity.py, fuzz_ba.py, fuzz_pose.py, fuzz_sim3.py) inside `-m gpu`, so that
 the driver's GPU record carries them: every case compares the HIP path, through the C ABI, with the CPU oracle.  The front-end
 cases draw a mapping reserve of 0 / 4 / 8 / 16: three quarters of them run the QUEUED extraction kernels (the ones bench.py times)
 directly against the oracle.  The cases live in tests/fuzz_cases.py; a case is a function of (seed, index) alone."""
@@ -33,4 +33,10 @@ def test_ba_fuzz(hiplib, oracle, small_ctx, case):
 @pytest.mark.parametrize("case", range(120))
 def test_pose_fuzz(hiplib, oracle, small_ctx, case):
     ok, tag, dr, dt = fuzz_cases.pose_case(oracle, small_ctx, SEED, case)
+    assert ok, tag
+
+
+@pytest.mark.parametrize("case", range(32))
+def test_sim3_fuzz(hiplib, oracle, small_ctx, case):
+    ok, tag = fuzz_cases.sim3_case(oracle, small_ctx, SEED, case)
     assert ok, tag

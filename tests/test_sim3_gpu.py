@@ -8,29 +8,14 @@ import pytest
 
 from conftest import golden
 from lpslam_amd import synth
+from sim3_cases import CHI_RTOL, ROT_TOL, TRANS_TOL, _check, rot_err
 
 pytestmark = pytest.mark.gpu
-
-ROT_TOL, TRANS_TOL, CHI_RTOL = 1e-4, 1e-3, 5e-4
-
-
-def rot_err(q1, q2):
-    return 2 * np.arccos(np.clip(np.abs(np.sum(q1 * q2, axis=1)), 0, 1))
 
 
 @pytest.fixture(scope="module")
 def ctx(hiplib):
     return hiplib.Context(320, 240, 400, 1.2, 4, max_images=1)
-
-
-def _check(vg, vo, lg, lo, n_cmp):
-    n_cmp = min(n_cmp, len(lo), len(lg))
-    assert np.allclose(lg["chi2_before"][:n_cmp], lo["chi2_before"][:n_cmp], rtol=CHI_RTOL)
-    assert np.allclose(lg["chi2_after"][:n_cmp], lo["chi2_after"][:n_cmp], rtol=CHI_RTOL)
-    assert np.array_equal(lg["trials"][:n_cmp], lo["trials"][:n_cmp])
-    assert np.allclose(lg["lambda"][:n_cmp], lo["lambda"][:n_cmp], rtol=CHI_RTOL)      # lambda follows rho, a ratio of chi2 differences
-    assert rot_err(vg[:, :4], vo[:, :4]).max() < ROT_TOL
-    assert np.abs(vg[:, 4:7] - vo[:, 4:7]).max() < TRANS_TOL and np.abs(vg[:, 7] - vo[:, 7]).max() < 1e-4
 
 
 def test_golden_pose_graph(hiplib, ctx):
