@@ -398,6 +398,11 @@ int64_t lpslam_hip_ba_wg_factorisations(lpslam_hip_ctx* ctx);
 #define LPSLAM_HIP_BA_SOLVER_DENSE 1
 #define LPSLAM_HIP_BA_SOLVER_BAND 2
 int lpslam_hip_ba_get_solver(lpslam_hip_ba* ba, int32_t* solver, int32_t* block_half_bandwidth);
+/* The dense path's Schur kernel cuts a window's long pose-block pair lists into parts of `part` terms, one workgroup each.  The
+ * build chooses `part` per window: the smallest of 128, 160, 192, 224 whose workgroups still run as one generation on the device
+ * (`capacity`: the further parts there is room for), else 256.  `part` depends on the window's own lists and on the device
+ * alone: built alone or in a batch, a window gets the same one.  Waits for the problem's stream.  Either pointer may be NULL. */
+int lpslam_hip_ba_get_schur_part(lpslam_hip_ba* ba, int32_t* part, int32_t* capacity);
 /* Hand-overs between workgroups that timed out on this problem so far: `band` -- the two chains of the twisted band factorisation
  * (k_chol_band), `update` -- the keyframe blocks of the one-launch update waiting for the trial landmarks (k_ba_update).  Both waits
  * are bounded so that a grid always drains; a time-out makes the optimize call that meets it fail with LPSLAM_HIP_ERR_DEVICE (its

@@ -37,11 +37,26 @@ using namespace lpslam;
 namespace {
 
 constexpr int SCH_PV = 42;            // values a part of a pose-block pair's list hands over in k_ba_schur: the 6 x 6 sum + the 6 of the keyframe's rhs (diagonal blocks)
-// How many workgroups of k_ba_schur share a pose-block pair's list: lists longer than 256 terms are cut into up to SCH_MAXP interleaved parts
+// How many workgroups of k_ba_schur share a pose-block pair's list: lists longer than `part` terms are cut into interleaved parts
 // (32-term chunks round-robin), so that the longest list -- a keyframe's diagonal block, one term per observation -- does not set the
-// kernel's duration; the part that finishes last adds the parts up in order (fixed summation order)
-constexpr int SCH_MAXP = 4, SCH_PART = 256;      // (8 parts of ~100 terms measured: 23.0 us against 22.2 -- the surplus workgroups of the larger table cost what the shorter chains gain)
-__host__ __device__ inline int schur_parts(int n_terms) { return n_terms > 256 ? ((n_terms + SCH_PART - 1) / SCH_PART < SCH_MAXP ? (n_terms + SCH_PART - 1) / SCH_PART : SCH_MAXP) : 1; }
+// kernel's duration; the part that finishes last adds the parts up in order (fixed summation order).
+// `part` is chosen per window when its lists are built (k_bs_blkscan): the smallest of 128, 160, 192, 224 (at most
+// SCH_MAXP parts) whose further parts still fit beside the launch's other workgroups in ONE generation of resident wavefronts, else
+// SCH_PART with at most SCH_MAXP_WIDE parts -- the cut every window had before.
+// (The earlier note here, "8 parts of ~100 terms measured: 23.0 us against 22.2", blamed the surplus workgroups of the larger table.
+// The arithmetic says otherwise: 128-term parts make ~2300 workgroups of the benchmark's window, the chip holds 2048 wavefronts of this
+// kernel, and the launch ran a second generation.)
+constexpr int SCH_MAXP = 8, SCH_PART = 256, SCH_MAXP_WIDE = 4, SCH_PART_MIN = 128, SCH_PART_STEP = 32;
+__host__ __device__ inline int schur_parts(int n_terms, int part)
+{
+    if (n_terms <= part) return 1;
+    const int p = (n_terms + part - 1) / part, cap = part >= SCH_PART ? SCH_MAXP_WIDE : SCH_MAXP;
+    return p < cap ? p : cap;
+}
+// head word of the table of further parts (behind the tickets): items in the low 24 bits (at most 1 << 18), part / 32 above them
+__host__ __device__ inline int schur_head(int count, int part) { return count | ((part / SCH_PART_STEP) << 24); }
+__host__ __device__ inline int schur_head_count(int head) { return head & 0xFFFFFF; }
+__host__ __device__ inline int schur_head_part(int head) { const int p = (head >> 24) * SCH_PART_STEP; return p >= SCH_PART_MIN && p < SCH_PART ? p : SCH_PART; }
 constexpr int SPLIT = 8;              // wavefronts per keyframe in the pose pass
 constexpr int PV = 28;                // partial-row stride per wavefront: 21 (H_pp upper) + 6 (b_p) (+1 pad; chi2 is kept apart)
 
@@ -678,7 +693,10 @@ __device__ __forceinline__ void obs_y_row(const double* h, double w0, double w1,
 //      AHEAD of their use (registers -> LDS -> the lanes of the term).  What bounds a workgroup since is its instruction count: ~115
 //      FP64 instructions (4 cycles each) + ~100 others per round of 32 terms, two wavefronts to a SIMD (1.3 us per round measured; with
 //      every load hitting the L1 still 0.9).  Measured and dropped: four lanes per term with two or three rounds in flight (128- and
-//      64-thread workgroups; 28.5 / 31 us: more instructions per term, or more wavefronts than the chip holds), eight parts per list.
+//      64-thread workgroups; 28.5 / 31 us: more instructions per term, or more wavefronts than the chip holds).
+//      What sets the launch's duration is its longest chain of rounds (3.1 us before the first row, then 1.3-1.8 us a round), as long as
+//      all workgroups are resident at once: 2048 wavefronts of this kernel (two to a SIMD).  The part size that cuts the lists is
+//      therefore chosen per window, the smallest whose workgroups still fit in one generation (k_bs_blkscan).
 //      The rhs of keyframe i, b_p,i - sum Y b_l over its observations, rides on the diagonal block (i, i), whose list has a term per
 //      observation: no workgroups of its own and no second pass over W.
 //      fused != 0 (single-GPU solve): lambda goes onto the pose diagonal, rhs straight into row `dim` of S and the failure
@@ -732,7 +750,8 @@ __global__ __launch_bounds__(64) void k_ba_schur(const BaView* __restrict__ view
     const bool further = bx >= 0 && (bx < efirst || bx >= efirst + nblk);
     GPTR(const int) ex = v.blk_ticket + nblk;              // [items | block * SCH_MAXP + part ...], written with the lists and constant since
     const int e = bx < efirst ? bx : bx - nblk;
-    const int count = ex[0];
+    const int head = ex[0];                                // items of the table and the window's part size (schur_head)
+    const int count = schur_head_count(head);
     const int item = bx < 0 ? 0 : (further ? ex[1 + min(max(e, 0), max(ecap - 1, 0))] : SCH_MAXP * v.blk_perm[bx - efirst]);
     const BaFlags fl = ba_flags(v.ctl);
     if (fl.idle()) return;
@@ -746,7 +765,7 @@ __global__ __launch_bounds__(64) void k_ba_schur(const BaView* __restrict__ view
     const int lane = threadIdx.x;
     const int n = v.dim_pad;
     const int t_begin = v.blk_start[blk], t_end = v.blk_start[blk + 1];
-    const int parts = schur_parts(t_end - t_begin);
+    const int parts = schur_parts(t_end - t_begin, schur_head_part(head));
     SCHUR_STAMP(3);
     // block -> (i, k), i <= k, blocks numbered row by row: row i starts at i N - i (i - 1) / 2
     int i;

@@ -39,7 +39,8 @@ __device__ __forceinline__ int bs_block_scan(int x, int* total)
 //      the maxima over the batch; a workgroup beyond its problem's extent leaves at once.
 struct BuildDesc {
     int n_poses, n_points, n_obs, n_free, n_blocks, dim, dim_pad, n_ord;
-    int extra_cap, pad_;                                   // entries the table of further Schur parts has room for (behind the tickets: [count | items])
+    int extra_cap;                                         // entries the table of further Schur parts has room for (behind the tickets: [head | items])
+    int extra_fit;                                         // further parts that fit beside the launch's other workgroups in one generation of resident wavefronts
     const lpslam_hip_ba_obs* obs;
     int *A, *R, *pt_count, *ps_count, *ps_start, *pt_start, *slot_of, *pt_obs, *o_orig, *o_pose, *o_point;
     double *o_u, *o_v, *o_ur, *o_w;
@@ -248,21 +249,49 @@ __global__ __launch_bounds__(256) void k_bs_paircount(const BuildDesc* __restric
 }
 
 // blk_start = exclusive scan of blk_count (n_blocks + 1 entries), tickets cleared; behind the tickets the table of the lists' FURTHER
-// parts (count, then block * SCH_MAXP + part in block order): k_ba_schur launches part 0 of every block and as many workgroups as this table
-// can hold at most (terms / SCH_PART, known on the host) instead of three surplus workgroups per block that leave at once -- 3675 of them
+// parts (head word, then block * SCH_MAXP + part in block order): k_ba_schur launches part 0 of every block and as many workgroups as this table
+// can hold at most (known on the host) instead of surplus workgroups per block that leave at once -- 3675 of them
 // for the 1225 pairs of a 50-keyframe window, and dispatching them took longer than the work (the last workgroups started 12 us in).
+// The window's part size is chosen here, where the pair counts are: the smallest candidate whose further parts number at most
+// extra_fit, else SCH_PART (schur_parts).  It follows from the window's lists and the device alone and is kept in the
+// table's head word, which every workgroup of k_ba_schur reads anyway.
+#ifdef LPSLAM_SCHUR_FORCE_PART                             // development build: this part size for every window whose table has room for it
+constexpr int SCH_FORCE_PART = LPSLAM_SCHUR_FORCE_PART;
+#else
+constexpr int SCH_FORCE_PART = 0;
+#endif
 __global__ __launch_bounds__(BS_THREADS) void k_bs_blkscan(const BuildDesc* __restrict__ descs)
 {
     const BuildDesc& d = descs[blockIdx.y];
     const int n_blocks = d.n_blocks;
     int* extra = d.blk_ticket + n_blocks;
+    constexpr int NCAND = (SCH_PART - SCH_PART_MIN) / SCH_PART_STEP;      // 128, 160, 192, 224
+    int part = SCH_PART;
+    {
+        int mine[NCAND];
+#pragma unroll
+        for (int c = 0; c < NCAND; ++c) mine[c] = 0;
+        for (int i = (int)threadIdx.x; i < n_blocks; i += BS_THREADS) {
+            const int x = d.blk_count[i];
+#pragma unroll
+            for (int c = 0; c < NCAND; ++c) mine[c] += schur_parts(x, SCH_PART_MIN + SCH_PART_STEP * c) - 1;
+        }
+        const int room = SCH_FORCE_PART ? d.extra_cap : (d.extra_fit < d.extra_cap ? d.extra_fit : d.extra_cap);
+#pragma unroll
+        for (int c = NCAND - 1; c >= 0; --c) {             // (integer sums: the same choice whatever the threads' order)
+            int tot;
+            (void)bs_block_scan(mine[c], &tot);
+            const int cand = SCH_PART_MIN + SCH_PART_STEP * c;
+            if (tot <= room && (!SCH_FORCE_PART || cand == SCH_FORCE_PART)) part = cand;
+        }
+    }
     int carry = 0, ecarry = 0;
     for (int i0 = 0; i0 < n_blocks; i0 += BS_THREADS) {
         const int i = i0 + (int)threadIdx.x;
         const int x = i < n_blocks ? d.blk_count[i] : 0;
         int tot, etot;
         const int pre = carry + bs_block_scan(x, &tot);
-        const int more = schur_parts(x) - 1;
+        const int more = schur_parts(x, part) - 1;
         const int epre = ecarry + bs_block_scan(more, &etot);
         if (i < n_blocks) {
             d.blk_start[i] = pre; d.blk_ticket[i] = 0;
@@ -270,7 +299,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_bs_blkscan(const BuildDesc* __re
         }
         carry += tot; ecarry += etot;
     }
-    if (threadIdx.x == 0) { d.blk_start[n_blocks] = carry; if (n_blocks == 0) d.blk_start[1] = 0; extra[0] = ecarry < d.extra_cap ? ecarry : d.extra_cap; }
+    if (threadIdx.x == 0) { d.blk_start[n_blocks] = carry; if (n_blocks == 0) d.blk_start[1] = 0; extra[0] = schur_head(ecarry < d.extra_cap ? ecarry : d.extra_cap, part); }
 }
 
 // the pair lists: keyframe a's observations in storage (= landmark) order, each with its partner(s) in keyframe c

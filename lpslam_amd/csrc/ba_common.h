@@ -88,7 +88,7 @@ struct BaView {                       // one problem, resident in device memory 
     // block-banded windows (ba_band.inl): block half-bandwidth of the reduced system when the problem takes the band path (-1: pair
     // lists + dense chain), landmark groups, [group records | first / last candidate group per free slot], entry table, group partials
     int band_hbw, band_groups, band_groups_cap;
-    int extra_pack;                   // k_ba_schur: workgroups for the further parts of long pair lists (table behind blk_ticket[n_blocks]: count, items):
+    int extra_pack;                   // k_ba_schur: workgroups for the further parts of long pair lists (table behind blk_ticket[n_blocks]: head word = items + the window's part size, then the items):
                                       // (cap << 12) | first -- the table holds at most `cap` items, `first` of them get workgroups in FRONT of the pairs'
                                       // part 0 (what the host expects: the diagonal blocks' parts), the rest behind them (one int: the view's size matters)
     GPTR(const int) band_tab; GPTR(const int) band_ent; GPTR(double) band_part;

@@ -34,6 +34,7 @@ struct lpslam_hip_ba {
     int faults_band = 0, faults_update = 0;            // timed-out hand-overs seen so far (report_faults)
     bool quiesced = false;                             // everything enqueued for this problem is known to be complete (a shared batch waited for it): destroy need not wait for its stream again
     bool built = false;                                // the structure build has been enqueued (lpslam_hip_ba_build_batch); prepare alone leaves the block untouched
+    int schur_fit = 0;                                 // further Schur parts that fit in one generation of k_ba_schur's workgroups (prepare), what the build chooses the part size by
     void* build_desc = nullptr;                        // BuildDesc of this problem (host copy), ba_build.inl
     size_t o_descs = 0;                                // offset of the descriptor array (device: in the block; host: in the staging block)
     hipEvent_t ev_built = nullptr;                     // a build enqueued on another problem's stream: this problem's stream waits for it
@@ -448,6 +449,20 @@ struct BandPlan {
     }
 };
 
+// wavefronts of k_ba_schur (one per workgroup) the device holds at once: what the runtime says fits on a compute unit x compute units,
+// asked once per device.  No kernel and no stream operation: lpslam_hip_ba_prepare stays callable from several threads.
+int schur_resident_waves(int device)
+{
+    static std::mutex mu;
+    static std::map<int, int> known;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = known.find(device);
+    if (it != known.end()) return it->second;
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ba_schur, 64, 0) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; cus = 0; }
+    return known[device] = per_cu * cus;               // (0: nothing is known, every window keeps SCH_PART)
+}
+
 struct Carve {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; }
@@ -530,14 +545,27 @@ int lpslam_hip_ba_prepare(lpslam_hip_ctx* ctx, const double* poses, const uint8_
     }
     const int land_blocks = (int)land_start.size() / 2 - 1;
 
-    // ---- k_ba_schur's further parts (ba_build.inl): the table holds at most terms / SCH_PART items (a list of n > 256 terms has at most n / SCH_PART
-    //      further parts); what the host can foresee are the diagonal blocks' (one term per observation of the keyframe) + some slack
-    int extra_cap = 0, extra_first = 0;
+    // ---- k_ba_schur's further parts (ba_build.inl).  The part size is chosen on the device, where the pair counts are; the host gives
+    //      it the room: extra_fit = the wavefronts of k_ba_schur the device holds at once - the leading pose-side workgroups
+    //      - part 0 of every block, so that a launch stays ONE generation of workgroups (a negative figure: no room, the window keeps
+    //      SCH_PART).  The table -- and the launch -- must hold that many items and what SCH_PART gives: a list of n > part terms has at
+    //      most n / part further parts and at most the part limit - 1.  What the host can foresee for the stretch in front of the pairs
+    //      are the diagonal blocks' parts (one term per observation of the keyframe) at the smallest part size + some slack.
+    int extra_cap = 0, extra_first = 0, extra_fit = 0;
     {
-        extra_cap = (int)std::min<size_t>(std::min<size_t>((SCH_MAXP - 1) * (size_t)b->n_blocks, terms_cap / SCH_PART), (size_t)1 << 18);
-        for (int i = 0; i < b->n_free; ++i) extra_first += schur_parts(kf_obs[(size_t)free_pose[(size_t)i]]) - 1;
+        const size_t cap_wide = std::min<size_t>((SCH_MAXP_WIDE - 1) * (size_t)b->n_blocks, terms_cap / SCH_PART);
+        const size_t cap_fine = std::min<size_t>((SCH_MAXP - 1) * (size_t)b->n_blocks, terms_cap / SCH_PART_MIN);
+        const long room = (long)schur_resident_waves(ctx->cfg.device) - (long)n_poses * SPLIT - (long)b->n_blocks;
+        extra_fit = (int)std::min<size_t>(std::min<size_t>((size_t)std::max(room, 0L), cap_fine), (size_t)1 << 18);
+#ifdef LPSLAM_SCHUR_FORCE_PART
+        extra_cap = (int)std::min<size_t>(std::max(cap_wide, cap_fine), (size_t)1 << 18);
+#else
+        extra_cap = (int)std::min<size_t>(std::max(cap_wide, (size_t)extra_fit), (size_t)1 << 18);
+#endif
+        for (int i = 0; i < b->n_free; ++i) extra_first += schur_parts(kf_obs[(size_t)free_pose[(size_t)i]], SCH_PART_MIN) - 1;
         extra_first = std::min(std::min(extra_first + 32, extra_cap), 4095);
     }
+    b->schur_fit = extra_fit;
     // ---- one block: [view | inputs as staged | zero-initialised part | the rest]
     const size_t np = (size_t)n_poses, npt = (size_t)std::max(n_points, 1), no = (size_t)std::max(n_obs, 1), n = (size_t)b->dim_pad;
     const size_t nblk = (size_t)std::max(b->n_blocks, 1), nfree = (size_t)std::max(b->n_free, 1);
@@ -676,7 +704,7 @@ int lpslam_hip_ba_prepare(lpslam_hip_ctx* ctx, const double* poses, const uint8_
         b->build_desc = d;
         d->n_poses = n_poses; d->n_points = n_points; d->n_obs = n_obs; d->n_free = b->n_free; d->n_blocks = b->n_blocks; d->dim = b->dim; d->dim_pad = b->dim_pad;
         d->n_ord = plan.hbw >= 0 ? (int)n_ord : 0;
-        d->extra_cap = extra_cap;
+        d->extra_cap = extra_cap; d->extra_fit = extra_fit;
         d->obs = (const lpslam_hip_ba_obs*)(base + o_obs_in);
         d->A = (int*)(base + o_A); d->R = (int*)(base + o_R); d->pt_count = (int*)(base + o_ptcount); d->ps_count = (int*)(base + o_pscount);
         d->ps_start = (int*)(base + o_ps_start); d->pt_start = (int*)(base + o_pt_start); d->slot_of = (int*)(base + o_slotof); d->pt_obs = (int*)(base + o_pt_obs);
@@ -1122,6 +1150,22 @@ int lpslam_hip_ba_get_solver(lpslam_hip_ba* b, int32_t* solver, int32_t* block_h
     if (!b) { set_error("null problem"); return LPSLAM_HIP_ERR_INVALID; }
     if (solver) *solver = b->h_view.band_hbw >= 0 ? LPSLAM_HIP_BA_SOLVER_BAND : LPSLAM_HIP_BA_SOLVER_DENSE;
     if (block_half_bandwidth) *block_half_bandwidth = b->band_hbw_structure;
+    return LPSLAM_HIP_OK;
+}
+
+// the part size k_ba_schur cuts this window's pair lists by (chosen by the build, read back from the table's head word: waits for
+// the problem's stream) and the room the choice was made for
+int lpslam_hip_ba_get_schur_part(lpslam_hip_ba* b, int32_t* part, int32_t* capacity)
+{
+    { const int nb = need_built(b); if (nb) return nb; }
+    if (capacity) *capacity = b->schur_fit;
+    if (part) {
+        int head = 0;
+        LP_HIP(hipSetDevice(b->ctx->cfg.device));
+        LP_HIP(hipStreamSynchronize(b->stream));
+        LP_HIP(hipMemcpy(&head, b->h_view.blk_ticket + b->n_blocks, sizeof(int), hipMemcpyDeviceToHost));
+        *part = schur_head_part(head);
+    }
     return LPSLAM_HIP_OK;
 }
 
