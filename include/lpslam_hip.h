@@ -575,6 +575,9 @@ int lpslam_hip_match_fuse(lpslam_hip_ctx* ctx, int image, const lpslam_hip_proj_
  * keypoint away from the earlier one (whose match_idx becomes -1). */
 int lpslam_hip_match_area(lpslam_hip_ctx* ctx, int image, const lpslam_hip_proj_query* queries, const uint8_t* q_desc32, int32_t nq,
                           int32_t hamming_thr, float lowe_ratio, int32_t* match_idx, int32_t* match_dist, int32_t* n_matches);
+/* Diagnostic: single-query rescans the last lpslam_hip_match_projection / _fuse / _area call on this context made (a query whose
+ * short candidate list earlier queries had used up is scanned again against the current assignment; fuse never rescans). */
+int32_t lpslam_hip_window_match_rescans(lpslam_hip_ctx* ctx);
 /* match::angle_checker: drops the matches whose angle difference (query - keypoint, degrees) lies outside the three most
  * populated 30-degree bins.  Host-side (a few thousand matches). */
 int lpslam_hip_match_orientation_filter(const float* angle_q, const float* angle_t, int32_t* match_idx, int32_t nq, int32_t* n_kept);

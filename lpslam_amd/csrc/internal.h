@@ -161,6 +161,7 @@ struct lpslam_hip_ctx {
     hipEvent_t ev_fe_ready = nullptr;  // session: "this frame's uploads are in the slots" for a shared front end (recorded on the session's stream)
     std::atomic<int> share_fe_pending{0};      // session: a shared front end has been launched and its delivery not yet collected
     int po_passes = 0;                 // passes the last pose optimisation made (diagnostic)
+    int wm_rescans = 0;                // single-query rescans the last window-matcher call made (diagnostic)
     int po_seq = 0;                    // sequence number the pose optimiser's kernel releases into its done flag (h_match + 64)
     int2* d_band_rows = nullptr;       // [band count 0..32][levels][bands]: rows of each level a band work-group computes
 
@@ -249,7 +250,7 @@ struct LpProjReq {                      // one window-matcher call (k_proj_topk_
     const void* kp; const uint8_t* desc; const float* stereo_xr; const int32_t* kp_count;
     const void* queries; const uint8_t* q_desc; const int16_t* best_so_far;
     unsigned long long* out_keys; int* out_count; unsigned* done_counter; int* done_flag;
-    int nq, grid_x, done_seq; float inv_w, inv_h; LpProjGate gate;
+    int nq, grid_x, done_seq; double inv_w, inv_h; LpProjGate gate;      // inv_w, inv_h: 64 / width, 48 / height (the candidates' grid cell)
 };
 struct LpPoseReq { uint8_t* blk; int n, seq; };        // one pose optimisation: the caller's page-locked block (pose_opt.hip, PO_BLK_*), observation count, flag value
 int lp_launch_proj_batch(hipStream_t s, const LpProjReq* table, int n, int grid_x_max);      // match.hip

@@ -393,7 +393,7 @@ __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __rest
                                                const float* __restrict__ stereo_xr, const int32_t* __restrict__ kp_count,
                                                const ProjQuery* __restrict__ queries, const uint8_t* __restrict__ q_desc,
                                                const int* __restrict__ q_ids, int nq, const int16_t* __restrict__ best_so_far,
-                                               float inv_w, float inv_h, const ProjGate& gate, unsigned long long* __restrict__ out_keys, int* __restrict__ out_count)
+                                               double inv_w, double inv_h, const ProjGate& gate, unsigned long long* __restrict__ out_keys, int* __restrict__ out_count)
 {
     // (out_keys / out_count may be page-locked host memory: with done_flag the kernel delivers the lists itself, lp_signal_done)
     const int lane = threadIdx.x & 63, qslot = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -444,7 +444,9 @@ __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __rest
 #pragma unroll
             for (int w = 0; w < 8; ++w) dist += __popc(a[w] ^ dw[w]);
             if (bsf_i <= dist) continue;                                // taken (0), or already matched at an equal or smaller distance
-            int cx = (int)floorf(k.x * inv_w), cy = (int)floorf(k.y * inv_h);
+            // the cell as the oracle's proj_cell computes it: a double product (a float one rounds x * 64 / w below the integer it
+            // equals at widths such as 752, x = 47 k, and ranks the keypoint one cell column early among equal distances)
+            int cx = (int)floor((double)k.x * inv_w), cy = (int)floor((double)k.y * inv_h);
             cx = min(max(cx, 0), 63); cy = min(max(cy, 0), 47);
             unsigned long long key = ((unsigned long long)dist << 32) | ((unsigned long long)(cx * 48 + cy) << 20) | ((unsigned long long)i << 4) | (unsigned)k.octave;
             ++cnt;
@@ -494,7 +496,7 @@ __global__ __launch_bounds__(256) void k_proj_topk(const lpslam_hip_keypoint* __
                                                    const float* __restrict__ stereo_xr, const int32_t* __restrict__ kp_count,
                                                    const ProjQuery* __restrict__ queries, const uint8_t* __restrict__ q_desc,
                                                    const int* __restrict__ q_ids, int nq, const int16_t* __restrict__ best_so_far,
-                                                   float inv_w, float inv_h, ProjGate gate, unsigned long long* __restrict__ out_keys, int* __restrict__ out_count,
+                                                   double inv_w, double inv_h, ProjGate gate, unsigned long long* __restrict__ out_keys, int* __restrict__ out_count,
                                                    unsigned* done_counter, int* done_flag, int done_seq)
 {
     proj_topk_body(kp, desc, stereo_xr, kp_count, queries, q_desc, q_ids, nq, best_so_far, inv_w, inv_h, gate, out_keys, out_count);
@@ -851,6 +853,7 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
     double tr_alloc = 0, tr_launch = 0, tr_wait = 0; int tr_rescans = 0;
     static_assert(sizeof(lpslam_hip_proj_query) == sizeof(ProjQuery), "query layout");
     if (n_matches) *n_matches = 0;
+    c->wm_rescans = 0;
     if (nq == 0) return LPSLAM_HIP_OK;
     hipStream_t s = c->stream;
     const size_t o = (size_t)image * c->slots_per_image;
@@ -899,7 +902,7 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
     // (a `taken` mask does not send the block down either: the second pass of the scan reads a candidate's best-so-far entry from the
     // page-locked mirror together with its descriptor -- one more PCIe read in a round of loads that is in flight anyway, one copy-engine
     // packet less in front of the kernel)
-    const float inv_w = (float)(64.0 / c->lt.w[0]), inv_h = (float)(48.0 / c->lt.h[0]);
+    const double inv_w = 64.0 / (double)c->lt.w[0], inv_h = 48.0 / (double)c->lt.h[0];
     const float* sxr = use_stereo ? c->d_stereo + (size_t)image * 2 * c->slots_per_image : nullptr;
     ProjGate gate{};
     gate.mode = policy == 1 ? 1 : 0;
@@ -983,8 +986,11 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
     if (trace) fprintf(stderr, "window_match: policy %d, %d queries, %d matches, %d rescans; us: setup %.1f, staged + launched %.1f, lists back %.1f, replayed %.1f\n",
                        policy, nq, found, tr_rescans, tr_alloc, tr_launch, tr_wait, tr_us());
     if (n_matches) *n_matches = found;
+    c->wm_rescans = tr_rescans;
     return LPSLAM_HIP_OK;
 }
+
+int32_t lpslam_hip_window_match_rescans(lpslam_hip_ctx* c) { return c ? c->wm_rescans : 0; }
 
 int lpslam_hip_match_projection(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_query* queries, const uint8_t* q_desc32, int32_t nq,
                                 int32_t hamming_thr, float lowe_ratio, const uint8_t* taken_in, int32_t use_stereo,

@@ -1,9 +1,10 @@
 """Seeded random parity cases shared by tests/test_fuzz_gpu.py (bounded slices inside `-m gpu`) and the open-ended sweeps
-tools/fuzz_parity.py / fuzz_ba.py / fuzz_pose.py / fuzz_sim3.py.  Every case is a function of (seed, case index) alone: a failing case can be
+tools/fuzz_parity.py / fuzz_ba.py / fuzz_pose.py / fuzz_sim3.py / fuzz_match.py.  Every case is a function of (seed, case index) alone: a failing case can be
 re-run by its number.  Each `*_case` returns (ok, tag): the HIP path through the C ABI against the CPU oracle, bit for bit for
 the front end and the matchers, within the tolerances of tests/test_ba_gpu.py for the optimisers (tests/sim3_cases.py for Sim3)."""
 import numpy as np
 
+import match_cases
 import sim3_cases
 from lpslam_amd import hip, synth
 
@@ -176,3 +177,91 @@ def sim3_case(O, ctx, seed, case):
     if not ok:
         tag += "  failed: " + ",".join(k for k, v in checks.items() if not v)
     return ok, tag + "  |dq| %.1e |dt| %.1e trials %s" % (info["rot_dev"], info["trans_dev"], list(info["lg"]["trials"]))
+
+
+WINDOW_LOG = {}      # (seed, case) -> what window_case saw: policy, skipped, the oracle's match count, the library's rescan count
+
+
+def window_draw(O, seed, case):
+    """The inputs of window_case, from the oracle alone: image size, level count, keypoint budget, image kind, frame 1 = frame 0 rolled by
+    a few pixels and its right image, the matcher policy and its queries.  None when frame 0 has no keypoints."""
+    rng = np.random.default_rng([int(seed), int(case), 8])
+    w = int(rng.choice([320, 376, 640, 752, 333])); h = int(rng.choice([240, 480, 251]))
+    levels = int(rng.integers(1, 9))
+    while levels > 1 and min(w, h) / 1.2 ** (levels - 1) < 64: levels -= 1
+    kpts = int(rng.integers(50, 1501))
+    kind = int(rng.integers(0, 2))
+    img0 = rng.integers(0, 256, (h, w)).astype(np.uint8) if kind == 0 else synth.random_image(w, h, seed=int(rng.integers(1 << 30)))
+    img1 = np.roll(img0, (int(rng.integers(-4, 5)), int(rng.integers(-6, 7))), axis=(0, 1))
+    right = np.roll(img1, -3, axis=1)
+    ties = rng.random() < 0.4
+    policy = match_cases.POLICIES[int(rng.integers(0, 3))]
+    nq_draw = rng.choice([1, 3, 4, 5, 64, 200, -1], p=[.05, .05, .1, .1, .2, .2, .3])
+    thr = int(rng.choice([50, 100, 256, 30, 0], p=[.3, .3, .2, .15, .05]))
+    ratio = float(rng.choice([0.8, 0.9, 1.0, 0.6, 0.0], p=[.3, .3, .2, .15, .05]))
+    use_stereo = bool(rng.integers(0, 2))
+    taken_density = float(rng.choice([0.1, 0.5, 1.0])) if (policy == "projection" and rng.integers(0, 2)) else None
+    p = O.params(kpts, 1.2, levels)
+    kp0, d0, _, _ = O.extract(img0, p)
+    tag = "case %d: %dx%d levels %d kpts %d kind %d ties %d %s thr %d ratio %.1f stereo %d taken %s" % (case, w, h, levels, kpts, kind, ties, policy, thr, ratio, use_stereo, taken_density)
+    if len(kp0) == 0: return None, tag
+    nq = len(kp0) if nq_draw < 0 else int(nq_draw)
+    src = rng.integers(0, len(kp0), nq)
+    sig = 1.0 if policy == "fuse" else 4.0
+    near = rng.random(nq) < 0.8
+    x = np.where(near, kp0["x"][src] + rng.normal(0, sig, nq), rng.uniform(-50, w + 50, nq))
+    y = np.where(near, kp0["y"][src] + rng.normal(0, sig, nq), rng.uniform(-50, h + 50, nq))
+    radius = np.exp(rng.uniform(np.log(4.0), np.log(300.0), nq))
+    special = rng.random(nq) < 0.1
+    radius = np.where(special, rng.choice([0.0, -5.0, 4000.0], nq), radius)
+    open_levels = rng.random(nq) < 0.5
+    lo = np.where(open_levels, -1, rng.integers(-1, levels + 1, nq)); hi = np.where(open_levels, -1, rng.integers(-1, levels + 1, nq))
+    xr = np.where(rng.random(nq) < 0.5, x - 3.0 + rng.normal(0, 1.0, nq), -1.0)
+    q = match_cases.queries(x, y, radius, lo, hi, xr)
+    qd = d0[src].copy()
+    proto = rng.integers(0, 256, (4, 32)).astype(np.uint8)
+    if ties: qd[rng.random(nq) < 0.3] = proto[0]
+    return dict(w=w, h=h, levels=levels, kpts=kpts, p=p, img1=img1, right=right, ties=ties, proto=proto, policy=policy, q=q, qd=qd, thr=thr, ratio=ratio,
+                use_stereo=use_stereo, taken_density=taken_density, rng=rng), tag
+
+
+def window_finish(d, n_kp, desc):
+    """what depends on the matched frame's own keypoint count: the planted descriptors (30 % of the frame copies of four prototypes) and
+    the `taken` mask"""
+    rng = d["rng"]
+    if d["ties"]:
+        desc = desc.copy()
+        planted = rng.random(n_kp) < 0.3
+        desc[planted] = d["proto"][rng.integers(0, 4, int(planted.sum()))]
+    taken = (rng.random(n_kp) < d["taken_density"]).astype(np.uint8) if d["taken_density"] is not None else None
+    return desc, taken
+
+
+def window_case(O, seed, case):
+    """lpslam_hip_match_projection / _fuse / _area against the oracle's matchers, bit for bit (tests/match_cases.py): random image size
+    (widths 376 and 752 among them: cell columns a float product misplaces), 1 ... 8 levels, 50 ... 1500 keypoints, white noise or a
+    synthetic scene; the matched frame is frame 0 rolled by a few pixels, its right image that rolled by 3; in 40 % of the cases 30 %
+    of the frame's descriptors are copies of four prototypes (ties, rescans).  1, 3, 4, 5, 64, 200 or as many queries as frame 0 has
+    keypoints: 80 % near a keypoint of frame 0, the rest anywhere in the image grown by 50 px; radius 4 ... 300 log-uniform, one in
+    ten 0, -5 or 4000; level bounds open or anything in -1 ... L, inverted pairs included; x_right on half the queries; thresholds
+    and ratios at their ends (0, 256; 0.0, 1.0) now and then; a `taken` mask of density 0.1 / 0.5 / 1.0 in half the projection
+    cases; the stereo column in half the cases.  A case whose frame has no keypoints is skipped.  Records itself in WINDOW_LOG."""
+    d, tag = window_draw(O, seed, case)
+    if d is None:
+        WINDOW_LOG[(seed, case)] = dict(policy=None, skipped=True, matches=0, rescans=0)
+        return True, tag + "  -> skipped (no keypoints)"
+    ctx = hip.Context(d["w"], d["h"], d["kpts"], 1.2, d["levels"], max_images=2)
+    try:
+        fr, bad = match_cases.load_frame(O, ctx, d["p"], 0, d["img1"], 1, d["right"], 40.0 * d["w"] / 640.0, 0.1)
+        if len(fr.kp) == 0:
+            WINDOW_LOG[(seed, case)] = dict(policy=None, skipped=True, matches=0, rescans=0)
+            return not bad, tag + "  -> skipped (no keypoints)" + ("  failed: " + ",".join(bad) if bad else "")
+        desc, taken = window_finish(d, len(fr.kp), fr.desc)
+        if d["ties"]: fr.set_descriptors(desc)
+        use_stereo = d["use_stereo"] and fr.xr is not None
+        why, (oi, od, on), rescans = match_cases.compare(O, fr, d["policy"], d["q"], d["qd"], d["thr"], d["ratio"], taken, use_stereo)
+        if why: bad.append(why)
+    finally:
+        ctx.close()
+    WINDOW_LOG[(seed, case)] = dict(policy=d["policy"], skipped=False, matches=int(on), rescans=int(rescans))
+    return not bad, tag + "  -> %d keypoints, %d queries, %d matches, %d rescans%s" % (len(fr.kp), len(d["q"]), on, rescans, ("  failed: " + "; ".join(bad)) if bad else "")

@@ -257,8 +257,9 @@ def test_projection_match_parity(hiplib, oracle, w, h, kpts, levels, radius):
 
 
 def test_projection_match_when_every_keypoint_is_a_candidate(hiplib, oracle):
-    """1280 x 720, 2000 keypoints, windows that cover the image and every level: each query's wavefront lists more candidates than its LDS
-    list holds at a time (the second pass runs in the middle of the scan as well as at its end)."""
+    """1280 x 720, 2000 keypoints, windows that cover the image and every level: each query's wavefront lists every keypoint, about 2000
+    of the 2048 entries its LDS list holds.  The scan has two iterations of 1024 keypoints, so the second pass runs once, at its end; the
+    pass in the middle of a scan needs a frame of more than 2048 keypoints (tests/test_window_match_gpu.py)."""
     w, h = 1280, 720
     ctx, q, qd, kp0, kp1, d1, xr1 = _proj_case(hiplib, oracle, w, h, 2000, 8, 11, n_queries=96)
     assert len(kp1) > 1500
@@ -279,6 +280,7 @@ def test_projection_match_sequential_semantics_and_rescans(hiplib, oracle):
     qd = np.repeat(qd[:1], len(q), axis=0)                                      # every query has the same descriptor
     gi, gd, gn = ctx.match_projection(2, q, qd, 256, 1.0, None, False)
     oi, od, on = oracle.match_projection(kp1, d1, None, 320, 240, q, qd, 256, 1.0)
+    assert ctx.window_match_rescans() > 0                                       # the re-scan did run
     assert gn == on and np.array_equal(gi, oi)
     m = gi[gi >= 0]
     assert len(m) > 20 and len(np.unique(m)) == len(m) and (np.diff(gd[gi >= 0]) >= 0).all()       # greedy: distances only grow

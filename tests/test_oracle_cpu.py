@@ -453,6 +453,42 @@ def test_fuse_and_area_match_semantics(oracle):
     assert list(idx3) == [k0, -1] and n3 == 1
 
 
+def test_equal_distances_at_width_752_are_ranked_by_the_double_cell(oracle):
+    """At width 752 a level-0 keypoint at x = 47, 94, 188, 376 has x * 64 / 752 = 4, 8, 16, 32 exactly: the oracle's proj_cell (a double
+    product) puts it in that cell column, a float product one column lower.  Per such x three keypoints with one descriptor: A at (x, 100),
+    B at (x - 3, 100) in the column before it, C at (x + 1, 88) in A's column, two cell rows higher.  A has the smallest index, so a matcher
+    that ranks A one column early answers A wherever the answers below are B or C.  (The library follows the oracle: tests/test_window_match_gpu.py.)"""
+    import match_cases
+    w, h = 752, 480
+    xs = np.array([47.0, 94.0, 188.0, 376.0], np.float32)
+    kp = np.zeros(12, oracle.KP_DTYPE)
+    kp["x"] = np.concatenate([xs, xs - 3, xs + 1]); kp["y"] = np.concatenate([np.full(8, 100.0), np.full(4, 88.0)])
+    A, B, C = np.arange(4), np.arange(4, 8), np.arange(8, 12)
+    cd, cf = match_cases.cell_columns(kp["x"], w)
+    assert list(cd[A]) == [4, 8, 16, 32] and list(cf[A]) == [3, 7, 15, 31] and np.array_equal(cd[B], cd[A] - 1) and np.array_equal(cd[C], cd[A])
+    assert np.array_equal(cf[B], cd[B]) and np.array_equal(cf[C], cd[C])           # only the A keypoints sit on the edge
+    desc = np.tile(np.arange(32, dtype=np.uint8), (12, 1))
+    q = match_cases.queries(xs, 100.0, 20.0)
+    qd = desc[:4]
+    for k in range(4):                                                              # single-query calls: only the scan order decides
+        i, d, n = oracle.match_projection(kp, desc, None, w, h, q[k:k + 1], qd[:1], 100, 1.0)
+        assert (list(i), list(d), n) == ([B[k]], [0], 1)                            # the column before A's comes first
+        taken = np.zeros(12, np.uint8); taken[B] = 1
+        i, d, n = oracle.match_projection(kp, desc, None, w, h, q[k:k + 1], qd[:1], 100, 1.0, taken)
+        assert (list(i), n) == ([C[k]], 1)                                          # A's column: C's cell row comes before A's
+    i, d, n = oracle.match_projection(kp, desc, None, w, h, np.repeat(q, 3), np.repeat(qd, 3, axis=0), 100, 1.0)
+    assert list(i) == [4, 8, 0, 5, 9, 1, 6, 10, 2, 7, 11, 3] and n == 12            # B, C, A per x when three queries compete
+    isq = np.ones(8, np.float32)
+    qf = match_cases.queries(xs - 1.5, 100.0, 20.0)                                 # 1.5 px from A and from B: both inside the gate, C is not
+    i, d, n = oracle.match_fuse(kp, desc, None, w, h, isq, qf, qd, 50)
+    assert list(i) == list(B) and n == 4
+    i, n = oracle.match_area(kp, desc, w, h, q, qd, 50, 1.0)
+    assert list(i) == [-1] * 4 and n == 0                                           # equal best and second: the strict ratio refuses
+    d2 = desc.copy(); d2[B, 0] ^= 1; d2[C, 0] ^= 3                                   # A exact, B one bit off, C two: no ties left
+    i, n = oracle.match_area(kp, d2, w, h, q, qd, 50, 1.0)
+    assert list(i) == list(A) and n == 4
+
+
 def test_closed_loop_oracle_is_reproducible(oracle):
     """the golden is what oracle/tracker.py makes today (first 8 frames; the whole sequence is regenerated by tools/make_golden_track.py)"""
     from oracle import tracker as T
