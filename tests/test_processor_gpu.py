@@ -35,26 +35,17 @@ def images(w, h):
             "two_level_lo_eq_hi": two_level(h, w, 100, 102)}
 
 
-_hip_rt = None
-
-
 def read_slot(ctx, image):
     """level 0 of a slot through lpslam_hip_image_ptr and a device-to-host copy of the whole pitched block: (pixels, padding)"""
-    global _hip_rt
-    if _hip_rt is None:
-        for name in ("libamdhip64.so", "/opt/rocm/lib/libamdhip64.so"):
-            try:
-                _hip_rt = C.CDLL(name)
-                break
-            except OSError:
-                continue
-        assert _hip_rt is not None, "the HIP runtime library was not found"
-        _hip_rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    # hipMemcpy is looked up through the library's own handle, i.e. in the HIP runtime it is linked against: once another copy of
+    # the runtime is in the process (torch brings one), a handle opened by name may be that copy, which knows no device
+    hip_memcpy = ctx.lib.hipMemcpy
+    hip_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     ctx.sync()
     ptr, pitch = ctx.image_ptr(image)
     h, w = ctx.cfg.height, ctx.cfg.width
     buf = np.zeros((h, pitch), np.uint8)
-    assert _hip_rt.hipMemcpy(buf.ctypes.data, ptr, buf.size, 2) == 0             # hipMemcpyDeviceToHost
+    assert hip_memcpy(buf.ctypes.data, ptr, buf.size, 2) == 0             # hipMemcpyDeviceToHost
     return buf[:, :w].copy(), buf[:, w:].copy()
 
 
