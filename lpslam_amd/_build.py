@@ -20,7 +20,7 @@ UNIT_DEPS = {
     "api.hip": [],
     "frontend.hip": ["orb_pattern.inc"],
     "match.hip": [],
-    "ba.hip": ["ba_common.h", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl", "ba_host.inl", "ba_partitioned.inl"],
+    "ba.hip": ["ba_common.h", "chol_panel.inl", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl", "ba_host.inl", "ba_partitioned.inl"],
     "pose_opt.hip": ["ba_common.h"],
     "sim3.hip": ["ba_common.h"],
     "bow.hip": [],

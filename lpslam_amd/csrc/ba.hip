@@ -971,7 +971,7 @@ __device__ __forceinline__ void pose_oplus(const double* pose, const double* d, 
 //   Two kinds of extra rows ride along so that no triangular substitution is ever run:
 //     row `dim` of S carries the rhs            -> after the last panel it holds y = L^-1 rhs,
 //     Minv starts as the identity (synthesised) -> its row blocks become L^-T; block (e, .) only exists from column e on.
-//   A panel is factored by ONE wavefront in two 16-column strips (chol_panel_dpp below): the diagonal block replicated in every
+//   A panel is factored by ONE wavefront in two 16-column strips (chol_panel_dpp, chol_panel.inl): the diagonal block replicated in every
 //   16-lane DPP row, the rows that ride along one per lane; the same rank-1 updates factor D and solve B L_jj^T = B.  The
 //   diagonal block is factored redundantly by every panel workgroup, which removes every dependence between workgroups of a launch.
 //   All working workgroups run on one XCD: the grid is launched 8x oversized and only every 8th workgroup works (workgroups go
@@ -995,202 +995,8 @@ constexpr int CP_BLK = NB * (NB + 1);                  // one padded 32x32 block
 constexpr int CP_LDS_BYTES = (11 * CP_BLK + 2 * (64 * 17 + 64 * 17)) * (int)sizeof(double);      // 11 blocks + the factor scratch of two wavefronts
 
 constexpr int CH_SCR = 64 * 17 + 64 * 17;              // doubles of scratch per factoring wavefront: L1 [64][17] and U [64][17]
-// ---- 16-column strip of a panel, rank-1 multipliers by DPP ---------------------------------------------------------------
-// The diagonal block D (16 x 16) is held REPLICATED: lane l keeps row l & 15 in d[0..15], so every 16-lane DPP row owns a full
-// copy, and x[0..15] is the lane's own row of whatever rides along below D (64 rows per wavefront).  The rank-1 update of column
-// jj, a[c] -= l[c] * l[row], then is ONE instruction per column and register set: v_fmac_f64_dpp with row_newbcast:c fetches
-// l[c] from lane c of the lane's own DPP row (the DP ALU only knows this DPP control, gfx90a+).  The readlane form it replaces
-// costs three issue slots per column (two v_readlane_b32 + the fma) and keeps the multipliers in SGPRs, which spilled; on
-// MI355X a strip with 64 riding rows takes 2.4k cycles against 3.4k (micro-benchmark) and 7.4k inside k_chol_pair.
-// Hazard: a VALU write of the DPP source needs two wait states before the DPP read and the compiler does not look into inline
-// assembly, so every block starts with s_nop 1.
-#define LP_DPPF(c) "v_fmac_f64_dpp %" #c ", %16, -%17 row_newbcast:" #c " row_mask:0xf bank_mask:0xf\n\t"
-#define LP_F15 LP_DPPF(15)
-#define LP_F14 LP_DPPF(14) LP_F15
-#define LP_F13 LP_DPPF(13) LP_F14
-#define LP_F12 LP_DPPF(12) LP_F13
-#define LP_F11 LP_DPPF(11) LP_F12
-#define LP_F10 LP_DPPF(10) LP_F11
-#define LP_F9 LP_DPPF(9) LP_F10
-#define LP_F8 LP_DPPF(8) LP_F9
-#define LP_F7 LP_DPPF(7) LP_F8
-#define LP_F6 LP_DPPF(6) LP_F7
-#define LP_F5 LP_DPPF(5) LP_F6
-#define LP_F4 LP_DPPF(4) LP_F5
-#define LP_F3 LP_DPPF(3) LP_F4
-#define LP_F2 LP_DPPF(2) LP_F3
-#define LP_F1 LP_DPPF(1) LP_F2
-#define LP_ACC16(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]), "+v"(a[9]), "+v"(a[10]), "+v"(a[11]), "+v"(a[12]), "+v"(a[13]), "+v"(a[14]), "+v"(a[15])
-// a[c] -= (src of lane c of this DPP row) * mul   for c = FROM .. 15
-template <int FROM>
-__device__ __forceinline__ void dpp_rank1(double (&a)[16], double src, double mul)
-{
-#define LP_CASE(k, S) if constexpr (FROM == k) asm("s_nop 1\n\t" S : LP_ACC16(a) : "v"(src), "v"(mul));
-    LP_CASE(1, LP_F1) LP_CASE(2, LP_F2) LP_CASE(3, LP_F3) LP_CASE(4, LP_F4) LP_CASE(5, LP_F5) LP_CASE(6, LP_F6) LP_CASE(7, LP_F7) LP_CASE(8, LP_F8)
-    LP_CASE(9, LP_F9) LP_CASE(10, LP_F10) LP_CASE(11, LP_F11) LP_CASE(12, LP_F12) LP_CASE(13, LP_F13) LP_CASE(14, LP_F14) LP_CASE(15, LP_F15)
-#undef LP_CASE
-}
-template <int L>
-__device__ __forceinline__ double dpp_bcast(double v)          // the value of lane L of this lane's DPP row
-{
-    double r;
-    asm("s_nop 1\n\tv_mov_b64_dpp %0, %1 row_newbcast:%2 row_mask:0xf bank_mask:0xf" : "=v"(r) : "v"(v), "n"(L));
-    return r;
-}
-// One pivot of a strip.  The strip is bound by its instruction COUNT (measured, tools/dev/strip_bench2.hip: 240 DPP updates at
-// 5.5 cycles + the per-pivot instructions at 4 to 5 cycles each; placing the next pivot's root between the updates by hand changes
-// nothing), so a pivot is written with as few instructions as the arithmetic allows:
-//   * 1 / sqrt(d) = y0 (1 + e / 2 + 3 e^2 / 8), e = 1 - d y0^2, y0 = v_rsq_f64 (2^-24, measured): one cubic step, five operations,
-//     1.4e-16 relative error over 4M samples (two Goldschmidt steps: eight operations, 2.1e-16);
-//   * the positivity guard sits BEFORE the root (compare + one 64-bit select; a failed pivot continues on 1.0: harmless finite
-//     numbers, the factorisation is flagged and its result discarded);
-//   * the next pivot is read back from the updated column with one DPP broadcast (a recurrence a(jj+1,jj+1) - l(jj+1)^2 on values
-//     broadcast beforehand shortens the dependent chain but costs four more instructions: 3.15 k against 2.84 k cycles per strip).
-template <int JJ>
-__device__ __forceinline__ void strip_step(double (&d)[16], double (&x)[16], double piv, bool& fail)
-{
-    const bool ok = piv > 0.0;
-    fail |= !ok;
-    const double pg = ok ? piv : 1.0;
-    const double y0 = __builtin_amdgcn_rsq(pg);
-    const double t = pg * y0;
-    const double e = fma(-t, y0, 1.0);
-    const double pp = fma(0.375, e, 0.5), ye = y0 * e;
-    const double rs = fma(ye, pp, y0);
-    const double l = d[JJ] * rs, lx = x[JJ] * rs;
-    d[JJ] = l; x[JJ] = lx;
-    if constexpr (JJ < 15) {
-        dpp_rank1<JJ + 1>(d, l, l);
-        const double next = dpp_bcast<JJ + 1>(d[JJ + 1]);
-        dpp_rank1<JJ + 1>(x, l, lx);
-        strip_step<JJ + 1>(d, x, next, fail);
-    }
-}
-// d <- chol(D) (lower part; rows above the diagonal of a column hold values nobody reads), x <- x chol(D)^-T
-__device__ __forceinline__ bool strip_factor(double (&d)[16], double (&x)[16])
-{
-    bool fail = false;
-    strip_step<0>(d, x, dpp_bcast<0>(d[0]), fail);
-    return fail;
-}
-// Register Cholesky of a 32-column panel [D; B] from two padded LDS blocks (B may be absent): two strips with the block product
-// between them on the matrix cores (through this wavefront's scratch).  Lane l carries row l & 15 of the replicated diagonal
-// block of each strip, and in x / y its own row of the stack  [D rows 16..31 (lanes 0-15); B rows 0..31 (lanes 16-47)]:
-//   dA = L00, x = [L10; L_B,0], dB = L11, y = [L11; L_B,1]  (lanes 48-63 idle along with zeros)
-struct PanelRegs { double dA[16], x[16], dB[16], y[16]; };
-// the two strips of a loaded panel with the block product between them; ROWS: lanes that carry rows (64, or 48 where the
-// scratch is short: 2 * ROWS * 17 doubles)
-template <int ROWS>
-__device__ __forceinline__ void panel_between(PanelRegs& p, int lane, double* scr)
-{
-    const int r = lane & 15;
-    double* Ls = scr; double* Us = scr + ROWS * 17;
-    if (ROWS == 64 || lane < ROWS) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) Ls[lane * 17 + k] = p.x[k];
-    }
-    const int lr = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {                        // U[16t.., :] = X[16t.., :] (X[0..15, :])^T, K = 16 (rows 48.. are zero)
-        f64x4 acc = {0, 0, 0, 0};
-#pragma unroll
-        for (int s4 = 0; s4 < 16; s4 += 4)
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ls[(16 * t + lr) * 17 + s4 + lk], Ls[lr * 17 + s4 + lk], acc, 0, 0, 0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Us[(16 * t + lk + 4 * q) * 17 + lr] = acc[q];
-    }
-    if (lane < 48) {
-#pragma unroll
-        for (int c = 0; c < 16; ++c) p.y[c] -= Us[lane * 17 + c];
-    }
-    // the second diagonal block, updated, goes back out to every DPP row
-    if (lane < 16) {
-#pragma unroll
-        for (int c = 0; c < 16; ++c) Ls[lane * 17 + c] = p.y[c];
-    }
-#pragma unroll
-    for (int c = 0; c < 16; ++c) p.dB[c] = Ls[r * 17 + c];
-}
-template <int ROWS>
-__device__ __forceinline__ bool chol_panel_core(PanelRegs& p, int lane, double* scr)
-{
-    bool fail = strip_factor(p.dA, p.x);
-    panel_between<ROWS>(p, lane, scr);
-    fail |= strip_factor(p.dB, p.y);
-    return fail;
-}
-__device__ __forceinline__ void panel_load(PanelRegs& p, const double* Dblk, const double* Bblk, int lane)
-{
-    const int r = lane & 15;
-    const double* own = lane < 16 ? Dblk + (16 + lane) * (NB + 1) : (Bblk != nullptr && lane < 48 ? Bblk + (lane - 16) * (NB + 1) : nullptr);
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        p.dA[c] = Dblk[r * (NB + 1) + c];
-        p.x[c] = own ? own[c] : 0.0;
-        p.y[c] = own ? own[16 + c] : 0.0;
-    }
-}
-__device__ __forceinline__ bool chol_panel_dpp(PanelRegs& p, const double* Dblk, const double* Bblk, int lane, double* scr)
-{
-    panel_load(p, Dblk, Bblk, lane);
-    return chol_panel_core<64>(p, lane, scr);
-}
-// ---- the LAST panel column of a system: only its first `need` = dim - 32 (nb - 1) columns are real ---------------------------
-// Behind them sit the diagonal of the rhs row (1e200) and the identity padding, and nothing reads a factor column >= dim:
-// k_chol_xsolve takes Minv[i][c] and y[c] for c < dim only, and the factor leaves this file through x_p alone.  Pivot c feeds the
-// columns right of c and never one left of it, so stopping after `need` pivots leaves columns < need exactly as the full panel does;
-// the columns from `need` on keep half-updated (finite) numbers.  strip_step_n is strip_step with a uniform branch behind every
-// pivot; the common panels keep the straight-line strip.
-template <int JJ>
-__device__ __forceinline__ void strip_step_n(double (&d)[16], double (&x)[16], double piv, bool& fail, int need)
-{
-    const bool ok = piv > 0.0;
-    fail |= !ok;
-    const double pg = ok ? piv : 1.0;
-    const double y0 = __builtin_amdgcn_rsq(pg);
-    const double t = pg * y0;
-    const double e = fma(-t, y0, 1.0);
-    const double pp = fma(0.375, e, 0.5), ye = y0 * e;
-    const double rs = fma(ye, pp, y0);
-    const double l = d[JJ] * rs, lx = x[JJ] * rs;
-    d[JJ] = l; x[JJ] = lx;
-    if constexpr (JJ < 15) {
-        if (JJ + 1 < need) {
-            dpp_rank1<JJ + 1>(d, l, l);
-            const double next = dpp_bcast<JJ + 1>(d[JJ + 1]);
-            dpp_rank1<JJ + 1>(x, l, lx);
-            strip_step_n<JJ + 1>(d, x, next, fail, need);
-        }
-    }
-}
-// the first `need` (0 .. 32) columns of the panel [D; B]
-__device__ __forceinline__ bool chol_panel_trim(PanelRegs& p, const double* Dblk, const double* Bblk, int lane, double* scr, int need)
-{
-    panel_load(p, Dblk, Bblk, lane);
-    bool fail = false;
-    if (need > 0) strip_step_n<0>(p.dA, p.x, dpp_bcast<0>(p.dA[0]), fail, min(need, 16));
-    if (need > 16) {
-        panel_between<64>(p, lane, scr);
-        strip_step_n<0>(p.dB, p.y, dpp_bcast<0>(p.dB[0]), fail, need - 16);
-    } else {                                             // the second strip's columns stay as loaded
-#pragma unroll
-        for (int c = 0; c < 16; ++c) p.dB[c] = 0.0;
-    }
-    return fail;
-}
-// acc += A[tr.., :] B[tc.., :]^T over one 32-wide k-block (16x16 tile, 8 x v_mfma_f64_16x16x4)
-__device__ __forceinline__ f64x4 mfma_tile32(const double* A, const double* B, int tr, int tc, int lr, int lk, f64x4 acc)
-{
-#pragma unroll
-    for (int s4 = 0; s4 < NB; s4 += 4)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(tr + lr) * (NB + 1) + s4 + lk], B[(tc + lr) * (NB + 1) + s4 + lk], acc, 0, 0, 0);
-    return acc;
-}
-__device__ __forceinline__ void tile_sub(double* D, int tr, int tc, int lr, int lk, f64x4 acc)
-{
-#pragma unroll
-    for (int q = 0; q < 4; ++q) D[(tr + lk + 4 * q) * (NB + 1) + tc + lr] -= acc[q];
-}
+// the strips, the panel [D; B] in registers and the 32-wide tile product: shared with tools/dev/panel_bench.hip
+#include "chol_panel.inl"
 
 __global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ views, int m, int pin, int skip_small)
 {

@@ -134,10 +134,11 @@ __global__ __launch_bounds__(CW_THREADS) void k_chol_wg(const BaView* __restrict
 #pragma unroll
                 for (int c = 0; c < 16; ++c) {
                     p.dA[c] = c <= r ? S[(size_t)r * n + c] : 0.0;
+                    const double yd = second ? (c <= r ? S[(size_t)(16 + r) * n + 16 + c] : 0.0) : (c == r ? 1.0 : 0.0);
                     double xv = 0.0, yv = 0.0;
-                    if (lane < 16) { xv = second ? S[(size_t)(16 + lane) * n + c] : 0.0; yv = second ? (c <= lane ? S[(size_t)(16 + lane) * n + 16 + c] : 0.0) : (c == lane ? 1.0 : 0.0); }
+                    if (lane < 16) { xv = second ? S[(size_t)(16 + lane) * n + c] : 0.0; yv = yd; }
                     else if (lane < 48) { xv = c == ir ? 1.0 : 0.0; yv = 16 + c == ir ? 1.0 : 0.0; }
-                    p.x[c] = xv; p.y[c] = yv;
+                    p.x[c] = xv; p.y[c] = yv; p.dB[c] = yd;                       // dB: the second diagonal block's row r, in every DPP row
                 }
             } else {
                 // wait for the block's tiles (a counter in LDS: no workgroup barrier, the other wavefronts go on with the lookahead)
@@ -150,10 +151,11 @@ __global__ __launch_bounds__(CW_THREADS) void k_chol_wg(const BaView* __restrict
                 for (int c = 0; c < 16; ++c) {
                     const double d0 = X[cw_swz(r, c)], x1 = row1[cw_swz(r, c)], y1 = row1[cw_swz(r, 16 + c)];
                     p.dA[c] = c <= r ? d0 : 0.0;
+                    const double yd = second ? (c <= r ? y1 : 0.0) : (c == r ? 1.0 : 0.0);
                     double xv = 0.0, yv = 0.0;
-                    if (lane < 16) { xv = second ? x1 : 0.0; yv = second ? (c <= lane ? y1 : 0.0) : (c == lane ? 1.0 : 0.0); }
+                    if (lane < 16) { xv = second ? x1 : 0.0; yv = yd; }
                     else if (lane < 48) { xv = c == ir ? 1.0 : 0.0; yv = 16 + c == ir ? 1.0 : 0.0; }
-                    p.x[c] = xv; p.y[c] = yv;
+                    p.x[c] = xv; p.y[c] = yv; p.dB[c] = yd;
                 }
             }
             const bool fail = chol_panel_core<48>(p, lane, Wb);          // scratch: Wb + the two vectors behind it (1664 >= 2 x 48 x 17 doubles)
