@@ -674,12 +674,14 @@ int lpslam_hip_jpeg_encode(lpslam_hip_jpeg* enc, int32_t n, const uint8_t* const
  * lpslam_jpeg_decode_gray), which are libjpeg's.  Calls on one decoder are serialised.  Every image gets a status: */
 #define LPSLAM_HIP_JPEG_DECODED 0      /* the samples are in outs[i] */
 #define LPSLAM_HIP_JPEG_NOT_TAKEN 1    /* a valid file of a class left to the host decoder: three components (see
-                                          lpslam_hip_jpeg_dec_create2 for the decoder that takes them), a restart interval, a 16-bit
-                                          quantisation table for the first component, larger than the decoder was made for, or more than
+                                          lpslam_hip_jpeg_dec_create2 for the decoder that takes them), a restart interval (see
+                                          lpslam_hip_jpeg_dec_take_restart for the switch that takes those), a 16-bit quantisation table for the first component, larger than the decoder was made for, or more than
                                           4 bytes per sample (12 in a decoder made for colour) + 4096 from the start of the
                                           entropy-coded data to the end of the file (a trailer counts) */
 #define LPSLAM_HIP_JPEG_IRREGULAR 2    /* the header does not parse, or the entropy-coded data does not end where the block count says
-                                          it must: the host decoder gives the verdict */
+                                          it must, or (restart intervals) it does not hold ceil(MCUs / Ri) - 1 restart markers, each
+                                          byte aligned behind exactly Ri whole MCUs -- fill bytes in front of a marker count as that:
+                                          the host decoder gives the verdict */
 typedef struct lpslam_hip_jpeg_dec lpslam_hip_jpeg_dec;
 int lpslam_hip_jpeg_dec_create(int32_t max_width, int32_t max_height, int32_t max_images, lpslam_hip_jpeg_dec** out);
 /* lpslam_hip_jpeg_dec_create is lpslam_hip_jpeg_dec_create2 with flags 0: such a decoder leaves every three-component stream NOT_TAKEN.
@@ -692,6 +694,12 @@ int lpslam_hip_jpeg_dec_create(int32_t max_width, int32_t max_height, int32_t ma
 #define LPSLAM_HIP_JPEG_DEC_COLOR 1u
 int lpslam_hip_jpeg_dec_create2(int32_t max_width, int32_t max_height, int32_t max_images, uint32_t flags, lpslam_hip_jpeg_dec** out);
 void lpslam_hip_jpeg_dec_destroy(lpslam_hip_jpeg_dec* dec);
+/* Off at creation (lpslam_hip_jpeg_dec_create and _create2 alike): every stream whose header sets a restart interval is NOT_TAKEN.
+ * on != 0: a stream that is otherwise of a class this decoder takes -- one component, or one interleaved Y/Cb/Cr scan on a decoder
+ * made with LPSLAM_HIP_JPEG_DEC_COLOR -- and has a DRI segment is decoded on the device, RSTn markers in the entropy-coded data
+ * included (Ri = 0, or Ri of the MCU count or more, means no marker: the path of a stream without DRI).  Non-interleaved and
+ * multi-scan files and 16-bit tables for the first component stay NOT_TAKEN.  Holds for the calls that follow; serialised with them. */
+int lpslam_hip_jpeg_dec_take_restart(lpslam_hip_jpeg_dec* dec, int32_t on);
 /* n complete JPEG files (host memory) -> samples in outs[i], rows out_strides[i] bytes apart, capacity out_caps[i] bytes.  widths[i] /
  * heights[i] are always set from the frame header when there is one (0 otherwise).  If the samples of an image the device takes do
  * not fit its out_caps[i] (or out_strides[i] is below its width): LPSLAM_HIP_ERR_INVALID, the sizes are reported and no output buffer

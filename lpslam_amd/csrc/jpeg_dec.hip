@@ -1,36 +1,47 @@
-// jpeg_dec.hip -- baseline JPEG decoder (no restart interval; one grey component, or -- a decoder made with LPSLAM_HIP_JPEG_DEC_COLOR
-// -- component 0 of a three-component 4:4:4 / 4:2:2 / 4:2:0 stream) on gfx950: the direction jpeg.hip lacks.  The samples are bit for bit
+// jpeg_dec.hip -- baseline JPEG decoder (one grey component, or -- a decoder made with LPSLAM_HIP_JPEG_DEC_COLOR -- component 0 of a
+// three-component 4:4:4 / 4:2:2 / 4:2:0 stream; with a restart interval only on a decoder switched to take them,
+// lpslam_hip_jpeg_dec_take_restart) on gfx950: the direction jpeg.hip lacks.  The samples are bit for bit
 // those of the host decoder LpSlam::decode_jpeg_gray (lpslam_amd/host/jpeg.cpp), which are libjpeg's.  The header is
-// parsed on the host by the routine the host decoder uses (host/jpeg_header.h); the entropy-coded data of one scan has no restart
-// markers, so it is decoded in parallel with the self-synchronising scheme of Weissenberger and Schmidt ("Accelerating JPEG
-// decompression on GPUs"): a Huffman decoder started in a wrong state falls into step with the true one after a few symbols.
+// parsed on the host by the routine the host decoder uses (host/jpeg_header.h); the entropy-coded data of one scan is decoded in
+// parallel with the self-synchronising scheme of Weissenberger and Schmidt ("Accelerating JPEG decompression on GPUs"): a Huffman
+// decoder started in a wrong state falls into step with the true one after a few symbols.  Restart markers do not change the grid:
+// they leave the clean bit string like the stuffed zeros, their places go into a boundary table per image, and a decoder that
+// reaches a boundary jumps to it with the true entry state of an interval.
 //
 // A batch of streams is one upload, one chain of launches on the decoder's stream and one wait at its end, plus one wait per batch of
 // synchronisation rounds:
 //   k_jdec_count    one workgroup per image: FF 00 pairs per 256-byte piece of the raw data, exclusive scan -> where every piece lands
-//                   without its stuffed zeros; the first real marker (an FF that no 00 follows) ends the data
-//   k_jdec_unstuff  a wave per piece, lane per word: every byte but the stuffed zeros to its place -> the clean bit string
+//                   without its stuffed zeros; the first real marker (an FF that no 00 follows) ends the data.  An image with a restart
+//                   interval: FF D0 .. FF D7 does not end the data, both bytes leave with the zeros (the FF may end one piece and the Dn
+//                   begin the next), and a second scan counts the markers in front of every piece; any other FF xx ends the data, FF FF
+//                   fill bytes included.  Another marker count than ceil(MCUs / Ri) - 1: no subsequences, irregular at once
+//   k_jdec_unstuff  a wave per piece, lane per word: every byte but the stuffed zeros and the restart markers to its place -> the clean
+//                   bit string; restart marker m (from 1, stream order) stores the clean offset behind it in the image's boundary table
 //   k_jdec_sync     one launch per round, lane = subsequence of kSubBits bits: decodes its subsequence from the exit state of its
 //                   predecessor (bit overhang, zigzag index, and in a batch with a three-component image the place of the block in its
 //                   MCU; subsequence 0 from the true state, every other one from (0, DC next, place 0) at first) whenever that state changed, and records its own exit state and the blocks it completed.  States are read
 //                   from the previous round's array and written to this round's (two arrays in turn), so no workgroup waits for
 //                   another one and a round does not depend on scheduling.  A round that changes nothing ends the iteration: at most
-//                   as many rounds as subsequences, since subsequence s is final after round s.
+//                   as many rounds as subsequences, since subsequence s is final after round s.  A subsequence that holds a boundary
+//                   leaves with a state that does not depend on its entry state: it is final after round 0.
 //   k_jdec_blocks   one workgroup per image: exclusive scan of the completed-block counts -> first block of every subsequence; the
 //                   total has to be the block count of the frame header, all components counted
 //   k_jdec_write    as k_jdec_sync, from the final entry states: coefficients of component 0 to int16[its blocks][64] (natural order,
 //                   zeroed before), DC differences in place 0, the symbols of the other components decoded and dropped; flags what the host decoder refuses (undecodable code, index past 63, DC category > 11)
+//                   and every jump to a boundary that is not made at (DC next, place 0, block m * Ri * blocks per MCU)
 //   k_jdec_dc       one workgroup per image: running sum of component 0's DC differences in decode order (integers, predictor 0 at the
-//                   first block; the predictors of the other components are never needed)
+//                   first block and at every multiple of Ri MCUs; the predictors of the other components are never needed)
 //   k_jdec_idct     one workgroup per chunk of 32 blocks: dequantisation and libjpeg's islow IDCT, lane = (block, column) for the first
 //                   pass, lane = (block, row) for the second one through LDS, range limit, 8 samples per store; a block's place in
 //                   the plane follows from its MCU and its place inside it (decode order is MCU by MCU, not the plane's raster)
 //   k_jdec_out      the planes and the per-image results to page-locked host memory with 16-byte stores
 // k_jdec_sync and k_jdec_write exist twice: <false> for a batch of one-component images (state without the MCU place, one table pair
 // in LDS -- the code of the grey-only decoder), <true> for a batch that holds a three-component image (a grey image in it is an MCU of
-// one block).  Every write is a plain store to a place of its own, an integer sum or an OR / MIN / MAX of integers: the output does
-// not depend on scheduling.  Every decode loop consumes at least one bit per turn and ends at its subsequence's last bit.  Plain C++
-// throughout: no inline assembly and no builtins beyond byte swap, shuffles and ballots.
+// one block); and each of those twice again: without the boundary handling for a batch in which no image has restart markers -- the
+// loop of a decoder that knows no restarts, which measured 15 to 35 % faster per round than the folded one -- and with it.
+// k_jdec_count, k_jdec_unstuff and k_jdec_dc are split the same way (a branch more per byte cost 30 to 40 us a stereo pair).  Every write is a plain store to a place of its own, an integer sum or an OR / MIN / MAX of integers: the output does
+// not depend on scheduling.  Every decode loop consumes at least one bit per turn or jumps forward to a boundary, and ends at its
+// subsequence's last bit.  Plain C++ throughout: no inline assembly and no builtins beyond byte swap, shuffles and ballots.
 #include "internal.h"
 #include "../host/jpeg_header.h"
 
@@ -94,6 +105,10 @@ struct DecImg {             // one image of a batch (device table)
     int sub0;               // first entry of its subsequence arrays
     int wg0, nwg;           // its workgroups in k_jdec_sync / k_jdec_write
     int chunk0, nchunks;    // its workgroups in k_jdec_idct
+    int nrst;               // restart markers its data must hold: ceil(MCUs / Ri) - 1 (0: no restart interval, or one of the MCU count or more)
+    int ribl;               // blocks of all components in a restart interval: Ri * mcu
+    int lumaseg;            // blocks of component 0 in one: Ri * h0 * v0 (nluma when nrst is 0)
+    int bound0;             // first entry of its boundary table; entry m (1 .. nrst): the clean byte offset behind restart marker m
 };
 struct DecStat {
     unsigned int marker;    // offset of the first real marker in the raw data (raw_n: none)
@@ -102,7 +117,8 @@ struct DecStat {
     int last_changed;       // the last round in which an exit state changed
     unsigned int blocks;    // blocks completed by all subsequences
     unsigned int err;       // the write pass met what the host decoder refuses
-    unsigned int pad[2];
+    unsigned int nrst;      // restart markers in front of the first real marker; another count than DecImg::nrst: nsub = 0, irregular
+    unsigned int pad;
 };
 
 struct DecArgs {
@@ -112,7 +128,9 @@ struct DecArgs {
     DecStat* stat;
     const DecTab* tabs;
     int n;
-    unsigned int* poff;     // stuffed zeros in front of every piece
+    unsigned int* poff;     // bytes that leave the clean string (stuffed zeros, restart markers) in front of every piece
+    unsigned int* moff;     // restart markers in front of every piece (images with a restart interval only)
+    unsigned int* bound;    // the boundary tables
     unsigned int* entry;    // per subsequence: the entry state of its last decode
     unsigned int* exit;     // 2 x sub_total: exit states of the even / odd rounds
     long long sub_total;
@@ -170,23 +188,26 @@ __device__ __forceinline__ int image_of(const DecImg* imgs, int n, int group, bo
     return i;
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kScanThreads) void k_jdec_count(DecArgs a)
 {
     __shared__ unsigned int wsum[kScanThreads / 64 + 1];
-    __shared__ unsigned int s_marker, s_removed;
+    __shared__ unsigned int s_marker, s_removed, s_markers;
     const int i = blockIdx.x;
     const DecImg im = a.imgs[i];
     const unsigned int raw_n = im.raw_n;
     const uint8_t* raw = a.raw + im.raw0;
     const uint4* src = reinterpret_cast<const uint4*>(raw);
     unsigned int* poff = a.poff + im.piece0;
+    unsigned int* moff = a.moff + im.piece0;
     const int npieces = (int)((raw_n + kPieceBytes - 1) / kPieceBytes);
-    if (threadIdx.x == 0) { s_marker = raw_n; s_removed = 0; }
+    const bool rst = RST && im.nrst > 0;                      // FF D0 .. FF D7 is a restart marker: both bytes leave, the data goes on
+    if (threadIdx.x == 0) { s_marker = raw_n; s_removed = 0; s_markers = 0; }
     __syncthreads();
-    unsigned int carry = 0, mk = 0xFFFFFFFFu;
+    unsigned int carry = 0, mcarry = 0, mk = 0xFFFFFFFFu;
     for (int base = 0; base < npieces; base += kScanThreads) {
         const int piece = base + (int)threadIdx.x;
-        unsigned int cnt = 0;
+        unsigned int cnt = 0, mc = 0;                         // bytes of the piece that leave; markers whose second byte is in it
         if (piece < npieces) {
             const unsigned int b0 = (unsigned int)piece * kPieceBytes;
             unsigned int prev = b0 ? raw[b0 - 1] : 0u;
@@ -199,26 +220,42 @@ __global__ __launch_bounds__(kScanThreads) void k_jdec_count(DecArgs a)
                     const unsigned int p = b0 + 16 * q + k;
                     if (p < raw_n) {
                         const unsigned int b = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                        if (prev == 0xFFu) { if (b == 0u) ++cnt; else mk = min(mk, p - 1); }
+                        if (prev == 0xFFu) {
+                            if (b == 0u) ++cnt;
+                            else if (rst && (b & 0xF8u) == 0xD0u) { ++mc; cnt += p > b0 ? 2u : 1u; }    // its FF may be the last byte of the piece in front
+                            else mk = min(mk, p - 1);
+                        }
                         if (b == 0xFFu && p + 1 == raw_n) mk = min(mk, p);          // an FF at the very end: the host reads a marker there
                         prev = b;
                     }
                 }
             }
+            // ... and this piece's last byte the FF of a marker whose second byte is the first of the next piece
+            if (rst && prev == 0xFFu && b0 + kPieceBytes < raw_n && (raw[b0 + kPieceBytes] & 0xF8u) == 0xD0u) ++cnt;
         }
         unsigned int total;
         const unsigned int pre = block_exclusive(cnt, wsum, &total);
         if (piece < npieces) poff[piece] = carry + pre;
         carry += total;
+        if (rst) {                                            // the same for everyone of the workgroup
+            const unsigned int mpre = block_exclusive(mc, wsum, &total);
+            if (piece < npieces) moff[piece] = mcarry + mpre;
+            mcarry += total;
+        }
     }
     if (mk != 0xFFFFFFFFu) atomicMin(&s_marker, mk);
-    if (threadIdx.x == 0) poff[npieces] = carry;
+    if (threadIdx.x == 0) { poff[npieces] = carry; if (rst) moff[npieces] = mcarry; }
     __syncthreads();
-    // the stuffed zeros in front of the marker: those of the pieces before its piece, and those inside it up to the marker
+    // what left in front of the marker: the bytes of the pieces before its piece, and those inside it up to the marker; the restart
+    // markers in front of it likewise
     const unsigned int marker = s_marker, mp = marker / kPieceBytes;
     if (threadIdx.x < kPieceBytes) {
         const unsigned int p = mp * kPieceBytes + threadIdx.x;
-        if (p >= 1 && p < marker && raw[p] == 0u && raw[p - 1] == 0xFFu) atomicAdd(&s_removed, 1u);
+        if (p >= 1 && p < marker && raw[p - 1] == 0xFFu) {
+            if (raw[p] == 0u) atomicAdd(&s_removed, 1u);
+            else if (rst && (raw[p] & 0xF8u) == 0xD0u) { atomicAdd(&s_removed, 1u); atomicAdd(&s_markers, 1u); }
+        }
+        if (rst && p + 1 < marker && raw[p] == 0xFFu && (raw[p + 1] & 0xF8u) == 0xD0u) atomicAdd(&s_removed, 1u);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -226,10 +263,13 @@ __global__ __launch_bounds__(kScanThreads) void k_jdec_count(DecArgs a)
         s.marker = marker;
         s.nbytes = marker - (poff[mp] + s_removed);
         s.nsub = (unsigned int)(((unsigned long long)s.nbytes * 8 + kSubBits - 1) / kSubBits);
+        s.nrst = rst ? moff[mp] + s_markers : 0u;
+        if (s.nrst != (unsigned int)im.nrst) s.nsub = 0u;     // irregular at once: nobody decodes against a table with holes
         a.stat[i] = s;
     }
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kThreads) void k_jdec_unstuff(DecArgs a)
 {
     const int lane = threadIdx.x & 63;
@@ -241,22 +281,37 @@ __global__ __launch_bounds__(kThreads) void k_jdec_unstuff(DecArgs a)
         const uint8_t* raw = a.raw + im.raw0;
         const unsigned int* words = reinterpret_cast<const unsigned int*>(raw);
         const unsigned int* poff = a.poff + im.piece0;
+        const unsigned int* moff = a.moff + im.piece0;
+        unsigned int* bound = a.bound + im.bound0;
+        const bool rst = RST && im.nrst > 0;
         uint8_t* clean = a.clean + im.raw0;
         for (int piece = gw; piece < npieces; piece += nw) {
             const unsigned int byte0 = (unsigned int)piece * kPieceBytes + 4u * lane;
             const int nb = byte0 >= raw_n ? 0 : (int)min(4u, raw_n - byte0);
             const unsigned int x = nb ? words[byte0 >> 2] : 0u;
             unsigned int prev = (nb && byte0) ? raw[byte0 - 1] : 0u;
-            int cnt = 0;
-            unsigned int removed = 0;
+            const unsigned int next = (rst && nb == 4 && byte0 + 4u < raw_n) ? raw[byte0 + 4u] : 0u;
+            int cnt = 0;                                      // bytes that leave, and in the upper half the markers among them
+            unsigned int removed = 0, marks = 0;
             for (int j = 0; j < nb; ++j) {
                 const unsigned int b = (x >> (8 * j)) & 0xFFu;
                 if (prev == 0xFFu && b == 0u) { ++cnt; removed |= 1u << j; }
+                else if (rst) {                               // as k_jdec_count: the second byte of a restart marker, or the FF of one
+                    if (prev == 0xFFu && (b & 0xF8u) == 0xD0u) { cnt += 0x10001; removed |= 1u << j; marks |= 1u << j; }
+                    else if (b == 0xFFu) {
+                        const unsigned int b2 = j + 1 < nb ? (x >> (8 * (j + 1))) & 0xFFu : (j == 3 ? next : 0u);
+                        if ((b2 & 0xF8u) == 0xD0u) { ++cnt; removed |= 1u << j; }
+                    }
+                }
                 prev = b;
             }
-            unsigned int pos = byte0 - poff[piece] - (unsigned int)wave_exclusive(cnt, lane);
-            for (int j = 0; j < nb; ++j)
+            const unsigned int before = (unsigned int)wave_exclusive(cnt, lane);             // at most 256 and 128: no carry between the halves
+            unsigned int pos = byte0 - poff[piece] - (before & 0xFFFFu);
+            unsigned int m = rst ? moff[piece] + (before >> 16) : 0u;
+            for (int j = 0; j < nb; ++j) {
                 if (!((removed >> j) & 1u)) clean[pos++] = (uint8_t)(x >> (8 * j));
+                else if ((marks >> j) & 1u) { ++m; if (m <= (unsigned int)im.nrst) bound[m] = pos; }      // a marker past the table is dropped
+            }
         }
     }
 }
@@ -293,8 +348,16 @@ __device__ __forceinline__ int extend(int v, int s) { return v < (1 << (s - 1)) 
 // reaches is a function of the entry state alone).  WRITE: the coefficients (DC: the difference) of component 0's blocks to coef,
 // inside [0, nluma): block first + nb of the scan is a block of component 0 iff (first + nb) % mcu < hv, and then its number
 // (first + nb) / mcu * hv + (first + nb) % mcu; the symbols of the other components are decoded and dropped.
-struct DecMcu { unsigned int mcu, hv, pairs; };
-template <bool WRITE, bool COLOR>
+// Restart intervals (nrst > 0): bound[1 .. nrst] are the places of the restart markers in the clean string, in bytes.  Every one is a
+// true entry state -- byte aligned, DC next, place 0, all predictors 0 -- so a symbol that would end behind the next boundary is not
+// decoded (it is the 1-bit padding, which no Huffman code consists of): the decoder jumps to the boundary with the fresh state and
+// goes on; what it leaves the subsequence with no longer depends on what it entered with.  The last boundary is the end of the data,
+// which the loop compares against anyway: a stream without restarts takes the same turns as before.  WRITE: at every jump the state
+// has to be (DC next, place 0) and the running block index m * ribl, or err is set -- a block too many, decoded out of padding that
+// is not 1-bits, breaks the count and cannot give other samples.  RST = false (no image of the batch has restart markers): none of
+// this is compiled in, and nrst is 0.
+struct DecMcu { unsigned int mcu, hv, pairs, nrst, ribl; const unsigned int* bound; };
+template <bool WRITE, bool COLOR, bool RST>
 __device__ __forceinline__ unsigned int decode_sub(const DecLds<COLOR ? kMaxPairs : 1>& t, const unsigned int* words, unsigned int start, unsigned int total,
                                                    unsigned int entry, unsigned int& nb, int16_t* coef, unsigned int first, unsigned int nluma,
                                                    unsigned int& err, const DecMcu mc)
@@ -309,10 +372,25 @@ __device__ __forceinline__ unsigned int decode_sub(const DecLds<COLOR ? kMaxPair
     if constexpr (COLOR) {
         j = (entry >> 8) & 15u;
         tp = &t.pair[(mc.pairs >> (4u * j)) & 3u];
-        if (WRITE) { const unsigned int m = first / mc.mcu; q = first - m * mc.mcu; lb = m * mc.hv + min(q, mc.hv); }
+        if (WRITE) { const unsigned int u = first / mc.mcu; q = first - u * mc.mcu; lb = u * mc.hv + min(q, mc.hv); }
+    }
+    unsigned int m = 1u, lim = total;                         // the next boundary: restart marker m, or (m > nrst) the end of the data
+    if (RST && mc.nrst) {                                     // the first one at or behind the entry position
+        unsigned int lo = 1u, hi = mc.nrst + 1u;
+        while (lo < hi) { const unsigned int mid = (lo + hi) >> 1; if (mc.bound[mid] * 8u >= p) hi = mid; else lo = mid + 1u; }
+        m = lo;
+        if (m <= mc.nrst) lim = mc.bound[m] * 8u;
     }
     unsigned int wi = 0xFFFFFFFFu, w0 = 0, w1 = 0;
-    while (p < end && p < total) {                            // at least one bit per turn
+    while (p < end) {                                         // at least one bit per turn, or forward to a boundary
+        if (p >= lim) {
+            if (!RST || m > mc.nrst) break;                   // the end of the data
+            if (WRITE && (k != 0 || j != 0u || first + nb != m * mc.ribl)) err = 1u;
+            p = lim; k = 0;                                   // restart marker m: byte aligned, DC next, place 0
+            if constexpr (COLOR) { j = 0u; tp = &t.pair[0]; }
+            ++m; lim = m <= mc.nrst ? mc.bound[m] * 8u : total;
+            continue;
+        }
         if ((p >> 5) != wi) { wi = p >> 5; w0 = __builtin_bswap32(words[wi]); w1 = __builtin_bswap32(words[wi + 1]); }
         const unsigned int bits = (unsigned int)(((((unsigned long long)w0) << 32) | w1) >> (32 - (p & 31)));
         const int tc = k ? 1 : 0;
@@ -324,21 +402,21 @@ __device__ __forceinline__ unsigned int decode_sub(const DecLds<COLOR ? kMaxPair
                 if (tp->maxcode[tc][l] >= 0 && code <= tp->maxcode[tc][l] && code >= tp->mincode[tc][l]) { len = l; sym = tp->vals[tc][tp->valptr[tc][l] + code - tp->mincode[tc][l]]; break; }
             }
             if (!len) {
-                if (p + 16 > total) return kStop;             // the data ends inside what may be a code
+                if (p + 16 > lim) { if (!RST || m > mc.nrst) return kStop; p = lim; continue; }      // the data, or the interval, ends inside what may be a code
                 err = 1u; len = 16; sym = 0;
             }
         }
         bool complete = false;
         if (k == 0) {
             const int s = sym & 15;
-            if (p + len + s > total) return kStop;            // before the verdict: behind the last block the window holds leftovers
+            if (p + len + s > lim) { if (!RST || m > mc.nrst) return kStop; p = lim; continue; }     // before the verdict: behind the last block the window holds leftovers
             if (sym > 11) err = 1u;
             if constexpr (COLOR) { if (WRITE && s && q < mc.hv && lb < nluma) coef[(long long)lb * 64] = (int16_t)extend((int)((bits << len) >> (32 - s)), s); }
             else { if (WRITE && s && first + nb < nluma) coef[(long long)(first + nb) * 64] = (int16_t)extend((int)((bits << len) >> (32 - s)), s); }
             p += len + s; k = 1;
         } else {
             const int r = sym >> 4, s = sym & 15;
-            if (p + len + s > total) return kStop;
+            if (p + len + s > lim) { if (!RST || m > mc.nrst) return kStop; p = lim; continue; }
             if (s == 0) {
                 if (r == 15) { k += 16; complete = k >= 64; }
                 else complete = true;
@@ -362,10 +440,11 @@ __device__ __forceinline__ unsigned int decode_sub(const DecLds<COLOR ? kMaxPair
             }
         }
     }
+    if (RST && WRITE && m <= mc.nrst && end >= total) err = 1u;       // the last subsequence: a boundary nobody jumped (a marker at the very end)
     return p >= end ? (((p - end) << (COLOR ? 12 : 8)) | (COLOR ? j << 8 : 0u) | (unsigned int)k) : kStop;
 }
 
-template <bool COLOR>
+template <bool COLOR, bool RST>
 __global__ __launch_bounds__(kSyncThreads) void k_jdec_sync(DecArgs a, int round)
 {
     __shared__ DecLds<COLOR ? kMaxPairs : 1> t;
@@ -392,8 +471,8 @@ __global__ __launch_bounds__(kSyncThreads) void k_jdec_sync(DecArgs a, int round
     bool changed = false;
     if (need) {
         unsigned int nb, err = 0;
-        const unsigned int ex = decode_sub<false, COLOR>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, total, entry, nb, nullptr, 0, 0, err,
-                                                         DecMcu{(unsigned int)im.mcu, (unsigned int)(im.h0 * im.v0), im.pairs});
+        const unsigned int ex = decode_sub<false, COLOR, RST>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, total, entry, nb, nullptr, 0, 0, err,
+                                                         DecMcu{(unsigned int)im.mcu, (unsigned int)(im.h0 * im.v0), im.pairs, (unsigned int)im.nrst, (unsigned int)im.ribl, a.bound + im.bound0});
         a.entry[g] = entry; a.nblk[g] = nb; cur[g] = ex;
         changed = ex != old_exit;
     }
@@ -418,7 +497,7 @@ __global__ __launch_bounds__(kScanThreads) void k_jdec_blocks(DecArgs a)
     if (threadIdx.x == 0) a.stat[i].blocks = carry;
 }
 
-template <bool COLOR>
+template <bool COLOR, bool RST>
 __global__ __launch_bounds__(kSyncThreads) void k_jdec_write(DecArgs a)
 {
     __shared__ DecLds<COLOR ? kMaxPairs : 1> t;
@@ -434,16 +513,18 @@ __global__ __launch_bounds__(kSyncThreads) void k_jdec_write(DecArgs a)
     if (s < st.nsub) {
         const long long g = im.sub0 + (long long)s;
         unsigned int nb;
-        decode_sub<true, COLOR>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, st.nbytes * 8u, a.entry[g], nb,
+        decode_sub<true, COLOR, RST>(t, reinterpret_cast<const unsigned int*>(a.clean + im.raw0), s * kSubBits, st.nbytes * 8u, a.entry[g], nb,
                                 a.coef + (long long)im.blk0 * 64, a.bfirst[g], (unsigned int)im.nluma, err,
-                                DecMcu{(unsigned int)im.mcu, (unsigned int)(im.h0 * im.v0), im.pairs});
+                                DecMcu{(unsigned int)im.mcu, (unsigned int)(im.h0 * im.v0), im.pairs, (unsigned int)im.nrst, (unsigned int)im.ribl, a.bound + im.bound0});
     }
     if (__ballot(err != 0u) && (threadIdx.x & 63) == 0) atomicOr(&a.stat[i].err, 1u);
 }
 
+template <bool RST>
 __global__ __launch_bounds__(kScanThreads) void k_jdec_dc(DecArgs a)
 {
     __shared__ unsigned int wsum[kScanThreads / 64 + 1];
+    __shared__ unsigned int pfx[RST ? kScanThreads : 1];
     const int i = blockIdx.x;
     const DecImg im = a.imgs[i];
     if (a.stat[i].blocks != (unsigned int)im.nblk) return;
@@ -454,7 +535,28 @@ __global__ __launch_bounds__(kScanThreads) void k_jdec_dc(DecArgs a)
     for (int b = b0; b < b1; ++b) sum += coef[(long long)b * 64];
     unsigned int total;
     int pred = (int)block_exclusive((unsigned int)sum, wsum, &total);
-    for (int b = b0; b < b1; ++b) { pred += coef[(long long)b * 64]; coef[(long long)b * 64] = (int16_t)pred; }
+    // restart intervals: the sum starts again at every multiple of lumaseg blocks, so a thread's predictor is the plain prefix less the
+    // plain prefix of the segment start in front of it -- which is in the range of the thread s0 / per (integers: exact whatever the wrap)
+    const bool rst = RST && im.nrst > 0;                      // the same for everyone of the workgroup
+    const int seg = im.lumaseg;
+    if (rst) {
+        pfx[threadIdx.x] = (unsigned int)pred;
+        __syncthreads();
+        const int s0 = b0 - b0 % seg;
+        if (b0 < b1 && s0 > 0) {
+            const int owner = s0 / per;
+            unsigned int ps = pfx[owner];
+            for (int b = owner * per; b < s0; ++b) ps += (unsigned int)(int)coef[(long long)b * 64];
+            pred = (int)((unsigned int)pred - ps);
+        }
+        __syncthreads();                                      // everyone has read the differences it needs before anyone overwrites one
+    }
+    int r = rst ? b0 % seg : 1;
+    for (int b = b0; b < b1; ++b) {
+        if (r == 0) pred = 0;
+        pred += coef[(long long)b * 64]; coef[(long long)b * 64] = (int16_t)pred;
+        if (rst && ++r == seg) r = 0;
+    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_jdec_idct(DecArgs a)
@@ -529,6 +631,8 @@ struct lpslam_hip_jpeg_dec {
     uint8_t* h_up = nullptr;           // page-locked: everything one call uploads
     uint8_t* d_up = nullptr;
     uint8_t* d_clean = nullptr;
+    bool take_restart = false;         // lpslam_hip_jpeg_dec_take_restart: streams with a restart interval are decoded too
+    unsigned int *d_moff = nullptr, *d_bound = nullptr;
     unsigned int *d_poff = nullptr, *d_entry = nullptr, *d_exit = nullptr, *d_nblk = nullptr, *d_bfirst = nullptr, *d_changed = nullptr;
     int16_t* d_coef = nullptr;
     uint8_t* d_plane = nullptr;
@@ -546,7 +650,7 @@ void jdec_free(lpslam_hip_jpeg_dec* e)
 {
     if (!e) return;
     if (e->stream) { (void)hipStreamSynchronize(e->stream); (void)hipStreamDestroy(e->stream); }
-    for (void* p : {(void*)e->d_up, (void*)e->d_clean, (void*)e->d_poff, (void*)e->d_entry, (void*)e->d_exit, (void*)e->d_nblk, (void*)e->d_bfirst,
+    for (void* p : {(void*)e->d_up, (void*)e->d_clean, (void*)e->d_moff, (void*)e->d_bound, (void*)e->d_poff, (void*)e->d_entry, (void*)e->d_exit, (void*)e->d_nblk, (void*)e->d_bfirst,
                     (void*)e->d_changed, (void*)e->d_coef, (void*)e->d_plane})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)e->h_up, (void*)e->h_plane, (void*)e->h_stat, (void*)e->h_changed})
@@ -604,6 +708,8 @@ int lpslam_hip_jpeg_dec_create2(int32_t max_width, int32_t max_height, int32_t m
     if ((err = hipMalloc((void**)&e->d_up, (size_t)(e->head_bytes + e->raw_total))) != hipSuccess) return fail(err, "hipMalloc(jpeg streams)");
     if ((err = hipMalloc((void**)&e->d_clean, (size_t)e->raw_total)) != hipSuccess) return fail(err, "hipMalloc(jpeg clean data)");
     if ((err = hipMalloc((void**)&e->d_poff, (size_t)e->piece_total * 4)) != hipSuccess) return fail(err, "hipMalloc(jpeg pieces)");
+    if ((err = hipMalloc((void**)&e->d_moff, (size_t)e->piece_total * 4)) != hipSuccess) return fail(err, "hipMalloc(jpeg restart markers)");
+    if ((err = hipMalloc((void**)&e->d_bound, (size_t)((blocks + 1) * max_images) * 4)) != hipSuccess) return fail(err, "hipMalloc(jpeg boundaries)");
     if ((err = hipMalloc((void**)&e->d_entry, (size_t)e->sub_total * 4)) != hipSuccess) return fail(err, "hipMalloc(jpeg entry states)");
     if ((err = hipMalloc((void**)&e->d_exit, (size_t)e->sub_total * 8)) != hipSuccess) return fail(err, "hipMalloc(jpeg exit states)");
     if ((err = hipMalloc((void**)&e->d_nblk, (size_t)e->sub_total * 4)) != hipSuccess) return fail(err, "hipMalloc(jpeg block counts)");
@@ -643,8 +749,9 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
     DecStat* stats = reinterpret_cast<DecStat*>(e->h_up + sizeof(DecImg) * e->max_images);
     DecTab* tabs = reinterpret_cast<DecTab*>(e->h_up + (sizeof(DecImg) + sizeof(DecStat)) * e->max_images);
     uint8_t* h_raw = e->h_up + e->head_bytes;
-    int nd = 0, blk = 0, piece = 0, sub = 0, wg = 0, chunks = 0;
+    int nd = 0, blk = 0, piece = 0, sub = 0, wg = 0, chunks = 0, bnd = 0;
     bool any_color = false;                                   // the batch holds a three-component image: the kernels that know the MCU
+    bool any_rst = false;                                     // ... an image with restart markers: the kernels that know the boundaries
     long long raw = 0, plane = 0;
     unsigned int max_sub = 0;
     bool fits = true;
@@ -660,8 +767,8 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
         const jpeg::Header& hd = p.hd;
         const long long raw_n = (long long)(size - p.scan.data);
         if (raw_n < 1) continue;
-        const bool grey = hd.ncomp == 1 && hd.restart_interval == 0 && !hd.q16[hd.comp[0].tq];
-        const bool ycc = e->color && jpeg::interleaved_ycc_scan(hd, p.scan);
+        const bool grey = jpeg::grey_scan(hd, e->take_restart);
+        const bool ycc = e->color && jpeg::interleaved_ycc_scan(hd, p.scan, e->take_restart);
         if (!(grey || ycc) || hd.X > e->max_w || hd.Y > e->max_h || raw_n > e->raw_cap) {
             p.status = status[i] = LPSLAM_HIP_JPEG_NOT_TAKEN;
             continue;
@@ -676,6 +783,11 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
         im.mcu = im.h0 * im.v0 + (ycc ? 2 : 0); im.nblk = im.nluma / (im.h0 * im.v0) * im.mcu;
         im.pairs = 0u;
         any_color = any_color || ycc;
+        // restart intervals: a table entry per marker the data must hold (fewer than its MCUs, so than the blocks the table is sized by)
+        im.nrst = jpeg::restart_markers(hd, im.nluma / (im.h0 * im.v0));
+        im.ribl = im.nrst ? hd.restart_interval * im.mcu : 0; im.lumaseg = im.nrst ? hd.restart_interval * im.h0 * im.v0 : im.nluma;
+        im.bound0 = bnd; bnd += im.nrst + 1;
+        any_rst = any_rst || im.nrst > 0;
         im.blk0 = blk; im.piece0 = piece; im.sub0 = sub;
         const unsigned int nsub_cap = (unsigned int)((raw_n * 8 + kSubBits - 1) / kSubBits);
         im.wg0 = wg; im.nwg = (int)((nsub_cap + kSyncThreads - 1) / kSyncThreads);
@@ -718,22 +830,23 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
     a.imgs = reinterpret_cast<const DecImg*>(e->d_up);
     a.stat = reinterpret_cast<DecStat*>(e->d_up + sizeof(DecImg) * e->max_images);
     a.tabs = reinterpret_cast<const DecTab*>(e->d_up + (sizeof(DecImg) + sizeof(DecStat)) * e->max_images);
-    a.n = nd; a.poff = e->d_poff; a.entry = e->d_entry; a.exit = e->d_exit; a.sub_total = e->sub_total; a.nblk = e->d_nblk; a.bfirst = e->d_bfirst;
+    a.n = nd; a.poff = e->d_poff; a.moff = e->d_moff; a.bound = e->d_bound; a.entry = e->d_entry; a.exit = e->d_exit; a.sub_total = e->sub_total; a.nblk = e->d_nblk; a.bfirst = e->d_bfirst;
     a.changed = e->d_changed; a.coef = e->d_coef; a.plane = e->d_plane; a.host_plane = e->dh_plane; a.host_stat = e->dh_stat;
     for (int k = 0; k < 64; ++k) a.nat[k] = (unsigned char)jpeg::kZigzag[k];
     hipStream_t s = e->stream;
     LP_HIP(hipMemcpyAsync(e->d_up, e->h_up, (size_t)(e->head_bytes + raw), hipMemcpyHostToDevice, s));
     LP_HIP(hipMemsetAsync(e->d_changed, 0, kRing * 4, s));
     LP_HIP(hipMemsetAsync(e->d_coef, 0, (size_t)blk * 64 * sizeof(int16_t), s));
-    hipLaunchKernelGGL(k_jdec_count, dim3(nd), dim3(kScanThreads), 0, s, a);
-    hipLaunchKernelGGL(k_jdec_unstuff, dim3(kStuffGrid), dim3(kThreads), 0, s, a);
+    if (any_rst) { hipLaunchKernelGGL(k_jdec_count<true>, dim3(nd), dim3(kScanThreads), 0, s, a); hipLaunchKernelGGL(k_jdec_unstuff<true>, dim3(kStuffGrid), dim3(kThreads), 0, s, a); }
+    else { hipLaunchKernelGGL(k_jdec_count<false>, dim3(nd), dim3(kScanThreads), 0, s, a); hipLaunchKernelGGL(k_jdec_unstuff<false>, dim3(kStuffGrid), dim3(kThreads), 0, s, a); }
+    void (*const sync_kernel)(DecArgs, int) = any_color ? (any_rst ? k_jdec_sync<true, true> : k_jdec_sync<true, false>) : (any_rst ? k_jdec_sync<false, true> : k_jdec_sync<false, false>);
+    void (*const write_kernel)(DecArgs) = any_color ? (any_rst ? k_jdec_write<true, true> : k_jdec_write<true, false>) : (any_rst ? k_jdec_write<false, true> : k_jdec_write<false, false>);
     // rounds until one changes nothing: subsequence s is final after round s, so max_sub + 1 rounds always do
     int round = 0;
     bool converged = false;
     for (int batch = kRoundsPerCheck; !converged && round <= (int)max_sub + 1; batch = std::min(2 * batch, kRing / 2)) {
         for (int b = 0; b < batch; ++b, ++round) {
-            if (any_color) hipLaunchKernelGGL(k_jdec_sync<true>, dim3(wg), dim3(kSyncThreads), 0, s, a, round);
-            else hipLaunchKernelGGL(k_jdec_sync<false>, dim3(wg), dim3(kSyncThreads), 0, s, a, round);
+            hipLaunchKernelGGL(sync_kernel, dim3(wg), dim3(kSyncThreads), 0, s, a, round);
         }
         LP_HIP(hipGetLastError());
         LP_HIP(hipMemcpyAsync(e->h_changed, e->d_changed + (round - 1) % kRing, 4, hipMemcpyDeviceToHost, s));
@@ -741,9 +854,9 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
         converged = *e->h_changed == 0u;
     }
     hipLaunchKernelGGL(k_jdec_blocks, dim3(nd), dim3(kScanThreads), 0, s, a);
-    if (any_color) hipLaunchKernelGGL(k_jdec_write<true>, dim3(wg), dim3(kSyncThreads), 0, s, a);
-    else hipLaunchKernelGGL(k_jdec_write<false>, dim3(wg), dim3(kSyncThreads), 0, s, a);
-    hipLaunchKernelGGL(k_jdec_dc, dim3(nd), dim3(kScanThreads), 0, s, a);
+    hipLaunchKernelGGL(write_kernel, dim3(wg), dim3(kSyncThreads), 0, s, a);
+    if (any_rst) hipLaunchKernelGGL(k_jdec_dc<true>, dim3(nd), dim3(kScanThreads), 0, s, a);
+    else hipLaunchKernelGGL(k_jdec_dc<false>, dim3(nd), dim3(kScanThreads), 0, s, a);
     hipLaunchKernelGGL(k_jdec_idct, dim3(chunks), dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(k_jdec_out, dim3(kCopyGrid), dim3(kThreads), 0, s, a);
     LP_HIP(hipGetLastError());
@@ -765,6 +878,14 @@ int lpslam_hip_jpeg_decode(lpslam_hip_jpeg_dec* e, int32_t n, const uint8_t* con
         for (int y = 0; y < im.h; ++y) std::memcpy(outs[i] + (long long)y * out_strides[i], src + (long long)y * 8 * im.bw, (size_t)im.w);
         status[i] = LPSLAM_HIP_JPEG_DECODED;
     }
+    return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_jpeg_dec_take_restart(lpslam_hip_jpeg_dec* e, int32_t on)
+{
+    if (!e) { set_error("jpeg_dec_take_restart: null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    std::lock_guard<std::mutex> lock(e->mutex);
+    e->take_restart = on != 0;
     return LPSLAM_HIP_OK;
 }
 

@@ -45,6 +45,7 @@ SYMBOLS = [
     "lpslam_hip_scan_geometry_put", "lpslam_hip_scan_store_put", "lpslam_hip_scan_store_drop", "lpslam_hip_occupancy_build",
     "lpslam_hip_jpeg_create", "lpslam_hip_jpeg_destroy", "lpslam_hip_jpeg_encode",
     "lpslam_hip_jpeg_dec_create", "lpslam_hip_jpeg_dec_create2", "lpslam_hip_jpeg_dec_destroy", "lpslam_hip_jpeg_decode", "lpslam_hip_jpeg_dec_last",
+    "lpslam_hip_jpeg_dec_take_restart",
     "lpslam_hip_adjust_intensity", "lpslam_hip_upload_raw_image_adjusted", "lpslam_hip_front_end_images_adjusted", "lpslam_hip_adjust_intensity_last",
 ]
 
@@ -1037,9 +1038,10 @@ class JpegDecoder:
     """Baseline JPEG decoder on the device (lpslam_hip_jpeg_dec_*): streams in, the host decoder's samples out, bit for bit.  Every
     image gets a status: JPEG_DECODED, JPEG_NOT_TAKEN (a class left to the host decoder) or JPEG_IRREGULAR (the host decoder gives the
     verdict).  color=True (LPSLAM_HIP_JPEG_DEC_COLOR): three-component 4:4:4 / 4:2:2 / 4:2:0 streams are taken too and give their first
-    component, as the host decoder does; without it they are JPEG_NOT_TAKEN."""
+    component, as the host decoder does; without it they are JPEG_NOT_TAKEN.  restart=True (lpslam_hip_jpeg_dec_take_restart): streams
+    of either class with a restart interval are taken too; without it they are JPEG_NOT_TAKEN."""
 
-    def __init__(self, max_width, max_height, max_images=2, color=False):
+    def __init__(self, max_width, max_height, max_images=2, color=False, restart=False):
         self.lib = load()
         self.lib.lpslam_hip_jpeg_dec_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         self.lib.lpslam_hip_jpeg_dec_create2.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p]
@@ -1053,6 +1055,12 @@ class JpegDecoder:
             _check(self.lib.lpslam_hip_jpeg_dec_create(int(max_width), int(max_height), int(max_images), C.byref(h)))
         self.h = h
         self.max_width, self.max_height, self.max_images = int(max_width), int(max_height), int(max_images)
+        if restart:
+            self.take_restart(True)
+
+    def take_restart(self, on):
+        self.lib.lpslam_hip_jpeg_dec_take_restart.argtypes = [C.c_void_p, C.c_int32]
+        _check(self.lib.lpslam_hip_jpeg_dec_take_restart(self.h, 1 if on else 0))
 
     def close(self):
         if getattr(self, "h", None):

@@ -266,12 +266,16 @@ struct BitWriter {
         while (n >= 8) { const uint8_t b = (uint8_t)(acc >> (n - 8)); out.push_back(b); if (b == 0xFF) out.push_back(0); n -= 8; }
     }
     void flush() { if (n) put(0x7F, 8 - n); }             // pad with ones
+    void restart(int number) { flush(); out.push_back(0xFF); out.push_back((uint8_t)(0xD0 + (number & 7))); }
 };
 
 }  // namespace
 
-bool encode_jpeg_gray(const GrayImage& img, int quality, std::vector<uint8_t>& out)
+bool encode_jpeg_gray(const GrayImage& img, int quality, std::vector<uint8_t>& out) { return encode_jpeg_gray_restart(img, quality, 0, out); }
+
+bool encode_jpeg_gray_restart(const GrayImage& img, int quality, int restart_interval, std::vector<uint8_t>& out)
 {
+    if (restart_interval < 0 || restart_interval > 65535) return false;
     if (img.width <= 0 || img.height <= 0 || img.width > 65535 || img.height > 65535 || img.pixels.size() < (size_t)img.width * img.height) return false;
     quality = std::min(100, std::max(1, quality));
     uint8_t q[64];
@@ -279,12 +283,13 @@ bool encode_jpeg_gray(const GrayImage& img, int quality, std::vector<uint8_t>& o
     EncTable dct, act;
     jpeg::make_enc_table(jpeg::kDcLumBits, jpeg::kDcLumVals, dct); jpeg::make_enc_table(jpeg::kAcLumBits, jpeg::kAcLumVals, act);
     out.clear();
-    jpeg::write_headers(out, img.width, img.height, q);
+    jpeg::write_headers(out, img.width, img.height, q, restart_interval);
     BitWriter bw{out};
     const int bw_n = (img.width + 7) / 8, bh_n = (img.height + 7) / 8;
-    int pred = 0;
+    int pred = 0, count = 0;
     for (int by = 0; by < bh_n; ++by)
-        for (int bx = 0; bx < bw_n; ++bx) {
+        for (int bx = 0; bx < bw_n; ++bx, ++count) {
+            if (restart_interval && count && count % restart_interval == 0) { bw.restart(count / restart_interval - 1); pred = 0; }
             int32_t blk[64];
             for (int r = 0; r < 8; ++r) {
                 const int y = std::min(8 * by + r, img.height - 1);                // edge blocks: the last row / column repeated (libjpeg's edge expansion)
@@ -332,6 +337,28 @@ extern "C" __attribute__((visibility("default"))) size_t lpslam_jpeg_encode_gray
     if (!LpSlam::encode_jpeg_gray(img, quality, buf) || buf.size() > cap) return 0;
     std::memcpy(out, buf.data(), buf.size());
     return buf.size();
+}
+
+// the same with a restart interval in blocks (0: the bytes of lpslam_jpeg_encode_gray)
+extern "C" __attribute__((visibility("default"))) size_t lpslam_jpeg_encode_gray_restart(const uint8_t* pixels, int w, int h, int quality, int restart_interval,
+                                                                                         uint8_t* out, size_t cap)
+{
+    LpSlam::GrayImage img; img.width = w; img.height = h; img.pixels.assign(pixels, pixels + (size_t)w * h);
+    std::vector<uint8_t> buf;
+    if (!LpSlam::encode_jpeg_gray_restart(img, quality, restart_interval, buf) || buf.size() > cap) return 0;
+    std::memcpy(out, buf.data(), buf.size());
+    return buf.size();
+}
+
+// tests: is the first scan of the stream of the class the device decoder takes (csrc/jpeg_dec.hip asks the same functions)?  color: a
+// decoder made for three-component streams; restart: one switched to take restart intervals.  1 yes, 0 no, -1 no scan header found.
+extern "C" __attribute__((visibility("default"))) int lpslam_jpeg_device_class(const uint8_t* data, size_t size, int color, int restart)
+{
+    using namespace LpSlam;
+    if (!jpeg::has_soi(data, size)) return -1;
+    jpeg::Header hd; jpeg::Scan sc; size_t pos = 2;
+    if (jpeg::walk_to_scan(data, size, pos, hd, sc, nullptr) != jpeg::Walk::scan) return -1;
+    return (jpeg::grey_scan(hd, restart != 0) || (color && jpeg::interleaved_ycc_scan(hd, sc, restart != 0))) ? 1 : 0;
 }
 
 // tests: decode into a caller buffer; returns 0 on success, 1 when the buffer is too small (w / h are set), 2 on a decoding error

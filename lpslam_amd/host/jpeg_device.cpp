@@ -25,6 +25,13 @@ void JpegDecoder::setUseDeviceForColor(bool on)
     if (!on) m_decColor = false;
 }
 
+void JpegDecoder::setUseDeviceForRestart(bool on)
+{
+    std::lock_guard<std::mutex> l(m_mutex);
+    m_useDeviceForRestart = on;
+    if (m_dec) lpslam_hip_jpeg_dec_take_restart(m_dec, on ? 1 : 0);
+}
+
 JpegDecodeCounters JpegDecoder::counters() const
 {
     JpegDecodeCounters c;
@@ -45,8 +52,8 @@ bool JpegDecoder::decode(int n, const uint8_t* const* data, const size_t* sizes,
             if (!looks_like_jpeg(data[i], sizes[i])) continue;
             jpeg::Header hd; jpeg::Scan sc; size_t pos = 2;
             if (jpeg::walk_to_scan(data[i], sizes[i], pos, hd, sc, nullptr) != jpeg::Walk::scan) continue;
-            const bool ycc = m_useDeviceForColor && jpeg::interleaved_ycc_scan(hd, sc);
-            if (hd.ncomp != 1 && !ycc) continue;
+            const bool ycc = m_useDeviceForColor && jpeg::interleaved_ycc_scan(hd, sc, m_useDeviceForRestart);
+            if (!jpeg::grey_scan(hd, m_useDeviceForRestart) && !ycc) continue;    // the device would answer "not taken"
             color = color || ycc;
             X[i] = hd.X; Y[i] = hd.Y;
             w = std::max(w, hd.X); h = std::max(h, hd.Y);
@@ -58,6 +65,8 @@ bool JpegDecoder::decode(int n, const uint8_t* const* data, const size_t* sizes,
             if (lpslam_hip_jpeg_dec_create2(m_decW, m_decH, 2, m_decColor ? LPSLAM_HIP_JPEG_DEC_COLOR : 0u, &m_dec) != LPSLAM_HIP_OK) {
                 logMessage(LpSlamLogLevel_Info, std::string("The device JPEG decoder cannot be created, decoding on the host: ") + lpslam_hip_last_error());
                 m_dec = nullptr; m_useDevice = false;
+            } else if (m_useDeviceForRestart) {
+                lpslam_hip_jpeg_dec_take_restart(m_dec, 1);
             }
         }
         if (m_dec && w > 0) {

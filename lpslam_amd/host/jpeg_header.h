@@ -166,15 +166,30 @@ inline Walk walk_to_scan(const uint8_t* d, size_t size, size_t& pos, Header& hd,
 
 // The three-component class the device decoder takes when it was made for colour (csrc/jpeg_dec.hip; DESIGN.md, the section on colour
 // streams): one interleaved scan of all three components in frame order, component 0 sampled 1 x 1, 2 x 1 or 2 x 2 (h x v), the other
-// two 1 x 1, no restart interval, an 8-bit quantisation table for component 0 (the chroma tables are never used).  Asked by the device
-// decoder and by the host layer that offers streams to it, so the two cannot disagree.
-inline bool interleaved_ycc_scan(const Header& hd, const Scan& scan)
+// two 1 x 1, an 8-bit quantisation table for component 0 (the chroma tables are never used), and no restart interval unless the caller
+// allows one (a decoder switched to take them: lpslam_hip_jpeg_dec_take_restart).  Asked by the device decoder and by the host layer
+// that offers streams to it, so the two cannot disagree.
+inline bool interleaved_ycc_scan(const Header& hd, const Scan& scan, bool restart_allowed = false)
 {
     if (hd.ncomp != 3 || scan.ns != 3 || scan.idx[0] != 0 || scan.idx[1] != 1 || scan.idx[2] != 2) return false;
     const Component& y = hd.comp[0];
     if (!((y.h == 1 && y.v == 1) || (y.h == 2 && y.v == 1) || (y.h == 2 && y.v == 2))) return false;
     if (hd.comp[1].h != 1 || hd.comp[1].v != 1 || hd.comp[2].h != 1 || hd.comp[2].v != 1) return false;
-    return hd.restart_interval == 0 && !hd.q16[y.tq];
+    return (restart_allowed || hd.restart_interval == 0) && !hd.q16[y.tq];
+}
+
+// The one-component class of the device decoder: an 8-bit quantisation table, and the same rule for a restart interval.
+inline bool grey_scan(const Header& hd, bool restart_allowed = false)
+{
+    return hd.ncomp == 1 && (restart_allowed || hd.restart_interval == 0) && !hd.q16[hd.comp[0].tq];
+}
+
+// Restart markers the entropy-coded data of a scan over `mcus` MCUs must hold: one behind every full interval but the last.  A DRI of
+// 0, or of the MCU count or more, means none.
+inline int restart_markers(const Header& hd, long long mcus)
+{
+    const long long ri = hd.restart_interval;
+    return ri > 0 && ri < mcus ? (int)((mcus + ri - 1) / ri - 1) : 0;
 }
 
 }  // namespace jpeg

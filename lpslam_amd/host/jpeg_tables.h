@@ -46,7 +46,7 @@ inline void quant_table(int quality, uint8_t q[64])
 }
 
 // SOI .. SOS of a one-component baseline stream of w x h samples (the entropy-coded segment and EOI follow)
-inline void write_headers(std::vector<uint8_t>& out, int w, int h, const uint8_t q[64])
+inline void write_headers(std::vector<uint8_t>& out, int w, int h, const uint8_t q[64], int restart_interval = 0)
 {
     auto put16 = [&](int v) { out.push_back((uint8_t)(v >> 8)); out.push_back((uint8_t)v); };
     auto marker = [&](int m) { out.push_back(0xFF); out.push_back((uint8_t)m); };
@@ -57,6 +57,7 @@ inline void write_headers(std::vector<uint8_t>& out, int w, int h, const uint8_t
     marker(0xC0); put16(11); out.push_back(8); put16(h); put16(w); out.push_back(1); out.push_back(1); out.push_back(0x11); out.push_back(0);
     marker(0xC4); put16(2 + 1 + 16 + 12); out.push_back(0x00); for (int l = 1; l <= 16; ++l) out.push_back(kDcLumBits[l]); for (uint8_t v : kDcLumVals) out.push_back(v);
     marker(0xC4); put16(2 + 1 + 16 + 162); out.push_back(0x10); for (int l = 1; l <= 16; ++l) out.push_back(kAcLumBits[l]); for (uint8_t v : kAcLumVals) out.push_back(v);
+    if (restart_interval > 0) { marker(0xDD); put16(4); put16(restart_interval); }                                     // DRI: where libjpeg writes it
     marker(0xDA); put16(8); out.push_back(1); out.push_back(1); out.push_back(0x00); out.push_back(0); out.push_back(63); out.push_back(0);
 }
 

@@ -136,6 +136,7 @@ bool SlamManager::readConfigurationFile(std::string const& filename)
             if (const Json* r = m->find("record_raw")) m_recorder.setWriteRawFile(r->asBool());
             if (const Json* r = m->find("jpeg_decode_device")) m_jpegDecoder->setUseDevice(r->asBool());
             if (const Json* r = m->find("jpeg_decode_color_device")) m_jpegDecoder->setUseDeviceForColor(r->asBool());
+            if (const Json* r = m->find("jpeg_decode_restart_device")) m_jpegDecoder->setUseDeviceForRestart(r->asBool());
             if (const Json* c = m->find("replay_chunks")) m_replayChunk = (size_t)std::max(1.0, c->asNumber());   // SlamManager.cpp:668-671
             // show_live belongs to a subsystem outside the accelerated path: accepted, ignored
         }

@@ -98,7 +98,8 @@ private:
     int64_t m_framesTaken = 0;           // worker thread only: frames taken since start() (the reference's numberPic)
     ReplayReader m_replay;
     // compressed frames (replay records and 8UC1_JPEPG frames handed in): on the device unless "manager": {"jpeg_decode_device": false}
-    // (three-component ones: unless "jpeg_decode_color_device": false)
+    // (three-component ones: unless "jpeg_decode_color_device": false; ones with a restart interval: only with
+    // "jpeg_decode_restart_device": true)
     std::shared_ptr<JpegDecoder> m_jpegDecoder = std::make_shared<JpegDecoder>();
     std::mutex m_replayMutex;
     size_t m_replayChunk = 500;          // ReplayEngine.h:53

@@ -65,6 +65,7 @@ PINHOLE, FISHEYE, OMNI = 0, 1, 2          # LpSlamCameraDistortionFunction
 ONE_IMAGE_COMPRESSED, STEREO_COMPRESSED = 4, 5          # LpSlamImageStructure
 JPEG_DECODE_DEVICE_KEY = "jpeg_decode_device"          # manager section of the configuration file: false = decode compressed frames on the host
 JPEG_DECODE_COLOR_DEVICE_KEY = "jpeg_decode_color_device"    # the same for three-component (YCbCr) streams alone; default true
+JPEG_DECODE_RESTART_DEVICE_KEY = "jpeg_decode_restart_device"    # true = streams with a restart interval go to the device too; default false
 _lib = None
 
 
