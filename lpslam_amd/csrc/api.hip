@@ -1166,6 +1166,21 @@ unsigned* lp_done_counter(lpslam_hip_ctx* c, int which)
     return c->d_done + 32 * (which & 7);
 }
 
+uint8_t* lp_match_staging(lpslam_hip_ctx* c, size_t need, size_t grow_to, hipStream_t s)
+{
+    if (c->h_match && c->h_match_bytes >= need) return c->h_match;
+    if (c->h_match) {
+        const hipError_t e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hip_fail(e, "hipStreamSynchronize(s) in front of the staging block's growth"); return nullptr; }
+        (void)hipHostFree(c->h_match);
+    }
+    c->h_match = nullptr; c->h_match_bytes = 0;
+    const hipError_t e = hipHostMalloc((void**)&c->h_match, grow_to, hipHostMallocDefault);
+    if (e != hipSuccess) { c->h_match = nullptr; (void)hip_fail(e, "hipHostMalloc of the staging block"); return nullptr; }
+    c->h_match_bytes = grow_to;
+    return c->h_match;
+}
+
 // After lp_wait_done reported failure on stream `s` (the flag did not arrive within 20 ms and was not there after the synchronisation
 // either).  Two cases.  The stream synchronises: its kernels are complete, so the device block they wrote may be handed back -- but
 // arrival counter `which` was left between 0 and total - 1 by whatever went wrong, and every later delivery through it would count
@@ -1174,9 +1189,24 @@ unsigned* lp_done_counter(lpslam_hip_ctx* c, int which)
 bool lp_wait_recover(lpslam_hip_ctx* c, int which, hipStream_t s)
 {
     if (hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); return false; }
-    unsigned* counter = lp_done_counter(c, which);
+    unsigned* counter = which < 0 ? nullptr : lp_done_counter(c, which);
     if (counter && (hipMemsetAsync(counter, 0, sizeof(unsigned), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) { (void)hipGetLastError(); return false; }
     return true;
+}
+
+int lp_done_arm(lpslam_hip_ctx* c, int which, int* flag, int& seq_counter, LpDone* d)
+{
+    unsigned* counter = which < 0 ? nullptr : lp_done_counter(c, which);
+    if (which >= 0 && !counter) { set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
+    *d = LpDone{counter, flag, lp_next_seq(seq_counter), which};
+    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
+    return LPSLAM_HIP_OK;
+}
+
+int lp_done_wait(lpslam_hip_ctx* c, const LpDone& d, hipStream_t s)
+{
+    if (lp_wait_done(d.flag, d.seq, s)) return LP_DONE_ARRIVED;
+    return lp_wait_recover(c, d.which, s) ? LP_DONE_LATE : LP_DONE_DEAD;
 }
 
 namespace {
@@ -1238,17 +1268,13 @@ static FrameStage frame_stage(const lpslam_hip_ctx* c)
 }
 enum { FRAME_KPTS = 1, FRAME_DESC = 2, FRAME_XR = 4, FRAME_DEPTH = 8 };
 
-// launches the delivery of image slot `image` into the block `st` on stream `s`; returns the sequence number the kernel will release
-static int frame_deliver(lpslam_hip_ctx* c, int image, int fields, uint8_t* st, int counter_id, hipStream_t s, int& seq_counter, int* seq_out)
+// launches the delivery of image slot `image` into the block `st` on stream `s`; *done is what to wait for
+static int frame_deliver(lpslam_hip_ctx* c, int image, int fields, uint8_t* st, int counter_id, hipStream_t s, int& seq_counter, LpDone* done)
 {
     static_assert(sizeof(lpslam_hip_keypoint) == 28, "k_frame_to_host moves keypoints as seven words");
     const FrameStage f = frame_stage(c);
     const size_t S = (size_t)c->slots_per_image;
-    unsigned* counter = lp_done_counter(c, counter_id);
-    if (!counter) { set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
-    int* flag = (int*)(st + 32);
-    const int seq = lp_next_seq(seq_counter);      // (the prefetch thread's deliveries count on their own: two threads never share a counter)
-    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
+    { const int rc = lp_done_arm(c, counter_id, (int*)(st + 32), seq_counter, done); if (rc) return rc; }
     const size_t o = (size_t)image * S;
     const float* fs = c->d_stereo + o * 2;
     const int want_words = (int)S * (((fields & FRAME_KPTS) ? 7 : 0) + ((fields & FRAME_DESC) ? 8 : 0) + ((fields & FRAME_XR) ? 1 : 0) + ((fields & FRAME_DEPTH) ? 1 : 0));
@@ -1256,9 +1282,27 @@ static int frame_deliver(lpslam_hip_ctx* c, int image, int fields, uint8_t* st, 
     hipLaunchKernelGGL(k_frame_to_host, dim3(blocks), dim3(256), 0, s, (const int*)(c->d_kp_count + image),
                        (fields & FRAME_KPTS) ? (const uint32_t*)(c->d_kpts + o) : nullptr, (fields & FRAME_DESC) ? (const uint32_t*)(c->d_desc + o * 32) : nullptr,
                        (fields & FRAME_XR) ? (const uint32_t*)fs : nullptr, (fields & FRAME_DEPTH) ? (const uint32_t*)(fs + S) : nullptr, (uint32_t*)st,
-                       (int)(f.o_kp / 4), (int)(f.o_desc / 4), (int)(f.o_xr / 4), (int)(f.o_dep / 4), (int)S, counter, flag, seq);
+                       (int)(f.o_kp / 4), (int)(f.o_desc / 4), (int)(f.o_xr / 4), (int)(f.o_dep / 4), (int)S, done->counter, done->flag, done->seq);
     LP_HIP(hipGetLastError());
-    *seq_out = seq;
+    return LPSLAM_HIP_OK;
+}
+
+// The block of the deliveries made ahead of time, ready for the next one: large enough, its frame voided, and the previous delivery
+// arrived -- one at a time: a copy that was voided instead of collected may still be on its way (another stream).
+static int pf_block_ready(lpslam_hip_ctx* c, const FrameStage& f, const char* who)
+{
+    if (c->h_stage_pf_bytes < f.need) {
+        if (c->h_stage_pf) { if (c->pf_stream) LP_HIP(hipStreamSynchronize(c->pf_stream)); (void)hipHostFree(c->h_stage_pf); }
+        c->h_stage_pf = nullptr; c->h_stage_pf_bytes = 0; c->pf_image = -1; c->pf_in_flight = false;
+        LP_HIP(hipHostMalloc((void**)&c->h_stage_pf, f.need, hipHostMallocDefault));
+        c->h_stage_pf_bytes = f.need;
+    }
+    c->pf_image = -1;
+    if (c->pf_in_flight) {
+        const int w = lp_done_wait(c, c->pf_done, c->pf_stream);
+        c->pf_in_flight = w == LP_DONE_DEAD;
+        if (w) { set_error("%s: the previous read-back did not complete", who); return LPSLAM_HIP_ERR_DEVICE; }
+    }
     return LPSLAM_HIP_OK;
 }
 
@@ -1270,20 +1314,10 @@ int lpslam_hip_prefetch_frame(lpslam_hip_ctx* c, int image, int32_t with_stereo)
     int rc = check_image(c, image); if (rc) return rc;
     const FrameStage f = frame_stage(c);
     hipStream_t s = lp_fe_stream(c);
-    if (c->h_stage_pf_bytes < f.need) {
-        if (c->h_stage_pf) { if (c->pf_stream) LP_HIP(hipStreamSynchronize(c->pf_stream)); (void)hipHostFree(c->h_stage_pf); }
-        c->h_stage_pf = nullptr; c->h_stage_pf_bytes = 0; c->pf_image = -1; c->pf_in_flight = false;
-        LP_HIP(hipHostMalloc((void**)&c->h_stage_pf, f.need, hipHostMallocDefault));
-        c->h_stage_pf_bytes = f.need;
-    }
+    if ((rc = pf_block_ready(c, f, "lpslam_hip_prefetch_frame"))) return rc;
     const int fields = FRAME_KPTS | FRAME_DESC | (with_stereo ? (FRAME_XR | FRAME_DEPTH) : 0);
-    int seq = 0;
-    c->pf_image = -1;
-    // one delivery into the block at a time: a copy that was voided instead of collected may still be on its way (another stream)
-    if (c->pf_in_flight && !lp_wait_done((int*)(c->h_stage_pf + 32), c->pf_seq, c->pf_stream)) { c->pf_in_flight = !lp_wait_recover(c, 3, c->pf_stream); set_error("lpslam_hip_prefetch_frame: the previous read-back did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
-    c->pf_in_flight = false;
-    if ((rc = frame_deliver(c, image, fields, c->h_stage_pf, 3, s, c->pf_seq_next, &seq))) return rc;
-    c->pf_seq = seq; c->pf_fields = fields; c->pf_stream = s; c->pf_in_flight = true;
+    if ((rc = frame_deliver(c, image, fields, c->h_stage_pf, 3, s, c->pf_seq_next, &c->pf_done))) return rc;
+    c->pf_fields = fields; c->pf_stream = s; c->pf_in_flight = true;
     c->pf_image = image;
     return LPSLAM_HIP_OK;
 }
@@ -1294,30 +1328,20 @@ int lpslam_hip_prefetch_frame(lpslam_hip_ctx* c, int image, int32_t with_stereo)
 int lp_prepare_delivery(lpslam_hip_ctx* c, int image, int with_stereo, LpDeliverReq* out)
 {
     const FrameStage f = frame_stage(c);
-    if (c->h_stage_pf_bytes < f.need) {
-        if (c->h_stage_pf) { if (c->pf_stream) LP_HIP(hipStreamSynchronize(c->pf_stream)); (void)hipHostFree(c->h_stage_pf); }
-        c->h_stage_pf = nullptr; c->h_stage_pf_bytes = 0; c->pf_image = -1; c->pf_in_flight = false;
-        LP_HIP(hipHostMalloc((void**)&c->h_stage_pf, f.need, hipHostMallocDefault));
-        c->h_stage_pf_bytes = f.need;
-    }
-    c->pf_image = -1;
-    if (c->pf_in_flight && !lp_wait_done((int*)(c->h_stage_pf + 32), c->pf_seq, c->pf_stream)) { c->pf_in_flight = !lp_wait_recover(c, 3, c->pf_stream); set_error("front end: the previous read-back did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
-    c->pf_in_flight = false;
-    unsigned* counter = lp_done_counter(c, 3);
-    if (!counter) { set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
+    int rc = pf_block_ready(c, f, "front end"); if (rc) return rc;
+    LpDone d{};
+    if ((rc = lp_done_arm(c, 3, (int*)(c->h_stage_pf + 32), c->pf_seq_next, &d))) return rc;
     const size_t S = (size_t)c->slots_per_image, o = (size_t)image * S;
     const float* fs = c->d_stereo + o * 2;
     const int words = (int)S * (7 + 8 + (with_stereo ? 2 : 0));
-    int* flag = (int*)(c->h_stage_pf + 32);
-    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
     *out = LpDeliverReq{(const int*)(c->d_kp_count + image), (const uint32_t*)(c->d_kpts + o), (const uint32_t*)(c->d_desc + o * 32),
-                        with_stereo ? (const uint32_t*)fs : nullptr, with_stereo ? (const uint32_t*)(fs + S) : nullptr, (uint32_t*)c->h_stage_pf, counter, flag,
-                        lp_next_seq(c->pf_seq_next), std::max(1, std::min(64, (words + 1023) / 1024))};
+                        with_stereo ? (const uint32_t*)fs : nullptr, with_stereo ? (const uint32_t*)(fs + S) : nullptr, (uint32_t*)c->h_stage_pf, d.counter, d.flag,
+                        d.seq, std::max(1, std::min(64, (words + 1023) / 1024))};
     return LPSLAM_HIP_OK;
 }
 void lp_commit_delivery(lpslam_hip_ctx* c, int image, int with_stereo, const LpDeliverReq& r, hipStream_t s)
 {
-    c->pf_seq = r.seq; c->pf_fields = FRAME_KPTS | FRAME_DESC | (with_stereo ? (FRAME_XR | FRAME_DEPTH) : 0); c->pf_stream = s; c->pf_in_flight = true;
+    c->pf_done = LpDone{r.counter, r.flag, r.seq, 3}; c->pf_fields = FRAME_KPTS | FRAME_DESC | (with_stereo ? (FRAME_XR | FRAME_DEPTH) : 0); c->pf_stream = s; c->pf_in_flight = true;
     c->pf_image = image;
 }
 int lp_launch_deliver_batch(hipStream_t s, const LpDeliverReq* reqs, int n, int slots_per_image, const lpslam_hip_ctx* layout)
@@ -1400,10 +1424,10 @@ static int frame_collect(lpslam_hip_ctx* c, int image, int fields, uint8_t** blo
         // delivered ahead of time by lpslam_hip_prefetch_frame
         st = c->h_stage_pf;
         c->pf_image = -1;
-        const bool arrived = lp_wait_done((int*)(st + 32), c->pf_seq, c->pf_stream);
+        const int w = lp_done_wait(c, c->pf_done, c->pf_stream);
         lp_share_front_end_collected(c);
-        if (!arrived) { c->pf_in_flight = !lp_wait_recover(c, 3, c->pf_stream); set_error("lpslam_hip_get_frame: the prefetched read-back did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
-        c->pf_in_flight = false;
+        c->pf_in_flight = w == LP_DONE_DEAD;
+        if (w) { set_error("lpslam_hip_get_frame: the prefetched read-back did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
     } else {
         if (c->h_stage_bytes < f.need) {
             if (c->h_stage) { LP_HIP(hipStreamSynchronize(c->stream)); (void)hipHostFree(c->h_stage); }
@@ -1412,9 +1436,9 @@ static int frame_collect(lpslam_hip_ctx* c, int image, int fields, uint8_t** blo
             c->h_stage_bytes = f.need;
         }
         st = c->h_stage;
-        int seq = 0;
-        if ((rc = frame_deliver(c, image, fields, st, 0, c->stream, c->done_seq, &seq))) return rc;
-        if (!lp_wait_done((int*)(st + 32), seq, c->stream)) { (void)lp_wait_recover(c, 0, c->stream); set_error("lpslam_hip_get_frame: the read-back kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+        LpDone done{};
+        if ((rc = frame_deliver(c, image, fields, st, 0, c->stream, c->done_seq, &done))) return rc;
+        if (lp_done_wait(c, done, c->stream)) { set_error("lpslam_hip_get_frame: the read-back kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
     }
     int32_t n = 0;
     memcpy(&n, st, sizeof(n));

@@ -221,22 +221,14 @@ static int bow_transform_device(lpslam_hip_ctx* c, lpslam_hip_vocab* v, const ui
     const size_t nm = (size_t)std::max(n_max, 1);
     // page-locked block: done flag | count | word ids | weights | node ids -- written by the kernel itself, released by its last store
     const size_t o_word = 64, o_w = o_word + nm * 4, o_node = o_w + nm * 4, total = o_node + nm * 4;
-    if (c->h_match_bytes < total) {
-        if (c->h_match) { LP_HIP(hipStreamSynchronize(s)); (void)hipHostFree(c->h_match); }
-        c->h_match = nullptr; c->h_match_bytes = 0;
-        LP_HIP(hipHostMalloc((void**)&c->h_match, total + total / 2, hipHostMallocDefault));
-        c->h_match_bytes = total + total / 2;
-    }
-    uint8_t* hb = c->h_match;
-    unsigned* counter = lp_done_counter(c, 4);
-    if (!counter) { set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
-    int* flag = (int*)hb;
-    const int seq = lp_next_seq(c->done_seq);
-    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
+    uint8_t* hb = lp_match_staging(c, total, total + total / 2, s);
+    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
+    LpDone done{};
+    { const int rc = lp_done_arm(c, 4, (int*)hb, c->done_seq, &done); if (rc) return rc; }
     hipLaunchKernelGGL(k_bow_transform16, dim3((unsigned)((nm * 16 + 255) / 256)), dim3(256), 0, s, d_desc, d_count, n_max, v->d_child_start, v->d_child_list, v->d_desc, v->d_weight,
-                       v->d_word, v->L, levels_up, n_max, (int32_t*)(hb + 32), (int32_t*)(hb + o_word), (float*)(hb + o_w), (int32_t*)(hb + o_node), counter, flag, seq);
+                       v->d_word, v->L, levels_up, n_max, (int32_t*)(hb + 32), (int32_t*)(hb + o_word), (float*)(hb + o_w), (int32_t*)(hb + o_node), done.counter, done.flag, done.seq);
     LP_HIP(hipGetLastError());
-    if (!lp_wait_done(flag, seq, s)) { (void)lp_wait_recover(c, 4, s); set_error("bow_transform: the kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+    if (lp_done_wait(c, done, s)) { set_error("bow_transform: the kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
     const int n = std::min(std::max(*(const int32_t*)(hb + 32), 0), n_max);
     if (n > 0) {
         if (word_id) memcpy(word_id, hb + o_word, (size_t)n * 4);
@@ -290,9 +282,7 @@ int lpslam_hip_match_bow_tree_multi(lpslam_hip_ctx* c, const uint8_t* q_desc32, 
     if (nq == 0 || n_sets == 0) return LPSLAM_HIP_OK;
     LP_HIP(hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
-    static const bool trace = getenv("LPSLAM_HIP_MATCH_TRACE") != nullptr;
-    const auto tr0 = std::chrono::steady_clock::now();
-    auto tr_us = [&tr0]() { return 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tr0).count(); };
+    const LpMatchTrace tr;
     double tr_staged = 0, tr_back = 0;
     // the order upstream visits the queries in: node by node (ascending id), keypoint order inside a node
     std::vector<int32_t> q_order;
@@ -327,17 +317,11 @@ int lpslam_hip_match_bow_tree_multi(lpslam_hip_ctx* c, const uint8_t* q_desc32, 
     const size_t out_end = at, o_ids = at, total = o_ids + 64;
     if (o_tab == al((size_t)nqa * 32)) return LPSLAM_HIP_OK;                 // no set has a target under any node
     if (at + 64 >= (size_t)0xffffffffu) { set_error("bow_tree: the sets do not fit one block"); return LPSLAM_HIP_ERR_CAPACITY; }
-    void* blk = nullptr; size_t cap = 0;
-    { const int rc = lp_pool_alloc(c, total, &blk, &cap); if (rc) return rc; }
-    auto release = [&]() { lp_pool_free(c, blk, cap); };
-#define B_HIP(x) do { if ((x) != hipSuccess) { release(); set_error("HIP call failed: %s", #x); return LPSLAM_HIP_ERR_DEVICE; } } while (0)
-    if (c->h_match_bytes < total) {
-        if (c->h_match) { B_HIP(hipStreamSynchronize(s)); (void)hipHostFree(c->h_match); }
-        c->h_match = nullptr; c->h_match_bytes = 0;
-        B_HIP(hipHostMalloc((void**)&c->h_match, total + total / 2, hipHostMallocDefault));
-        c->h_match_bytes = total + total / 2;
-    }
-    uint8_t* base = (uint8_t*)blk; uint8_t* hb = c->h_match;
+    LpPoolBlock blk(c);
+    { const int rc = blk.alloc(total); if (rc) return rc; }
+    uint8_t* base = (uint8_t*)blk.ptr;
+    uint8_t* hb = lp_match_staging(c, total, total + total / 2, s);
+    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
     for (int a = 0; a < nqa; ++a) memcpy(hb + 32 * (size_t)a, q_desc32 + 32 * (size_t)q_order[(size_t)a], 32);
     std::vector<std::vector<uint8_t>> taken_of((size_t)n_sets);              // by target index, as the replay keeps it
     for (int i = 0; i < n_sets; ++i) {
@@ -367,13 +351,13 @@ int lpslam_hip_match_bow_tree_multi(lpslam_hip_ctx* c, const uint8_t* q_desc32, 
         BowSetOff* tab = (BowSetOff*)(hb + o_tab);
         for (Set& st : sets) if (st.live) tab[n_live++] = BowSetOff{(unsigned)st.o_seg, (unsigned)st.o_td, (unsigned)st.o_taken, (unsigned)st.o_keys, (unsigned)st.o_cnt, {0, 0, 0}};
     }
-    tr_staged = tr_us();
-    B_HIP(hipMemcpyAsync(base, hb, in_end, hipMemcpyHostToDevice, s));
+    tr_staged = tr.us();
+    LP_HIP(hipMemcpyAsync(base, hb, in_end, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_bow_topk_sets, dim3((unsigned)((nqa + 3) / 4), (unsigned)n_live), dim3(256), 0, s, (const uint8_t*)base, (const BowSetOff*)(base + o_tab), nqa);
-    B_HIP(hipGetLastError());
-    B_HIP(hipMemcpyAsync(hb + in_end, base + in_end, out_end - in_end, hipMemcpyDeviceToHost, s));
-    B_HIP(hipStreamSynchronize(s));
-    tr_back = tr_us();
+    LP_HIP(hipGetLastError());
+    LP_HIP(hipMemcpyAsync(hb + in_end, base + in_end, out_end - in_end, hipMemcpyDeviceToHost, s));
+    LP_HIP(hipStreamSynchronize(s));
+    tr_back = tr.us();
     int* d_ids = (int*)(base + o_ids);
     int found_all = 0;
     for (int i = 0; i < n_sets; ++i) {
@@ -397,13 +381,13 @@ int lpslam_hip_match_bow_tree_multi(lpslam_hip_ctx* c, const uint8_t* q_desc32, 
                 // the short list was eaten by earlier queries: scan again for this query with the current assignment
                 uint8_t* tk = hb + st.o_taken;
                 for (int j = 0; j < st.nto; ++j) tk[j] = taken[(size_t)t_order[(size_t)j]];
-                B_HIP(hipMemcpyAsync(base + st.o_taken, tk, (size_t)st.nto, hipMemcpyHostToDevice, s));
-                B_HIP(hipMemcpyAsync(d_ids, &a, sizeof(int), hipMemcpyHostToDevice, s));
+                LP_HIP(hipMemcpyAsync(base + st.o_taken, tk, (size_t)st.nto, hipMemcpyHostToDevice, s));
+                LP_HIP(hipMemcpyAsync(d_ids, &a, sizeof(int), hipMemcpyHostToDevice, s));
                 hipLaunchKernelGGL(k_bow_topk, dim3(1), dim3(256), 0, s, base, (const int2*)(base + st.o_seg), (const int*)d_ids, 1, base + st.o_td,
                                    (const int32_t*)nullptr, base + st.o_taken, (unsigned long long*)(base + st.o_keys), (int*)(base + st.o_cnt));
-                B_HIP(hipGetLastError());
-                B_HIP(hipMemcpyAsync(cand, base + st.o_keys, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-                B_HIP(hipStreamSynchronize(s));
+                LP_HIP(hipGetLastError());
+                LP_HIP(hipMemcpyAsync(cand, base + st.o_keys, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+                LP_HIP(hipStreamSynchronize(s));
                 m = free_ones(fr);
             }
             if (m == 0) continue;
@@ -419,9 +403,7 @@ int lpslam_hip_match_bow_tree_multi(lpslam_hip_ctx* c, const uint8_t* q_desc32, 
         if (n_matches) n_matches[i] = found;
         found_all += found;
     }
-#undef B_HIP
-    release();
-    if (trace) fprintf(stderr, "bow_tree_match: %d queries, %d targets, %d matches; us: sorted %.1f, staged %.1f, lists back %.1f, replayed %.1f\n", nq, n_sets, found_all, 0.0, tr_staged, tr_back, tr_us());
+    if (tr.on()) fprintf(stderr, "bow_tree_match: %d queries, %d targets, %d matches; us: sorted %.1f, staged %.1f, lists back %.1f, replayed %.1f\n", nq, n_sets, found_all, 0.0, tr_staged, tr_back, tr.us());
     return LPSLAM_HIP_OK;
 }
 

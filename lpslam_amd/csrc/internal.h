@@ -13,6 +13,7 @@
 #include <utility>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -77,6 +78,9 @@ int hip_fail(hipError_t e, const char* what);
 
 }  // namespace lpslam
 
+// One armed completion flag ("results delivered by the kernel itself", below): what the launch is given and what the wait needs.
+struct LpDone { unsigned* counter; int* flag; int seq, which; };
+
 struct lpslam_hip_ctx {
     lpslam_hip_frontend_config cfg{};
     lpslam::LevelTable lt{};
@@ -118,7 +122,9 @@ struct lpslam_hip_ctx {
     uint8_t* h_stage = nullptr;        // pinned host staging of lpslam_hip_get_frame (one frame's results)
     size_t h_stage_bytes = 0;
     // a frame's results delivered ahead of time (lpslam_hip_prefetch_frame): block of its own, the image it holds (-1: none), what it holds
-    uint8_t* h_stage_pf = nullptr; size_t h_stage_pf_bytes = 0; std::atomic<int> pf_image{-1}; int pf_seq = 0, pf_seq_next = 0, pf_fields = 0; bool pf_in_flight = false; hipStream_t pf_stream = nullptr;
+    // (pf_done: the delivery in flight, armed in one call and waited for in a later one; pf_seq_next: the prefetch thread's deliveries count
+    // on their own -- two threads never share a sequence counter)
+    uint8_t* h_stage_pf = nullptr; size_t h_stage_pf_bytes = 0; std::atomic<int> pf_image{-1}; LpDone pf_done{}; int pf_seq_next = 0, pf_fields = 0; bool pf_in_flight = false; hipStream_t pf_stream = nullptr;
     // host mirror of d_kp_count: valid after any call that fetched it, invalidated by whatever rewrites it on the device
     std::vector<int32_t> h_kp_count; std::vector<uint8_t> h_kp_valid;
     // descriptor sets kept on the device under a caller's key (lpslam_hip_desc_store_put: a tracker's keyframes), blocks of the pool
@@ -142,7 +148,7 @@ struct lpslam_hip_ctx {
     std::atomic<long> ba_timeouts_band{0}, ba_timeouts_update{0};      // timed-out hand-overs of every problem of this context (report_faults)
     std::atomic<long> ba_graph_replays{0};   // hipGraphLaunch calls so far (lpslam_hip_ba_graph_replays: lets a test see that it exercised the replay path)
     std::vector<std::pair<size_t, void*>> pin_big;   // idle page-locked staging blocks (capacity, block) of lp_pin_big_alloc / free
-    uint8_t* h_match = nullptr;        // pinned host staging of the window matchers (queries in, candidate lists out)
+    uint8_t* h_match = nullptr;        // pinned host staging of the matchers, the vocabulary walk and the pose optimiser, one call at a time (lp_match_staging owns it)
     size_t h_match_bytes = 0;
     // A session on the role streams uploads its frames on a stream of ITS OWN that carries copies and their events only: the sessions'
     // copies run side by side on the copy engines and beside the chains on the front-end stream (16 images one after the other on one
@@ -213,6 +219,20 @@ struct lpslam_hip_ctx {
 inline hipStream_t lp_fe_stream(lpslam_hip_ctx* c) { if (lpslam::lp_tls_stream) { lpslam::lp_tls_stream_used = true; return lpslam::lp_tls_stream; } return c->stream; }
 int lp_pool_alloc(lpslam_hip_ctx* c, size_t bytes, void** out, size_t* capacity);
 void lp_pool_free(lpslam_hip_ctx* c, void* p, size_t capacity);
+// A block of the cache held for the length of one call: it goes back when the holder returns, whichever way (LP_HIP included);
+// leak() after a wait that found the stream dead -- its kernels may still write the block.
+struct LpPoolBlock {
+    lpslam_hip_ctx* ctx; void* ptr = nullptr; size_t cap = 0;
+    explicit LpPoolBlock(lpslam_hip_ctx* c) : ctx(c) {}
+    LpPoolBlock(const LpPoolBlock&) = delete;
+    LpPoolBlock& operator=(const LpPoolBlock&) = delete;
+    ~LpPoolBlock() { if (ptr) lp_pool_free(ctx, ptr, cap); }
+    int alloc(size_t bytes) { return lp_pool_alloc(ctx, bytes, &ptr, &cap); }
+    void leak() { ptr = nullptr; }
+};
+// the context's page-locked block h_match with at least `need` bytes; when it is smaller, the caller's stream `s` is synchronised,
+// the block freed and one of `grow_to` bytes allocated (the growth policy is the caller's).  nullptr: failed, error set
+uint8_t* lp_match_staging(lpslam_hip_ctx* c, size_t need, size_t grow_to, hipStream_t s);
 hipStream_t lp_stream_acquire(lpslam_hip_ctx* c);   // high-priority non-blocking stream from the context's cache (nullptr on failure)
 void lp_stream_release(lpslam_hip_ctx* c, hipStream_t s);
 void* lp_pin_big_alloc(lpslam_hip_ctx* c, size_t bytes, size_t* capacity);      // page-locked staging of any size, recycled through the context
@@ -307,7 +327,7 @@ __device__ __forceinline__ void lp_signal_done(unsigned* counter, int* flag, int
 #endif
 inline void lp_pf_invalidate(lpslam_hip_ctx* c, int first, int n) { const int p = c->pf_image.load(std::memory_order_relaxed); if (p >= first && p < first + n) c->pf_image.store(-1, std::memory_order_relaxed); }      // the slot's results are being rewritten
 unsigned* lp_done_counter(lpslam_hip_ctx* c, int which);      // arrival counter number `which` (0 .. 7) of the context, nullptr on failure
-bool lp_wait_recover(lpslam_hip_ctx* c, int which, hipStream_t s);      // after a failed lp_wait_done: counter re-zeroed; false = the stream is dead, leak what its kernels touch
+bool lp_wait_recover(lpslam_hip_ctx* c, int which, hipStream_t s);      // after a failed lp_wait_done: counter re-zeroed (which < 0: none); false = the stream is dead, leak what its kernels touch
 // the next sequence number of a completion flag: positive, never 0 (0 is what the flag is reset to before a launch)
 inline int lp_next_seq(int& s) { s = s >= 0x7ffffff0 ? 1 : s + 1; return s; }
 // One step of a host-side poll: a pause while the wait is young (a tracker call's kernel is back in 20 - 130 us), then the core is
@@ -332,3 +352,18 @@ inline bool lp_wait_done(int* flag, int seq, hipStream_t s)
     if (hipStreamSynchronize(s) != hipSuccess) return false;
     return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq;
 }
+// The host half of a delivery, once for every caller.  Arm, in front of the launch: arrival counter `which` of the context (LP_NO_COUNTER:
+// the kernel signals without one), the next number of `seq_counter` (the context's done_seq, or a counter of its own where the flag shares
+// memory or threads with others), the flag zeroed; *d is what the launch and the wait are given.  Returns an LPSLAM_HIP_ERR_* code.
+enum { LP_NO_COUNTER = -1 };
+int lp_done_arm(lpslam_hip_ctx* c, int which, int* flag, int& seq_counter, LpDone* d);
+// Wait: lp_wait_done and, when the flag did not come, lp_wait_recover.  LP_DONE_LATE: no flag, but the stream is alive and idle -- what its
+// kernels touched may be released; LP_DONE_DEAD: leak it.  (The error text is the caller's.)
+enum { LP_DONE_ARRIVED = 0, LP_DONE_LATE = 1, LP_DONE_DEAD = 2 };
+int lp_done_wait(lpslam_hip_ctx* c, const LpDone& d, hipStream_t s);
+// LPSLAM_HIP_MATCH_TRACE: the matchers print where a call's microseconds went
+struct LpMatchTrace {
+    const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    static bool on() { static const bool v = getenv("LPSLAM_HIP_MATCH_TRACE") != nullptr; return v; }
+    double us() const { return 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
+};

@@ -537,6 +537,23 @@ static int chk(lpslam_hip_ctx* c, int a, int b)
     return LPSLAM_HIP_OK;
 }
 
+// Which of a 2-NN search's nq results are matches: best distance within max_dist, Lowe ratio against the second (ratio > 0), and
+// -- cross_check -- the train side's best (rbi) is this query.  Returns their number, or -1 (error set) when `capacity` does not hold them.
+static int bf_filter(const int32_t* bi, const int32_t* bd, const int32_t* sd, const int32_t* rbi, int nq, int32_t max_dist, float ratio, int32_t cross_check,
+                     int32_t* out_q, int32_t* out_t, int32_t* out_d, int32_t capacity)
+{
+    int n = 0;
+    for (int i = 0; i < nq; ++i) {
+        if (bi[i] < 0) continue;
+        if (bd[i] > max_dist) continue;
+        if (ratio > 0.f && ratio * (float)sd[i] < (float)bd[i]) continue;
+        if (cross_check && rbi[bi[i]] != i) continue;
+        if (n >= capacity) { set_error("match buffer too small"); return -1; }
+        out_q[n] = i; out_t[n] = bi[i]; out_d[n] = bd[i]; ++n;
+    }
+    return n;
+}
+
 int lpslam_hip_match_bf(lpslam_hip_ctx* c, int query, int train)
 {
     int rc = chk(c, query, train); if (rc) return rc;
@@ -580,15 +597,8 @@ int lpslam_hip_get_bf_matches(lpslam_hip_ctx* c, int query, int train, int32_t m
         rbi.resize(nt);
         if ((rc = lpslam_hip_get_bf_knn2(c, train, rbi.data(), nullptr, nullptr, nt, nullptr))) return rc;
     }
-    int n = 0;
-    for (int i = 0; i < nq; ++i) {
-        if (bi[i] < 0) continue;
-        if (bd[i] > max_dist) continue;
-        if (ratio > 0.f && ratio * (float)sd[i] < (float)bd[i]) continue;
-        if (cross_check && rbi[bi[i]] != i) continue;
-        if (n >= capacity) { set_error("match buffer too small"); return LPSLAM_HIP_ERR_CAPACITY; }
-        out_q[n] = i; out_t[n] = bi[i]; out_d[n] = bd[i]; ++n;
-    }
+    const int n = bf_filter(bi.data(), bd.data(), sd.data(), rbi.data(), nq, max_dist, ratio, cross_check, out_q, out_t, out_d, capacity);
+    if (n < 0) return LPSLAM_HIP_ERR_CAPACITY;
     if (count) *count = n;
     return LPSLAM_HIP_OK;
 }
@@ -633,35 +643,19 @@ int lpslam_hip_match_bf_descriptors(lpslam_hip_ctx* c, int query, int scratch, c
     if (cross_check && (rc = lp_launch_bf_strided(c, scratch, query, 0, 1))) return rc;
     // page-locked block: flag | best index, best distance, second distance of the queries | best index of the train side
     const size_t o_bi = 16, o_bd = o_bi + (size_t)nq, o_sd = o_bd + (size_t)nq, o_rbi = o_sd + (size_t)nq, words = o_rbi + (size_t)n_train;
-    if (c->h_match_bytes < words * 4) {
-        if (c->h_match) { LP_HIP(hipStreamSynchronize(s)); (void)hipHostFree(c->h_match); }
-        c->h_match = nullptr; c->h_match_bytes = 0;
-        LP_HIP(hipHostMalloc((void**)&c->h_match, words * 8, hipHostMallocDefault));
-        c->h_match_bytes = words * 8;
-    }
-    unsigned* done_counter = lp_done_counter(c, 2);
-    if (!done_counter) { set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
-    uint32_t* st = (uint32_t*)c->h_match;
-    int* flag = (int*)st;
-    const int seq = lp_next_seq(c->done_seq);
-    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
+    uint32_t* st = (uint32_t*)lp_match_staging(c, words * 4, words * 8, s);
+    if (!st) return LPSLAM_HIP_ERR_DEVICE;
+    LpDone done{};
+    if ((rc = lp_done_arm(c, 2, (int*)st, c->done_seq, &done))) return rc;
     const uint32_t* fq = (const uint32_t*)(c->d_bf + (size_t)query * 3 * S);
     const uint32_t* ft = (const uint32_t*)(c->d_bf + (size_t)scratch * 3 * S);
     WordRuns r{{fq, fq + S, fq + 2 * S, ft}, {nq, nq, nq, cross_check ? n_train : 0}, {(int)o_bi, (int)o_bd, (int)o_sd, (int)o_rbi}};
-    hipLaunchKernelGGL(k_words_to_host, dim3(std::max(1, std::min(16, (int)(words / 1024) + 1))), dim3(256), 0, s, r, st, done_counter, flag, seq);
+    hipLaunchKernelGGL(k_words_to_host, dim3(std::max(1, std::min(16, (int)(words / 1024) + 1))), dim3(256), 0, s, r, st, done.counter, done.flag, done.seq);
     LP_HIP(hipGetLastError());
-    if (!lp_wait_done(flag, seq, s)) { (void)lp_wait_recover(c, 2, s); set_error("lpslam_hip_match_bf_descriptors: the read-back kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
-    const int32_t* bi = (const int32_t*)(st + o_bi); const int32_t* bd = (const int32_t*)(st + o_bd); const int32_t* sd = (const int32_t*)(st + o_sd);
-    const int32_t* rbi = (const int32_t*)(st + o_rbi);
-    int n = 0;
-    for (int i = 0; i < nq; ++i) {       // the filter of lpslam_hip_get_bf_matches
-        if (bi[i] < 0) continue;
-        if (bd[i] > max_dist) continue;
-        if (ratio > 0.f && ratio * (float)sd[i] < (float)bd[i]) continue;
-        if (cross_check && rbi[bi[i]] != i) continue;
-        if (n >= capacity) { set_error("match buffer too small"); return LPSLAM_HIP_ERR_CAPACITY; }
-        out_q[n] = i; out_t[n] = bi[i]; out_d[n] = bd[i]; ++n;
-    }
+    if (lp_done_wait(c, done, s)) { set_error("lpslam_hip_match_bf_descriptors: the read-back kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+    const int32_t* hw = (const int32_t*)st;
+    const int n = bf_filter(hw + o_bi, hw + o_bd, hw + o_sd, hw + o_rbi, nq, max_dist, ratio, cross_check, out_q, out_t, out_d, capacity);
+    if (n < 0) return LPSLAM_HIP_ERR_CAPACITY;
     if (count) *count = n;
     return LPSLAM_HIP_OK;
 }
@@ -736,25 +730,17 @@ int lpslam_hip_match_bf_stored(lpslam_hip_ctx* c, int query, const int32_t* keys
     // page-locked block: flag | pair list | run list | results
     const size_t o_pairs = 64, o_runs = o_pairs + 2 * (size_t)n_keys * sizeof(BfPair), o_res = (o_runs + 2 * (size_t)n_keys * sizeof(WordRun) + 63) & ~(size_t)63;
     const size_t host_bytes = o_res + host_words * 4;
-    if (c->h_match_bytes < host_bytes) {
-        // sized at once for a search over 48 full sets (a tracker's candidate list grows one keyframe at a time: growing the block with
-        // it cost a page-locked reallocation -- 1 ms -- on every frame that crossed the previous size)
-        const size_t roomy = std::max(host_bytes * 2, (size_t)4096 + 96 * (sizeof(BfPair) + sizeof(WordRun)) + (size_t)48 * 4 * S * 4);
-        if (c->h_match) { LP_HIP(hipStreamSynchronize(s)); (void)hipHostFree(c->h_match); }
-        c->h_match = nullptr; c->h_match_bytes = 0;
-        LP_HIP(hipHostMalloc((void**)&c->h_match, roomy, hipHostMallocDefault));
-        c->h_match_bytes = roomy;
-    }
-    void* blk = nullptr; size_t cap = 0;
+    // when it grows, sized at once for a search over 48 full sets (a tracker's candidate list grows one keyframe at a time: growing the
+    // block with it cost a page-locked reallocation -- 1 ms -- on every frame that crossed the previous size)
+    const size_t roomy = std::max(host_bytes * 2, (size_t)4096 + 96 * (sizeof(BfPair) + sizeof(WordRun)) + (size_t)48 * 4 * S * 4);
+    uint8_t* hb = lp_match_staging(c, host_bytes, roomy, s);
+    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
+    LpPoolBlock blk(c);
     // (always the size of a 48-set search: the context's block cache then serves every call from the same block -- a request that
     // grows by one keyframe per call would miss it every time, 1 ms of hipMalloc)
-    if ((rc = lp_pool_alloc(c, std::max(dev_words * 4, (size_t)48 * 6 * S * 4), &blk, &cap))) return rc;
-    auto release = [&]() { lp_pool_free(c, blk, cap); };
-    unsigned* done_counter = lp_done_counter(c, 2);
-    if (!done_counter) { release(); set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
-    uint8_t* hb = c->h_match;
+    if ((rc = blk.alloc(std::max(dev_words * 4, (size_t)48 * 6 * S * 4)))) return rc;
     BfPair* pairs = (BfPair*)(hb + o_pairs); WordRun* runs = (WordRun*)(hb + o_runs);
-    int32_t* d_res = (int32_t*)blk;
+    int32_t* d_res = (int32_t*)blk.ptr;
     const uint8_t* qdesc = c->d_desc + (size_t)query * S * 32;
     size_t w = 0;
     std::vector<size_t> h_fwd((size_t)n_keys), h_rev((size_t)n_keys);
@@ -770,36 +756,24 @@ int lpslam_hip_match_bf_stored(lpslam_hip_ctx* c, int query, const int32_t* keys
     }
     // a set without descriptors leaves its forward arrays unwritten by the kernel (no train descriptor: best index -1): preset them
     for (int k = 0; k < n_keys; ++k)
-        if (c->desc_store[keys[k]].n == 0) {
-            if (hipMemsetAsync(d_res + o_fwd[(size_t)k], 0xff, (size_t)nq * 4, s) != hipSuccess) { release(); set_error("hipMemsetAsync failed"); return LPSLAM_HIP_ERR_DEVICE; }
-        }
-    int* flag = (int*)hb;
-    const int seq = lp_next_seq(c->done_seq);
-    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
+        if (c->desc_store[keys[k]].n == 0) LP_HIP(hipMemsetAsync(d_res + o_fwd[(size_t)k], 0xff, (size_t)nq * 4, s));
+    LpDone done{};
+    if ((rc = lp_done_arm(c, 2, (int*)hb, c->done_seq, &done))) return rc;
     const int q_blocks = (std::max(nq, nt_max) + BF_QPW - 1) / BF_QPW;
     hipLaunchKernelGGL(k_bf_knn2_pairs, dim3(q_blocks, n_pairs), dim3(256), 0, s, (const BfPair*)pairs);
-    hipLaunchKernelGGL(k_runs_to_host, dim3(4, n_runs), dim3(256), 0, s, (const WordRun*)runs, (uint32_t*)hb, done_counter, flag, seq);
-    if (hipGetLastError() != hipSuccess) { release(); set_error("launch failed"); return LPSLAM_HIP_ERR_DEVICE; }
+    hipLaunchKernelGGL(k_runs_to_host, dim3(4, n_runs), dim3(256), 0, s, (const WordRun*)runs, (uint32_t*)hb, done.counter, done.flag, done.seq);
+    LP_HIP(hipGetLastError());
     // (a failed wait: the block goes back to the pool only when the stream still synchronises -- its kernels are then complete --, and the
     // arrival counter they left part-way is zeroed; on a dead stream the block is leaked rather than handed to the next caller)
-    if (!lp_wait_done(flag, seq, s)) { if (lp_wait_recover(c, 2, s)) release(); set_error("lpslam_hip_match_bf_stored: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
-    release();
+    if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("lpslam_hip_match_bf_stored: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
     const int32_t* hw = (const int32_t*)hb;
     for (int k = 0; k < n_keys; ++k) {
         const int nt = c->desc_store[keys[k]].n;
         if (nt == 0) continue;
-        const int32_t* bi = hw + h_fwd[(size_t)k]; const int32_t* bd = bi + nq; const int32_t* sd = bd + nq;
-        const int32_t* rbi = hw + h_rev[(size_t)k];
-        int n = 0;
-        for (int i = 0; i < nq; ++i) {       // the filter of lpslam_hip_get_bf_matches
-            if (bi[i] < 0) continue;
-            if (bd[i] > max_dist) continue;
-            if (ratio > 0.f && ratio * (float)sd[i] < (float)bd[i]) continue;
-            if (cross_check && rbi[bi[i]] != i) continue;
-            if (n >= capacity_per_key) { set_error("match buffer too small"); return LPSLAM_HIP_ERR_CAPACITY; }
-            const size_t at = (size_t)k * capacity_per_key + n;
-            out_q[at] = i; out_t[at] = bi[i]; out_d[at] = bd[i]; ++n;
-        }
+        const int32_t* bi = hw + h_fwd[(size_t)k];      // best index, then best distance, then second distance of the nq queries
+        const size_t at = (size_t)k * capacity_per_key;
+        const int n = bf_filter(bi, bi + nq, bi + 2 * (size_t)nq, hw + h_rev[(size_t)k], nq, max_dist, ratio, cross_check, out_q + at, out_t + at, out_d + at, capacity_per_key);
+        if (n < 0) return LPSLAM_HIP_ERR_CAPACITY;
         counts[k] = n;
     }
     return LPSLAM_HIP_OK;
@@ -847,9 +821,7 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
 {
     int rc = chk(c, image, image); if (rc) return rc;
     if (nq < 0 || (nq > 0 && (!queries || !q_desc32 || !match_idx))) { set_error("bad window-match arguments"); return LPSLAM_HIP_ERR_INVALID; }
-    static const bool trace = getenv("LPSLAM_HIP_MATCH_TRACE") != nullptr;
-    const auto tr0 = std::chrono::steady_clock::now();
-    auto tr_us = [&tr0]() { return 1e-3 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tr0).count(); };
+    const LpMatchTrace tr;
     double tr_alloc = 0, tr_launch = 0, tr_wait = 0; int tr_rescans = 0;
     static_assert(sizeof(lpslam_hip_proj_query) == sizeof(ProjQuery), "query layout");
     if (n_matches) *n_matches = 0;
@@ -863,28 +835,21 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
     const size_t o_keys = 0, o_q = o_keys + (size_t)nq * 4 * sizeof(unsigned long long), o_qd = o_q + (size_t)nq * sizeof(ProjQuery), o_cnt = o_qd + (size_t)nq * 32,
                  o_ids = o_cnt + (size_t)nq * sizeof(int), o_bsf = o_ids + 64;
     const size_t total = o_bsf + nk * sizeof(int16_t);
-    void* blk = nullptr; size_t cap = 0;
-    { const int rc2 = lp_pool_alloc(c, total, &blk, &cap); if (rc2) return rc2; }
-    auto release = [&]() { lp_pool_free(c, blk, cap); };
-#define P_HIP(x) do { if ((x) != hipSuccess) { release(); set_error("HIP call failed: %s", #x); return LPSLAM_HIP_ERR_DEVICE; } } while (0)
+    LpPoolBlock blk(c);
+    if ((rc = blk.alloc(total))) return rc;
     // pinned mirror of that block on the host: inputs are assembled there and go down as ONE copy (queries, descriptors,
     // counts, ids and best-so-far are contiguous), the candidate lists come back as one copy
-    if (c->h_match_bytes < total) {
-        if (c->h_match) (void)hipHostFree(c->h_match);
-        c->h_match = nullptr; c->h_match_bytes = 0;
-        P_HIP(hipHostMalloc((void**)&c->h_match, total + total / 2, hipHostMallocDefault));
-        c->h_match_bytes = total + total / 2;
-    }
-    tr_alloc = tr_us();
-    uint8_t* base = (uint8_t*)blk;
-    uint8_t* hb = c->h_match;
+    uint8_t* hb = lp_match_staging(c, total, total + total / 2, s);
+    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
+    tr_alloc = tr.us();
+    uint8_t* base = (uint8_t*)blk.ptr;
     unsigned long long* d_keys = (unsigned long long*)(base + o_keys); ProjQuery* d_q = (ProjQuery*)(base + o_q); uint8_t* d_qd = base + o_qd;
     int* d_cnt = (int*)(base + o_cnt); int* d_ids = (int*)(base + o_ids); int16_t* d_bsf = (int16_t*)(base + o_bsf);
     int16_t* bsf = (int16_t*)(hb + o_bsf);
     for (size_t i = 0; i < nk; ++i) bsf[i] = (int16_t)32767;
     if (taken_in) {                        // one byte per keypoint of the image: the count is needed (host mirror, else one round trip)
         int32_t n_kp = 0;
-        { const int rc3 = lpslam_hip_keypoint_count(c, image, &n_kp); if (rc3) { release(); return rc3; } }
+        if ((rc = lpslam_hip_keypoint_count(c, image, &n_kp))) return rc;
         for (int i = 0; i < n_kp; ++i) if (taken_in[i]) bsf[(size_t)i] = 0;
     }
     std::vector<int> owner(policy == 2 ? nk : 0, -1);
@@ -894,11 +859,6 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
     // the kernel takes them straight from the page-locked mirror (one PCIe read per wavefront, all in flight together) and the block
     // goes down to the device only if a rescan asks for it -- one copy-engine packet less in front of every matcher call.
     bool on_device = false;
-    auto to_device = [&]() -> bool {
-        if (on_device) return true;
-        if (hipMemcpyAsync(base + o_q, hb + o_q, total - o_q, hipMemcpyHostToDevice, s) != hipSuccess) return false;
-        on_device = true;
-        return true; };
     // (a `taken` mask does not send the block down either: the second pass of the scan reads a candidate's best-so-far entry from the
     // page-locked mirror together with its descriptor -- one more PCIe read in a round of loads that is in flight anyway, one copy-engine
     // packet less in front of the kernel)
@@ -909,11 +869,8 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
     for (int l = 0; l < LPSLAM_HIP_MAX_LEVELS; ++l) { const float sc = l < c->lt.n_levels ? c->lt.scale[l] : 1.0f; gate.inv_sigma_sq[l] = 1.0f / (sc * sc); }
     // the candidate lists and counts are written by the kernel straight into the page-locked mirror, and its last store releases a
     // sequence number there (internal.h, lp_signal_done): no copy-engine packet on the way back
-    unsigned* done_counter = lp_done_counter(c, 1);
-    if (!done_counter) { release(); set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
-    int* done_flag = (int*)(hb + o_ids + 32);
-    const int done_seq = lp_next_seq(c->done_seq);
-    __atomic_store_n(done_flag, 0, __ATOMIC_RELAXED);
+    LpDone done{};
+    if ((rc = lp_done_arm(c, 1, (int*)(hb + o_ids + 32), c->done_seq, &done))) return rc;
     const int16_t* first_bsf = taken_in ? (const int16_t*)(hb + o_bsf) : (const int16_t*)nullptr;
     // several sessions tracking at once: the first scan joins the other sessions' pending scans in one launch (share.hip)
     int shared = LP_SHARE_DIRECT;
@@ -921,24 +878,25 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
         LpProjReq rq{};
         rq.kp = c->d_kpts + o; rq.desc = c->d_desc + o * 32; rq.stereo_xr = sxr; rq.kp_count = c->d_kp_count + image;
         rq.queries = hb + o_q; rq.q_desc = hb + o_qd; rq.best_so_far = first_bsf;
-        rq.out_keys = (unsigned long long*)(hb + o_keys); rq.out_count = (int*)(hb + o_cnt); rq.done_counter = done_counter; rq.done_flag = done_flag;
-        rq.nq = nq; rq.grid_x = (nq + 3) / 4; rq.done_seq = done_seq; rq.inv_w = inv_w; rq.inv_h = inv_h;
+        rq.out_keys = (unsigned long long*)(hb + o_keys); rq.out_count = (int*)(hb + o_cnt); rq.done_counter = done.counter; rq.done_flag = done.flag;
+        rq.nq = nq; rq.grid_x = (nq + 3) / 4; rq.done_seq = done.seq; rq.inv_w = inv_w; rq.inv_h = inv_h;
         rq.gate.mode = gate.mode; for (int l = 0; l < LPSLAM_HIP_MAX_LEVELS; ++l) rq.gate.inv_sigma_sq[l] = gate.inv_sigma_sq[l];
         shared = lp_share_proj(c, rq);
-        if (shared < 0) { release(); return -shared; }
+        if (shared < 0) return -shared;
     }
     if (shared == LP_SHARE_DIRECT) {
         hipLaunchKernelGGL(k_proj_topk, dim3((nq + 3) / 4), dim3(256), 0, s, c->d_kpts + o, c->d_desc + o * 32, sxr, c->d_kp_count + image,
                            (const ProjQuery*)(hb + o_q), (const uint8_t*)(hb + o_qd), (const int*)nullptr, nq,
                            first_bsf, inv_w, inv_h, gate, (unsigned long long*)(hb + o_keys), (int*)(hb + o_cnt),
-                           done_counter, done_flag, done_seq);
-        P_HIP(hipGetLastError());
+                           done.counter, done.flag, done.seq);
+        LP_HIP(hipGetLastError());
     }
     const unsigned long long* keys = (const unsigned long long*)(hb + o_keys);
     const int* cnt = (const int*)(hb + o_cnt);
-    tr_launch = tr_us();
-    if (shared == LP_SHARE_DIRECT && !lp_wait_done(done_flag, done_seq, s)) { if (lp_wait_recover(c, 1, s)) release(); set_error("window matcher: the kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
-    tr_wait = tr_us();
+    tr_launch = tr.us();
+    if (shared == LP_SHARE_DIRECT)       // (a shared scan comes back with its flag arrived)
+        if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("window matcher: the kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+    tr_wait = tr.us();
     int found = 0;
     for (int k = 0; k < nq; ++k) {
         match_idx[k] = -1;
@@ -953,14 +911,14 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
         if (policy != 1 && m < 2 && cnt[k] > 4) {
             // the short list was eaten by earlier queries: scan again for this query with the current assignment
             ++tr_rescans;
-            P_HIP(to_device() ? hipSuccess : hipErrorUnknown);
-            P_HIP(hipMemcpyAsync(d_bsf, bsf, nk * sizeof(int16_t), hipMemcpyHostToDevice, s));
-            P_HIP(hipMemcpyAsync(d_ids, &k, sizeof(int), hipMemcpyHostToDevice, s));
+            if (!on_device) { LP_HIP(hipMemcpyAsync(base + o_q, hb + o_q, total - o_q, hipMemcpyHostToDevice, s)); on_device = true; }
+            LP_HIP(hipMemcpyAsync(d_bsf, bsf, nk * sizeof(int16_t), hipMemcpyHostToDevice, s));
+            LP_HIP(hipMemcpyAsync(d_ids, &k, sizeof(int), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(k_proj_topk, dim3(1), dim3(256), 0, s, c->d_kpts + o, c->d_desc + o * 32, sxr, c->d_kp_count + image,
                                d_q, d_qd, (const int*)d_ids, 1, (const int16_t*)d_bsf, inv_w, inv_h, gate, d_keys, d_cnt, (unsigned*)nullptr, (int*)nullptr, 0);
-            P_HIP(hipGetLastError());
-            P_HIP(hipMemcpyAsync(cand, d_keys, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-            P_HIP(hipStreamSynchronize(s));
+            LP_HIP(hipGetLastError());
+            LP_HIP(hipMemcpyAsync(cand, d_keys, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+            LP_HIP(hipStreamSynchronize(s));
             m = free_ones(fr);
         }
         if (m == 0) continue;
@@ -981,10 +939,8 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
         if (match_dist) match_dist[k] = best;
         ++found;
     }
-#undef P_HIP
-    release();
-    if (trace) fprintf(stderr, "window_match: policy %d, %d queries, %d matches, %d rescans; us: setup %.1f, staged + launched %.1f, lists back %.1f, replayed %.1f\n",
-                       policy, nq, found, tr_rescans, tr_alloc, tr_launch, tr_wait, tr_us());
+    if (tr.on()) fprintf(stderr, "window_match: policy %d, %d queries, %d matches, %d rescans; us: setup %.1f, staged + launched %.1f, lists back %.1f, replayed %.1f\n",
+                       policy, nq, found, tr_rescans, tr_alloc, tr_launch, tr_wait, tr.us());
     if (n_matches) *n_matches = found;
     c->wm_rescans = tr_rescans;
     return LPSLAM_HIP_OK;
@@ -1141,7 +1097,7 @@ __global__ __launch_bounds__(RK_THREADS) void k_rank_votes(const uint8_t* __rest
                 if (lane >= 64 - m) atomicMin(&rev[base + jc + lane - (64 - m)], acc);
             }
         }
-        // the filter of lpslam_hip_get_bf_matches without the cross check (that needs every pass's reverse minimum)
+        // the host's bf_filter without the cross check (that needs every pass's reverse minimum)
         if (qv) fwd[q] = (bidx < 0 || best > max_dist || (ratio > 0.f && ratio * (float)second < (float)best)) ? -1 : bidx;
     }
     __syncthreads();
@@ -1294,44 +1250,43 @@ int lpslam_hip_rank_stored(lpslam_hip_ctx* c, int query, const int32_t* keys, in
         const lpslam_hip_ctx::StoredDesc& e = *list[(size_t)k].second;
         table[(size_t)k] = RankSet{(const uint8_t*)e.blk, e.has_mask ? (const uint8_t*)e.mask : nullptr, e.n, list[(size_t)k].first};
     }
-    size_t hcap = 0;
-    uint8_t* hb = (uint8_t*)lp_pin_big_alloc(c, h_bytes, &hcap);
-    if (!hb) { set_error("page-locked memory for rank_stored"); return LPSLAM_HIP_ERR_DEVICE; }
-    void* blk = nullptr; size_t cap = 0;
-    if ((rc = lp_pool_alloc(c, o_tab + (size_t)n * sizeof(RankSet), &blk, &cap))) { lp_pin_big_free(c, hb, hcap); return rc; }
-    auto release = [&]() { lp_pool_free(c, blk, cap); lp_pin_big_free(c, hb, hcap); };
-    RankSet* sets = (RankSet*)((uint8_t*)blk + o_tab);
+    LpPoolBlock blk(c);
+    if ((rc = blk.alloc(o_tab + (size_t)n * sizeof(RankSet)))) return rc;
+    RankSet* sets = (RankSet*)((uint8_t*)blk.ptr + o_tab);
     // (a pageable source: the runtime has staged the table when the call returns)
-    if (hipMemcpyAsync(sets, table.data(), (size_t)n * sizeof(RankSet), hipMemcpyHostToDevice, s) != hipSuccess) { release(); set_error("rank_stored: set table upload"); return LPSLAM_HIP_ERR_DEVICE; }
-    unsigned* done_counter = lp_done_counter(c, 2);
-    if (!done_counter) { release(); set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
+    LP_HIP(hipMemcpyAsync(sets, table.data(), (size_t)n * sizeof(RankSet), hipMemcpyHostToDevice, s));
     if (lds > 64 * 1024) {
         static std::atomic<bool> attr_set[64];
         const int dev = c->cfg.device;
         if (dev >= 0 && dev < 64 && !attr_set[dev].load()) {
-            if (hipFuncSetAttribute((const void*)k_rank_votes, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) { release(); set_error("rank_stored: LDS attribute"); return LPSLAM_HIP_ERR_DEVICE; }
+            LP_HIP(hipFuncSetAttribute((const void*)k_rank_votes, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             attr_set[dev].store(true);
         }
     }
-    int* flag = (int*)hb;
-    const int seq = lp_next_seq(c->done_seq);
-    __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
-    const uint8_t* qdesc = c->d_desc + (size_t)query * c->slots_per_image * 32;
-    int32_t* d_votes = (int32_t*)blk;
-    int32_t* out = (int32_t*)(hb + o_out);
-    hipLaunchKernelGGL(k_rank_votes, dim3((unsigned)n), dim3(RK_THREADS), lds, s, qdesc, (int)nq, (const RankSet*)sets, (int)max_dist, ratio, d_votes);
-    hipLaunchKernelGGL(k_rank_topk, dim3(1), dim3(1024), 0, s, (const int32_t*)d_votes, (const RankSet*)sets, n, (int)top_k, out, done_counter, flag, seq);
-    if (hipGetLastError() != hipSuccess) { release(); set_error("launch failed"); return LPSLAM_HIP_ERR_DEVICE; }
-    if (!lp_wait_done(flag, seq, s)) {
-        // (a dead stream: its kernels may still read the table and write the votes -- leak both rather than hand them on)
-        if (lp_wait_recover(c, 2, s)) release();
-        set_error("lpslam_hip_rank_stored: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE;
+    // the page-locked block is handed back by hand: from here on every way out passes the end of the function
+    size_t hcap = 0;
+    uint8_t* hb = (uint8_t*)lp_pin_big_alloc(c, h_bytes, &hcap);
+    if (!hb) { set_error("page-locked memory for rank_stored"); return LPSLAM_HIP_ERR_DEVICE; }
+    LpDone done{};
+    int w = LP_DONE_ARRIVED;
+    if (!(rc = lp_done_arm(c, 2, (int*)hb, c->done_seq, &done))) {
+        const uint8_t* qdesc = c->d_desc + (size_t)query * c->slots_per_image * 32;
+        int32_t* d_votes = (int32_t*)blk.ptr;
+        const int32_t* out = (const int32_t*)(hb + o_out);
+        hipLaunchKernelGGL(k_rank_votes, dim3((unsigned)n), dim3(RK_THREADS), lds, s, qdesc, (int)nq, (const RankSet*)sets, (int)max_dist, ratio, d_votes);
+        hipLaunchKernelGGL(k_rank_topk, dim3(1), dim3(1024), 0, s, (const int32_t*)d_votes, (const RankSet*)sets, n, (int)top_k, (int32_t*)(hb + o_out), done.counter, done.flag, done.seq);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = hip_fail(e, "the launches of rank_stored");
+        else if ((w = lp_done_wait(c, done, s))) { set_error("lpslam_hip_rank_stored: the kernels did not complete"); rc = LPSLAM_HIP_ERR_DEVICE; }
+        else {
+            const int ns = std::min(out[0], (int)top_k);
+            for (int i = 0; i < ns; ++i) { out_keys[i] = out[1 + i]; out_votes[i] = out[1 + RK_TOPK_MAX + i]; }
+            *n_out = ns;
+        }
     }
-    const int ns = std::min(out[0], (int)top_k);
-    for (int i = 0; i < ns; ++i) { out_keys[i] = out[1 + i]; out_votes[i] = out[1 + RK_TOPK_MAX + i]; }
-    *n_out = ns;
-    release();
-    return LPSLAM_HIP_OK;
+    // (a dead stream: its kernels may still read the table and write the votes and the page-locked block -- leak both rather than hand them on)
+    if (w == LP_DONE_DEAD) blk.leak(); else lp_pin_big_free(c, hb, hcap);
+    return rc;
 }
 
 }  // extern "C"

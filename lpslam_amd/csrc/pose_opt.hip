@@ -736,13 +736,8 @@ int lpslam_hip_pose_optimize(lpslam_hip_ctx* ctx, double* pose7, const double* p
     const size_t off_pts = 128, off_obs = off_pts + 3 * np * sizeof(double), off_out = off_obs + no * sizeof(lpslam_hip_ba_obs);
     const size_t off_packed = 128, off_flags = off_packed + no * sizeof(PoObs);
     const size_t need = all_cached ? off_flags + no : off_out + no;
-    if (ctx->h_match_bytes < need) {
-        if (ctx->h_match) { LP_HIP(hipStreamSynchronize(s)); (void)hipHostFree(ctx->h_match); }
-        ctx->h_match = nullptr; ctx->h_match_bytes = 0;
-        LP_HIP(hipHostMalloc((void**)&ctx->h_match, need * 2, hipHostMallocDefault));
-        ctx->h_match_bytes = need * 2;
-    }
-    uint8_t* hb = ctx->h_match;
+    uint8_t* hb = lp_match_staging(ctx, need, need * 2, s);
+    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
     memcpy(hb, pose7, 7 * sizeof(double));
     int32_t inl = 0;
     if (all_cached) {
@@ -752,26 +747,27 @@ int lpslam_hip_pose_optimize(lpslam_hip_ctx* ctx, double* pose7, const double* p
             const double* p = points + 3 * (size_t)o.point;
             packed[k] = PoObs{o.u, o.v, o.ur, o.inv_sigma2, {p[0], p[1], p[2]}};
         }
-        int* flag = (int*)(hb + PO_BLK_FLAG);
-        const int seq = lp_next_seq(ctx->po_seq);
-        __atomic_store_n(flag, 0, __ATOMIC_RELAXED);          // (the block is shared with the matchers' staging: whatever they left here is not a sequence number)
+        // (no arrival counter: one workgroup signals.  The block is shared with the matchers' staging -- whatever they left in the flag is
+        // not a sequence number -- and the flag counts on its own, po_seq)
+        LpDone done{};
+        { const int rc = lp_done_arm(ctx, LP_NO_COUNTER, (int*)(hb + PO_BLK_FLAG), ctx->po_seq, &done); if (rc) return rc; }
         bool delivered = false;
         if (n_obs <= 256) {
             // a tracked frame: one observation per lane on 1, 2 or 4 wavefronts (k_pose_optimize_req); the camera travels in the block
             memcpy(hb + PO_BLK_CAM, &c, sizeof(BaCam));
-            const LpPoseReq req{hb, n_obs, seq};
+            const LpPoseReq req{hb, n_obs, done.seq};
             // several sessions tracking at once: the request joins the others' in one launch (share.hip) and comes back delivered
-            const int shared = lp_share_pose(ctx, req, flag);
+            const int shared = lp_share_pose(ctx, req, done.flag);
             if (shared < 0) return -shared;
             if (shared == LP_SHARE_DONE) delivered = true;
             else { const int rc = lp_launch_pose_batch(s, &req, 1); if (rc) return rc; }
         } else
         hipLaunchKernelGGL(k_pose_optimize<true>, dim3(1), dim3(PO_T), lds, s, (double*)hb, (const double*)nullptr, (const lpslam_hip_ba_obs*)nullptr, packed, n_obs, c,
-                           hb + off_flags, (int*)(hb + 56), cache_n, flag, seq);
+                           hb + off_flags, (int*)(hb + 56), cache_n, done.flag, done.seq);
         LP_HIP(hipGetLastError());
         // the kernel's last store releases `seq`: poll it (a few hundred microseconds at most), fall back to the stream when it does not come
         const auto t0 = std::chrono::steady_clock::now();
-        if (!delivered && !lp_wait_done(flag, seq, s)) { set_error("pose optimiser: the kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+        if (!delivered && lp_done_wait(ctx, done, s)) { set_error("pose optimiser: the kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
         memcpy(pose7, hb, 7 * sizeof(double));
         memcpy(&inl, hb + 56, sizeof(int));
         memcpy(&ctx->po_passes, hb + 60, sizeof(int));
@@ -785,27 +781,23 @@ int lpslam_hip_pose_optimize(lpslam_hip_ctx* ctx, double* pose7, const double* p
         return LPSLAM_HIP_OK;
     }
     // more observations than the LDS holds: one block of the context's cache, pose | n_inliers | points | observations | outlier
-    void* blk = nullptr; size_t cap = 0;
-    { const int rc = lp_pool_alloc(ctx, off_out + no, &blk, &cap); if (rc) return rc; }
-    auto release = [&]() { lp_pool_free(ctx, blk, cap); };
-#define PO_HIP(x) do { if ((x) != hipSuccess) { release(); set_error("HIP call failed: %s", #x); return LPSLAM_HIP_ERR_DEVICE; } } while (0)
-    uint8_t* base = (uint8_t*)blk;
+    LpPoolBlock blk(ctx);
+    { const int rc = blk.alloc(off_out + no); if (rc) return rc; }
+    uint8_t* base = (uint8_t*)blk.ptr;
     double* d_pose = (double*)base; int* d_n = (int*)(base + 64); double* d_pts = (double*)(base + off_pts);
     lpslam_hip_ba_obs* d_obs = (lpslam_hip_ba_obs*)(base + off_obs); uint8_t* d_out = base + off_out;
     if (n_points) memcpy(hb + off_pts, points, 3 * (size_t)n_points * sizeof(double));
     if (n_obs) memcpy(hb + off_obs, obs, (size_t)n_obs * sizeof(lpslam_hip_ba_obs));
-    PO_HIP(hipMemcpyAsync(base, hb, off_out, hipMemcpyHostToDevice, s));
+    LP_HIP(hipMemcpyAsync(base, hb, off_out, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_pose_optimize<false>, dim3(1), dim3(PO_T), lds, s, d_pose, d_pts, d_obs, (const PoObs*)nullptr, n_obs, c, d_out, d_n, cache_n, (int*)nullptr, 0);
-    PO_HIP(hipGetLastError());
-    PO_HIP(hipMemcpyAsync(hb, base, 128, hipMemcpyDeviceToHost, s));                    // pose and inlier count
-    if (outlier && n_obs) PO_HIP(hipMemcpyAsync(hb + off_out, d_out, (size_t)n_obs, hipMemcpyDeviceToHost, s));
-    PO_HIP(hipStreamSynchronize(s));
+    LP_HIP(hipGetLastError());
+    LP_HIP(hipMemcpyAsync(hb, base, 128, hipMemcpyDeviceToHost, s));                    // pose and inlier count
+    if (outlier && n_obs) LP_HIP(hipMemcpyAsync(hb + off_out, d_out, (size_t)n_obs, hipMemcpyDeviceToHost, s));
+    LP_HIP(hipStreamSynchronize(s));
     memcpy(pose7, hb, 7 * sizeof(double));
     memcpy(&inl, hb + 64, sizeof(int));
     memcpy(&ctx->po_passes, hb + 68, sizeof(int));
     if (outlier && n_obs) memcpy(outlier, hb + off_out, (size_t)n_obs);
-#undef PO_HIP
-    release();
     if (n_inliers) *n_inliers = inl;
     return LPSLAM_HIP_OK;
 }
