@@ -17,49 +17,6 @@
 
 namespace LpSlam {
 
-namespace {
-
-struct Mat3 { double m[9]; };
-
-Mat3 quatToRot(const double* q)
-{
-    const double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    const double w = q[0] / n, x = q[1] / n, y = q[2] / n, z = q[3] / n;
-    return {{1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-             2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-             2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)}};
-}
-
-void quatMul(const double* a, const double* b, double* o)
-{
-    const double r[4] = {a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
-                         a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]};
-    const double n = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
-    for (int i = 0; i < 4; ++i) o[i] = r[i] / n;
-}
-
-// Eigen::Quaterniond(R) for a rotation matrix
-void rotToQuat(const Mat3& R, double* q)
-{
-    const double* m = R.m;
-    const double tr = m[0] + m[4] + m[8];
-    if (tr > 0) {
-        const double s = std::sqrt(tr + 1.0) * 2;
-        q[0] = 0.25 * s; q[1] = (m[7] - m[5]) / s; q[2] = (m[2] - m[6]) / s; q[3] = (m[3] - m[1]) / s;
-    } else if (m[0] > m[4] && m[0] > m[8]) {
-        const double s = std::sqrt(1.0 + m[0] - m[4] - m[8]) * 2;
-        q[0] = (m[7] - m[5]) / s; q[1] = 0.25 * s; q[2] = (m[1] + m[3]) / s; q[3] = (m[2] + m[6]) / s;
-    } else if (m[4] > m[8]) {
-        const double s = std::sqrt(1.0 + m[4] - m[0] - m[8]) * 2;
-        q[0] = (m[2] - m[6]) / s; q[1] = (m[1] + m[3]) / s; q[2] = 0.25 * s; q[3] = (m[5] + m[7]) / s;
-    } else {
-        const double s = std::sqrt(1.0 + m[8] - m[0] - m[4]) * 2;
-        q[0] = (m[3] - m[1]) / s; q[1] = (m[2] + m[6]) / s; q[2] = (m[5] + m[7]) / s; q[3] = 0.25 * s;
-    }
-}
-
-}  // namespace
-
 HipVslamTrackerBase::HipVslamTrackerBase()
 {
     auto& o = getConfigOptions();
@@ -285,7 +242,7 @@ void HipVslamTrackerBase::warmUpContext(bool stereo)
         }
     }
     if (ok) {
-        const lpslam_hip_ba_camera cam{m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y, stereo ? m_cam.focal_x_baseline : 0.0, std::sqrt(5.991), std::sqrt(7.815)};
+        const lpslam_hip_ba_camera cam = baCamera(stereo);
         // a 4 x 4 grid of landmarks five metres ahead, seen from the origin and from a camera 0.1 m to the side
         std::vector<double> pts, poses = {1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0, -0.1, 0, 0};
         std::vector<lpslam_hip_ba_obs> obs;
@@ -339,16 +296,13 @@ std::array<double, 16> HipVslamTrackerBase::currentCamPose()
 // (src/Trackers/OpenVSLAMTrackerBase.cpp:307-329)
 TrackerResult HipVslamTrackerBase::createTrackerResult(const Pose& p, TimeStamp timestamp) const
 {
-    const Mat3 R = quatToRot(p.q);
-    const double cx = -(R.m[0] * p.t[0] + R.m[3] * p.t[1] + R.m[6] * p.t[2]);
-    const double cy = -(R.m[1] * p.t[0] + R.m[4] * p.t[1] + R.m[7] * p.t[2]);
-    const double cz = -(R.m[2] * p.t[0] + R.m[5] * p.t[1] + R.m[8] * p.t[2]);
-    double q[4];
-    rotToQuat(R, q);
+    double C[3], q[4];
+    centre(p, C);
+    rotToQuat(quatToRot(p.q), q);
     TrackerResult t;
     t.type = ResultType::TrackedVehicle;
     t.id = 0;
-    t.position.value = {-cy, cx, cz};
+    t.position.value = {-C[1], C[0], C[2]};
     t.orientation.value = {q[0], -q[2], q[1], q[3]};
     t.timestamp.system_time = timestamp;
     return t;
@@ -406,10 +360,8 @@ bool HipVslamTrackerBase::initializeMap(FrameData& f, const Pose& at)
 // update_normal_and_depth / compute_descriptor, reference observation only)
 void HipVslamTrackerBase::initLandmarkView(Landmark& lm, const Pose& pose, const lpslam_hip_keypoint& kp, const uint8_t* desc32) const
 {
-    const Mat3 R = quatToRot(pose.q);
-    // camera centre C = -R^T t
-    const double C[3] = {-(R.m[0] * pose.t[0] + R.m[3] * pose.t[1] + R.m[6] * pose.t[2]), -(R.m[1] * pose.t[0] + R.m[4] * pose.t[1] + R.m[7] * pose.t[2]),
-                         -(R.m[2] * pose.t[0] + R.m[5] * pose.t[1] + R.m[8] * pose.t[2])};
+    double C[3];
+    centre(pose, C);
     const double ray[3] = {lm.p[0] - C[0], lm.p[1] - C[1], lm.p[2] - C[2]};
     const double dist = std::sqrt(ray[0] * ray[0] + ray[1] * ray[1] + ray[2] * ray[2]);
     for (int a = 0; a < 3; ++a) lm.normal[a] = dist > 0 ? ray[a] / dist : 0.0;
@@ -441,8 +393,8 @@ void HipVslamTrackerBase::fuseInto(int c, int slot, const std::vector<int>& land
 {
     Keyframe& kc = m_kfs[(size_t)c];
     const Mat3 R = quatToRot(kc.pose.q);
-    const double C[3] = {-(R.m[0] * kc.pose.t[0] + R.m[3] * kc.pose.t[1] + R.m[6] * kc.pose.t[2]), -(R.m[1] * kc.pose.t[0] + R.m[4] * kc.pose.t[1] + R.m[7] * kc.pose.t[2]),
-                         -(R.m[2] * kc.pose.t[0] + R.m[5] * kc.pose.t[1] + R.m[8] * kc.pose.t[2])};
+    double C[3];
+    centre(kc.pose, C);
     const double log_sf = std::log((double)m_scaleFactor);
     std::vector<lpslam_hip_proj_query> q;
     std::vector<uint8_t> qd;
@@ -452,21 +404,15 @@ void HipVslamTrackerBase::fuseInto(int c, int slot, const std::vector<int>& land
         if (it == m_landmarks.end()) continue;
         const Landmark& lm = it->second;
         const double* X = lm.p;
-        const double pc[3] = {R.m[0] * X[0] + R.m[1] * X[1] + R.m[2] * X[2] + kc.pose.t[0], R.m[3] * X[0] + R.m[4] * X[1] + R.m[5] * X[2] + kc.pose.t[1],
-                              R.m[6] * X[0] + R.m[7] * X[1] + R.m[8] * X[2] + kc.pose.t[2]};
-        if (!(pc[2] > 0)) continue;
-        const double u = m_cam.f_x * pc[0] / pc[2] + m_cam.c_x, v = m_cam.f_y * pc[1] / pc[2] + m_cam.c_y;
-        if (u < 0 || v < 0 || u >= m_cam.resolution_x || v >= m_cam.resolution_y) continue;
+        double pc[3], u, v;
+        if (!project(R, kc.pose.t, X, pc, u, v)) continue;
         const double ray[3] = {X[0] - C[0], X[1] - C[1], X[2] - C[2]};
         const double dist = std::sqrt(ray[0] * ray[0] + ray[1] * ray[1] + ray[2] * ray[2]);
         if (!(dist > 0) || dist < 0.8 * lm.min_valid || dist > 1.2 * lm.max_valid) continue;
         if ((ray[0] * lm.normal[0] + ray[1] * lm.normal[1] + ray[2] * lm.normal[2]) / dist < 0.5) continue;
         const int lvl = std::min(std::max((int)std::ceil(std::log(lm.max_valid / dist) / log_sf), 0), m_numLevels - 1);
-        lpslam_hip_proj_query e{};
-        e.x = (float)u; e.y = (float)v; e.x_right = m_stereo ? (float)(u - m_cam.focal_x_baseline / pc[2]) : -1.0f;
-        e.radius = 3.0f * m_scales[lvl];                 // match::fuse: margin 3 px x scale factor of the predicted level
-        e.min_level = std::max(0, lvl - 1); e.max_level = lvl;
-        q.push_back(e);
+        // match::fuse: margin 3 px x scale factor of the predicted level
+        q.push_back(projQuery(u, v, pc[2], 3.0f * m_scales[lvl], std::max(0, lvl - 1), lvl, m_stereo));
         qd.insert(qd.end(), lm.desc, lm.desc + 32);
         q_lm.push_back(id);
     }
@@ -622,6 +568,34 @@ struct ScopedSeconds {                                   // adds the scope's wal
 };
 }  // namespace
 
+// the bundle adjuster's camera: chi-square bounds of 2 (monocular) and 3 (stereo) degrees of freedom at 95 %
+lpslam_hip_ba_camera HipVslamTrackerBase::baCamera(bool with_baseline) const
+{
+    return {m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y, with_baseline ? m_cam.focal_x_baseline : 0.0, std::sqrt(5.991), std::sqrt(7.815)};
+}
+
+void HipVslamTrackerBase::associate(const int32_t* mq, const int32_t* mt, int n, const std::vector<int>& landmark, std::vector<int>& cur_idx, std::vector<int>& lm_ids) const
+{
+    for (int k = 0; k < n; ++k) {
+        const int id = mq[k] < 0 ? -1 : resolve(landmark[(size_t)(mt ? mt[k] : k)]);
+        if (id < 0) continue;
+        cur_idx.push_back(mq[k]); lm_ids.push_back(id);
+    }
+}
+
+std::vector<float> HipVslamTrackerBase::keypointAngles(const std::vector<lpslam_hip_keypoint>& kpts)
+{
+    std::vector<float> a(kpts.size());
+    for (size_t i = 0; i < kpts.size(); ++i) a[i] = kpts[i].angle;
+    return a;
+}
+
+bool HipVslamTrackerBase::frameSizeOk(const CameraQueueEntry& cam, bool stereo) const
+{
+    return cam.image.width == m_cam.resolution_x && cam.image.height == m_cam.resolution_y &&
+           (!stereo || (cam.image_second->width == cam.image.width && cam.image_second->height == cam.image.height));
+}
+
 bool HipVslamTrackerBase::poseFromMatches(FrameData& cur, const std::vector<int>& cur_idx, const std::vector<int>& lm_ids, const Pose& init, int& n_inliers, int min_inliers)
 {
     n_inliers = 0;
@@ -643,7 +617,7 @@ bool HipVslamTrackerBase::poseFromMatches(FrameData& cur, const std::vector<int>
     }
     if (obs.size() < 10) return false;
     double pose7[7] = {init.q[0], init.q[1], init.q[2], init.q[3], init.t[0], init.t[1], init.t[2]};
-    lpslam_hip_ba_camera cam{m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y, m_cam.focal_x_baseline, std::sqrt(5.991), std::sqrt(7.815)};
+    const lpslam_hip_ba_camera cam = baCamera(true);      // (monocular too: no observation carries a right column there)
     std::vector<uint8_t> outlier(obs.size());
     int32_t inl = 0;
     // one launch: the whole 4 x 10 iteration flow runs in one workgroup on the device
@@ -664,24 +638,8 @@ bool HipVslamTrackerBase::poseFromMatches(FrameData& cur, const std::vector<int>
 bool HipVslamTrackerBase::navDelta(Pose& v) const
 {
     if (!(m_forwardNavState && m_navPrev && m_navCur)) return false;
-    // v = T_nav_cur * T_nav_prev^-1
-    const Mat3 Rc = quatToRot(m_navCur->q), Rp = quatToRot(m_navPrev->q);
-    Mat3 Rv;
-    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Rv.m[r * 3 + c] = Rc.m[r * 3] * Rp.m[c * 3] + Rc.m[r * 3 + 1] * Rp.m[c * 3 + 1] + Rc.m[r * 3 + 2] * Rp.m[c * 3 + 2];
-    rotToQuat(Rv, v.q);
-    for (int r = 0; r < 3; ++r) v.t[r] = m_navCur->t[r] - (Rv.m[r * 3] * m_navPrev->t[0] + Rv.m[r * 3 + 1] * m_navPrev->t[1] + Rv.m[r * 3 + 2] * m_navPrev->t[2]);
+    v = relative(*m_navCur, *m_navPrev);                 // T_nav_cur * T_nav_prev^-1
     return true;
-}
-
-void HipVslamTrackerBase::movePose(const Pose& v, const Pose& from, Pose& to)        // to = v * from
-{
-    double q[4];
-    quatMul(v.q, from.q, q);
-    const Mat3 Rv = quatToRot(v.q);
-    double t[3];
-    for (int r = 0; r < 3; ++r) t[r] = Rv.m[r * 3] * from.t[0] + Rv.m[r * 3 + 1] * from.t[1] + Rv.m[r * 3 + 2] * from.t[2] + v.t[r];
-    for (int k = 0; k < 4; ++k) to.q[k] = q[k];
-    for (int k = 0; k < 3; ++k) to.t[k] = t[k];
 }
 
 bool HipVslamTrackerBase::predictedPose(Pose& init) const
@@ -689,7 +647,7 @@ bool HipVslamTrackerBase::predictedPose(Pose& init) const
     Pose v;
     if (m_haveVelocity) v = m_velocity;
     else if (!navDelta(v)) return false;
-    movePose(v, m_prev.pose, init);
+    init = compose(v, m_prev.pose);
     return true;
 }
 
@@ -714,26 +672,18 @@ bool HipVslamTrackerBase::trackWithMotionModel(FrameData& cur, int& n_inliers)
         if (id < 0) continue;
         const Landmark* l = lm(id);
         if (!l) continue;
-        const double* X = l->p;
-        const double pc[3] = {R.m[0] * X[0] + R.m[1] * X[1] + R.m[2] * X[2] + init.t[0], R.m[3] * X[0] + R.m[4] * X[1] + R.m[5] * X[2] + init.t[1],
-                              R.m[6] * X[0] + R.m[7] * X[1] + R.m[8] * X[2] + init.t[2]};
-        if (!(pc[2] > 0)) continue;
-        const double u = m_cam.f_x * pc[0] / pc[2] + m_cam.c_x, v = m_cam.f_y * pc[1] / pc[2] + m_cam.c_y;
-        if (u < 0 || v < 0 || u >= m_cam.resolution_x || v >= m_cam.resolution_y) continue;
+        double pc[3], u, v;
+        if (!project(R, init.t, l->p, pc, u, v)) continue;
         const int lvl = m_prev.kpts[i].octave;
-        lpslam_hip_proj_query e{};
-        e.x = (float)u; e.y = (float)v; e.x_right = m_stereo ? (float)(u - m_cam.focal_x_baseline / pc[2]) : -1.0f;
-        e.radius = (m_stereo ? 10.0f : 20.0f) * m_scales[lvl];       // match_current_and_last_frames: margin 10 (stereo) / 20 (monocular)
-        e.min_level = std::max(0, lvl - 1); e.max_level = std::min(n_levels - 1, lvl + 1);
-        q.push_back(e);
+        // match_current_and_last_frames: margin 10 (stereo) / 20 (monocular)
+        q.push_back(projQuery(u, v, pc[2], (m_stereo ? 10.0f : 20.0f) * m_scales[lvl], std::max(0, lvl - 1), std::min(n_levels - 1, lvl + 1), m_stereo));
         qd.insert(qd.end(), m_prev.desc.begin() + 32 * (long)i, m_prev.desc.begin() + 32 * (long)(i + 1));
         q_angle.push_back(m_prev.kpts[i].angle);
         q_lm.push_back(id);
     }
     if (q.size() < 20) return false;
     std::vector<int32_t> idx(q.size()), dist(q.size());
-    std::vector<float> cur_angle(cur.kpts.size());
-    for (size_t i = 0; i < cur.kpts.size(); ++i) cur_angle[i] = cur.kpts[i].angle;
+    const std::vector<float> cur_angle = keypointAngles(cur.kpts);
     int32_t n_m = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         ScopedSeconds timed(m_stats.t_dev_match);
@@ -759,9 +709,8 @@ bool HipVslamTrackerBase::trackLocalMap(FrameData& cur, int& n_inliers)
     const int32_t n_levels = m_numLevels;
     const double log_sf = std::log((double)m_scaleFactor);
     const Mat3 R = quatToRot(cur.pose.q);
-    const double C[3] = {-(R.m[0] * cur.pose.t[0] + R.m[3] * cur.pose.t[1] + R.m[6] * cur.pose.t[2]),
-                         -(R.m[1] * cur.pose.t[0] + R.m[4] * cur.pose.t[1] + R.m[7] * cur.pose.t[2]),
-                         -(R.m[2] * cur.pose.t[0] + R.m[5] * cur.pose.t[1] + R.m[8] * cur.pose.t[2])};
+    double C[3];
+    centre(cur.pose, C);
     std::vector<uint8_t> taken(cur.kpts.size(), 0);
     IdMarks& held = m_marksA;
     held.begin((size_t)m_nextLandmarkId);
@@ -787,22 +736,15 @@ bool HipVslamTrackerBase::trackLocalMap(FrameData& cur, int& n_inliers)
             if (!lp) continue;
             Landmark& lm = *lp;
             const double* X = lm.p;
-            const double pc[3] = {R.m[0] * X[0] + R.m[1] * X[1] + R.m[2] * X[2] + cur.pose.t[0], R.m[3] * X[0] + R.m[4] * X[1] + R.m[5] * X[2] + cur.pose.t[1],
-                                  R.m[6] * X[0] + R.m[7] * X[1] + R.m[8] * X[2] + cur.pose.t[2]};
-            if (!(pc[2] > 0)) continue;
-            const double u = m_cam.f_x * pc[0] / pc[2] + m_cam.c_x, v = m_cam.f_y * pc[1] / pc[2] + m_cam.c_y;
-            if (u < 0 || v < 0 || u >= m_cam.resolution_x || v >= m_cam.resolution_y) continue;
+            double pc[3], u, v;
+            if (!project(R, cur.pose.t, X, pc, u, v)) continue;
             const double ray[3] = {X[0] - C[0], X[1] - C[1], X[2] - C[2]};
             const double dist = std::sqrt(ray[0] * ray[0] + ray[1] * ray[1] + ray[2] * ray[2]);
             if (!(dist > 0) || dist < 0.8 * lm.min_valid || dist > 1.2 * lm.max_valid) continue;           // can_observe: scale range
             if ((ray[0] * lm.normal[0] + ray[1] * lm.normal[1] + ray[2] * lm.normal[2]) / dist < 0.5) continue;    // viewing angle < 60 deg
             const int lvl = std::min(std::max((int)std::ceil(std::log(lm.max_valid / dist) / log_sf), 0), n_levels - 1);
             ++lm.n_observable;                           // in the frustum at a plausible scale: tracking expects to find it
-            lpslam_hip_proj_query e{};
-            e.x = (float)u; e.y = (float)v; e.x_right = m_stereo ? (float)(u - m_cam.focal_x_baseline / pc[2]) : -1.0f;
-            e.radius = 5.0f * m_scales[lvl];
-            e.min_level = std::max(0, lvl - 1); e.max_level = lvl;
-            q.push_back(e);
+            q.push_back(projQuery(u, v, pc[2], 5.0f * m_scales[lvl], std::max(0, lvl - 1), lvl, m_stereo));
             qd.insert(qd.end(), lm.desc, lm.desc + 32);
             q_lm.push_back(lid);
         }
@@ -839,11 +781,7 @@ bool HipVslamTrackerBase::trackAgainstPrevious(FrameData& cur, int& n_inliers)
     // HAMMING_DIST_THR_LOW = 50, Lowe ratio 0.9, mutual best
     if (lpslam_hip_get_bf_matches(m_ctx, cur.slot, m_prev.slot, 50, 0.9f, 1, mq.data(), mt.data(), md.data(), m_maxKp, &nm) != LPSLAM_HIP_OK) return false;
     std::vector<int> cur_idx, lm_ids;
-    for (int k = 0; k < nm; ++k) {
-        const int id = resolve(m_prev.landmark[(size_t)mt[k]]);
-        if (id < 0) continue;
-        cur_idx.push_back(mq[k]); lm_ids.push_back(id);
-    }
+    associate(mq.data(), mt.data(), nm, m_prev.landmark, cur_idx, lm_ids);
     Pose init = m_prev.pose;
     (void)predictedPose(init);                           // constant velocity / navigation prior, else the previous pose
     if (!poseFromMatches(cur, cur_idx, lm_ids, init, n_inliers)) return false;
@@ -1033,24 +971,22 @@ std::unique_ptr<HipVslamTrackerBase::MappingJob> HipVslamTrackerBase::prepareMap
 // runs on the mapping thread: touches the job and the GPU only
 void HipVslamTrackerBase::solveMapping(MappingJob& job) const
 {
-    lpslam_hip_ba_camera cam{m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y, m_stereo ? m_cam.focal_x_baseline : 0.0, std::sqrt(5.991), std::sqrt(7.815)};
+    const lpslam_hip_ba_camera cam = baCamera(m_stereo);
+    if (job.global) { runGlobalBundle(job, 10, cam); return; }
+    // the keyframe's window: created, solved (5 robust + 10 plain iterations around the outlier classification), read back and destroyed
+    // by one call -- which the windows of the other sessions' mapping threads join (one launch chain for all of them)
+    job.solved = lpslam_hip_ba_local_window(m_ctx, job.poses.data(), job.fixed.data(), (int32_t)job.kfs.size(), job.pts.data(), (int32_t)job.ids.size(), job.obs.data(),
+                                            (int32_t)job.obs.size(), &cam, 5, 10, job.outlier.data()) == LPSLAM_HIP_OK;
+}
+
+// a global bundle adjustment: plain robust iterations over the whole job, no outlier pass
+void HipVslamTrackerBase::runGlobalBundle(MappingJob& job, int iterations, const lpslam_hip_ba_camera& cam) const
+{
     lpslam_hip_ba* ba = nullptr;
-    if (!job.global) {
-        // the keyframe's window: created, solved (5 robust + 10 plain iterations around the outlier classification), read back and destroyed
-        // by one call -- which the windows of the other sessions' mapping threads join (one launch chain for all of them)
-        job.solved = lpslam_hip_ba_local_window(m_ctx, job.poses.data(), job.fixed.data(), (int32_t)job.kfs.size(), job.pts.data(), (int32_t)job.ids.size(), job.obs.data(),
-                                                (int32_t)job.obs.size(), &cam, 5, 10, job.outlier.data()) == LPSLAM_HIP_OK;
-        return;
-    }
     if (lpslam_hip_ba_create(m_ctx, job.poses.data(), job.fixed.data(), (int32_t)job.kfs.size(), job.pts.data(), (int32_t)job.ids.size(), job.obs.data(),
                              (int32_t)job.obs.size(), &cam, &ba) != LPSLAM_HIP_OK) return;
-    if (job.global) {
-        int32_t done = 0;
-        job.solved = lpslam_hip_ba_optimize(ba, 1, 10, nullptr, &done) == LPSLAM_HIP_OK && lpslam_hip_ba_get(ba, job.poses.data(), job.pts.data()) == LPSLAM_HIP_OK;
-    } else {
-        job.solved = lpslam_hip_ba_local(ba, 5, 10, job.outlier.data()) == LPSLAM_HIP_OK &&
-                     lpslam_hip_ba_get(ba, job.poses.data(), job.pts.data()) == LPSLAM_HIP_OK;
-    }
+    int32_t done = 0;
+    job.solved = lpslam_hip_ba_optimize(ba, 1, iterations, nullptr, &done) == LPSLAM_HIP_OK && lpslam_hip_ba_get(ba, job.poses.data(), job.pts.data()) == LPSLAM_HIP_OK;
     lpslam_hip_ba_destroy(ba);
 }
 
@@ -1109,10 +1045,7 @@ bool HipVslamTrackerBase::monoInitialize(FrameData& cur)
     std::vector<float> q_angle;
     for (size_t i = 0; i < ref.kpts.size(); ++i) {
         if (ref.kpts[i].octave > 0) continue;
-        lpslam_hip_proj_query e{};
-        e.x = m_monoPrevMatched[2 * i]; e.y = m_monoPrevMatched[2 * i + 1]; e.x_right = -1.0f; e.radius = 100.0f;
-        e.min_level = 0; e.max_level = 0;
-        q.push_back(e);
+        q.push_back(projQuery(m_monoPrevMatched[2 * i], m_monoPrevMatched[2 * i + 1], 0.0, 100.0f, 0, 0, false));
         qd.insert(qd.end(), ref.desc.begin() + 32 * (long)i, ref.desc.begin() + 32 * (long)(i + 1));
         q_ref.push_back((int)i); q_angle.push_back(ref.kpts[i].angle);
     }
@@ -1120,9 +1053,7 @@ bool HipVslamTrackerBase::monoInitialize(FrameData& cur)
     std::vector<int32_t> idx(q.size()), dist(q.size());
     int32_t n_m = 0;
     if (lpslam_hip_match_area(m_ctx, cur.slot, q.data(), qd.data(), (int32_t)q.size(), 50 /* HAMMING_DIST_THR_LOW */, 0.9f, idx.data(), dist.data(), &n_m) != LPSLAM_HIP_OK) return false;
-    std::vector<float> cur_angle(cur.kpts.size());
-    for (size_t i = 0; i < cur.kpts.size(); ++i) cur_angle[i] = cur.kpts[i].angle;
-    lpslam_hip_match_orientation_filter(q_angle.data(), cur_angle.data(), idx.data(), (int32_t)q.size(), &n_m);
+    lpslam_hip_match_orientation_filter(q_angle.data(), keypointAngles(cur.kpts).data(), idx.data(), (int32_t)q.size(), &n_m);
     if (n_m < 100) { m_haveMonoRef = false; return false; }          // too few: a new reference with the next frame
     std::vector<int32_t> matches;
     for (size_t k = 0; k < q.size(); ++k) {
@@ -1154,8 +1085,7 @@ bool HipVslamTrackerBase::monoInitialize(FrameData& cur)
     FrameData reff = ref;
     reff.pose = Pose();
     reff.landmark.assign(reff.kpts.size(), -1);
-    Mat3 Rm; std::copy(tv.R, tv.R + 9, Rm.m);
-    rotToQuat(Rm, cur.pose.q);
+    rotToQuat(tv.R, cur.pose.q);
     for (int a = 0; a < 3; ++a) cur.pose.t[a] = tv.t[a] * inv;
     cur.landmark.assign(cur.kpts.size(), -1);
     Keyframe k0, k1;
@@ -1190,15 +1120,8 @@ bool HipVslamTrackerBase::monoInitialize(FrameData& cur)
     {
         auto job = prepareBundle({i0, i1}, {});
         if (job) {
-            lpslam_hip_ba_camera cam{m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y, 0.0, std::sqrt(5.991), std::sqrt(7.815)};
-            lpslam_hip_ba* ba = nullptr;
-            if (lpslam_hip_ba_create(m_ctx, job->poses.data(), job->fixed.data(), (int32_t)job->kfs.size(), job->pts.data(), (int32_t)job->ids.size(), job->obs.data(),
-                                     (int32_t)job->obs.size(), &cam, &ba) == LPSLAM_HIP_OK) {
-                int32_t done = 0;
-                job->solved = lpslam_hip_ba_optimize(ba, 1, 20, nullptr, &done) == LPSLAM_HIP_OK && lpslam_hip_ba_get(ba, job->poses.data(), job->pts.data()) == LPSLAM_HIP_OK;
-                lpslam_hip_ba_destroy(ba);
-                if (job->solved) applyMapping(*job);
-            }
+            runGlobalBundle(*job, 20, baCamera(false));
+            if (job->solved) applyMapping(*job);
         }
     }
     cur.pose = m_kfs.back().pose;
@@ -1231,9 +1154,8 @@ void HipVslamTrackerBase::monoTriangulate(int prev_kf, Keyframe& kf, FrameData& 
     };
     double P1[12], P2[12];
     proj(R1, prev.pose.t, P1); proj(R2, f.pose.t, P2);
-    auto centre = [](const Mat3& R, const double* t, double* C) { for (int a = 0; a < 3; ++a) C[a] = -(R.m[a] * t[0] + R.m[3 + a] * t[1] + R.m[6 + a] * t[2]); };
     double C1[3], C2[3];
-    centre(R1, prev.pose.t, C1); centre(R2, f.pose.t, C2);
+    centre(prev.pose, C1); centre(f.pose, C2);
     // relative pose prev -> cur and the fundamental matrix x2^T F x1 = 0
     double R21[9], t21[3];
     for (int r = 0; r < 3; ++r) for (int c2 = 0; c2 < 3; ++c2) R21[r * 3 + c2] = R2.m[r * 3] * R1.m[c2 * 3] + R2.m[r * 3 + 1] * R1.m[c2 * 3 + 1] + R2.m[r * 3 + 2] * R1.m[c2 * 3 + 2];
@@ -1261,10 +1183,8 @@ void HipVslamTrackerBase::monoTriangulate(int prev_kf, Keyframe& kf, FrameData& 
         const double p1[2] = {k1.x, k1.y}, p2[2] = {k2.x, k2.y};
         double X[3];
         if (!triangulate_point(P1, P2, p1, p2, X)) continue;
-        const double Xc1[3] = {R1.m[0] * X[0] + R1.m[1] * X[1] + R1.m[2] * X[2] + prev.pose.t[0], R1.m[3] * X[0] + R1.m[4] * X[1] + R1.m[5] * X[2] + prev.pose.t[1],
-                               R1.m[6] * X[0] + R1.m[7] * X[1] + R1.m[8] * X[2] + prev.pose.t[2]};
-        const double Xc2[3] = {R2.m[0] * X[0] + R2.m[1] * X[1] + R2.m[2] * X[2] + f.pose.t[0], R2.m[3] * X[0] + R2.m[4] * X[1] + R2.m[5] * X[2] + f.pose.t[1],
-                               R2.m[6] * X[0] + R2.m[7] * X[1] + R2.m[8] * X[2] + f.pose.t[2]};
+        double Xc1[3], Xc2[3];
+        transform(R1, prev.pose.t, X, Xc1); transform(R2, f.pose.t, X, Xc2);
         if (!(Xc1[2] > 0) || !(Xc2[2] > 0)) continue;
         const double s1 = scales[k1.octave] * scales[k1.octave];
         const double e1x = fx * Xc1[0] / Xc1[2] + cx - k1.x, e1y = fy * Xc1[1] / Xc1[2] + cy - k1.y;
@@ -1289,32 +1209,6 @@ void HipVslamTrackerBase::monoTriangulate(int prev_kf, Keyframe& kf, FrameData& 
     (void)kf;
 }
 
-namespace {
-// SE3 as (q, t): x_c = R x_w + t
-struct Se3 { double q[4]; double t[3]; };
-Se3 se3_mul(const Se3& a, const Se3& b)            // a after b
-{
-    Se3 o;
-    quatMul(a.q, b.q, o.q);
-    const Mat3 Ra = quatToRot(a.q);
-    for (int r = 0; r < 3; ++r) o.t[r] = Ra.m[r * 3] * b.t[0] + Ra.m[r * 3 + 1] * b.t[1] + Ra.m[r * 3 + 2] * b.t[2] + a.t[r];
-    return o;
-}
-Se3 se3_inv(const Se3& a)
-{
-    Se3 o;
-    o.q[0] = a.q[0]; o.q[1] = -a.q[1]; o.q[2] = -a.q[2]; o.q[3] = -a.q[3];
-    const Mat3 R = quatToRot(a.q);
-    for (int r = 0; r < 3; ++r) o.t[r] = -(R.m[r] * a.t[0] + R.m[3 + r] * a.t[1] + R.m[6 + r] * a.t[2]);
-    return o;
-}
-void pose_centre(const double* q, const double* t, double* C)
-{
-    const Mat3 R = quatToRot(q);
-    for (int a = 0; a < 3; ++a) C[a] = -(R.m[a] * t[0] + R.m[3 + a] * t[1] + R.m[6 + a] * t[2]);
-}
-}  // namespace
-
 // ---- relocalisation ([UPSTREAM] module::relocalizer, reached while the tracker state is Lost) -----------------------------------
 // Candidates: the keyframes nearest to the last pose that was tracked (the reference picks them from the BoW database; with
 // relocWithNavigation the navigation prior moves that pose along).  Each candidate's descriptors are matched against the frame
@@ -1324,12 +1218,12 @@ bool HipVslamTrackerBase::relocalise(FrameData& cur)
 {
     if (m_kfs.empty()) return false;
     double Cl[3];
-    pose_centre(m_lastGoodPose.q, m_lastGoodPose.t, Cl);
+    centre(m_lastGoodPose, Cl);
     std::vector<std::pair<double, int>> near;
     for (size_t k = 0; k < m_kfs.size(); ++k) {
         if (m_kfs[k].erased) continue;
         double C[3];
-        pose_centre(m_kfs[k].pose.q, m_kfs[k].pose.t, C);
+        centre(m_kfs[k].pose, C);
         near.emplace_back(std::sqrt((C[0] - Cl[0]) * (C[0] - Cl[0]) + (C[1] - Cl[1]) * (C[1] - Cl[1]) + (C[2] - Cl[2]) * (C[2] - Cl[2])), (int)k);
     }
     std::sort(near.begin(), near.end());
@@ -1369,20 +1263,13 @@ bool HipVslamTrackerBase::relocalise(FrameData& cur)
             int32_t nm = 0;
             if (lpslam_hip_match_bow_tree(m_ctx, kf.desc.data(), qn.data(), (int32_t)qn.size(), cur.desc.data(), cur_node.data(), (int32_t)cur_node.size(), nullptr, 50, 0.75f,
                                           idx.data(), nullptr, &nm) != LPSLAM_HIP_OK) continue;
-            std::vector<float> aq(kf.kpts.size()), at(cur.kpts.size());
-            for (size_t i = 0; i < aq.size(); ++i) aq[i] = kf.kpts[i].angle;
-            for (size_t i = 0; i < at.size(); ++i) at[i] = cur.kpts[i].angle;
             int32_t kept = 0;
-            (void)lpslam_hip_match_orientation_filter(aq.data(), at.data(), idx.data(), (int32_t)idx.size(), &kept);
-            for (size_t i = 0; i < idx.size(); ++i) if (idx[i] >= 0) { cur_idx.push_back(idx[i]); lm_ids.push_back(resolve(kf.landmark[i])); }
+            (void)lpslam_hip_match_orientation_filter(keypointAngles(kf.kpts).data(), keypointAngles(cur.kpts).data(), idx.data(), (int32_t)idx.size(), &kept);
+            associate(idx.data(), nullptr, (int)idx.size(), kf.landmark, cur_idx, lm_ids);     // (a keypoint whose landmark is gone was no query: qn above)
         } else {
             int32_t nm = 0;
             if (lpslam_hip_match_bf_descriptors(m_ctx, cur.slot, scratch, kf.desc.data(), (int32_t)kf.kpts.size(), 50, 0.75f, 1, mq.data(), mt.data(), md.data(), m_maxKp, &nm) != LPSLAM_HIP_OK) continue;
-            for (int k = 0; k < nm; ++k) {
-                const int id = resolve(kf.landmark[(size_t)mt[k]]);
-                if (id < 0) continue;
-                cur_idx.push_back(mq[k]); lm_ids.push_back(id);
-            }
+            associate(mq.data(), mt.data(), nm, kf.landmark, cur_idx, lm_ids);
         }
         if (cur_idx.size() < 15) continue;
         // [UPSTREAM] solve::pnp_solver: the pose from the matches alone -- no prior, the camera may be anywhere that sees these
@@ -1434,12 +1321,12 @@ bool HipVslamTrackerBase::detectAndCloseLoop(FrameData& cur, int c)
     std::unordered_map<int, char> covis;
     for (int k : covisible(c, (int)m_kfs.size(), 15)) covis[k] = 1;      // the covisibility graph's neighbours (edges of weight >= 15) are no loop
     double Cc[3];
-    pose_centre(kc.pose.q, kc.pose.t, Cc);
+    centre(kc.pose, Cc);
     std::vector<std::pair<double, int>> cands;
     for (int a = 0; a <= newest_candidate; ++a) {
         if (covis.count(a) || m_kfs[(size_t)a].erased) continue;
         double C[3];
-        pose_centre(m_kfs[(size_t)a].pose.q, m_kfs[(size_t)a].pose.t, C);
+        centre(m_kfs[(size_t)a].pose, C);
         cands.emplace_back(std::sqrt((C[0] - Cc[0]) * (C[0] - Cc[0]) + (C[1] - Cc[1]) * (C[1] - Cc[1]) + (C[2] - Cc[2]) * (C[2] - Cc[2])), a);
     }
     if (cands.empty()) { m_loopSets.clear(); return false; }
@@ -1564,11 +1451,8 @@ bool HipVslamTrackerBase::detectAndCloseLoop(FrameData& cur, int c)
         if (use_bow && ka.node.size() == ka.kpts.size()) {
             if (bow_slot[ci] < 0) continue;
             std::vector<int32_t>& idx = bow_idx[(size_t)bow_slot[ci]];
-            std::vector<float> aq(kc.kpts.size()), at(ka.kpts.size());
-            for (size_t i = 0; i < aq.size(); ++i) aq[i] = kc.kpts[i].angle;
-            for (size_t i = 0; i < at.size(); ++i) at[i] = ka.kpts[i].angle;
             int32_t kept = 0;
-            (void)lpslam_hip_match_orientation_filter(aq.data(), at.data(), idx.data(), (int32_t)idx.size(), &kept);
+            (void)lpslam_hip_match_orientation_filter(keypointAngles(kc.kpts).data(), keypointAngles(ka.kpts).data(), idx.data(), (int32_t)idx.size(), &kept);
             for (size_t i = 0; i < idx.size(); ++i) if (idx[i] >= 0) { mq[(size_t)nm] = (int32_t)i; mt[(size_t)nm] = idx[i]; ++nm; }
         } else if (batched && ka.desc_on_device) {
             const size_t at = b_at++ * (size_t)m_maxKp;
@@ -1606,11 +1490,8 @@ bool HipVslamTrackerBase::detectAndCloseLoop(FrameData& cur, int c)
             const Landmark& lc = m_landmarks.at(resolve(kc.landmark[ic]));
             const Landmark& la = m_landmarks.at(resolve(ka.landmark[ia]));
             lpslam_hip_sim3_pair pr{};
-            for (int r = 0; r < 3; ++r) {
-                pr.p1c[r] = Rc.m[r * 3] * lc.p[0] + Rc.m[r * 3 + 1] * lc.p[1] + Rc.m[r * 3 + 2] * lc.p[2] + kc.pose.t[r];
-                pr.p2c[r] = Ra.m[r * 3] * la.p[0] + Ra.m[r * 3 + 1] * la.p[1] + Ra.m[r * 3 + 2] * la.p[2] + ka.pose.t[r];
-                p1[3 * n_ + (size_t)r] = pr.p1c[r]; p2[3 * n_ + (size_t)r] = pr.p2c[r];
-            }
+            transform(Rc, kc.pose.t, lc.p, pr.p1c); transform(Ra, ka.pose.t, la.p, pr.p2c);
+            std::copy(pr.p1c, pr.p1c + 3, &p1[3 * n_]); std::copy(pr.p2c, pr.p2c + 3, &p2[3 * n_]);
             pr.obs1[0] = kc.kpts[ic].x; pr.obs1[1] = kc.kpts[ic].y; pr.obs2[0] = ka.kpts[ia].x; pr.obs2[1] = ka.kpts[ia].y;
             const double s1 = m_scales[kc.kpts[ic].octave], s2 = m_scales[ka.kpts[ia].octave];
             pr.inv_sigma2_1 = 1.0 / (s1 * s1); pr.inv_sigma2_2 = 1.0 / (s2 * s2);
@@ -1642,16 +1523,15 @@ bool HipVslamTrackerBase::detectAndCloseLoop(FrameData& cur, int c)
     std::vector<double> verts(8 * (size_t)n);
     std::vector<uint8_t> fixed((size_t)n, 0);
     fixed[0] = 1;
-    std::vector<Se3> old((size_t)n);
+    std::vector<Pose> old((size_t)n);
     for (int v = 0; v < n; ++v) {
-        const Pose& p = m_kfs[(size_t)(a0 + v)].pose;
-        old[(size_t)v] = Se3{{p.q[0], p.q[1], p.q[2], p.q[3]}, {p.t[0], p.t[1], p.t[2]}};
+        const Pose& p = old[(size_t)v] = m_kfs[(size_t)(a0 + v)].pose;
         const double row[8] = {p.q[0], p.q[1], p.q[2], p.q[3], p.t[0], p.t[1], p.t[2], 1.0};
         std::copy(row, row + 8, verts.begin() + 8 * (long)v);
     }
     std::vector<lpslam_hip_sim3_edge> edges;
     for (int v = 0; v + 1 < n; ++v) {                    // consecutive keyframes: measurement = S_j S_i^-1 of the current estimates
-        const Se3 m = se3_mul(old[(size_t)v + 1], se3_inv(old[(size_t)v]));
+        const Pose m = compose(old[(size_t)v + 1], inverse(old[(size_t)v]));
         lpslam_hip_sim3_edge e{};
         e.i = v; e.j = v + 1;
         const double row[8] = {m.q[0], m.q[1], m.q[2], m.q[3], m.t[0], m.t[1], m.t[2], 1.0};
@@ -1671,27 +1551,23 @@ bool HipVslamTrackerBase::detectAndCloseLoop(FrameData& cur, int c)
     lpslam_hip_sim3_destroy(graph);
     if (!ok) return false;
     finishMapping();                                     // no window solve may be in flight while the map moves
-    std::vector<Se3> neu((size_t)n);
     std::vector<double> scale((size_t)n, 1.0);
     for (int v = 0; v < n; ++v) {
         const double* r = &verts[8 * (size_t)v];
         const double qn = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]), s = r[7] > 0 ? r[7] : 1.0;
         scale[(size_t)v] = s;                            // Sim3 (R, t, s) -> SE3 (R, t / s): camera coordinates shrink by s
-        neu[(size_t)v] = Se3{{r[0] / qn, r[1] / qn, r[2] / qn, r[3] / qn}, {r[4] / s, r[5] / s, r[6] / s}};
         Pose& p = m_kfs[(size_t)(a0 + v)].pose;
-        for (int k = 0; k < 4; ++k) p.q[k] = neu[(size_t)v].q[k];
-        for (int k = 0; k < 3; ++k) p.t[k] = neu[(size_t)v].t[k];
+        for (int k = 0; k < 4; ++k) p.q[k] = r[k] / qn;
+        for (int k = 0; k < 3; ++k) p.t[k] = r[4 + k] / s;
     }
     for (auto& kv : m_landmarks) {                       // X_new = T_ref_new^-1 (T_ref_old X)
         const int rk = kv.second.ref_kf;
         if (rk < a0 || rk > c) continue;
-        const Se3& To = old[(size_t)(rk - a0)]; const Se3 Tni = se3_inv(neu[(size_t)(rk - a0)]);
-        const Mat3 Ro = quatToRot(To.q), Rn = quatToRot(Tni.q);
-        double xc[3], xw[3];
-        const double sc = scale[(size_t)(rk - a0)];
-        for (int r = 0; r < 3; ++r) xc[r] = (Ro.m[r * 3] * kv.second.p[0] + Ro.m[r * 3 + 1] * kv.second.p[1] + Ro.m[r * 3 + 2] * kv.second.p[2] + To.t[r]) / sc;
-        for (int r = 0; r < 3; ++r) xw[r] = Rn.m[r * 3] * xc[0] + Rn.m[r * 3 + 1] * xc[1] + Rn.m[r * 3 + 2] * xc[2] + Tni.t[r];
-        for (int r = 0; r < 3; ++r) kv.second.p[r] = xw[r];
+        const Pose& To = old[(size_t)(rk - a0)]; const Pose Tni = inverse(m_kfs[(size_t)rk].pose);
+        double xc[3];
+        transform(quatToRot(To.q), To.t, kv.second.p, xc);
+        for (int r = 0; r < 3; ++r) xc[r] /= scale[(size_t)(rk - a0)];
+        transform(quatToRot(Tni.q), Tni.t, xc, kv.second.p);
     }
     cur.pose = m_kfs[(size_t)c].pose;
     // ---- the revisited structure exists twice: the landmarks of the candidate and of its covisible keyframes are searched in the
@@ -1976,8 +1852,7 @@ void HipVslamTrackerBase::prefetchFrame(CameraQueueEntry const& cam, bool stereo
     m_prefetched.valid = false;
     if (!m_ctx || !m_prefetch) return;
     if (stereo && !cam.image_second.has_value()) return;
-    if (cam.image.width != m_cam.resolution_x || cam.image.height != m_cam.resolution_y ||
-        (stereo && (cam.image_second->width != cam.image.width || cam.image_second->height != cam.image.height))) return;
+    if (!frameSizeOk(cam, stereo)) return;
     const int slot = slotOf(m_imageTracked);              // the current frame has been counted already
     if (lpslam_hip_prefetch_begin(m_ctx) != LPSLAM_HIP_OK) { logMessage(LpSlamLogLevel_Error, std::string("prefetch_begin: ") + lpslam_hip_last_error()); return; }
     m_prefetched.issued = true;       // from here on uploads / kernels may be queued on the prefetch stream, even if a later step fails
@@ -2043,8 +1918,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     std::scoped_lock lock(m_slamLock);
     if (!m_ctx) { logMessage(LpSlamLogLevel_Error, "VSLAM instance not created"); return res; }
     if (stereo && !cam.image_second.has_value()) { logMessage(LpSlamLogLevel_Error, "VSLAM stereo needs two images"); return res; }
-    if (cam.image.width != m_cam.resolution_x || cam.image.height != m_cam.resolution_y ||
-        (stereo && (cam.image_second->width != cam.image.width || cam.image_second->height != cam.image.height))) {
+    if (!frameSizeOk(cam, stereo)) {
         logMessage(LpSlamLogLevel_Error, "Image size does not match the camera configuration");
         return res;
     }
@@ -2057,14 +1931,10 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     if (navOdom && m_forwardNavState && navOdom->second.stateValid) {
         const Quaternion& ql = navOdom->second.orientation.value; const Vector3& pl = navOdom->second.position.value;
         const double qwc[4] = {ql.w, ql.y, -ql.x, ql.z};            // camera orientation in the world
-        const double Cw[3] = {pl.y, -pl.x, pl.z};
         const double nn = std::sqrt(qwc[0] * qwc[0] + qwc[1] * qwc[1] + qwc[2] * qwc[2] + qwc[3] * qwc[3]);
         if (nn > 0) {
-            Pose p;
-            p.q[0] = qwc[0] / nn; p.q[1] = -qwc[1] / nn; p.q[2] = -qwc[2] / nn; p.q[3] = -qwc[3] / nn;      // world -> camera rotation
-            const Mat3 R = quatToRot(p.q);
-            for (int r = 0; r < 3; ++r) p.t[r] = -(R.m[r * 3] * Cw[0] + R.m[r * 3 + 1] * Cw[1] + R.m[r * 3 + 2] * Cw[2]);
-            m_navCur = p;
+            const Pose cam_in_world{{qwc[0] / nn, qwc[1] / nn, qwc[2] / nn, qwc[3] / nn}, {pl.y, -pl.x, pl.z}};
+            m_navCur = inverse(cam_in_world);
         }
     }
 
@@ -2119,7 +1989,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
         // in, moved along by the navigation prior where there is one
         Pose nav_step;
         if (m_lostSinceUnset) { m_lostSince = cam.timestamp; m_lostSinceUnset = false; }
-        if (m_relocWithNavigation && navDelta(nav_step)) movePose(nav_step, m_lastGoodPose, m_lastGoodPose);
+        if (m_relocWithNavigation && navDelta(nav_step)) m_lastGoodPose = compose(nav_step, m_lastGoodPose);
         if (relocalise(cur)) {
             m_state = TrackerState::Tracking;
             ++m_stats.relocalised;
@@ -2165,12 +2035,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
             (void)lpslam_hip_frame_done(m_ctx);            // the frame's pose is final: other sessions' shared launches need not wait for this one
             for (int id : cur.landmark) if (id >= 0) { auto it = m_landmarks.find(id); if (it != m_landmarks.end()) ++it->second.n_observed; }      // inliers of the final pose optimisation
             lap(m_stats.t_local);
-            // velocity = T_cur * T_prev^-1
-            const Mat3 Rc = quatToRot(cur.pose.q), Rp = quatToRot(m_prev.pose.q);
-            Mat3 Rv;
-            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Rv.m[r * 3 + c] = Rc.m[r * 3] * Rp.m[c * 3] + Rc.m[r * 3 + 1] * Rp.m[c * 3 + 1] + Rc.m[r * 3 + 2] * Rp.m[c * 3 + 2];
-            rotToQuat(Rv, m_velocity.q);
-            for (int r = 0; r < 3; ++r) m_velocity.t[r] = cur.pose.t[r] - (Rv.m[r * 3] * m_prev.pose.t[0] + Rv.m[r * 3 + 1] * m_prev.pose.t[1] + Rv.m[r * 3 + 2] * m_prev.pose.t[2]);
+            m_velocity = relative(cur.pose, m_prev.pose);      // T_cur * T_prev^-1
             m_haveVelocity = true;
             ++m_framesSinceKeyframe;
             if (!m_localiseOnly && keyframeNeeded(inliers)) {
@@ -2420,3 +2285,17 @@ TrackerBase::ProcessImageResult HipMonoTracker::processImage(CameraQueueEntry& c
 bool HipMonoTracker::start(SensorQueue&) { return startContext(false); }
 
 }  // namespace LpSlam
+
+// ---- C shim of pose_math.h for the ctypes tests: poses as 7 doubles (q w x y z, t), rotations as 9 (row major) -------------------
+namespace {
+LpSlam::Pose pose_of(const double* p7) { return {{p7[0], p7[1], p7[2], p7[3]}, {p7[4], p7[5], p7[6]}}; }
+void pose_out(const LpSlam::Pose& p, double* p7) { std::copy(p.q, p.q + 4, p7); std::copy(p.t, p.t + 3, p7 + 4); }
+}  // namespace
+extern "C" {
+__attribute__((visibility("default"))) void lpslam_pose_compose(const double* a7, const double* b7, double* out7) { pose_out(LpSlam::compose(pose_of(a7), pose_of(b7)), out7); }
+__attribute__((visibility("default"))) void lpslam_pose_inverse(const double* a7, double* out7) { pose_out(LpSlam::inverse(pose_of(a7)), out7); }
+__attribute__((visibility("default"))) void lpslam_pose_relative(const double* a7, const double* b7, double* out7) { pose_out(LpSlam::relative(pose_of(a7), pose_of(b7)), out7); }
+__attribute__((visibility("default"))) void lpslam_pose_centre(const double* a7, double* c3) { LpSlam::centre(pose_of(a7), c3); }
+__attribute__((visibility("default"))) void lpslam_quat_to_rot(const double* q4, double* r9) { const LpSlam::Mat3 R = LpSlam::quatToRot(q4); std::copy(R.m, R.m + 9, r9); }
+__attribute__((visibility("default"))) void lpslam_rot_to_quat(const double* r9, double* q4) { LpSlam::rotToQuat(r9, q4); }
+}

@@ -9,6 +9,7 @@
 #pragma once
 #include "core.h"
 #include "bow.h"
+#include "pose_math.h"
 #include "../../include/lpslam_hip.h"
 
 #include <array>
@@ -42,7 +43,7 @@ public:
     std::array<double, 16> currentCamPose();          // T_cw, row-major 4x4 (get_current_cam_pose)
 
 protected:
-    struct Pose { double q[4] = {1, 0, 0, 0}; double t[3] = {0, 0, 0}; };   // world -> camera
+    using Pose = LpSlam::Pose;                        // world -> camera (pose_math.h)
     // laser scans (src/Trackers/OpenVSLAMStereoTracker.cpp:232-285,344-371): the latest scan waits in a one-slot buffer; a frame
     // whose ROS time is within maxLaserAge of it takes it along, with the laser's pose in the camera's lpslam frame
     struct LaserScan { std::vector<float> ranges; float range_min = 0, range_max = 0, angle_min = 0, increment = 0, range_threshold = 0; std::optional<LpSlamROSTimestamp> ros; };
@@ -110,9 +111,30 @@ protected:
     TrackerResult createTrackerResult(const Pose& pose_cw, TimeStamp timestamp) const;
     bool initializeMap(FrameData& f, const Pose& at);
     bool poseFromMatches(FrameData& cur, const std::vector<int>& cur_idx, const std::vector<int>& lm_ids, const Pose& init, int& n_inliers, int min_inliers = 10);
+    // pc = R X + t and its pinhole image (u, v): false when the point is not in front of the camera or falls outside the image
+    // (defined here, as projQuery is, so that the per-landmark loops of the query builders keep them inline)
+    bool project(const Mat3& R, const double* t, const double* X, double* pc, double& u, double& v) const
+    {
+        transform(R, t, X, pc);
+        if (!(pc[2] > 0)) return false;
+        u = m_cam.f_x * pc[0] / pc[2] + m_cam.c_x; v = m_cam.f_y * pc[1] / pc[2] + m_cam.c_y;
+        return !(u < 0 || v < 0 || u >= m_cam.resolution_x || v >= m_cam.resolution_y);
+    }
+    lpslam_hip_proj_query projQuery(double u, double v, double z, float radius, int min_level, int max_level, bool stereo) const
+    {
+        lpslam_hip_proj_query e{};
+        e.x = (float)u; e.y = (float)v; e.x_right = stereo ? (float)(u - m_cam.focal_x_baseline / z) : -1.0f;
+        e.radius = radius; e.min_level = min_level; e.max_level = max_level;
+        return e;
+    }
+    lpslam_hip_ba_camera baCamera(bool with_baseline) const;
+    // descriptor matches (mq[k]: keypoint of the frame, < 0 = none; mt[k]: keypoint of the other side, NULL = k) -> keypoint <-> landmark
+    // associations through the other side's landmark list
+    void associate(const int32_t* mq, const int32_t* mt, int n, const std::vector<int>& landmark, std::vector<int>& cur_idx, std::vector<int>& lm_ids) const;
+    static std::vector<float> keypointAngles(const std::vector<lpslam_hip_keypoint>& kpts);
+    bool frameSizeOk(const CameraQueueEntry& cam, bool stereo) const;
     bool predictedPose(Pose& init) const;
     bool navDelta(Pose& v) const;                     // motion of the navigation prior between the last two frames (world -> camera)
-    static void movePose(const Pose& v, const Pose& from, Pose& to);
     bool trackWithMotionModel(FrameData& cur, int& n_inliers);
     bool trackAgainstPrevious(FrameData& cur, int& n_inliers);
     bool trackLocalMap(FrameData& cur, int& n_inliers);
@@ -151,6 +173,7 @@ protected:
     std::unique_ptr<MappingJob> prepareMapping(int c);
     std::unique_ptr<MappingJob> prepareBundle(const std::vector<int>& free_kfs, const std::vector<int>& fixed_kfs);
     void solveMapping(MappingJob& job) const;
+    void runGlobalBundle(MappingJob& job, int iterations, const lpslam_hip_ba_camera& cam) const;      // create / optimise / get / destroy
     void applyMapping(const MappingJob& job);
     void startMapping(int c);                         // prepare + solve on the mapping thread (or inline when asyncMapping is off)
     void finishMapping();                             // wait for the mapping thread and apply its result

@@ -1,5 +1,6 @@
 // two_view.cpp -- see two_view.h
 #include "two_view.h"
+#include "pose_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -498,16 +499,6 @@ bool horn_absolute_orientation(const double* x1, const double* x2, int n, bool f
     return true;
 }
 
-// rotation matrix (row major) -> quaternion w x y z (Eigen::Quaterniond(R))
-static void rot_to_quat(const double* R, double* q)
-{
-    const double tr = R[0] + R[4] + R[8];
-    if (tr > 0) { const double s4 = std::sqrt(tr + 1.0) * 2; q[0] = 0.25 * s4; q[1] = (R[7] - R[5]) / s4; q[2] = (R[2] - R[6]) / s4; q[3] = (R[3] - R[1]) / s4; }
-    else if (R[0] > R[4] && R[0] > R[8]) { const double s4 = std::sqrt(1.0 + R[0] - R[4] - R[8]) * 2; q[0] = (R[7] - R[5]) / s4; q[1] = 0.25 * s4; q[2] = (R[1] + R[3]) / s4; q[3] = (R[2] + R[6]) / s4; }
-    else if (R[4] > R[8]) { const double s4 = std::sqrt(1.0 + R[4] - R[0] - R[8]) * 2; q[0] = (R[2] - R[6]) / s4; q[1] = (R[1] + R[3]) / s4; q[2] = 0.25 * s4; q[3] = (R[5] + R[7]) / s4; }
-    else { const double s4 = std::sqrt(1.0 + R[8] - R[0] - R[4]) * 2; q[0] = (R[3] - R[1]) / s4; q[1] = (R[2] + R[6]) / s4; q[2] = (R[5] + R[7]) / s4; q[3] = 0.25 * s4; }
-}
-
 int sim3_solve_ransac(const double* p1c, const double* p2c, const double* obs1, const double* obs2, const double* inv_sigma2_1, const double* inv_sigma2_2,
                       int n, const double* cam1, const double* cam2, bool fix_scale, int iterations, uint32_t seed, double* s12, uint8_t* inlier)
 {
@@ -539,7 +530,7 @@ int sim3_solve_ransac(const double* p1c, const double* p2c, const double* obs1, 
         if (count > best) {
             best = count;
             double q[4];
-            rot_to_quat(R, q);
+            rotToQuat(R, q);
             s12[0] = q[0]; s12[1] = q[1]; s12[2] = q[2]; s12[3] = q[3]; s12[4] = t[0]; s12[5] = t[1]; s12[6] = t[2]; s12[7] = sc;
             if (inlier) std::copy(cur.begin(), cur.end(), inlier);
         }
@@ -778,7 +769,7 @@ int pnp_solve_ransac(const double* pw, const double* obs, const double* inv_sigm
         }
     }
     double q[4];
-    rot_to_quat(bestR, q);
+    rotToQuat(bestR, q);
     for (int k = 0; k < 4; ++k) pose7[k] = q[k];
     for (int k = 0; k < 3; ++k) pose7[4 + k] = bestT[k];
     return best;
