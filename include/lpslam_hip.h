@@ -216,6 +216,39 @@ int lpslam_hip_front_end_images_adjusted(lpslam_hip_ctx* ctx, int image, const u
                                          float focal_x_baseline, float baseline, const lpslam_hip_adjust_params* params);
 int lpslam_hip_adjust_intensity_last(lpslam_hip_ctx* ctx, int image, int32_t* lo, int32_t* hi, uint32_t* hist256);
 
+/* Colour and YUV frames: the grey conversion of the reference's ingest (cv::cvtColor in src/Manager/SlamManager.cpp:1051-1063,
+ * 1190-1260) on the device, behind the upload and in front of everything else: convert, then adjust (SlamManager.cpp:114), then
+ * rectify (OpenVSLAMStereoTracker.cpp:198-213).  The arithmetic is integer and exact:
+ *   RGB8 / BGR8   3 bytes per pixel; grey = (R 4899 + G 9617 + B 1868 + 8192) >> 14, BGR8 swaps the roles of bytes 0 and 2
+ *   NV12          a width x height Y plane at `data` (rows `stride` bytes apart), then height / 2 rows of interleaved U V pairs, one
+ *                 pair per 2 x 2 block, at `chroma` (rows `chroma_stride` apart; NULL = right behind the Y plane, at
+ *                 data + stride * height, with the Y plane's stride); width and height even
+ *   UYVY          bytes U0 Y0 V0 Y1 per pixel pair, 2 width bytes per row; width even
+ *   YUV -> RGB    BT.601 limited range, chroma replicated; then the grey formula
+ *   GRAY8         1 byte per pixel: the call behaves exactly as the grey call it is the colour form of
+ * The frame is copied to page-locked staging and from there to a staging block in HBM (both per slot, up to 3 width height bytes,
+ * allocated at the first colour frame of the context: grey-only contexts pay nothing); one kernel launch -- both eyes of a frame in
+ * the same launch -- writes level 0 of the slot(s), or the raw-frame block in front of the remap.  Asynchronous, no host
+ * synchronisation, inside or outside a prefetch section; a shared front end waits for it as it waits for an adjustment.
+ * An unknown format, a null pointer, an odd width / height where the format needs an even one or a stride smaller than a row:
+ * LPSLAM_HIP_ERR_INVALID, and nothing is enqueued.
+ *   lpslam_hip_upload_pixels      the colour form of lpslam_hip_upload_image
+ *   lpslam_hip_upload_raw_pixels  the colour form of lpslam_hip_upload_raw_image (params NULL) / _adjusted (params given)
+ *   lpslam_hip_front_end_pixels   the colour form of lpslam_hip_front_end_images (params NULL) / _adjusted (params given); right NULL =
+ *                                 monocular */
+enum { LPSLAM_HIP_PIXEL_GRAY8 = 0, LPSLAM_HIP_PIXEL_RGB8 = 1, LPSLAM_HIP_PIXEL_BGR8 = 2, LPSLAM_HIP_PIXEL_NV12 = 3, LPSLAM_HIP_PIXEL_UYVY = 4 };
+typedef struct lpslam_hip_pixels {
+    const uint8_t* data;      /* first row (NV12: of the Y plane) */
+    int32_t stride;           /* bytes between rows of `data` */
+    const uint8_t* chroma;    /* NV12 only: the interleaved U V rows; NULL = data + stride * height */
+    int32_t chroma_stride;    /* NV12 only, with a non-NULL chroma: bytes between its rows */
+    int32_t format;           /* LPSLAM_HIP_PIXEL_* */
+} lpslam_hip_pixels;
+int lpslam_hip_upload_pixels(lpslam_hip_ctx* ctx, int image, const lpslam_hip_pixels* pixels);
+int lpslam_hip_upload_raw_pixels(lpslam_hip_ctx* ctx, int image, int32_t eye, const lpslam_hip_pixels* pixels, const lpslam_hip_adjust_params* params);
+int lpslam_hip_front_end_pixels(lpslam_hip_ctx* ctx, int image, const lpslam_hip_pixels* left, const lpslam_hip_pixels* right,
+                                float focal_x_baseline, float baseline, const lpslam_hip_adjust_params* params);
+
 /* Prefetch: between prefetch_begin and prefetch_end every upload / remap / extract / stereo-match call of this context is enqueued
  * on a second stream, so the front end of the NEXT frame (into image slots nothing else touches) runs on the GPU beside the
  * matching and pose optimisation of the current one; prefetch_join makes the context's main stream wait (on the device, not the

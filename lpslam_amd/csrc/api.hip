@@ -631,6 +631,7 @@ void lpslam_hip_destroy(lpslam_hip_ctx* c)
     if (c->d_fe_counters) (void)hipFree(c->d_fe_counters);
     if (c->d_done) (void)hipFree(c->d_done);
     lp_adjust_free(c);
+    lp_ingest_free(c);
     for (int i = 0; i < LPSLAM_HIP_MAX_TIMERS; ++i) { if (c->ev_begin[i]) (void)hipEventDestroy(c->ev_begin[i]); if (c->ev_end[i]) (void)hipEventDestroy(c->ev_end[i]); }
     for (void* p : c->pin_free) (void)hipHostFree(p);
     c->pin_free.clear();
@@ -838,13 +839,19 @@ static bool ensure_upload_staging(lpslam_hip_ctx* c, int image)
     if (hipEventCreateWithFlags(&c->ev_upload[(size_t)image], hipEventDisableTiming) != hipSuccess) { set_error("hipEventCreate failed"); return false; }
     return true;
 }
+// the slot's staging and upload event exist and whatever the event was last recorded behind is through (the staging may be rewritten)
+static bool await_slot_upload(lpslam_hip_ctx* c, int image)
+{
+    const bool fresh = c->h_upload.size() <= (size_t)image || !c->h_upload[(size_t)image];
+    if (!ensure_upload_staging(c, image)) return false;
+    if (!fresh && hipEventSynchronize(c->ev_upload[(size_t)image]) != hipSuccess) { set_error("hipEventSynchronize failed"); return false; }
+    return true;
+}
 static const uint8_t* stage_upload(lpslam_hip_ctx* c, int image, const uint8_t* host, int32_t stride)
 {
     const size_t w = (size_t)c->lt.w[0], h = (size_t)c->lt.h[0];
-    const bool fresh = c->h_upload.size() <= (size_t)image || !c->h_upload[(size_t)image];
-    if (!ensure_upload_staging(c, image)) return nullptr;
+    if (!await_slot_upload(c, image)) return nullptr;
     uint8_t* buf = c->h_upload[(size_t)image];
-    if (!fresh && hipEventSynchronize(c->ev_upload[(size_t)image]) != hipSuccess) { set_error("hipEventSynchronize failed"); return nullptr; }
     if ((size_t)stride == w) memcpy(buf, host, w * h);
     else for (size_t r = 0; r < h; ++r) memcpy(buf + r * w, host + r * (size_t)stride, w);
     return buf;
@@ -886,13 +893,28 @@ int lp_wait_own_uploads(lpslam_hip_ctx* c, int first, int n, hipStream_t s)
     return LPSLAM_HIP_OK;
 }
 
-extern "C" {
-
-int lpslam_hip_upload_image(lpslam_hip_ctx* c, int image, const uint8_t* host, int32_t stride)
+static lpslam_hip_pixels gray_pixels(const uint8_t* host, int32_t stride)
 {
-    int rc = check_image(c, image); if (rc) return rc;
-    if (!host || stride < c->lt.w[0]) { set_error("bad host image (stride %d < width %d)", stride, c->lt.w[0]); return LPSLAM_HIP_ERR_INVALID; }
+    lpslam_hip_pixels px{};
+    px.data = host; px.stride = stride; px.format = LPSLAM_HIP_PIXEL_GRAY8;
+    return px;
+}
+
+// One frame into a slot, arguments checked by the caller (check_image, lp_ingest_check).  A grey frame goes straight into level 0.  A
+// colour / YUV frame goes into the slot's staging block in HBM, on the same stream and behind the same event; convert_slots turns it
+// into level 0 -- a call of its own, so that both eyes of a frame are converted in ONE launch.
+static int upload_px(lpslam_hip_ctx* c, int image, const lpslam_hip_pixels* px)
+{
+    const uint8_t* host = px->data; const int32_t stride = px->stride;
     LP_HIP(hipSetDevice(c->cfg.device));
+    if (px->format != LPSLAM_HIP_PIXEL_GRAY8) {
+        if (!await_slot_upload(c, image)) return LPSLAM_HIP_ERR_DEVICE;
+        hipStream_t us = lp_upload_stream(c);
+        int rc = lp_ingest_stage(c, image, px, us); if (rc) return rc;
+        LP_HIP(hipEventRecord(c->ev_upload[(size_t)image], us));
+        if (us == c->up_stream && (size_t)image < c->up_pending.size()) c->up_pending[(size_t)image] = 1;
+        return LPSLAM_HIP_OK;
+    }
     if (c->cfg.max_images > 8) {
         // a large resident ring (bench, batch callers): the runtime's own staged copy of pageable memory moves more bytes per second
         // than a single-threaded memcpy into page-locked buffers (measured: 2571 against 2177 frames/s with uploads in the loop)
@@ -908,6 +930,46 @@ int lpslam_hip_upload_image(lpslam_hip_ctx* c, int image, const uint8_t* host, i
     LP_HIP(hipEventRecord(c->ev_upload[(size_t)image], us));
     if (us == c->up_stream && (size_t)image < c->up_pending.size()) c->up_pending[(size_t)image] = 1;
     return LPSLAM_HIP_OK;
+}
+
+// The staged colour / YUV frames among slots [first, first + n), n <= 2, converted into level 0 by one launch on the front-end stream of
+// the calling thread, behind their uploads (formats[k]: the format of slot first + k; grey slots are left alone).  As with an
+// adjustment (adjust_slots), whoever reads the slots next on another stream finds their upload events re-recorded behind the kernel;
+// so does the next upload of the slot, which rewrites the staging the kernel reads.
+static int convert_slots(lpslam_hip_ctx* c, int first, int n, const int32_t* formats)
+{
+    int images[2], m = 0; int32_t fm[2]; uint8_t* dst[2];
+    for (int k = 0; k < n && k < 2; ++k)
+        if (formats[k] != LPSLAM_HIP_PIXEL_GRAY8) { images[m] = first + k; fm[m] = formats[k]; dst[m] = c->d_pyr + (size_t)(first + k) * c->image_slab; ++m; }
+    if (!m) return LPSLAM_HIP_OK;
+    hipStream_t s = lp_fe_stream(c);
+    int rc;
+    for (int k = 0; k < m; ++k) {
+        if ((rc = lp_wait_uploads(c, images[k], 1))) return rc;
+        if ((rc = lp_wait_own_uploads(c, images[k], 1, s))) return rc;
+    }
+    if ((rc = lp_ingest_launch(c, s, m, images, fm, dst, c->lt.pitch[0]))) return rc;
+    for (int k = 0; k < m; ++k) {
+        LP_HIP(hipEventRecord(c->ev_upload[(size_t)images[k]], s));
+        if ((size_t)images[k] < c->up_pending.size()) c->up_pending[(size_t)images[k]] = 1;
+    }
+    return LPSLAM_HIP_OK;
+}
+
+extern "C" {
+
+int lpslam_hip_upload_image(lpslam_hip_ctx* c, int image, const uint8_t* host, int32_t stride)
+{
+    const lpslam_hip_pixels px = gray_pixels(host, stride);
+    return lpslam_hip_upload_pixels(c, image, &px);
+}
+
+int lpslam_hip_upload_pixels(lpslam_hip_ctx* c, int image, const lpslam_hip_pixels* px)
+{
+    int rc = check_image(c, image); if (rc) return rc;
+    if ((rc = lp_ingest_check(c, px))) return rc;
+    if ((rc = upload_px(c, image, px))) return rc;
+    return convert_slots(c, image, 1, &px->format);
 }
 
 // ---- page-locked frames and asynchronous uploads ----------------------------------------------------------------------------
@@ -1037,29 +1099,46 @@ int lpslam_hip_set_rectify_map(lpslam_hip_ctx* c, int32_t eye, const float* map_
     return LPSLAM_HIP_OK;
 }
 
-static int upload_raw_image_impl(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride, const lpslam_hip_adjust_params* adjust)
+static int upload_raw_image_impl(lpslam_hip_ctx* c, int image, int32_t eye, const lpslam_hip_pixels* px, const lpslam_hip_adjust_params* adjust)
 {
     int rc = check_image(c, image); if (rc) return rc;
     if (eye < 0 || eye > 1 || !c->d_map_xy[eye]) { set_error("no rectify map set for eye %d", eye); return LPSLAM_HIP_ERR_INVALID; }
-    if (!host || stride < c->lt.w[0]) { set_error("bad host image (stride %d < width %d)", stride, c->lt.w[0]); return LPSLAM_HIP_ERR_INVALID; }
+    if ((rc = lp_ingest_check(c, px))) return rc;
     if (adjust && (rc = lp_adjust_check(c, adjust))) return rc;
     LP_HIP(hipSetDevice(c->cfg.device));
-    // the staging buffer is reused by every upload: copy and remap are ordered on the context stream
-    const uint8_t* src = stage_upload(c, image, host, stride);
-    if (!src) return LPSLAM_HIP_ERR_DEVICE;
-    LP_HIP(hipMemcpy2DAsync(c->d_raw, c->lt.w[0], src, c->lt.w[0], c->lt.w[0], c->lt.h[0], hipMemcpyHostToDevice, lp_fe_stream(c)));
+    if (px->format != LPSLAM_HIP_PIXEL_GRAY8) {
+        // a colour / YUV frame: into the slot's staging block, converted into the raw-frame block; everything on the context stream
+        if (!await_slot_upload(c, image)) return LPSLAM_HIP_ERR_DEVICE;
+        if ((rc = lp_ingest_stage(c, image, px, lp_fe_stream(c)))) return rc;
+        if ((rc = lp_ingest_launch(c, lp_fe_stream(c), 1, &image, &px->format, &c->d_raw, c->lt.w[0]))) return rc;
+    } else {
+        // the staging buffer is reused by every upload: copy and remap are ordered on the context stream
+        const uint8_t* src = stage_upload(c, image, px->data, px->stride);
+        if (!src) return LPSLAM_HIP_ERR_DEVICE;
+        LP_HIP(hipMemcpy2DAsync(c->d_raw, c->lt.w[0], src, c->lt.w[0], c->lt.w[0], c->lt.h[0], hipMemcpyHostToDevice, lp_fe_stream(c)));
+    }
     LP_HIP(hipEventRecord(c->ev_upload[(size_t)image], lp_fe_stream(c)));
     // the raw frame is adjusted, the result remapped (the order of the reference; interpolation does not commute with the table)
     if (adjust && (rc = lp_adjust_launch(c, lp_fe_stream(c), c->d_raw, 0, c->lt.w[0], image, 1, adjust))) return rc;
     return lp_launch_remap(c, image, eye);
 }
 
-int lpslam_hip_upload_raw_image(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride) { return upload_raw_image_impl(c, image, eye, host, stride, nullptr); }
+int lpslam_hip_upload_raw_image(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride)
+{
+    const lpslam_hip_pixels px = gray_pixels(host, stride);
+    return upload_raw_image_impl(c, image, eye, &px, nullptr);
+}
+
+int lpslam_hip_upload_raw_pixels(lpslam_hip_ctx* c, int image, int32_t eye, const lpslam_hip_pixels* px, const lpslam_hip_adjust_params* adjust)
+{
+    return upload_raw_image_impl(c, image, eye, px, adjust);
+}
 
 int lpslam_hip_upload_raw_image_adjusted(lpslam_hip_ctx* c, int image, int32_t eye, const uint8_t* host, int32_t stride, const lpslam_hip_adjust_params* adjust)
 {
     if (!adjust) { set_error("null argument"); return LPSLAM_HIP_ERR_INVALID; }
-    return upload_raw_image_impl(c, image, eye, host, stride, adjust);
+    const lpslam_hip_pixels px = gray_pixels(host, stride);
+    return upload_raw_image_impl(c, image, eye, &px, adjust);
 }
 
 int lpslam_hip_remap_staged(lpslam_hip_ctx* c, int image, int32_t eye)
@@ -1378,21 +1457,24 @@ int lpslam_hip_front_end(lpslam_hip_ctx* c, int image, int32_t stereo, float fxb
 }
 
 // lpslam_hip_front_end with the frame itself: upload of the slot (stereo: the pair) + front end.
-static int front_end_images_impl(lpslam_hip_ctx* c, int image, const uint8_t* left, const uint8_t* right, int32_t stride, float fxb, float baseline,
+static int front_end_images_impl(lpslam_hip_ctx* c, int image, const lpslam_hip_pixels* left, const lpslam_hip_pixels* right, float fxb, float baseline,
                                 const lpslam_hip_adjust_params* adjust)
 {
     int rc = check_image(c, image); if (rc) return rc;
     const bool stereo = right != nullptr;
     if (stereo && (rc = check_image(c, image + 1))) return rc;
-    if (!left || stride < c->lt.w[0]) { set_error("bad host image (stride %d < width %d)", stride, c->lt.w[0]); return LPSLAM_HIP_ERR_INVALID; }
+    if ((rc = lp_ingest_check(c, left))) return rc;
+    if (stereo && (rc = lp_ingest_check(c, right))) return rc;
     if (stereo && (!(baseline > 0.f) || !(fxb > 0.f))) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
     if (adjust && (rc = lp_adjust_check(c, adjust))) return rc;
     LP_HIP(hipSetDevice(c->cfg.device));
     // the uploads are enqueued at once, by the calling thread, on the context's front-end stream -- for a session that joined a pool that
     // IS the front-end role stream the shared chain will run on: the copies of the sessions' frames proceed while the gather waits for the
     // last session, and the chain's kernels queue behind them
-    if ((rc = lpslam_hip_upload_image(c, image, left, stride))) return rc;
-    if (stereo && (rc = lpslam_hip_upload_image(c, image + 1, right, stride))) return rc;
+    if ((rc = upload_px(c, image, left))) return rc;
+    if (stereo && (rc = upload_px(c, image + 1, right))) return rc;
+    const int32_t formats[2] = {left->format, stereo ? right->format : LPSLAM_HIP_PIXEL_GRAY8};
+    if ((rc = convert_slots(c, image, stereo ? 2 : 1, formats))) return rc;      // colour / YUV eyes: one launch for both, behind the uploads
     if (adjust && (rc = adjust_slots(c, image, stereo ? 2 : 1, adjust))) return rc;      // both eyes in each of its two launches, right behind the uploads
     const int shared = lp_share_front_end(c, image, stereo ? 1 : 0, fxb, baseline);
     if (shared < 0) return -shared;
@@ -1404,14 +1486,22 @@ static int front_end_images_impl(lpslam_hip_ctx* c, int image, const uint8_t* le
 
 int lpslam_hip_front_end_images(lpslam_hip_ctx* c, int image, const uint8_t* left, const uint8_t* right, int32_t stride, float fxb, float baseline)
 {
-    return front_end_images_impl(c, image, left, right, stride, fxb, baseline, nullptr);
+    const lpslam_hip_pixels l = gray_pixels(left, stride), r = gray_pixels(right, stride);
+    return front_end_images_impl(c, image, &l, right ? &r : nullptr, fxb, baseline, nullptr);
+}
+
+int lpslam_hip_front_end_pixels(lpslam_hip_ctx* c, int image, const lpslam_hip_pixels* left, const lpslam_hip_pixels* right, float fxb, float baseline,
+                                const lpslam_hip_adjust_params* adjust)
+{
+    return front_end_images_impl(c, image, left, right, fxb, baseline, adjust);
 }
 
 int lpslam_hip_front_end_images_adjusted(lpslam_hip_ctx* c, int image, const uint8_t* left, const uint8_t* right, int32_t stride, float fxb, float baseline,
                                          const lpslam_hip_adjust_params* adjust)
 {
     if (!adjust) { set_error("null argument"); return LPSLAM_HIP_ERR_INVALID; }
-    return front_end_images_impl(c, image, left, right, stride, fxb, baseline, adjust);
+    const lpslam_hip_pixels l = gray_pixels(left, stride), r = gray_pixels(right, stride);
+    return front_end_images_impl(c, image, &l, right ? &r : nullptr, fxb, baseline, adjust);
 }
 
 // the block that holds `fields` of slot `image` once this returns (delivered ahead of time, or read back now)

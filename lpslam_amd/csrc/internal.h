@@ -200,6 +200,9 @@ struct lpslam_hip_ctx {
     uint32_t* d_adj_hist = nullptr;                // [max_images][2][256]
     int32_t* d_adj_lohi = nullptr;                 // [max_images][2]
     std::vector<uint8_t> adj_set, adj_seen;        // per slot: the set its next adjustment counts into / it has been adjusted at all
+    // colour / YUV ingest (ingest.hip): per image slot a page-locked and a device staging block of the frame as it came, made at the
+    // context's first colour frame
+    std::vector<uint8_t*> h_color, d_color;
     uint8_t* d_mask[2] = {nullptr, nullptr};       // camera masks (level-0 size, pitch = width, 0 = masked out), left / right eye; nullptr = none
     // cache of device blocks for the short-lived objects the tracker makes every frame / keyframe (bundle-adjustment problems, pose
     // optimiser and projection-matcher staging): hipMalloc / hipFree cost ~50-100 us each and a problem needs ~40 buffers
@@ -249,6 +252,13 @@ int lp_launch_remap(lpslam_hip_ctx* c, int image, int eye);
 int lp_adjust_check(lpslam_hip_ctx* c, const lpslam_hip_adjust_params* p);
 int lp_adjust_launch(lpslam_hip_ctx* c, hipStream_t s, uint8_t* base, size_t slab, int pitch, int first, int n, const lpslam_hip_adjust_params* p);
 void lp_adjust_free(lpslam_hip_ctx* c);
+// ingest.hip: argument check of a pixel descriptor; its frame staged for slot `image` and copied to the slot's device staging on stream
+// `us` (the caller has awaited the slot's previous upload); ONE launch on stream s that converts the staged frames of n <= 2 slots into
+// dst[k] (rows dst_pitch bytes apart)
+int lp_ingest_check(lpslam_hip_ctx* c, const lpslam_hip_pixels* px);
+int lp_ingest_stage(lpslam_hip_ctx* c, int image, const lpslam_hip_pixels* px, hipStream_t us);
+int lp_ingest_launch(lpslam_hip_ctx* c, hipStream_t s, int n, const int* images, const int32_t* formats, uint8_t* const* dst, int dst_pitch);
+void lp_ingest_free(lpslam_hip_ctx* c);
 int lp_launch_fast(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
 int lp_launch_distribute(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
 int lp_launch_describe(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);

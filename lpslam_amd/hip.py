@@ -47,6 +47,7 @@ SYMBOLS = [
     "lpslam_hip_jpeg_dec_create", "lpslam_hip_jpeg_dec_create2", "lpslam_hip_jpeg_dec_destroy", "lpslam_hip_jpeg_decode", "lpslam_hip_jpeg_dec_last",
     "lpslam_hip_jpeg_dec_take_restart",
     "lpslam_hip_adjust_intensity", "lpslam_hip_upload_raw_image_adjusted", "lpslam_hip_front_end_images_adjusted", "lpslam_hip_adjust_intensity_last",
+    "lpslam_hip_upload_pixels", "lpslam_hip_upload_raw_pixels", "lpslam_hip_front_end_pixels",
 ]
 
 
@@ -78,6 +79,22 @@ class AdjustParams(C.Structure):
 
     def __init__(self, low_out=-0.3, high_out=1.4, low_fraction=0.01, high_fraction=0.99):
         super().__init__(float(low_out), float(high_out), float(low_fraction), float(high_fraction))
+
+
+PIXEL_GRAY8, PIXEL_RGB8, PIXEL_BGR8, PIXEL_NV12, PIXEL_UYVY = range(5)          # LPSLAM_HIP_PIXEL_*
+
+
+class Pixels(C.Structure):
+    """lpslam_hip_pixels: one frame as it came.  `arr` (kept alive by the object) holds the bytes: (h, w) for GRAY8, (h, w, 3) for
+    RGB8 / BGR8, (h, 2 w) for UYVY, (3 h / 2, w) for NV12 (the chroma rows right behind the Y plane) -- or, with `chroma`, (h, w)
+    and an array of (h / 2, w) chroma rows of its own.  Rows may be strided (a view of a wider array)."""
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_int32), ("chroma", C.c_void_p), ("chroma_stride", C.c_int32), ("format", C.c_int32)]
+
+    def __init__(self, arr, fmt, chroma=None, stride=None):
+        assert arr.dtype == np.uint8
+        self.arr, self.chroma_arr = arr, chroma
+        super().__init__(arr.ctypes.data, int(arr.strides[0]) if stride is None else int(stride),
+                         None if chroma is None else chroma.ctypes.data, 0 if chroma is None else int(chroma.strides[0]), int(fmt))
 
 
 class BaKernelTimes(C.Structure):
@@ -209,6 +226,28 @@ class Context:
         left = np.ascontiguousarray(left); right = None if right is None else np.ascontiguousarray(right)
         p = params if params is not None else AdjustParams()
         _check(f(self.h, int(image), _p(left), None if right is None else _p(right), left.shape[1], float(fxb), float(baseline), C.byref(p)))
+
+    def front_end_pixels(self, image, left, right=None, fxb=0.0, baseline=0.0, params=None):
+        """the colour form of front_end_images / front_end_images_adjusted: left, right are Pixels (right None: monocular), params an
+        AdjustParams or None (no adjustment)"""
+        f = self.lib.lpslam_hip_front_end_pixels
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.POINTER(Pixels), C.POINTER(Pixels), C.c_float, C.c_float, C.POINTER(AdjustParams)]
+        _check(f(self.h, int(image), C.byref(left), None if right is None else C.byref(right), float(fxb), float(baseline),
+                 None if params is None else C.byref(params)))
+
+    def upload_pixels(self, image, pixels):
+        """the colour form of upload: a Pixels into a slot, converted to grey on the device"""
+        f = self.lib.lpslam_hip_upload_pixels
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.POINTER(Pixels)]
+        _check(f(self.h, int(image), C.byref(pixels)))
+        self.sync()
+
+    def upload_raw_pixels(self, image, eye, pixels, params=None):
+        """the colour form of upload_raw / upload_raw_adjusted (params an AdjustParams or None): convert, adjust, remap"""
+        f = self.lib.lpslam_hip_upload_raw_pixels
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.POINTER(Pixels), C.POINTER(AdjustParams)]
+        _check(f(self.h, int(image), int(eye), C.byref(pixels), None if params is None else C.byref(params)))
+        self.sync()
 
     def adjust_intensity(self, first, n, params=None):
         """image slots [first, first + n) adjusted in place on level 0 (asynchronous; AdjustParams, default: the reference's constants)"""

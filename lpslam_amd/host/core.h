@@ -79,12 +79,22 @@ struct IntensityAdjust {
     bool operator==(const IntensityAdjust& o) const { return low_out == o.low_out && high_out == o.high_out && low_fraction == o.low_fraction && high_fraction == o.high_fraction; }
 };
 
+// A colour or YUV frame as it came, copied at enqueue and not yet converted (ingest.h): while it is pending, the eye's GrayImage carries
+// the size and no pixels.  Whoever reads the pixels next converts it -- a HIP tracker on the device, behind the upload; everybody else
+// through realiseGray(), on the host.  The two give the same bytes.
+struct ColorSource {
+    std::vector<uint8_t> bytes;       // rows `stride` bytes apart; NV12: the Y plane, then height / 2 rows of U V pairs with the same stride
+    int format = 0;                   // LPSLAM_HIP_PIXEL_* (include/lpslam_hip.h), never GRAY8
+    size_t stride = 0;
+};
+
 struct CameraQueueEntry {
     bool valid = false;               // false = exit signal for the worker
     TimeStamp timestamp{};
     uint32_t cameraNumber = 0, cameraNumberSecond = 0;
     GrayImage image;
     std::optional<GrayImage> image_second;
+    std::optional<ColorSource> color, color_second;   // pending: `image` / `image_second` have no pixels yet
     std::optional<LpSlamROSTimestamp> ros_timestamp;
     std::optional<IntensityAdjust> adjust;            // requested, not yet applied to `image` / `image_second`
     bool processed = false;           // the manager's processors have seen this entry (a lookahead frame: before it became the current one)
@@ -150,6 +160,8 @@ public:
     // true: processImage applies a pending CameraQueueEntry::adjust itself (and leaves the entry as it is); false: the manager applies it
     // on the host before the call
     virtual bool realisesAdjust() const { return false; }
+    // true: processImage converts a pending CameraQueueEntry::color itself; false: the manager converts it on the host before the call
+    virtual bool realisesGray() const { return false; }
     virtual void addRequestNavTransformationCallback(RequestNavTransformationCallback_t, void*) {}
     virtual std::optional<unsigned long> mappingGetMapRawSize() { return std::nullopt; }
     virtual std::optional<LpMapInfo> mappingGetMapRaw(int8_t*, std::size_t) { return std::nullopt; }

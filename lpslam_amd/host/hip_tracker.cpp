@@ -590,6 +590,10 @@ std::vector<float> HipVslamTrackerBase::keypointAngles(const std::vector<lpslam_
     return a;
 }
 
+// the bytes a frame's front end uploads (its first eye's): what a prefetch is recognised by -- a colour frame converted on the host in
+// between has other bytes, and is uploaded again
+static const uint8_t* frameSource(const CameraQueueEntry& cam) { return cam.color ? cam.color->bytes.data() : cam.image.pixels.data(); }
+
 bool HipVslamTrackerBase::frameSizeOk(const CameraQueueEntry& cam, bool stereo) const
 {
     return cam.image.width == m_cam.resolution_x && cam.image.height == m_cam.resolution_y &&
@@ -1806,12 +1810,12 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
                   s.ba_failed, (long)dev[LPSLAM_HIP_BA_COUNTER_SIGNATURES], (long)dev[LPSLAM_HIP_BA_COUNTER_GRAPHS], (long)dev[LPSLAM_HIP_BA_COUNTER_REPLAYS],
-                  (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted,
+                  (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted, s.color_converted,
                   s.t_total * per, s.t_front * per, s.t_track * per, s.t_local * per, s.t_keyframe * per,
                   s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per);
     m_lastStatistics = buf;
@@ -1827,6 +1831,20 @@ bool HipVslamTrackerBase::frontEnd(CameraQueueEntry const& cam, bool stereo, int
     const bool adjust = cam.adjust.has_value();
     if (adjust) adj = lpslam_hip_adjust_params{cam.adjust->low_out, cam.adjust->high_out, cam.adjust->low_fraction, cam.adjust->high_fraction};
     const float baseline = (float)(m_cam.focal_x_baseline / m_cam.f_x);
+    if (cam.color || (stereo && cam.color_second)) {
+        // a colour / YUV frame the manager only copied: the colour forms of the same calls convert it on the device, in front of the adjustment
+        auto px = [](const GrayImage& img, const std::optional<ColorSource>& col) {
+            lpslam_hip_pixels p{};
+            if (col) { p.data = col->bytes.data(); p.stride = (int32_t)col->stride; p.format = col->format; }
+            else { p.data = img.pixels.data(); p.stride = img.width; p.format = LPSLAM_HIP_PIXEL_GRAY8; }
+            return p;
+        };
+        const lpslam_hip_pixels left = px(cam.image, cam.color), right = stereo ? px(*cam.image_second, cam.color_second) : lpslam_hip_pixels{};
+        if (!m_rectify) return lpslam_hip_front_end_pixels(m_ctx, slot, &left, stereo ? &right : nullptr, (float)m_cam.focal_x_baseline, baseline, adjust ? &adj : nullptr) == LPSLAM_HIP_OK;
+        if (lpslam_hip_upload_raw_pixels(m_ctx, slot, 0, &left, adjust ? &adj : nullptr) != LPSLAM_HIP_OK) return false;
+        if (stereo && lpslam_hip_upload_raw_pixels(m_ctx, slot + 1, 1, &right, adjust ? &adj : nullptr) != LPSLAM_HIP_OK) return false;
+        return lpslam_hip_front_end(m_ctx, slot, stereo ? 1 : 0, (float)m_cam.focal_x_baseline, baseline) == LPSLAM_HIP_OK;
+    }
     if (!m_rectify) {
         // upload, extraction, stereo match and the read-back that rides behind them: ONE call, which the frames that other sessions of the
         // process have pending join (one upload + launch chain for all of them, share.hip)
@@ -1859,7 +1877,7 @@ void HipVslamTrackerBase::prefetchFrame(CameraQueueEntry const& cam, bool stereo
     const bool ok = frontEnd(cam, stereo, slot);
     if (!ok) logMessage(LpSlamLogLevel_Error, std::string("prefetch front end: ") + lpslam_hip_last_error());
     if (lpslam_hip_prefetch_end(m_ctx) != LPSLAM_HIP_OK || !ok) return;
-    m_prefetched.valid = true; m_prefetched.data = cam.image.pixels.data(); m_prefetched.timestamp = cam.timestamp;
+    m_prefetched.valid = true; m_prefetched.data = frameSource(cam); m_prefetched.timestamp = cam.timestamp;
     m_prefetched.slot = slot; m_prefetched.stereo = stereo; m_prefetched.adjust = cam.adjust;
 }
 
@@ -1943,7 +1961,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     bool ok;
     auto t_dev = std::chrono::steady_clock::now();
     auto dev_lap = [&t_dev](double& acc) { const auto now = std::chrono::steady_clock::now(); acc += std::chrono::duration<double>(now - t_dev).count(); t_dev = now; };
-    if (m_prefetched.valid && m_prefetched.data == cam.image.pixels.data() && m_prefetched.timestamp == cam.timestamp &&
+    if (m_prefetched.valid && m_prefetched.data == frameSource(cam) && m_prefetched.timestamp == cam.timestamp &&
         m_prefetched.slot == cur.slot && m_prefetched.stereo == stereo && m_prefetched.adjust == cam.adjust) {
         // this frame's front end was started while the previous frame was tracked: the main stream waits for it on the device
         ok = lpslam_hip_prefetch_join(m_ctx) == LPSLAM_HIP_OK;
@@ -1974,6 +1992,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     dev_lap(m_stats.t_dev_get);
     ++m_imageTracked; ++m_stats.frames;
     if (cam.adjust) ++m_stats.intensity_adjusted;
+    if (cam.color || (stereo && cam.color_second)) ++m_stats.color_converted;
     // The next frame's upload + front end: a helper thread stages and enqueues it (0.2 ms of host time at 1280x720 stereo, mostly the
     // copy of the cold frame into page-locked memory) on the context's prefetch stream while this thread goes on tracking; the
     // future joins before this call returns (the frame is only valid that long) and on every early return.

@@ -95,6 +95,7 @@ protected:
         long culled_landmarks = 0, culled_keyframes = 0;
         long ba_failed = 0;                           // windows whose solve failed on the device (result dropped)
         long local_ba = 0, loops_closed = 0, loop_fused = 0, global_ba = 0, lost = 0, relocalised = 0, reinitialised = 0, nav_priors = 0, prefetched = 0;
+        long color_converted = 0;                     // frames whose colour / YUV source was converted to grey on the device
         long intensity_adjusted = 0;                  // frames whose intensity adjustment ran on the device (a request the host had applied already does not count)
         // where the frames' time went (seconds, summed): front end (upload, extraction, stereo, read-back), tracking against the
         // previous frame, local-map tracking, keyframe work on the tracking thread (insertion, fusion, loop search, BA set-up / wait)
@@ -246,6 +247,7 @@ protected:
     CameraQueueEntry const* m_nextFrame = nullptr;
     void setNextFrame(CameraQueueEntry const* next) override { m_nextFrame = next; }
     bool realisesAdjust() const override { return true; }      // a pending intensity adjustment runs on the device, inside frontEnd
+    bool realisesGray() const override { return true; }        // ... and so does a pending colour conversion, in front of it
     bool frontEnd(CameraQueueEntry const& cam, bool stereo, int slot);
     double m_lastFrameSeconds = 0;
     int m_maxKp = 0;

@@ -1,5 +1,6 @@
 // intensity.cpp -- see intensity.h.
 #include "intensity.h"
+#include "ingest.h"
 
 #include <cmath>
 
@@ -52,6 +53,7 @@ bool adjust_intensity_host(uint8_t* pixels, int width, int height, size_t stride
 void realiseAdjust(CameraQueueEntry& cam)
 {
     if (!cam.adjust) return;
+    realiseGray(cam);                   // the adjustment works on the grey image
     const IntensityAdjust p = *cam.adjust;
     cam.adjust.reset();
     if (!cam.image.empty() && !adjust_intensity_host(cam.image, p))

@@ -4,6 +4,7 @@
 #include <atomic>
 #include "../../include/lpslam_manager.h"
 #include "slam_manager.h"
+#include "ingest.h"
 #include "intensity.h"
 #include "jpeg.h"
 #include "map_file.h"
@@ -41,8 +42,8 @@ bool LpSlamManager::compressImage(uint8_t* buffer, LpSlamImageDescription desc, 
     size_t in_bytes = 4 * n;
     if (desc.format == LpSlamImageFormat_8UC1) { std::memcpy(g.pixels.data(), buffer, n); in_bytes = n; }
     else if (desc.format == LpSlamImageFormat_8UC3) {
-        const bool bgr = desc.image_conversion == LpSlamImageConversion_BGR2RGB;
-        for (size_t i = 0; i < n; ++i) g.pixels[i] = (uint8_t)((buffer[3 * i + (bgr ? 2 : 0)] * 4899 + buffer[3 * i + 1] * 9617 + buffer[3 * i + (bgr ? 0 : 2)] * 1868 + (1 << 13)) >> 14);
+        const int format = desc.image_conversion == LpSlamImageConversion_BGR2RGB ? LPSLAM_HIP_PIXEL_BGR8 : LPSLAM_HIP_PIXEL_RGB8;
+        if (!LpSlam::gray_from_pixels_host(g.pixels.data(), desc.width, g.width, g.height, buffer, 3 * (size_t)desc.width, nullptr, 0, format)) return false;
         in_bytes = 3 * n;
     } else {
         for (size_t i = 0; i < n; ++i) g.pixels[i] = (uint8_t)((buffer[4 * i] * 1868 + buffer[4 * i + 1] * 9617 + buffer[4 * i + 2] * 4899 + (1 << 13)) >> 14);
@@ -212,6 +213,27 @@ LPS_API int lpslam_adjust_intensity(uint8_t* pixels, int width, int height, size
     LpSlam::IntensityAdjust p;
     if (params) { p.low_out = params[0]; p.high_out = params[1]; p.low_fraction = params[2]; p.high_fraction = params[3]; }
     return LpSlam::adjust_intensity_host(pixels, width, height, stride, p, out_lo_hi) ? 1 : 0;
+}
+
+// the host implementation of the colour / YUV -> grey conversion (ingest.h); format: LPSLAM_HIP_PIXEL_*.  0: invalid arguments, nothing written.
+LPS_API int lpslam_gray_from_pixels(uint8_t* out, size_t out_stride, int width, int height, const uint8_t* data, size_t stride, const uint8_t* chroma,
+                                    size_t chroma_stride, int format) {
+    return LpSlam::gray_from_pixels_host(out, out_stride, width, height, data, stride, chroma, chroma_stride, format) ? 1 : 0;
+}
+// test hook: a camera-queue entry with one pending colour source (tightly packed, `format`) and, with params, a pending intensity
+// adjustment, taken through realiseGray() and realiseAdjust() as the manager's worker does for a reader of host pixels; out: width *
+// height grey bytes.  0: something stayed pending or the image has another size.
+LPS_API int lpslam_realise_entry(const uint8_t* data, size_t bytes, size_t stride, int width, int height, int format, const double* params, uint8_t* out) {
+    LpSlam::CameraQueueEntry e;
+    e.valid = true; e.image.width = width; e.image.height = height;
+    e.color.emplace();
+    e.color->bytes.assign(data, data + bytes); e.color->format = format; e.color->stride = stride;
+    if (params) { e.adjust.emplace(); e.adjust->low_out = params[0]; e.adjust->high_out = params[1]; e.adjust->low_fraction = params[2]; e.adjust->high_fraction = params[3]; }
+    LpSlam::realiseGray(e);
+    LpSlam::realiseAdjust(e);
+    if (e.color || e.adjust || e.image.pixels.size() != (size_t)width * (size_t)height) return 0;
+    std::memcpy(out, e.image.pixels.data(), e.image.pixels.size());
+    return 1;
 }
 
 LPS_API void lpslam_roundtrip_state(const LpSlamGlobalStateInTime* in, LpSlamGlobalStateInTime* out) {

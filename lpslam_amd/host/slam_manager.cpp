@@ -1,5 +1,6 @@
 // slam_manager.cpp -- see slam_manager.h.
 #include "slam_manager.h"
+#include "ingest.h"
 #include "intensity.h"
 #include "jpeg.h"
 #include "replay.h"
@@ -80,12 +81,12 @@ void SlamManager::runProcessors(CameraQueueEntry& cam)
     if (cam.processed) return;
     cam.processed = true;
     for (auto& p : m_processors) {
-        if (p->readsPixels()) realiseAdjust(cam);
+        if (p->readsPixels()) { realiseGray(cam); realiseAdjust(cam); }
         p->processImage(cam);
     }
     // somebody will need the pixels on the host anyway (the recorder, a tracker that does not adjust on its own): now, before a tracker
     // may prefetch the frame -- the prefetch then carries the adjusted pixels, and nobody rewrites a buffer an upload reads
-    if (cam.adjust && m_recorder.active()) realiseAdjust(cam);
+    if (m_recorder.active()) { realiseGray(cam); realiseAdjust(cam); }
 }
 
 bool SlamManager::addSource(std::string const& name, std::string const&)
@@ -245,23 +246,28 @@ void recycleFrame(CameraQueueEntry& e)
 {
     recycleFrameBuffer(std::move(e.image.pixels));
     if (e.image_second) recycleFrameBuffer(std::move(e.image_second->pixels));
+    if (e.color) recycleFrameBuffer(std::move(e.color->bytes));
+    if (e.color_second) recycleFrameBuffer(std::move(e.color_second->bytes));
 }
 }  // namespace
 
-static GrayImage toGray(const uint8_t* buf, const LpSlamImageDescription& d)
+// One eye of a frame into the entry: `rows` rows of `row_bytes` bytes, `src_stride` apart in the caller's buffer, copied into a pooled
+// buffer.  8UC1 is the image itself.  Every other format is only copied: the entry carries it as a pending colour source (core.h,
+// ColorSource) and whoever reads the pixels converts it -- a HIP tracker on the device, realiseGray() on the host (ingest.h).
+static void takeEye(GrayImage& g, std::optional<ColorSource>& color, const uint8_t* buf, size_t src_stride, uint32_t width, uint32_t height,
+                    const LpSlamImageDescription& d)
 {
-    GrayImage g; g.width = (int)d.width; g.height = (int)d.height;
-    const size_t n = (size_t)d.width * d.height;
-    g.pixels = takeFrameBuffer(n);
-    if (d.format == LpSlamImageFormat_8UC1) std::memcpy(g.pixels.data(), buf, n);
-    else {      // 8UC3, RGB -> grey with cv::cvtColor's fixed-point weights (R 4899, G 9617, B 1868, >> 14)
-        const bool bgr = d.image_conversion == LpSlamImageConversion_BGR2RGB;
-        for (size_t i = 0; i < n; ++i) {
-            const int r = buf[3 * i + (bgr ? 2 : 0)], gg = buf[3 * i + 1], b = buf[3 * i + (bgr ? 0 : 2)];
-            g.pixels[i] = (uint8_t)((r * 4899 + gg * 9617 + b * 1868 + (1 << 13)) >> 14);
-        }
-    }
-    return g;
+    g.width = (int)width; g.height = (int)height;
+    size_t row_bytes = width, rows = height; int format = LPSLAM_HIP_PIXEL_GRAY8;
+    if (d.format == LpSlamImageFormat_8UC3) { row_bytes = 3 * (size_t)width; format = d.image_conversion == LpSlamImageConversion_BGR2RGB ? LPSLAM_HIP_PIXEL_BGR8 : LPSLAM_HIP_PIXEL_RGB8; }
+    else if (d.format == LpSlamImageFormat_NV12) { rows = (size_t)height + height / 2; format = LPSLAM_HIP_PIXEL_NV12; }      // the Y plane, then the U V rows
+    else if (d.format == LpSlamImageFormat_YUV16) { row_bytes = 2 * (size_t)width; format = LPSLAM_HIP_PIXEL_UYVY; }
+    std::vector<uint8_t> bytes = takeFrameBuffer(row_bytes * rows);
+    if (src_stride == row_bytes) std::memcpy(bytes.data(), buf, row_bytes * rows);
+    else for (size_t y = 0; y < rows; ++y) std::memcpy(bytes.data() + y * row_bytes, buf + y * src_stride, row_bytes);
+    if (format == LPSLAM_HIP_PIXEL_GRAY8) { g.pixels = std::move(bytes); return; }
+    color.emplace();
+    color->bytes = std::move(bytes); color->format = format; color->stride = row_bytes;
 }
 
 bool SlamManager::addStereoImageFromBuffer(uint32_t cameraNumber, LpSlamTimestamp timestamp, uint8_t* left, uint8_t* right, LpSlamImageDescription desc)
@@ -275,7 +281,10 @@ bool SlamManager::addStereoImageFromBuffer(uint32_t cameraNumber, LpSlamTimestam
     CameraQueueEntry q;
     q.valid = true; q.timestamp = int64ToTimeStamp((int64_t)timestamp);
     q.cameraNumber = cameraNumber; q.cameraNumberSecond = cameraNumber + 1;
-    q.image = toGray(left, desc); q.image_second = toGray(right, desc);
+    const size_t px = (desc.format == LpSlamImageFormat_8UC3) ? 3 : 1;
+    q.image_second.emplace();
+    takeEye(q.image, q.color, left, px * desc.width, desc.width, desc.height, desc);
+    takeEye(*q.image_second, q.color_second, right, px * desc.width, desc.width, desc.height, desc);
     if (desc.hasRosTimestamp > 0) q.ros_timestamp = desc.rosTimestamp;
     m_camQueue.push(std::move(q));
     return true;
@@ -307,23 +316,43 @@ bool SlamManager::addImageFromBuffer(uint32_t cameraNumber, LpSlamTimestamp time
         m_camQueue.push(std::move(q));
         return true;
     }
+    if (desc.format == LpSlamImageFormat_NV12 || desc.format == LpSlamImageFormat_YUV16) {
+        // The VivePro / Valve Index layouts of the reference (SlamManager.cpp:1190-1260), only as Stereo_LeftTop_RightBottom: desc.height
+        // counts both eyes, each eye is a complete picture of desc.height / 2 rows (NV12: its Y plane, then its U V rows), and the second
+        // one starts at buffer + imageSize / 2.  As in the reference's NV12 branch the LOWER block is the left camera.  The reference
+        // converts a YUV16 frame and then drops it (:1234-1260 falls through); here it is enqueued like an NV12 one.
+        const bool nv12 = desc.format == LpSlamImageFormat_NV12;
+        const char* name = nv12 ? "NV12" : "YUV16";
+        if (desc.structure != LpSlamImageStructure_Stereo_LeftTop_RightBottom) { logMessage(LpSlamLogLevel_Error, std::string("Image structure not supported for ") + name); return false; }
+        const uint64_t want = nv12 ? (uint64_t)desc.width * desc.height * 3 / 2 : (uint64_t)desc.width * desc.height * 2;
+        if ((desc.width & 1) || desc.height % (nv12 ? 4 : 2) != 0 || (uint64_t)desc.imageSize != want) {
+            logMessage(LpSlamLogLevel_Error, std::string("Malformed ") + name + " frame: " + std::to_string(desc.width) + " x " + std::to_string(desc.height) + ", imageSize " + std::to_string(desc.imageSize));
+            return false;
+        }
+        const uint32_t h = desc.height / 2;
+        const size_t row = nv12 ? desc.width : 2 * (size_t)desc.width;
+        q.image_second.emplace();
+        takeEye(q.image, q.color, buffer + desc.imageSize / 2, row, desc.width, h, desc);
+        takeEye(*q.image_second, q.color_second, buffer, row, desc.width, h, desc);
+        q.cameraNumberSecond = cameraNumber + 1;
+        m_camQueue.push(std::move(q));
+        return true;
+    }
     if (desc.format != LpSlamImageFormat_8UC1 && desc.format != LpSlamImageFormat_8UC3) { logMessage(LpSlamLogLevel_Error, "Image format not supported"); return false; }
     const size_t px = (desc.format == LpSlamImageFormat_8UC3) ? 3 : 1;
-    if (desc.structure == LpSlamImageStructure_OneImage) q.image = toGray(buffer, desc);
+    if (desc.structure == LpSlamImageStructure_OneImage) takeEye(q.image, q.color, buffer, px * desc.width, desc.width, desc.height, desc);
     else if (desc.structure == LpSlamImageStructure_Stereo_LeftTop_RightBottom) {
-        LpSlamImageDescription half = desc; half.height = desc.height / 2;
-        q.image = toGray(buffer, half);
-        q.image_second = toGray(buffer + (size_t)half.height * desc.width * px, half);
+        const uint32_t h = desc.height / 2;
+        q.image_second.emplace();
+        takeEye(q.image, q.color, buffer, px * desc.width, desc.width, h, desc);
+        takeEye(*q.image_second, q.color_second, buffer + (size_t)h * desc.width * px, px * desc.width, desc.width, h, desc);
         q.cameraNumberSecond = cameraNumber + 1;
     } else if (desc.structure == LpSlamImageStructure_Stereo_LeftLeft_RightRight) {
-        // de-interleave the two halves of every row
-        LpSlamImageDescription half = desc; half.width = desc.width / 2;
-        std::vector<uint8_t> l((size_t)half.width * desc.height * px), r(l.size());
-        for (uint32_t y = 0; y < desc.height; ++y) {
-            std::memcpy(&l[(size_t)y * half.width * px], buffer + (size_t)y * desc.width * px, (size_t)half.width * px);
-            std::memcpy(&r[(size_t)y * half.width * px], buffer + ((size_t)y * desc.width + half.width) * px, (size_t)half.width * px);
-        }
-        q.image = toGray(l.data(), half); q.image_second = toGray(r.data(), half);
+        // de-interleave the two halves of every row: a row copy
+        const uint32_t w = desc.width / 2;
+        q.image_second.emplace();
+        takeEye(q.image, q.color, buffer, px * desc.width, w, desc.height, desc);
+        takeEye(*q.image_second, q.color_second, buffer + (size_t)w * px, px * desc.width, w, desc.height, desc);
         q.cameraNumberSecond = cameraNumber + 1;
     } else { logMessage(LpSlamLogLevel_Error, "Image structure not supported"); return false; }
     m_camQueue.push(std::move(q));
@@ -389,6 +418,7 @@ bool SlamManager::workerStep()
         copy.image = from.image; copy.image_second = from.image_second;
         return copy;
     };
+    if (m_pushToImageCallbackQueue) realiseGray(cam);      // the image callback is handed grey pixels: a pending colour source is converted here, on the host
     if (m_pushToImageCallbackQueue) m_imageCallbackQueue.push(callbackCopy ? std::move(*callbackCopy) : imageCallbackCopy(cam));
     runProcessors(cam);
     // one frame of lookahead, owned by this thread: if another frame is already queued the trackers learn about it, and may start
@@ -398,6 +428,7 @@ bool SlamManager::workerStep()
         CameraQueueEntry next;
         if (m_camQueue.try_pop(next)) {
             if (next.valid) {
+                if (m_pushToImageCallbackQueue) realiseGray(next);
                 if (m_pushToImageCallbackQueue && !m_processors.empty()) m_lookaheadCallbackCopy = imageCallbackCopy(next);
                 runProcessors(next);
             }
@@ -425,6 +456,7 @@ bool SlamManager::workerStep()
     }
     // the recorder gets every frame taken, before the trackers run (SlamManager.cpp:187): frames skipped for lack of odometry too
     if (m_recorder.active()) {
+        realiseGray(cam);
         realiseAdjust(cam);                             // the recorder stores the frame the trackers get (SlamManager.cpp:187 comes after :114); done by runProcessors already
         const int64_t n = m_framesTaken++;
         m_recorder.storeCameraImage(cam, odom, map, (m_writeImageFiles && n % 10 == 0) ? n : -1);
@@ -436,6 +468,7 @@ bool SlamManager::workerStep()
             ++m_framesSkipped;
             break;
         }
+        if (!tracker->realisesGray()) realiseGray(cam);
         if (!tracker->realisesAdjust()) realiseAdjust(cam);
         tracker->setNextFrame(next_frame);
         const auto t_in = std::chrono::steady_clock::now();

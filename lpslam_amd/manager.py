@@ -63,6 +63,10 @@ NAV_CB = C.CFUNCTYPE(C.c_int, ROSTimestamp, C.POINTER(GlobalStateInTime), C.POIN
 STEREO_TWO_BUFFER, FORMAT_8UC1, FORMAT_8UC3, NO_DISTORTION, ODOM_ONLY = 3, 1, 2, 3, 1
 PINHOLE, FISHEYE, OMNI = 0, 1, 2          # LpSlamCameraDistortionFunction
 ONE_IMAGE_COMPRESSED, STEREO_COMPRESSED = 4, 5          # LpSlamImageStructure
+ONE_IMAGE, STEREO_LEFT_TOP_RIGHT_BOTTOM, STEREO_LEFT_LEFT_RIGHT_RIGHT = 0, 1, 2
+FORMAT_8UC4, FORMAT_NV12, FORMAT_YUV16 = 3, 4, 5          # LpSlamImageFormat (YUV16: UYVY, two bytes per pixel)
+CONVERSION_NONE, CONVERSION_BGR2RGB = 0, 1          # LpSlamImageConversion
+PIXEL_GRAY8, PIXEL_RGB8, PIXEL_BGR8, PIXEL_NV12, PIXEL_UYVY = range(5)          # LPSLAM_HIP_PIXEL_* (include/lpslam_hip.h)
 JPEG_DECODE_DEVICE_KEY = "jpeg_decode_device"          # manager section of the configuration file: false = decode compressed frames on the host
 JPEG_DECODE_COLOR_DEVICE_KEY = "jpeg_decode_color_device"    # the same for three-component (YCbCr) streams alone; default true
 JPEG_DECODE_RESTART_DEVICE_KEY = "jpeg_decode_restart_device"    # true = streams with a restart interval go to the device too; default false
@@ -213,8 +217,19 @@ class Manager:
         f = NAV_CB(cb); self._keep.append(f)
         self.lib.lpslam_manager_request_nav_data(self.h, f, None)
 
-    def add_stereo(self, ts_ns, left, right, ros=True):
-        d = ImageDescription(STEREO_TWO_BUFFER, FORMAT_8UC1, 0, left.shape[0], left.shape[1], left.size, right.size,
+    def add_buffer(self, ts_ns, buf, width, height, fmt, structure=ONE_IMAGE, conversion=CONVERSION_NONE, image_size=None, camera=0, ros=True):
+        """addImageFromBuffer with a single-buffer frame of any format and structure: `buf` holds the bytes as the client has them
+        (Stereo_LeftTop_RightBottom: `height` counts both eyes; NV12 / YUV16: each eye a complete picture, the LOWER one the left
+        camera's); image_size: desc.imageSize (default: the buffer's size)"""
+        import numpy as np
+        buf = np.ascontiguousarray(buf, np.uint8)
+        d = ImageDescription(int(structure), int(fmt), int(conversion), int(height), int(width), buf.size if image_size is None else int(image_size), 0,
+                             1 if ros else 0, ROSTimestamp(int(ts_ns // 10**9), int(ts_ns)))
+        return bool(self.lib.lpslam_manager_add_image(self.h, camera, int(ts_ns), buf.ctypes.data, C.byref(d)))
+
+    def add_stereo(self, ts_ns, left, right, ros=True, fmt=FORMAT_8UC1, conversion=CONVERSION_NONE):
+        """two buffers: (h, w) uint8 each, or -- fmt=FORMAT_8UC3 -- (h, w, 3)"""
+        d = ImageDescription(STEREO_TWO_BUFFER, int(fmt), int(conversion), left.shape[0], left.shape[1], left.size, right.size,
                              1 if ros else 0, ROSTimestamp(int(ts_ns // 10**9), int(ts_ns)))
         return bool(self.lib.lpslam_manager_add_stereo_image(self.h, 0, int(ts_ns), left.ctypes.data, right.ctypes.data, C.byref(d)))
 
@@ -377,6 +392,44 @@ def adjust_intensity(img, low_out=-0.3, high_out=1.4, low_fraction=0.01, high_fr
     if padding is not None:
         padding.append(buf.reshape(h, stride)[:, w:].copy())
     return rows.copy(), int(lo_hi[0]), int(lo_hi[1])
+
+
+def gray_from_pixels(data, width, height, fmt, stride=None, chroma=None, chroma_stride=0, padding=None, out_stride=None):
+    """the host implementation of the colour / YUV -> grey conversion (lpslam_gray_from_pixels), CPU only: `data` is a uint8 array
+    that holds the frame (rows `stride` bytes apart, default: tightly packed), fmt a PIXEL_* constant; returns the (height, width) grey
+    image, or None when the library rejects the arguments.  padding: a list that receives the bytes between the output rows (0xA5)"""
+    import numpy as np
+    data = np.ascontiguousarray(data, np.uint8)
+    row = {PIXEL_GRAY8: width, PIXEL_RGB8: 3 * width, PIXEL_BGR8: 3 * width, PIXEL_NV12: width, PIXEL_UYVY: 2 * width}.get(fmt, width)
+    stride = row if stride is None else int(stride)
+    ostride = width if out_stride is None else int(out_stride)
+    out = np.full(height * ostride, 0xA5, np.uint8)
+    f = load().lpslam_gray_from_pixels
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]
+    ch = None if chroma is None else np.ascontiguousarray(chroma, np.uint8)
+    if not f(out.ctypes.data, ostride, int(width), int(height), data.ctypes.data, stride, None if ch is None else ch.ctypes.data, int(chroma_stride), int(fmt)):
+        return None
+    out = out.reshape(height, ostride)
+    if padding is not None:
+        padding.append(out[:, width:].copy())
+    return out[:, :width].copy()
+
+
+def realise_entry(data, width, height, fmt, adjust=None):
+    """test hook (lpslam_realise_entry): a queue entry with `data` as its pending colour source (tightly packed) and, with
+    adjust = (low_out, high_out, low_fraction, high_fraction), a pending intensity adjustment, through realiseGray + realiseAdjust"""
+    import numpy as np
+    data = np.ascontiguousarray(data, np.uint8)
+    row = {PIXEL_RGB8: 3 * width, PIXEL_BGR8: 3 * width, PIXEL_NV12: width, PIXEL_UYVY: 2 * width}[fmt]
+    out = np.zeros((height, width), np.uint8)
+    f = load().lpslam_realise_entry
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]
+    params = None if adjust is None else (C.c_double * 4)(*[float(v) for v in adjust])
+    if not f(data.ctypes.data, data.size, row, int(width), int(height), int(fmt), params, out.ctypes.data):
+        return None
+    return out
 
 
 def laser_state(R, t):
