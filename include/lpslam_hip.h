@@ -276,6 +276,33 @@ int lpslam_hip_stage_fast(lpslam_hip_ctx* ctx, int n_images);
 int lpslam_hip_stage_distribute(lpslam_hip_ctx* ctx, int n_images);
 int lpslam_hip_stage_describe(lpslam_hip_ctx* ctx, int n_images);
 
+/* ---- fisheye keypoints (monocular tracker) ---------------------------------------------------------------- */
+/* The equidistant camera model of a monocular session: the reference hands Camera.model = fisheye with k1 .. k4 to its tracker
+ * (src/Trackers/OpenVSLAMTrackerBase.cpp:170-175), which undistorts every keypoint ([UPSTREAM] camera::fisheye::undistort_keypoints =
+ * cv::fisheye::undistortPoints with R = I, P = K) and works in undistorted pinhole coordinates from there on.  max_angle in radians:
+ * a keypoint whose ray lies further from the axis, or beyond 90 degrees, or whose iteration did not converge, is REMOVED
+ * (lpslam_amd/csrc/fisheye_math.h holds the definition, DESIGN.md section 30 the reasons). */
+typedef struct lpslam_hip_fisheye {
+    double fx, fy, cx, cy;
+    double k[4];
+    double max_angle;
+} lpslam_hip_fisheye;
+/* Sets (NULL: clears) the model of every image slot of the context; synchronises the device.  Non-finite values, fx or fy <= 0, or
+ * max_angle outside (0, 89 degrees]: LPSLAM_HIP_ERR_INVALID and the context keeps what it had.  With a model set, lpslam_hip_extract,
+ * lpslam_hip_extract_range and every lpslam_hip_front_end call run the stage below after the descriptors; lpslam_hip_match_stereo and
+ * lpslam_hip_match_stereo_strided answer LPSLAM_HIP_ERR_INVALID (stereo frames are rectified: the stereo tracker sets no model). */
+int lpslam_hip_set_keypoint_camera(lpslam_hip_ctx* ctx, const lpslam_hip_fisheye* model);
+/* The fifth stage, beside the four above, for image slots [0, n_images): x, y of every keypoint become the undistorted position,
+ * invalid keypoints are removed from the keypoint and the descriptor array together (survivors keep their order, every other field
+ * its bits) and the slot's count is rewritten.  Without a model: LPSLAM_HIP_OK, nothing is launched. */
+int lpslam_hip_stage_undistort(lpslam_hip_ctx* ctx, int n_images);
+/* How many keypoints the last run of that stage removed from slot `image` (0 when it has not run); call it once the slot's frame has
+ * been collected.  Synchronising. */
+int lpslam_hip_undistort_dropped(lpslam_hip_ctx* ctx, int image, int32_t* dropped);
+/* The stage's arithmetic on caller points (host memory): xy = n pairs in, xy_out = n pairs out, valid = n bytes (1 / 0; the pair of
+ * an invalid point is left as NaN).  The same device function, no compaction.  Synchronising. */
+int lpslam_hip_undistort_points(lpslam_hip_ctx* ctx, const lpslam_hip_fisheye* model, const float* xy, int32_t n, float* xy_out, uint8_t* valid);
+
 /* Synchronising readbacks (device -> caller memory). */
 int lpslam_hip_keypoint_count(lpslam_hip_ctx* ctx, int image, int32_t* count);
 int lpslam_hip_get_keypoints(lpslam_hip_ctx* ctx, int image, lpslam_hip_keypoint* kpts, uint8_t* desc32,

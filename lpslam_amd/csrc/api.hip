@@ -1,6 +1,7 @@
 // api.hip -- C ABI of the lpslam HIP library: context life cycle, geometry tables, frame upload, stage launches and
 // readbacks.  Declarations and the reference interfaces they replace: include/lpslam_hip.h.
 #include "internal.h"
+#include "fisheye_math.h"
 #include <cstring>
 #include <vector>
 #include <cmath>
@@ -368,8 +369,20 @@ static int ctx_alloc(lpslam_hip_ctx* c)
         LP_HIP(hipMemsetAsync(c->d_kp_count, 0, B * sizeof(int32_t), c->stream));
         LP_HIP(hipMemsetAsync(c->d_sel_count, 0, B * L * sizeof(int32_t), c->stream));
         LP_HIP(hipMemsetAsync(c->d_cand_count, 0, B * L * sizeof(int32_t), c->stream));
+        // the slots may have belonged to a fisheye session that left: no model until this one sets its own
+        if (p->d_fe_model) {
+            LP_HIP(hipMemsetAsync(p->d_fe_model + f, 0, B * sizeof(LpFisheyeEntry), c->stream));
+            LP_HIP(hipMemsetAsync(p->d_fe_dropped + f, 0, B * sizeof(int32_t), c->stream));
+            std::lock_guard<std::mutex> lock(c->sess_pool->pool_mutex);
+            for (size_t i = f; i < f + B && i < c->sess_pool->fe_model_on.size(); ++i) c->sess_pool->fe_model_on[i] = 0;
+        }
         return LPSLAM_HIP_OK;
     }
+    LP_HIP(hipMalloc((void**)&c->d_fe_model, B * sizeof(LpFisheyeEntry)));
+    LP_HIP(hipMalloc((void**)&c->d_fe_dropped, B * sizeof(int32_t)));
+    LP_HIP(hipMemsetAsync(c->d_fe_model, 0, B * sizeof(LpFisheyeEntry), c->stream));
+    LP_HIP(hipMemsetAsync(c->d_fe_dropped, 0, B * sizeof(int32_t), c->stream));
+    c->fe_model_on.assign(B, 0);
     LP_HIP(hipMalloc((void**)&c->d_pyr, B * c->image_slab));
     LP_HIP(hipMemsetAsync(c->d_pyr, 0, B * c->image_slab, c->stream));
     LP_HIP(hipMalloc((void**)&c->d_cell_keys, B * c->cells_per_image * kCellSlots * sizeof(uint32_t)));
@@ -625,7 +638,7 @@ void lpslam_hip_destroy(lpslam_hip_ctx* c)
     void* bufs[] = {c->d_pyr, c->d_band_rows, c->d_rs_pack, c->d_cell_keys, c->d_cell_count, c->d_cand_key, c->d_cand_node,
                     c->d_cand_count, c->d_sel_key, c->d_sel_count, c->d_kpts, c->d_desc,
                     c->d_kp_count, c->d_bf, c->d_stereo, c->d_stereo_idx, c->d_stereo_corr, c->d_st_row_start, c->d_st_row_list, c->d_tmp_desc, c->d_tmp_res,
-                    c->d_map_xy[0], c->d_map_xy[1], c->d_map_frac[0], c->d_map_frac[1], c->d_raw, c->d_mask[0], c->d_mask[1]};
+                    c->d_map_xy[0], c->d_map_xy[1], c->d_map_frac[0], c->d_map_frac[1], c->d_raw, c->d_mask[0], c->d_mask[1], c->d_fe_model, c->d_fe_dropped};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (c->d_cu_table) (void)hipFree(c->d_cu_table);
     if (c->d_fe_counters) (void)hipFree(c->d_fe_counters);
@@ -1199,7 +1212,76 @@ int lpslam_hip_extract_range(lpslam_hip_ctx* c, int first, int n)
     if ((rc = lp_launch_pyramid(c, first, n))) return rc;
     if ((rc = lp_launch_fast(c, first, n))) return rc;
     if ((rc = lp_launch_distribute(c, first, n))) return rc;
-    return lp_launch_describe(c, first, n);
+    if ((rc = lp_launch_describe(c, first, n))) return rc;
+    return c->has_fisheye ? lp_launch_undistort(c, first, n) : LPSLAM_HIP_OK;
+}
+
+// ---- fisheye keypoints (frontend.hip: k_undistort_compact; the definition is fisheye_math.h) --------------------------------
+static bool fisheye_entry(const lpslam_hip_fisheye* m, LpFisheyeEntry* e)
+{
+    const lpslam_fisheye::Model mm{m->fx, m->fy, m->cx, m->cy, {m->k[0], m->k[1], m->k[2], m->k[3]}, m->max_angle};
+    if (!lpslam_fisheye::model_ok(mm)) { set_error("fisheye model: values must be finite, fx and fy positive, max_angle in (0, 89 degrees]"); return false; }
+    *e = LpFisheyeEntry{m->fx, m->fy, m->cx, m->cy, {m->k[0], m->k[1], m->k[2], m->k[3]}, m->max_angle, 1, 0};
+    return true;
+}
+
+int lpslam_hip_set_keypoint_camera(lpslam_hip_ctx* c, const lpslam_hip_fisheye* model)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    LpFisheyeEntry e{};
+    if (model && !fisheye_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
+    LP_HIP(hipSetDevice(c->cfg.device));
+    lpslam_hip_ctx* const o = lp_slot_owner(c);
+    const size_t off = c->sess_pool ? (size_t)c->pool_first : 0, B = (size_t)c->cfg.max_images;
+    if (!o->d_fe_model || off + B > o->fe_model_on.size()) { set_error("set_keypoint_camera: the context has no model table"); return LPSLAM_HIP_ERR_DEVICE; }
+    // a launch that reads the entries may be in flight on any stream of the device (a session's chain runs on its pool's): all of it first
+    LP_HIP(hipDeviceSynchronize());
+    const std::vector<LpFisheyeEntry> entries(B, e);
+    LP_HIP(hipMemcpy(o->d_fe_model + off, entries.data(), B * sizeof(LpFisheyeEntry), hipMemcpyHostToDevice));
+    LP_HIP(hipMemset(o->d_fe_dropped + off, 0, B * sizeof(int32_t)));
+    LP_HIP(hipDeviceSynchronize());
+    {
+        std::lock_guard<std::mutex> lock(o->pool_mutex);
+        for (size_t i = off; i < off + B; ++i) o->fe_model_on[i] = model ? 1 : 0;
+    }
+    c->has_fisheye = model != nullptr;
+    return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_stage_undistort(lpslam_hip_ctx* c, int n) { int rc = check_batch(c, n); return rc ? rc : lp_launch_undistort(c, 0, n); }
+
+int lpslam_hip_undistort_dropped(lpslam_hip_ctx* c, int image, int32_t* dropped)
+{
+    int rc = check_image(c, image); if (rc) return rc;
+    if (!dropped) { set_error("null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    *dropped = 0;
+    if (!c->has_fisheye) return LPSLAM_HIP_OK;
+    LP_HIP(hipSetDevice(c->cfg.device));
+    LP_HIP(hipMemcpy(dropped, lp_slot_owner(c)->d_fe_dropped + (c->sess_pool ? c->pool_first : 0) + image, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_undistort_points(lpslam_hip_ctx* c, const lpslam_hip_fisheye* model, const float* xy, int32_t n, float* xy_out, uint8_t* valid)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    if (!model || n < 0 || (n && (!xy || !xy_out || !valid))) { set_error("undistort_points: null argument or negative count"); return LPSLAM_HIP_ERR_INVALID; }
+    LpFisheyeEntry e{};
+    if (!fisheye_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
+    if (n == 0) return LPSLAM_HIP_OK;
+    LP_HIP(hipSetDevice(c->cfg.device));
+    // one block of the cache: points in | points out | flags
+    const size_t pts = (size_t)n * 2 * sizeof(float);
+    LpPoolBlock blk(c);
+    if (int rc = blk.alloc(2 * pts + (size_t)n)) return rc;
+    float* d_in = (float*)blk.ptr; float* d_out = d_in + 2 * (size_t)n; uint8_t* d_valid = (uint8_t*)(d_out + 2 * (size_t)n);
+    hipStream_t s = c->stream;
+    LP_HIP(hipMemcpyAsync(d_in, xy, pts, hipMemcpyHostToDevice, s));
+    if (int rc = lp_launch_undistort_points(c, e, d_in, n, d_out, d_valid, s)) return rc;
+    LP_HIP(hipMemcpyAsync(xy_out, d_out, pts, hipMemcpyDeviceToHost, s));
+    LP_HIP(hipMemcpyAsync(valid, d_valid, (size_t)n, hipMemcpyDeviceToHost, s));
+    const hipError_t err = hipStreamSynchronize(s);
+    if (err != hipSuccess) { blk.leak(); return hip_fail(err, "undistort_points"); }
+    return LPSLAM_HIP_OK;
 }
 
 int lpslam_hip_extract(lpslam_hip_ctx* c, int n) { return lpslam_hip_extract_range(c, 0, n); }
@@ -1446,6 +1528,7 @@ int lpslam_hip_front_end(lpslam_hip_ctx* c, int image, int32_t stereo, float fxb
 {
     int rc = check_image(c, image); if (rc) return rc;
     if (stereo && (rc = check_image(c, image + 1))) return rc;
+    if (stereo && c->has_fisheye) { set_error("stereo front end on a context with a fisheye keypoint camera (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
     if (stereo && (!(baseline > 0.f) || !(fxb > 0.f))) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
     LP_HIP(hipSetDevice(c->cfg.device));
     const int shared = lp_share_front_end(c, image, stereo ? 1 : 0, fxb, baseline);
@@ -1465,6 +1548,7 @@ static int front_end_images_impl(lpslam_hip_ctx* c, int image, const lpslam_hip_
     if (stereo && (rc = check_image(c, image + 1))) return rc;
     if ((rc = lp_ingest_check(c, left))) return rc;
     if (stereo && (rc = lp_ingest_check(c, right))) return rc;
+    if (stereo && c->has_fisheye) { set_error("stereo front end on a context with a fisheye keypoint camera (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
     if (stereo && (!(baseline > 0.f) || !(fxb > 0.f))) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
     if (adjust && (rc = lp_adjust_check(c, adjust))) return rc;
     LP_HIP(hipSetDevice(c->cfg.device));

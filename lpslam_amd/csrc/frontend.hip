@@ -10,6 +10,7 @@
 // Layout in HBM: one slab per image holding all pyramid levels (row pitch = width rounded up to 64 B), images of a
 // batch back to back; FAST results in fixed 1024-entry slots per 64x64 cell; keypoints/descriptors per image.
 #include "internal.h"
+#include "fisheye_math.h"
 
 #pragma clang fp contract(off)
 
@@ -1167,6 +1168,74 @@ __global__ __launch_bounds__(256) void k_remap(const uint8_t* __restrict__ raw, 
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// K5: fisheye keypoints.  The monocular tracker of the reference undistorts every keypoint of a fisheye camera
+// and works in undistorted pinhole coordinates (src/Trackers/OpenVSLAMTrackerBase.cpp:170-175 hands the model over; [UPSTREAM]
+// camera::fisheye::undistort_keypoints).  Here: x, y of every keypoint of a slot with a model become the undistorted position
+// (fisheye_math.h, FP64), keypoints without one are removed by a STABLE compaction of keypoints and descriptors in place, and the
+// slot's count is rewritten -- whatever reads the slot afterwards (window matchers, read-back, delivery, descriptor stores) sees a
+// dense slot in undistorted coordinates.
+// One 1024-thread workgroup per image, chunks of 1024 slots in index order.  Per chunk a thread loads its keypoint (7 words) and
+// descriptor (8 words) into registers and evaluates the point; ballot + popcount give its rank inside the wave, the 16 wave totals
+// go through LDS; then ONE barrier, then the stores.  The barrier is what makes "in place" safe: a destination index never exceeds its
+// source index, but inside a chunk it may be another lane's source -- every load of the chunk is complete before any store of it.
+// Destinations of a chunk lie below the chunk's first slot, so later chunks' sources are never touched; the wave totals are double
+// buffered by chunk parity (a wave two chunks ahead has passed the barrier every reader of the buffer it overwrites arrived at).
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_undistort_compact(const LpFisheyeEntry* __restrict__ models, lpslam_hip_keypoint* kpts, uint8_t* desc,
+                                                            int32_t* kp_count, int32_t* __restrict__ dropped, int slots_per_image, ImgSel image0)
+{
+    const int image = lp_image(image0, blockIdx.x);
+    const LpFisheyeEntry e = models[image];
+    if (!e.on) return;                                   // (uniform: the whole workgroup leaves)
+    __shared__ int wave_total[2][16];
+    const lpslam_fisheye::Model m{e.fx, e.fy, e.cx, e.cy, {e.k[0], e.k[1], e.k[2], e.k[3]}, e.max_angle};
+    const int n = min(max(kp_count[image], 0), slots_per_image);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t* const kw = reinterpret_cast<uint32_t*>(kpts + (size_t)image * slots_per_image);
+    uint4* const dw = reinterpret_cast<uint4*>(desc + (size_t)image * slots_per_image * 32);
+    int base = 0;
+    for (int c0 = 0, chunk = 0; c0 < n; c0 += 1024, ++chunk) {
+        const int i = c0 + tid;
+        uint32_t k[7] = {0, 0, 0, 0, 0, 0, 0};
+        uint4 d0 = make_uint4(0, 0, 0, 0), d1 = d0;
+        bool valid = false;
+        if (i < n) {
+#pragma unroll
+            for (int q = 0; q < 7; ++q) k[q] = kw[(size_t)i * 7 + q];
+            d0 = dw[(size_t)i * 2]; d1 = dw[(size_t)i * 2 + 1];
+            float ux, uy;
+            valid = lpslam_fisheye::undistort(m, (double)__uint_as_float(k[0]), (double)__uint_as_float(k[1]), &ux, &uy);
+            if (valid) { k[0] = __float_as_uint(ux); k[1] = __float_as_uint(uy); }
+        }
+        const unsigned long long b = __ballot(valid);
+        if (lane == 0) wave_total[chunk & 1][wave] = __popcll(b);
+        __syncthreads();                                 // the chunk's loads are in registers, its wave totals in LDS
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) { const int t = wave_total[chunk & 1][w]; total += t; if (w < wave) before += t; }
+        if (valid) {
+            const int dst = base + before + __popcll(b & ((1ull << lane) - 1ull));      // <= i
+#pragma unroll
+            for (int q = 0; q < 7; ++q) kw[(size_t)dst * 7 + q] = k[q];
+            dw[(size_t)dst * 2] = d0; dw[(size_t)dst * 2 + 1] = d1;
+        }
+        base += total;
+    }
+    if (tid == 0) { kp_count[image] = base; dropped[image] = n - base; }      // (every thread read the count before the first barrier; n == 0: the same value)
+}
+
+// the same device function on caller points, no compaction (lpslam_hip_undistort_points)
+__global__ __launch_bounds__(256) void k_undistort_points(LpFisheyeEntry e, const float* __restrict__ xy, int n, float* __restrict__ xy_out, uint8_t* __restrict__ valid)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const lpslam_fisheye::Model m{e.fx, e.fy, e.cx, e.cy, {e.k[0], e.k[1], e.k[2], e.k[3]}, e.max_angle};
+    float ux = __uint_as_float(0x7fc00000u), uy = ux;
+    const bool ok = lpslam_fisheye::undistort(m, (double)xy[2 * (size_t)i], (double)xy[2 * (size_t)i + 1], &ux, &uy);
+    xy_out[2 * (size_t)i] = ux; xy_out[2 * (size_t)i + 1] = uy; valid[i] = ok ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------------------
 // the queue of one extraction launch under a mapping reserve (its counter zeroed on the stream in front of the launch); without a
@@ -1325,6 +1394,36 @@ int lp_launch_describe(lpslam_hip_ctx* c, int first, int n_images, const uint16_
     else
         hipLaunchKernelGGL(k_describe, dim3(blocks, n_images), dim3(64 * DESC_WAVES), 0, lp_fe_stream(c), c->d_pyr, c->image_slab, c->lt, c->d_sel_key,
                            c->d_sel_count, c->slots_per_image, c->d_kpts, c->d_desc, c->d_kp_count, sel);
+    LP_HIP(hipGetLastError());
+    return LPSLAM_HIP_OK;
+}
+
+int lp_launch_undistort(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list)
+{
+    if (n_images <= 0) return LPSLAM_HIP_OK;
+    lpslam_hip_ctx* const o = lp_slot_owner(c);
+    const int off = c->sess_pool ? c->pool_first : 0;    // the owner's number of this context's slot 0
+    bool any = false;
+    {
+        std::lock_guard<std::mutex> lock(o->pool_mutex);
+        for (int k = 0; k < n_images && !any; ++k) { const size_t i = (size_t)(off + (list ? (int)list[k] : first + k)); any = i < o->fe_model_on.size() && o->fe_model_on[i]; }
+    }
+    if (!any || !o->d_fe_model) return LPSLAM_HIP_OK;    // grey and pinhole sessions: nothing is enqueued
+    if (!list) {
+        for (int i = first; i < first + n_images && (size_t)i < c->h_kp_valid.size(); ++i) c->h_kp_valid[(size_t)i] = 0;      // counts are rewritten
+        lp_pf_invalidate(c, first, n_images);
+    }
+    // one small workgroup per image: no queued (FeQueue) form -- under a mapping reserve it may land on a reserved compute unit for its few microseconds
+    hipLaunchKernelGGL(k_undistort_compact, dim3(n_images), dim3(1024), 0, lp_fe_stream(c), o->d_fe_model + off, c->d_kpts, c->d_desc, c->d_kp_count,
+                       o->d_fe_dropped + off, c->slots_per_image, lp_img_sel(first, n_images, list));
+    LP_HIP(hipGetLastError());
+    return LPSLAM_HIP_OK;
+}
+
+int lp_launch_undistort_points(lpslam_hip_ctx* c, const LpFisheyeEntry& e, const float* d_xy, int n, float* d_out, uint8_t* d_valid, hipStream_t s)
+{
+    if (n <= 0) return LPSLAM_HIP_OK;
+    hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, s, e, d_xy, n, d_out, d_valid);
     LP_HIP(hipGetLastError());
     return LPSLAM_HIP_OK;
 }

@@ -400,7 +400,8 @@ void combine_front(Share& sh)
         }
         const int64_t t_copied = now_ns();
         ok = ok && lp_launch_pyramid(pool, 0, n, list) == LPSLAM_HIP_OK && lp_launch_fast(pool, 0, n, list) == LPSLAM_HIP_OK &&
-             lp_launch_distribute(pool, 0, n, list) == LPSLAM_HIP_OK && lp_launch_describe(pool, 0, n, list) == LPSLAM_HIP_OK;
+             lp_launch_distribute(pool, 0, n, list) == LPSLAM_HIP_OK && lp_launch_describe(pool, 0, n, list) == LPSLAM_HIP_OK &&
+             lp_launch_undistort(pool, 0, n, list) == LPSLAM_HIP_OK;      // (launches only when a listed slot has a fisheye model: its table is the pool's)
         if (ok && reqs[i0].stereo) ok = lp_launch_stereo_strided(pool, 0, 0, 0, n / 2, reqs[i0].fxb, reqs[i0].baseline, list) == LPSLAM_HIP_OK;
         ok = ok && lp_launch_deliver_batch(s, deliver.data(), (int)deliver.size(), pool->slots_per_image, pool) == LPSLAM_HIP_OK;
         if (ok) {

@@ -48,6 +48,7 @@ SYMBOLS = [
     "lpslam_hip_jpeg_dec_take_restart",
     "lpslam_hip_adjust_intensity", "lpslam_hip_upload_raw_image_adjusted", "lpslam_hip_front_end_images_adjusted", "lpslam_hip_adjust_intensity_last",
     "lpslam_hip_upload_pixels", "lpslam_hip_upload_raw_pixels", "lpslam_hip_front_end_pixels",
+    "lpslam_hip_set_keypoint_camera", "lpslam_hip_stage_undistort", "lpslam_hip_undistort_dropped", "lpslam_hip_undistort_points",
 ]
 
 
@@ -66,6 +67,14 @@ class FrontendConfig(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("max_keypoints", C.c_int32),
                 ("scale_factor", C.c_float), ("num_levels", C.c_int32), ("ini_fast_threshold", C.c_int32),
                 ("min_fast_threshold", C.c_int32), ("max_images", C.c_int32), ("device", C.c_int32)]
+
+
+class Fisheye(C.Structure):
+    """lpslam_hip_fisheye: intrinsics, k1 .. k4 and the angle limit in radians"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("k", C.c_double * 4), ("max_angle", C.c_double)]
+
+    def __init__(self, fx, fy, cx, cy, k=(0.0, 0.0, 0.0, 0.0), max_angle_deg=70.0):
+        super().__init__(float(fx), float(fy), float(cx), float(cy), (C.c_double * 4)(*[float(v) for v in k]), float(np.deg2rad(max_angle_deg)))
 
 
 class BaCamera(C.Structure):
@@ -449,6 +458,34 @@ class Context:
 
     def stage(self, name, n_images):
         _check(getattr(self.lib, "lpslam_hip_stage_" + name)(self.h, n_images))
+
+    def set_keypoint_camera(self, model):
+        """fisheye model of every slot (a Fisheye, or None to clear it): extraction then ends with the undistort stage"""
+        f = self.lib.lpslam_hip_set_keypoint_camera
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.POINTER(Fisheye)]
+        _check(f(self.h, None if model is None else C.byref(model)))
+
+    def stage_undistort(self, n_images):
+        f = self.lib.lpslam_hip_stage_undistort
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int]
+        _check(f(self.h, int(n_images)))
+
+    def undistort_dropped(self, image):
+        """keypoints the undistort stage's last run removed from the slot"""
+        f = self.lib.lpslam_hip_undistort_dropped
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+        n = C.c_int32()
+        _check(f(self.h, int(image), C.byref(n)))
+        return n.value
+
+    def undistort_points(self, model, xy):
+        """the stage's arithmetic on an (n, 2) float32 array of pixels: (undistorted (n, 2) float32, valid (n,) bool)"""
+        f = self.lib.lpslam_hip_undistort_points
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.POINTER(Fisheye), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.full(xy.shape, np.nan, np.float32); valid = np.zeros(len(xy), np.uint8)
+        _check(f(self.h, C.byref(model), _p(xy), len(xy), _p(out), _p(valid)))
+        return out, valid.astype(bool)
 
     def keypoints(self, image):
         kp = np.zeros(self.max_kp, KP_DTYPE); desc = np.zeros((self.max_kp, 32), np.uint8)

@@ -32,6 +32,8 @@ HipVslamTrackerBase::HipVslamTrackerBase()
     // runtime ORB parameters the reference hard-codes in its generated YAML (:193-198), plus device selection
     o.optional("numLevels", 3); o.optional("scaleFactor", 1.2); o.optional("iniFastThr", 20); o.optional("minFastThr", 7);
     o.optional("device", 0); o.optional("keyframeInterval", 6); o.optional("localWindow", 10); o.optional("asyncMapping", true); o.optional("prefetch", true); o.optional("mapCulling", true); o.optional("mappingReserve", 0);
+    // monocular fisheye cameras: keypoints whose ray lies further than this from the optical axis are dropped (degrees, (0, 89])
+    o.optional("fisheyeMaxAngleDeg", 70.0);
 }
 
 HipVslamTrackerBase::~HipVslamTrackerBase() { stop(); }
@@ -56,6 +58,56 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_asyncMapping = o.getBool("asyncMapping");
     m_mappingReserve = std::min(16, std::max(0, o.getInteger("mappingReserve")));
     m_prefetch = o.getBool("prefetch"); m_mapCulling = o.getBool("mapCulling");
+    m_fisheyeMaxAngleDeg = o.getDouble("fisheyeMaxAngleDeg");
+}
+
+// The keypoint camera of a monocular session: the fisheye model from the camera configuration (f_x, f_y, c_x, c_y, dist[0..3]) with
+// the YAML keys Camera.model / Camera.k1 .. k4 on top (the file-configuration path) and the angle limit in degrees.  1: *out is the
+// model; 0: the camera is not a fisheye one (pinhole, omni and no-distortion cameras reach the monocular tracker without coefficients, in
+// the reference too); -1: refused, *why says it.
+int resolveFisheyeModel(const LpSlamCameraConfiguration& cam, const std::unordered_map<std::string, std::string>& yaml, double max_angle_deg,
+                        lpslam_fisheye::Model* out, std::string* why)
+{
+    bool fisheye = cam.distortion_function == LpSlamCameraDistortionFunction_Fisheye;
+    auto it = yaml.find("Camera.model");
+    if (it != yaml.end()) fisheye = it->second == "fisheye";
+    if (!fisheye) return 0;
+    lpslam_fisheye::Model m{cam.f_x, cam.f_y, cam.c_x, cam.c_y, {0, 0, 0, 0}, 0};
+    if (cam.distortion_function == LpSlamCameraDistortionFunction_Fisheye) for (int i = 0; i < 4; ++i) m.k[i] = cam.dist[i];
+    const char* keys[4] = {"Camera.k1", "Camera.k2", "Camera.k3", "Camera.k4"};
+    for (int i = 0; i < 4; ++i) {
+        it = yaml.find(keys[i]);
+        if (it == yaml.end()) continue;
+        char* e = nullptr; const double v = std::strtod(it->second.c_str(), &e);
+        if (e == it->second.c_str()) { if (why) *why = std::string(keys[i]) + " is not a number"; return -1; }
+        m.k[i] = v;
+    }
+    if (!(max_angle_deg > 0.0) || !(max_angle_deg <= 89.0)) { if (why) *why = "fisheyeMaxAngleDeg " + std::to_string(max_angle_deg) + " outside (0, 89]"; return -1; }
+    m.max_angle = max_angle_deg * (lpslam_fisheye::kHalfPi / 90.0);
+    if (!lpslam_fisheye::model_ok(m)) { if (why) *why = "fisheye camera: intrinsics and coefficients must be finite, f_x and f_y positive"; return -1; }
+    *out = m;
+    return 1;
+}
+
+bool loadFlatYaml(const std::string& path, std::unordered_map<std::string, std::string>& yaml, std::string* bad_line)
+{
+    std::ifstream f(path);
+    if (!f) return false;
+    std::string line, section;
+    auto trim = [](std::string v) { const size_t a = v.find_first_not_of(" \t\r\"'"), b = v.find_last_not_of(" \t\r\"'"); return a == std::string::npos ? std::string() : v.substr(a, b - a + 1); };
+    while (std::getline(f, line)) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos) line.erase(hash);
+        if (trim(line).empty() || line[0] == '%' || line.rfind("---", 0) == 0) continue;
+        const size_t colon = line.find(':');
+        if (colon == std::string::npos) { if (bad_line) *bad_line = trim(line); return false; }
+        const bool indented = line[0] == ' ' || line[0] == '\t';
+        const std::string key = trim(line.substr(0, colon)), val = trim(line.substr(colon + 1));
+        if (!indented) section.clear();
+        if (val.empty()) { if (!indented) section = key; continue; }
+        yaml[(indented && !section.empty()) ? section + "." + key : key] = val;
+    }
+    return true;
 }
 
 bool HipVslamTrackerBase::startContext(bool stereo)
@@ -67,24 +119,14 @@ bool HipVslamTrackerBase::startContext(bool stereo)
     // (src/Trackers/OpenVSLAMTrackerBase.cpp:114-123: a file that cannot be loaded fails the start).  The keys this path has a use for
     // are read -- Camera.{fx, fy, cx, cy, cols, rows, focal_x_baseline}, Feature.{max_num_keypoints, scale_factor, num_levels,
     // ini_fast_threshold, min_fast_threshold}, Initializer.{num_min_triangulated_pts, parallax_deg_threshold}, time_to_relocalize,
-    // relocalize_with_nav_data -- nested ("Camera:" + indented "fx: ...") or flat ("Camera.fx: ..."); the rest is ignored.
+    // relocalize_with_nav_data, and for a monocular session Camera.model (fisheye) with Camera.k1 .. k4 -- nested ("Camera:" + indented "fx: ...") or flat ("Camera.fx: ..."); the rest is ignored.
     std::unordered_map<std::string, std::string> yaml;
     if (!m_configFromFile.empty()) {
-        std::ifstream f(m_configFromFile);
-        if (!f) { logMessage(LpSlamLogLevel_Error, "Failed to load OpenVSLAM config file " + m_configFromFile); return false; }
-        std::string line, section;
-        auto trim = [](std::string v) { const size_t a = v.find_first_not_of(" \t\r\"'"), b = v.find_last_not_of(" \t\r\"'"); return a == std::string::npos ? std::string() : v.substr(a, b - a + 1); };
-        while (std::getline(f, line)) {
-            const size_t hash = line.find('#');
-            if (hash != std::string::npos) line.erase(hash);
-            if (trim(line).empty() || line[0] == '%' || line.rfind("---", 0) == 0) continue;
-            const size_t colon = line.find(':');
-            if (colon == std::string::npos) { logMessage(LpSlamLogLevel_Error, "OpenVSLAM config file " + m_configFromFile + ": cannot parse \"" + trim(line) + "\""); return false; }
-            const bool indented = line[0] == ' ' || line[0] == '\t';
-            const std::string key = trim(line.substr(0, colon)), val = trim(line.substr(colon + 1));
-            if (!indented) section.clear();
-            if (val.empty()) { if (!indented) section = key; continue; }
-            yaml[(indented && !section.empty()) ? section + "." + key : key] = val;
+        std::string bad_line;
+        if (!loadFlatYaml(m_configFromFile, yaml, &bad_line)) {
+            if (bad_line.empty()) logMessage(LpSlamLogLevel_Error, "Failed to load OpenVSLAM config file " + m_configFromFile);
+            else logMessage(LpSlamLogLevel_Error, "OpenVSLAM config file " + m_configFromFile + ": cannot parse \"" + bad_line + "\"");
+            return false;
         }
         logMessage(LpSlamLogLevel_Info, "VSLAM config loaded from file " + m_configFromFile + " (" + std::to_string(yaml.size()) + " keys)");
     }
@@ -121,7 +163,16 @@ bool HipVslamTrackerBase::startContext(bool stereo)
     }
     // ImageProcessing::Undistort (reference: src/Utils/ImageProcessing.h:134-250): the maps are built once from the camera
     // pair and every frame is remapped -- here on the device (lpslam_hip_upload_raw_image).  The reference does this for the
-    // stereo tracker only (src/Trackers/OpenVSLAMStereoTracker.cpp:198-213); the monocular one feeds frames as they come.
+    // stereo tracker only (src/Trackers/OpenVSLAMStereoTracker.cpp:198-213); the monocular one feeds frames as they come and
+    // hands the camera model to its tracker (OpenVSLAMTrackerBase.cpp:170-175), which undistorts the KEYPOINTS of a fisheye
+    // camera -- here the context does, behind the descriptors (lpslam_hip_set_keypoint_camera, below).
+    m_fisheye = false;
+    if (!stereo) {
+        std::string why;
+        const int r = resolveFisheyeModel(m_cam, yaml, m_fisheyeMaxAngleDeg, &m_fisheyeModel, &why);
+        if (r < 0) { logMessage(LpSlamLogLevel_Error, "Fisheye camera refused: " + why); return false; }
+        m_fisheye = r == 1;
+    }
     m_rectify = stereo && m_cam.distortion_function != LpSlamCameraDistortionFunction_NoDistortion;
     RectifyMaps maps[2];
     if (m_rectify) {
@@ -151,6 +202,16 @@ bool HipVslamTrackerBase::startContext(bool stereo)
     // (lpslam_hip.h).  Off by default: it pays where the front end runs in chip-filling batches (bench.py: +4 % frames/s at 16 frames
     // per launch); this tracker's per-frame launches are small and every one of them is slower on a masked stream (1250 -> 950 frames/s)
     if (m_asyncMapping && m_mappingReserve > 0) (void)lpslam_hip_set_mapping_reserve(m_ctx, m_mappingReserve);
+    if (m_fisheye) {
+        const lpslam_fisheye::Model& fm = m_fisheyeModel;
+        const lpslam_hip_fisheye model{fm.fx, fm.fy, fm.cx, fm.cy, {fm.k[0], fm.k[1], fm.k[2], fm.k[3]}, fm.max_angle};
+        if (lpslam_hip_set_keypoint_camera(m_ctx, &model) != LPSLAM_HIP_OK) {
+            logMessage(LpSlamLogLevel_Error, std::string("Cannot set the fisheye keypoint camera: ") + lpslam_hip_last_error());
+            lpslam_hip_destroy(m_ctx); m_ctx = nullptr;
+            return false;
+        }
+        logMessage(LpSlamLogLevel_Info, "Fisheye camera: keypoints are undistorted on the device, angle limit " + std::to_string(m_fisheyeMaxAngleDeg) + " degrees");
+    }
     for (int eye = 0; m_rectify && eye < 2; ++eye)
         if (lpslam_hip_set_rectify_map(m_ctx, eye, maps[eye].map_x.data(), maps[eye].map_y.data()) != LPSLAM_HIP_OK) {
             logMessage(LpSlamLogLevel_Error, std::string("Cannot upload the rectification maps: ") + lpslam_hip_last_error());
@@ -1679,7 +1740,15 @@ int HipVslamTrackerBase::sharedRefKf(const FrameData& f) const
     return best;
 }
 
-static bool close_to(double a, double b) { return std::fabs(a - b) <= 1e-6 * std::max(1.0, std::max(std::fabs(a), std::fabs(b))); }
+MapFileCamera HipVslamTrackerBase::sessionMapCamera() const
+{
+    MapFileCamera c;
+    c.stereo = m_stereo ? 1 : 0; c.width = m_cam.resolution_x; c.height = m_cam.resolution_y;
+    c.fx = m_cam.f_x; c.fy = m_cam.f_y; c.cx = m_cam.c_x; c.cy = m_cam.c_y; c.focal_x_baseline = m_cam.focal_x_baseline;
+    c.num_levels = m_numLevels; c.scale_factor = m_scaleFactor;
+    if (m_fisheye) { c.model = kMapFileModelFisheye; std::copy(m_fisheyeModel.k, m_fisheyeModel.k + 4, c.k); c.max_angle = m_fisheyeModel.max_angle; }
+    return c;
+}
 
 void HipVslamTrackerBase::loadMap()
 {
@@ -1696,13 +1765,7 @@ void HipVslamTrackerBase::loadMap()
         logMessage(LpSlamLogLevel_Error, "Map file " + m_mapFilename + " rejected (" + err + "): starting with an empty map; the file will not be overwritten");
         return;
     }
-    const MapFileCamera& c = d.cam;
-    std::string why;
-    if ((c.stereo != 0) != m_stereo) why = "camera setup";
-    else if (c.width != m_cam.resolution_x || c.height != m_cam.resolution_y) why = "resolution";
-    else if (!close_to(c.fx, m_cam.f_x) || !close_to(c.fy, m_cam.f_y) || !close_to(c.cx, m_cam.c_x) || !close_to(c.cy, m_cam.c_y)) why = "intrinsics";
-    else if (m_stereo && !close_to(c.focal_x_baseline, m_cam.focal_x_baseline)) why = "focal_x_baseline";
-    else if (c.num_levels != m_numLevels || !close_to(c.scale_factor, m_scaleFactor)) why = "numLevels / scaleFactor";
+    const std::string why = map_camera_mismatch(d.cam, sessionMapCamera());
     if (!why.empty()) {
         m_mapRejected = true;
         logMessage(LpSlamLogLevel_Error, "Map file " + m_mapFilename + " was made with another camera (" + why + " differs): starting with an empty map; the file will not be overwritten");
@@ -1756,9 +1819,7 @@ void HipVslamTrackerBase::saveMap()
 {
     const auto t0 = std::chrono::steady_clock::now();
     MapData d;
-    d.cam.stereo = m_stereo ? 1 : 0; d.cam.width = m_cam.resolution_x; d.cam.height = m_cam.resolution_y;
-    d.cam.fx = m_cam.f_x; d.cam.fy = m_cam.f_y; d.cam.cx = m_cam.c_x; d.cam.cy = m_cam.c_y; d.cam.focal_x_baseline = m_cam.focal_x_baseline;
-    d.cam.num_levels = m_numLevels; d.cam.scale_factor = m_scaleFactor;
+    d.cam = sessionMapCamera();      // (a fisheye session: the version-2 record)
     d.next_landmark_id = m_nextLandmarkId; d.segment = m_segment;
     d.kfs.resize(m_kfs.size());
     long live = 0;
@@ -1810,12 +1871,12 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
                   s.ba_failed, (long)dev[LPSLAM_HIP_BA_COUNTER_SIGNATURES], (long)dev[LPSLAM_HIP_BA_COUNTER_GRAPHS], (long)dev[LPSLAM_HIP_BA_COUNTER_REPLAYS],
-                  (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted, s.color_converted,
+                  (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted, s.color_converted, s.fisheye_dropped,
                   s.t_total * per, s.t_front * per, s.t_track * per, s.t_local * per, s.t_keyframe * per,
                   s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per);
     m_lastStatistics = buf;
@@ -1989,6 +2050,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     else { cur.x_right.assign((size_t)n, -1.0f); cur.depth.assign((size_t)n, -1.0f); }
     cur.landmark.assign((size_t)n, -1);
     cur.scan = std::move(scan);
+    if (m_fisheye) { int32_t dropped = 0; if (lpslam_hip_undistort_dropped(m_ctx, cur.slot, &dropped) == LPSLAM_HIP_OK) m_stats.fisheye_dropped += dropped; }      // (the slot's frame is collected: its stage has run)
     dev_lap(m_stats.t_dev_get);
     ++m_imageTracked; ++m_stats.frames;
     if (cam.adjust) ++m_stats.intensity_adjusted;

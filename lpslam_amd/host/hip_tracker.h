@@ -10,6 +10,8 @@
 #include "core.h"
 #include "bow.h"
 #include "pose_math.h"
+#include "map_file.h"
+#include "../csrc/fisheye_math.h"
 #include "../../include/lpslam_hip.h"
 
 #include <array>
@@ -96,6 +98,7 @@ protected:
         long ba_failed = 0;                           // windows whose solve failed on the device (result dropped)
         long local_ba = 0, loops_closed = 0, loop_fused = 0, global_ba = 0, lost = 0, relocalised = 0, reinitialised = 0, nav_priors = 0, prefetched = 0;
         long color_converted = 0;                     // frames whose colour / YUV source was converted to grey on the device
+        long fisheye_dropped = 0;                     // fisheye session: keypoints the undistort stage removed (beyond the angle limit or 90 degrees, not converged), summed
         long intensity_adjusted = 0;                  // frames whose intensity adjustment ran on the device (a request the host had applied already does not count)
         // where the frames' time went (seconds, summed): front end (upload, extraction, stereo, read-back), tracking against the
         // previous frame, local-map tracking, keyframe work on the tracking thread (insertion, fusion, loop search, BA set-up / wait)
@@ -113,12 +116,16 @@ protected:
     bool initializeMap(FrameData& f, const Pose& at);
     bool poseFromMatches(FrameData& cur, const std::vector<int>& cur_idx, const std::vector<int>& lm_ids, const Pose& init, int& n_inliers, int min_inliers = 10);
     // pc = R X + t and its pinhole image (u, v): false when the point is not in front of the camera or falls outside the image
+    // (the ONE visibility test of the tracker: nothing else compares against the resolution)
     // (defined here, as projQuery is, so that the per-landmark loops of the query builders keep them inline)
     bool project(const Mat3& R, const double* t, const double* X, double* pc, double& u, double& v) const
     {
         transform(R, t, X, pc);
         if (!(pc[2] > 0)) return false;
         u = m_cam.f_x * pc[0] / pc[2] + m_cam.c_x; v = m_cam.f_y * pc[1] / pc[2] + m_cam.c_y;
+        // a fisheye session matches at the pinhole (u, v) -- its keypoints are undistorted -- but what the SENSOR sees decides visibility:
+        // inside the angle limit and the distorted pixel inside the image (fisheye_math.h)
+        if (m_fisheye) return lpslam_fisheye::visible(m_fisheyeModel, pc[0], pc[1], pc[2], m_cam.resolution_x, m_cam.resolution_y);
         return !(u < 0 || v < 0 || u >= m_cam.resolution_x || v >= m_cam.resolution_y);
     }
     lpslam_hip_proj_query projQuery(double u, double v, double z, float radius, int min_level, int max_level, bool stereo) const
@@ -223,6 +230,12 @@ protected:
     lpslam_hip_ctx* m_ctx = nullptr;
     LpSlamCameraConfiguration m_cam{};
     bool m_started = false, m_stereo = false, m_rectify = false;
+    // monocular fisheye session (src/Trackers/OpenVSLAMTrackerBase.cpp:170-175 hands Camera.model = fisheye, k1 .. k4 to its tracker):
+    // the context undistorts and compacts the keypoints (lpslam_hip_set_keypoint_camera), project() tests visibility on the sensor
+    bool m_fisheye = false;
+    lpslam_fisheye::Model m_fisheyeModel{};
+    double m_fisheyeMaxAngleDeg = 70.0;
+    MapFileCamera sessionMapCamera() const;           // the camera record a map file of this session carries
     TrackerState m_state = TrackerState::NotInitialized;
     std::optional<TimeStamp> m_firstImageTimestamp;
     uint64_t m_imageTracked = 0;
@@ -311,6 +324,12 @@ protected:
     void mappingLoop();
     void stopMappingThread();
 };
+
+// the keypoint camera of a monocular session and the flat "Section.key" view of an OpenVSLAM YAML file (hip_tracker.cpp; also reached
+// through the C shim, for tests without a device)
+int resolveFisheyeModel(const LpSlamCameraConfiguration& cam, const std::unordered_map<std::string, std::string>& yaml, double max_angle_deg,
+                        lpslam_fisheye::Model* out, std::string* why);
+bool loadFlatYaml(const std::string& path, std::unordered_map<std::string, std::string>& yaml, std::string* bad_line);
 
 class HipStereoTracker : public HipVslamTrackerBase {
 public:

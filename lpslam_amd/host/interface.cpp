@@ -9,7 +9,11 @@
 #include "jpeg.h"
 #include "map_file.h"
 #include "occupancy.h"
+#include "hip_tracker.h"
+#include "../csrc/fisheye_math.h"
 #include <cstring>
+#include <limits>
+#include <unordered_map>
 #include <vector>
 
 namespace LpSlam { LpSlamCameraConfiguration defaultCameraConfiguration(); }
@@ -170,6 +174,64 @@ LPS_API int lpslam_map_file_rewrite(const char* in, const char* out, char* why, 
     const bool ok = in && out && LpSlam::read_map_file(in, d, &err) && LpSlam::write_map_file(out, d, &err);
     if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
     return ok ? 1 : 0;
+}
+// compares the camera record of a map file with a session's: session = {stereo, width, height, fx, fy, cx, cy, focal_x_baseline,
+// num_levels, scale_factor, model (0 / 1 = fisheye), k1 .. k4, max_angle in radians}.  1: they agree; 0: why = what differs, as the tracker
+// logs it ("camera model", ...); -1: the file itself was rejected, why = the reader's reason
+LPS_API int lpslam_map_file_camera_check(const char* path, const double* session, char* why, size_t why_cap) {
+    LpSlam::MapData d; std::string err;
+    int rc = -1;
+    if (path && session && LpSlam::read_map_file(path, d, &err)) {
+        LpSlam::MapFileCamera s;
+        s.stereo = session[0] != 0 ? 1 : 0; s.width = (int32_t)session[1]; s.height = (int32_t)session[2];
+        s.fx = session[3]; s.fy = session[4]; s.cx = session[5]; s.cy = session[6]; s.focal_x_baseline = session[7];
+        s.num_levels = (int32_t)session[8]; s.scale_factor = session[9]; s.model = (uint32_t)session[10];
+        for (int i = 0; i < 4; ++i) s.k[i] = session[11 + i];
+        s.max_angle = session[15];
+        err = LpSlam::map_camera_mismatch(d.cam, s);
+        rc = err.empty() ? 1 : 0;
+    }
+    if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
+    return rc;
+}
+// ---- the fisheye model's host forms (csrc/fisheye_math.h), for tests without a device; model = {fx, fy, cx, cy, k1 .. k4, max_angle} ----
+static lpslam_fisheye::Model fisheye_model_of(const double* m) { return lpslam_fisheye::Model{m[0], m[1], m[2], m[3], {m[4], m[5], m[6], m[7]}, m[8]}; }
+// n pixels (x, y as doubles) -> out (2 floats each, NaN where invalid), valid (bytes), theta (may be NULL: the angle the iteration ended at)
+LPS_API void lpslam_fisheye_undistort(const double* model, const double* xy, size_t n, float* out, uint8_t* valid, double* theta) {
+    const lpslam_fisheye::Model m = fisheye_model_of(model);
+    for (size_t i = 0; i < n; ++i) {
+        float ux = std::numeric_limits<float>::quiet_NaN(), uy = ux; double th = 0;
+        valid[i] = lpslam_fisheye::undistort(m, xy[2 * i], xy[2 * i + 1], &ux, &uy, &th) ? 1 : 0;
+        out[2 * i] = ux; out[2 * i + 1] = uy;
+        if (theta) theta[i] = th;
+    }
+}
+// n camera-frame points (X, Y, Z) -> the sensor pixel, the angle from the axis and the visibility rule of the tracker's projection
+LPS_API void lpslam_fisheye_forward(const double* model, const double* xyz, size_t n, int width, int height, double* sensor_xy, double* theta, uint8_t* visible) {
+    const lpslam_fisheye::Model m = fisheye_model_of(model);
+    for (size_t i = 0; i < n; ++i) {
+        lpslam_fisheye::forward(m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &sensor_xy[2 * i], &sensor_xy[2 * i + 1], &theta[i]);
+        visible[i] = lpslam_fisheye::visible(m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], width, height) ? 1 : 0;
+    }
+}
+// the keypoint camera a monocular tracker of this manager would start with: camera 0 of its registry (the configuration file's
+// cameras[]), the YAML file of configFromFile (NULL or "": none) and fisheyeMaxAngleDeg.  1: model[9] filled; 0: not a fisheye camera;
+// -1: refused (the start would fail), why says it
+LPS_API int lpslam_manager_fisheye_session_model(lpslam_c_manager* m, const char* yaml_path, double max_angle_deg, double* model, char* why, size_t why_cap) {
+    LpSlam::SlamManager* impl = *reinterpret_cast<LpSlam::SlamManager**>(&m->mgr);
+    std::string err;
+    int rc = -1;
+    std::unordered_map<std::string, std::string> yaml;
+    const auto cam = impl ? impl->cameraRegistry().getConfiguration((LpSlamCameraNumber)0) : std::nullopt;
+    if (!cam) err = "no camera 0";
+    else if (yaml_path && *yaml_path && !LpSlam::loadFlatYaml(yaml_path, yaml, &err)) { if (err.empty()) err = "cannot load the YAML file"; }
+    else {
+        lpslam_fisheye::Model fm{};
+        rc = LpSlam::resolveFisheyeModel(*cam, yaml, max_angle_deg, &fm, &err);
+        if (rc == 1) { const double v[9] = {fm.fx, fm.fy, fm.cx, fm.cy, fm.k[0], fm.k[1], fm.k[2], fm.k[3], fm.max_angle}; std::copy(v, v + 9, model); }
+    }
+    if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
+    return rc;
 }
 // laser scans and the occupancy grid.  ros_ts: the scan's ROS time as the frames of lpslam_manager_add_stereo_image carry it.
 LPS_API void lpslam_manager_add_laser_scan(lpslam_c_manager* m, const LpSlamROSTimestamp* ros_ts, float* ranges, size_t n, float range_min,

@@ -1,6 +1,8 @@
 // map_file.cpp -- reader and writer of the map database file (map_file.h; layout in INTEGRATION.md).
 #include "map_file.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -42,10 +44,13 @@ bool write_map_file(const std::string& path, const MapData& m, std::string* err)
 {
     Out o;
     o.raw(kMagic, 8);
-    o.v<uint32_t>(kMapFileVersion);
+    const bool fisheye = m.cam.model == kMapFileModelFisheye;
+    if (m.cam.model != 0 && !fisheye) { if (err) *err = "camera model " + std::to_string(m.cam.model) + " cannot be written"; return false; }
+    o.v<uint32_t>(fisheye ? kMapFileVersionFisheye : kMapFileVersion);
     o.v<uint32_t>(m.cam.stereo); o.v<int32_t>(m.cam.width); o.v<int32_t>(m.cam.height);
     o.v<double>(m.cam.fx); o.v<double>(m.cam.fy); o.v<double>(m.cam.cx); o.v<double>(m.cam.cy); o.v<double>(m.cam.focal_x_baseline);
     o.v<int32_t>(m.cam.num_levels); o.v<double>(m.cam.scale_factor);
+    if (fisheye) { o.v<uint32_t>(m.cam.model); for (double x : m.cam.k) o.v<double>(x); o.v<double>(m.cam.max_angle); }
     o.v<uint32_t>((uint32_t)m.kfs.size()); o.v<uint32_t>((uint32_t)m.lms.size()); o.v<int32_t>(m.next_landmark_id); o.v<int32_t>(m.segment);
     for (const auto& k : m.kfs) {
         o.v<uint8_t>(k.erased ? 1 : 0);
@@ -97,14 +102,23 @@ bool read_map_file(const std::string& path, MapData& m, std::string* err)
     uint32_t version = 0;
     if (b.size() < 12) return fail("truncated: no version");
     std::memcpy(&version, b.data() + 8, 4);
-    if (version != kMapFileVersion) return fail("unsupported format version " + std::to_string(version) + " (this build reads " + std::to_string(kMapFileVersion) + ")");
+    if (version != kMapFileVersion && version != kMapFileVersionFisheye)
+        return fail("unsupported format version " + std::to_string(version) + " (this build reads " + std::to_string(kMapFileVersion) + " and " + std::to_string(kMapFileVersionFisheye) + ")");
     if (b.size() < 20) return fail("truncated: no checksum");
     // the records first (a file cut short runs out of bytes: "truncated"), the checksum over all of it last
     In in{b.data(), b.size() - 8, 12};
     m = MapData{};
     uint32_t nk = 0, nl = 0;
     bool ok = in.v(m.cam.stereo) && in.v(m.cam.width) && in.v(m.cam.height) && in.v(m.cam.fx) && in.v(m.cam.fy) && in.v(m.cam.cx) && in.v(m.cam.cy) &&
-              in.v(m.cam.focal_x_baseline) && in.v(m.cam.num_levels) && in.v(m.cam.scale_factor) && in.v(nk) && in.v(nl) && in.v(m.next_landmark_id) && in.v(m.segment);
+              in.v(m.cam.focal_x_baseline) && in.v(m.cam.num_levels) && in.v(m.cam.scale_factor);
+    if (ok && version == kMapFileVersionFisheye) {
+        ok = in.v(m.cam.model);
+        // version 2 exists for the fisheye model alone: any other value is a format this build does not know
+        if (ok && m.cam.model != kMapFileModelFisheye)
+            return fail("unsupported format version 2 with camera model " + std::to_string(m.cam.model) + " (this build reads model " + std::to_string(kMapFileModelFisheye) + ", fisheye)");
+        ok = ok && in.raw(m.cam.k, sizeof(m.cam.k)) && in.v(m.cam.max_angle);
+    }
+    ok = ok && in.v(nk) && in.v(nl) && in.v(m.next_landmark_id) && in.v(m.segment);
     if (!ok) return fail("truncated: header");
     if (m.next_landmark_id < 0 || nl > (uint32_t)m.next_landmark_id) return fail("landmark count " + std::to_string(nl) + " exceeds next landmark id " + std::to_string(m.next_landmark_id));
     if ((size_t)nk > in.left()) return fail("keyframe count " + std::to_string(nk) + " exceeds the file size");
@@ -151,6 +165,20 @@ bool read_map_file(const std::string& path, MapData& m, std::string* err)
     std::memcpy(&stored, b.data() + b.size() - 8, 8);
     if (fnv1a64(b.data(), b.size() - 8) != stored) return fail("checksum mismatch: the file is damaged");
     return true;
+}
+
+static bool close_to(double a, double b) { return std::fabs(a - b) <= 1e-6 * std::max(1.0, std::max(std::fabs(a), std::fabs(b))); }
+
+std::string map_camera_mismatch(const MapFileCamera& c, const MapFileCamera& s)
+{
+    if ((c.stereo != 0) != (s.stereo != 0)) return "camera setup";
+    if (c.width != s.width || c.height != s.height) return "resolution";
+    if (!close_to(c.fx, s.fx) || !close_to(c.fy, s.fy) || !close_to(c.cx, s.cx) || !close_to(c.cy, s.cy)) return "intrinsics";
+    if (s.stereo && !close_to(c.focal_x_baseline, s.focal_x_baseline)) return "focal_x_baseline";
+    if (c.num_levels != s.num_levels || !close_to(c.scale_factor, s.scale_factor)) return "numLevels / scaleFactor";
+    if (c.model != s.model) return "camera model";
+    if (c.model != 0 && !(close_to(c.k[0], s.k[0]) && close_to(c.k[1], s.k[1]) && close_to(c.k[2], s.k[2]) && close_to(c.k[3], s.k[3]) && close_to(c.max_angle, s.max_angle))) return "camera model";
+    return std::string();
 }
 
 }  // namespace LpSlam

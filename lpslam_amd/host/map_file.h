@@ -16,6 +16,10 @@ struct MapFileCamera {
     double fx = 0, fy = 0, cx = 0, cy = 0, focal_x_baseline = 0;
     int32_t num_levels = 0;
     double scale_factor = 0;
+    // version 2 only (a monocular fisheye session): model = 1 (LpSlamCameraDistortionFunction_Fisheye), k1 .. k4, the angle limit in
+    // radians.  model = 0: a version-1 record, which has none of the three.
+    uint32_t model = 0;
+    double k[4] = {0, 0, 0, 0}, max_angle = 0;
 };
 
 struct MapFileKeyframe {
@@ -46,11 +50,17 @@ struct MapData {
     std::vector<MapFileLandmark> lms;
 };
 
-constexpr uint32_t kMapFileVersion = 1;
+constexpr uint32_t kMapFileVersion = 1;              // every session but a fisheye one writes it, byte for byte as before
+constexpr uint32_t kMapFileVersionFisheye = 2;       // version 1 with model, k[4], max_angle behind the camera record
+constexpr uint32_t kMapFileModelFisheye = 1;
 
 // <path>.tmp, then rename: a crash never leaves half a map under the name.  false + *err on failure.
 bool write_map_file(const std::string& path, const MapData& m, std::string* err);
 // Checks magic, version, sizes, id ranges and the checksum; false + *err saying which check failed.
 bool read_map_file(const std::string& path, MapData& m, std::string* err);
+// What differs between the camera a file was made with and the session's ("camera setup", "resolution", "intrinsics",
+// "focal_x_baseline", "numLevels / scaleFactor", "camera model"), or an empty string.  A version-1 file in a fisheye session, a
+// version-2 file in any other, other coefficients or another angle limit: "camera model".
+std::string map_camera_mismatch(const MapFileCamera& file, const MapFileCamera& session);
 
 }  // namespace LpSlam

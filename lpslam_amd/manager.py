@@ -477,3 +477,54 @@ def map_file_rewrite(src, dst):
     why = C.create_string_buffer(512)
     ok = bool(f(str(src).encode(), str(dst).encode(), why, 512))
     return ok, why.value.decode()
+
+
+def map_file_camera_check(path, session):
+    """compares a map file's camera record with a session's (lpslam_map_file_camera_check): session = 16 numbers {stereo, width, height,
+    fx, fy, cx, cy, focal_x_baseline, num_levels, scale_factor, model, k1 .. k4, max_angle}.  (1, "") they agree; (0, what differs);
+    (-1, why the file itself was rejected)"""
+    import numpy as np
+    lib = load()
+    f = lib.lpslam_map_file_camera_check; f.argtypes = [C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t]; f.restype = C.c_int
+    s = np.ascontiguousarray(session, np.float64)
+    assert s.size == 16
+    why = C.create_string_buffer(512)
+    rc = int(f(str(path).encode(), s.ctypes.data, why, 512))
+    return rc, why.value.decode()
+
+
+def fisheye_undistort(model, xy):
+    """the host form of the fisheye undistortion (csrc/fisheye_math.h), CPU only: model = 9 numbers {fx, fy, cx, cy, k1 .. k4, max_angle
+    in radians}, xy (n, 2) float64 pixels.  Returns (out (n, 2) float32 with NaN where invalid, valid (n,) bool, theta (n,))"""
+    import numpy as np
+    lib = load()
+    f = lib.lpslam_fisheye_undistort; f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = None
+    m = np.ascontiguousarray(model, np.float64); xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    n = len(xy)
+    out = np.zeros((n, 2), np.float32); valid = np.zeros(n, np.uint8); theta = np.zeros(n, np.float64)
+    f(m.ctypes.data, xy.ctypes.data, n, out.ctypes.data, valid.ctypes.data, theta.ctypes.data)
+    return out, valid.astype(bool), theta
+
+
+def fisheye_forward(model, xyz, width, height):
+    """the host form of the forward model and the tracker's visibility rule, CPU only: xyz (n, 3) camera-frame points.  Returns (sensor
+    pixel (n, 2), angle from the axis (n,), visible (n,) bool)"""
+    import numpy as np
+    lib = load()
+    f = lib.lpslam_fisheye_forward; f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = None
+    m = np.ascontiguousarray(model, np.float64); xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    n = len(xyz)
+    s = np.zeros((n, 2), np.float64); theta = np.zeros(n, np.float64); vis = np.zeros(n, np.uint8)
+    f(m.ctypes.data, xyz.ctypes.data, n, int(width), int(height), s.ctypes.data, theta.ctypes.data, vis.ctypes.data)
+    return s, theta, vis.astype(bool)
+
+
+def fisheye_session_model(mgr, yaml_path=None, max_angle_deg=70.0):
+    """the keypoint camera a monocular tracker of Manager `mgr` would start with (camera 0 of its configuration, the YAML file of
+    configFromFile, fisheyeMaxAngleDeg), without a device: (1, 9 numbers), (0, None) for a camera that is not a fisheye one, (-1, reason)"""
+    import numpy as np
+    f = mgr.lib.lpslam_manager_fisheye_session_model
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_double, C.c_void_p, C.c_char_p, C.c_size_t]; f.restype = C.c_int
+    model = np.zeros(9, np.float64); why = C.create_string_buffer(512)
+    rc = int(f(mgr.h, (str(yaml_path).encode() if yaml_path else None), float(max_angle_deg), model.ctypes.data, why, 512))
+    return (rc, model) if rc == 1 else (rc, why.value.decode() if rc < 0 else None)
