@@ -642,6 +642,53 @@ int32_t lpslam_hip_window_match_rescans(lpslam_hip_ctx* ctx);
  * populated 30-degree bins.  Host-side (a few thousand matches). */
 int lpslam_hip_match_orientation_filter(const float* angle_q, const float* angle_t, int32_t* match_idx, int32_t nq, int32_t* n_kept);
 
+/* ---- new landmarks between keyframes ---------------------------------------------------------------------------------
+ * [UPSTREAM] mapping_module::create_new_landmarks (match::robust::match_for_triangulation, then the two-view triangulation and its
+ * checks), which openvslam::system's mapping thread runs for every keyframe with Mapping.baseline_dist_thr as the reference forwards
+ * it (src/Trackers/OpenVSLAMTrackerBase.cpp:72,202).  Upstream is absent from the reference tree: the rule is this project's own,
+ * lpslam_amd/csrc/triangulate_math.h holds it and DESIGN.md section 31 the reasons.
+ * View 1 is the new keyframe c, whose keypoints, descriptors and last stereo match sit in image slot `image`; each set is a
+ * neighbour keyframe n in host memory.  Poses are world -> camera, qw qx qy qz tx ty tz.  A keypoint with depth > 0 under a camera
+ * with focal_x_baseline > 0 is a stereo keypoint (focal_x_baseline = 0: a monocular camera, the slot's stereo columns are not read).
+ * Keypoint i of c takes part when group1[i] >= 0, keypoint j of n when group[j] >= 0; j is a candidate of i when the groups are equal,
+ * the Hamming distance is <= 50, j lies at least 10 sqrt(scale[octave_j]) pixels from the epipole (only when neither is a stereo
+ * keypoint and has_epipole != 0) and (l . (x_j, y_j, 1))^2 <= 3.84 scale[octave_j]^2 (l0^2 + l1^2) for l = F (x_i, y_i, 1), l0^2 + l1^2 > 0. */
+typedef struct lpslam_hip_tri_camera {
+    double fx, fy, cx, cy;
+    double focal_x_baseline;      /* fx x the true baseline; 0: monocular */
+    double scale_factor;          /* Feature.scale_factor: the distance-ratio check allows 1.5 x this */
+} lpslam_hip_tri_camera;
+typedef struct lpslam_hip_tri_keypoint {
+    float x, y;
+    int32_t octave;
+    float x_right, depth;         /* depth <= 0: not a stereo keypoint */
+} lpslam_hip_tri_keypoint;
+typedef struct lpslam_hip_tri_set {
+    const lpslam_hip_keypoint* kpts;
+    const uint8_t* desc32;
+    const int32_t* group;
+    const float* x_right;         /* x_right and depth: both NULL = no stereo keypoints */
+    const float* depth;
+    int32_t n;
+    double pose[7];
+    double F[9];                  /* row major, pixels: x_n^T F x_c = 0 */
+    double epipole[2];            /* c's centre projected into n */
+    int32_t has_epipole;          /* 0: that centre has z = 0 in n's frame */
+} lpslam_hip_tri_set;
+/* Per (set s, query i < *n_queries = the slot's keypoint count) at row s * capacity + i: the eight nearest candidates by (distance,
+ * index) -- out_j (-1: none), out_dist (256), out_code (0: no landmark, 1: triangulated, 2 / 3: back-projection of i / of j), out_X
+ * (3 doubles, NaN with code 0) -- and out_count, how many candidates passed (it may exceed eight: there is no rescan).  One upload, two
+ * launches and one wait.  n_sets > 32, a set above lpslam_hip_max_keypoints_per_image(), capacity below the slot's count or an image
+ * slot out of range: LPSLAM_HIP_ERR_CAPACITY; a null argument, an octave outside [0, n_levels), a value that is no number or a slot
+ * that has never held an extraction: LPSLAM_HIP_ERR_INVALID.  On a session context the call runs directly (no shared launch). */
+int lpslam_hip_triangulate_neighbours(lpslam_hip_ctx* ctx, int image, const int32_t* group1, const double* pose1, const lpslam_hip_tri_camera* cam,
+                                      const lpslam_hip_tri_set* sets, int32_t n_sets, const float* scale, int32_t n_levels, int32_t capacity,
+                                      int32_t* n_queries, int32_t* out_j, int32_t* out_dist, int32_t* out_code, double* out_X, int32_t* out_count);
+/* The same tri_pair on n caller-given pairs (kp1[k] in view pose1, kp2[k] in view pose2): code[k], X[3 k ..] (NaN with code 0).
+ * The parity hook of the kernel's arithmetic.  Synchronising. */
+int lpslam_hip_triangulate_pairs(lpslam_hip_ctx* ctx, const lpslam_hip_tri_camera* cam, const float* scale, int32_t n_levels, const double* pose1, const double* pose2,
+                                 const lpslam_hip_tri_keypoint* kp1, const lpslam_hip_tri_keypoint* kp2, int32_t n, int32_t* code, double* X);
+
 /* ---- Sim3 pose graph ---------------------------------------------------------------------------------------------
  * Replaces what openvslam::system runs on its global-optimisation thread after a loop closure while the loop detector
  * is enabled (reference: src/Trackers/OpenVSLAMTrackerBase.cpp:250-255): [UPSTREAM] optimize::graph_optimizer on

@@ -490,7 +490,7 @@ static int create_impl(const lpslam_hip_frontend_config* cfg, lpslam_hip_ctx* po
 
     lpslam_hip_ctx* c = new lpslam_hip_ctx();
     c->cfg = *cfg;
-    c->h_kp_count.assign((size_t)cfg->max_images, 0); c->h_kp_valid.assign((size_t)cfg->max_images, 0);
+    c->h_kp_count.assign((size_t)cfg->max_images, 0); c->h_kp_valid.assign((size_t)cfg->max_images, 0); c->kp_written.assign((size_t)cfg->max_images, 0);
     std::vector<int16_t> ofs, coef;
     int rc = build_level_table(*cfg, c->lt, c->image_slab, ofs, coef);
     if (rc != LPSLAM_HIP_OK) { delete c; return rc; }
@@ -1692,6 +1692,7 @@ int lpslam_hip_keypoint_buffers(lpslam_hip_ctx* c, int image, void** kpts_dev, v
     if (kpts_dev) *kpts_dev = c->d_kpts + o;
     if (desc_dev) *desc_dev = c->d_desc + o * 32;
     if (count_dev) { *count_dev = c->d_kp_count + image; if ((size_t)image < c->h_kp_valid.size()) c->h_kp_valid[(size_t)image] = 0; }
+    if ((size_t)image < c->kp_written.size()) c->kp_written[(size_t)image] = 1;      // (the caller writes the slot itself)
     lp_pf_invalidate(c, image, 1);
     return LPSLAM_HIP_OK;
 }
@@ -1704,7 +1705,7 @@ int lpslam_hip_set_descriptors(lpslam_hip_ctx* c, int image, const uint8_t* desc
     if (n) LP_HIP(hipMemcpyAsync(c->d_desc + (size_t)image * c->slots_per_image * 32, desc32, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
     LP_HIP(hipMemcpyAsync(c->d_kp_count + image, &n, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     LP_HIP(hipStreamSynchronize(c->stream));
-    if ((size_t)image < c->h_kp_valid.size()) { c->h_kp_count[(size_t)image] = n; c->h_kp_valid[(size_t)image] = 1; }
+    if ((size_t)image < c->h_kp_valid.size()) { c->h_kp_count[(size_t)image] = n; c->h_kp_valid[(size_t)image] = 1; c->kp_written[(size_t)image] = 1; }
     lp_pf_invalidate(c, image, 1);
     return LPSLAM_HIP_OK;
 }

@@ -1383,7 +1383,7 @@ int lp_launch_describe(lpslam_hip_ctx* c, int first, int n_images, const uint16_
 {
     const ImgSel sel = lp_img_sel(first, n_images, list);
     if (!list) {
-        for (int i = first; i < first + n_images && (size_t)i < c->h_kp_valid.size(); ++i) c->h_kp_valid[(size_t)i] = 0;      // counts are rewritten
+        for (int i = first; i < first + n_images && (size_t)i < c->h_kp_valid.size(); ++i) { c->h_kp_valid[(size_t)i] = 0; c->kp_written[(size_t)i] = 1; }      // counts are rewritten
         lp_pf_invalidate(c, first, n_images);
     }      // (a listed launch runs on the session pool's context: the sessions' own mirrors are invalidated by the caller, share.hip)
     const int blocks = (c->slots_per_image + DESC_WAVES - 1) / DESC_WAVES;

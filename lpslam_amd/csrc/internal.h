@@ -127,6 +127,7 @@ struct lpslam_hip_ctx {
     uint8_t* h_stage_pf = nullptr; size_t h_stage_pf_bytes = 0; std::atomic<int> pf_image{-1}; LpDone pf_done{}; int pf_seq_next = 0, pf_fields = 0; bool pf_in_flight = false; hipStream_t pf_stream = nullptr;
     // host mirror of d_kp_count: valid after any call that fetched it, invalidated by whatever rewrites it on the device
     std::vector<int32_t> h_kp_count; std::vector<uint8_t> h_kp_valid;
+    std::vector<uint8_t> kp_written;   // per image slot: an extraction (or a caller's own keypoints) has been enqueued into it since the context was made
     // descriptor sets kept on the device under a caller's key (lpslam_hip_desc_store_put: a tracker's keyframes), blocks of the pool
     // (mask: per-descriptor byte of lpslam_hip_desc_store_mask, valid while has_mask -- a put clears it)
     struct StoredDesc { void* blk = nullptr; size_t cap = 0; int n = 0; void* mask = nullptr; size_t mask_cap = 0; bool has_mask = false; };

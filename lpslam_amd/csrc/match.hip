@@ -636,7 +636,7 @@ int lpslam_hip_match_bf_descriptors(lpslam_hip_ctx* c, int query, int scratch, c
     // the scratch slot receives the descriptors and their count (lpslam_hip_set_descriptors, without its wait)
     if (n_train) LP_HIP(hipMemcpyAsync(c->d_desc + (size_t)scratch * S * 32, train_desc32, (size_t)n_train * 32, hipMemcpyHostToDevice, s));
     LP_HIP(hipMemcpyAsync(c->d_kp_count + scratch, &n_train, sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if ((size_t)scratch < c->h_kp_valid.size()) { c->h_kp_count[(size_t)scratch] = n_train; c->h_kp_valid[(size_t)scratch] = 1; }
+    if ((size_t)scratch < c->h_kp_valid.size()) { c->h_kp_count[(size_t)scratch] = n_train; c->h_kp_valid[(size_t)scratch] = 1; c->kp_written[(size_t)scratch] = 1; }
     lp_pf_invalidate(c, scratch, 1);
     if (nq == 0 || n_train == 0) { LP_HIP(hipStreamSynchronize(s)); return LPSLAM_HIP_OK; }
     if ((rc = lp_launch_bf_strided(c, query, scratch, 0, 1))) return rc;

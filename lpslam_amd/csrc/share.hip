@@ -505,7 +505,7 @@ int lp_share_front_end(lpslam_hip_ctx* c, int slot, int stereo, float fxb, float
     { std::lock_guard<std::mutex> lock(sh.m); if (!share_init(sh)) return LP_SHARE_DIRECT; }
     if (own && own != sh.s_front && hipEventRecord(c->ev_fe_ready, own) != hipSuccess) { (void)hipGetLastError(); return LP_SHARE_DIRECT; }
     // the slots' results are about to be rewritten: the session's host mirrors go stale now
-    for (int i = slot; i < slot + (stereo ? 2 : 1) && (size_t)i < c->h_kp_valid.size(); ++i) c->h_kp_valid[(size_t)i] = 0;
+    for (int i = slot; i < slot + (stereo ? 2 : 1) && (size_t)i < c->h_kp_valid.size(); ++i) { c->h_kp_valid[(size_t)i] = 0; c->kp_written[(size_t)i] = 1; }
     Ticket t;
     r.t = &t;
     {

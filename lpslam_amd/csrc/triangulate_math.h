@@ -1,0 +1,316 @@
+// triangulate_math.h -- new landmarks between keyframes, once, for the device kernels (triangulate.hip), the
+// host tracker (lpslam_amd/host/hip_tracker.cpp) and the CPU tests: FP64 throughout.
+//   candidate gate   which keypoint j of a neighbour keyframe n may be the partner of keypoint i of the new keyframe c: same group,
+//                    Hamming distance <= 50, away from the epipole (two monocular keypoints), on the epipolar line of i
+//   tri_pair         the landmark of a pair (i, j): linear triangulation when the rays have parallax, the back-projection of the
+//                    stereo keypoint with the smaller stereo angle otherwise, then the depth / reprojection / scale checks
+// [UPSTREAM] mapping_module::create_new_landmarks, match::robust::match_for_triangulation and ORB-SLAM2's CreateNewMapPoints /
+// SearchForTriangulation, written down from memory and not checked against either: the definition in this file is THIS PROJECT'S
+// OWN RULE.  View 1 is the new keyframe c (keypoint i), view 2 the neighbour n (keypoint j).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define LP_TRI_FN __host__ __device__ __forceinline__
+#define LP_TRI_UNROLL _Pragma("unroll")      // constant indices: the small matrices stay in registers on the device
+#else
+#define LP_TRI_FN inline
+#define LP_TRI_UNROLL
+#endif
+
+namespace lpslam_tri {
+
+constexpr int kListed = 8;            // candidates a query keeps per neighbour: part of the definition, there is no rescan
+constexpr int kMaxSets = 32;          // neighbours of one call
+constexpr int kHammingMax = 50;
+constexpr unsigned long long kNoKey = ~0ull;      // an empty list entry; a key is distance << 32 | j
+
+struct Camera { double fx, fy, cx, cy, fxb, scale_factor; };      // fxb = fx x the true baseline; 0: a monocular camera (no keypoint is a stereo keypoint)
+struct View { double R[9], t[3]; };                                // world -> camera, R row major
+struct Keypoint { float x, y; int32_t octave; float x_right, depth; };      // depth > 0 (and a camera with a baseline): a stereo keypoint
+struct Epipolar { double F[9], ex, ey; int32_t has_epipole, pad; };         // x_n^T F x_c = 0 in pixels; (ex, ey): c's centre seen from n
+
+// quatToRot of lpslam_amd/host/pose_math.h: pose = qw qx qy qz tx ty tz
+LP_TRI_FN View view_from_pose(const double* p)
+{
+    const double n = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3]);
+    const double w = p[0] / n, x = p[1] / n, y = p[2] / n, z = p[3] / n;
+    View v;
+    v.R[0] = 1 - 2 * (y * y + z * z); v.R[1] = 2 * (x * y - w * z); v.R[2] = 2 * (x * z + w * y);
+    v.R[3] = 2 * (x * y + w * z); v.R[4] = 1 - 2 * (x * x + z * z); v.R[5] = 2 * (y * z - w * x);
+    v.R[6] = 2 * (x * z - w * y); v.R[7] = 2 * (y * z + w * x); v.R[8] = 1 - 2 * (x * x + y * y);
+    v.t[0] = p[4]; v.t[1] = p[5]; v.t[2] = p[6];
+    return v;
+}
+
+LP_TRI_FN bool is_stereo(const Camera& cam, float depth) { return cam.fxb > 0.0 && depth > 0.0f; }
+
+LP_TRI_FN int hamming(const uint32_t* a, const uint32_t* b)
+{
+    int h = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+    for (int w = 0; w < 8; ++w) h += __popc(a[w] ^ b[w]);
+#else
+    for (int w = 0; w < 8; ++w) h += __builtin_popcount(a[w] ^ b[w]);
+#endif
+    return h;
+}
+
+// l = F (x, y, 1): the epipolar line of keypoint i in the neighbour's image
+LP_TRI_FN void epipolar_line(const double* F, double x, double y, double* l)
+{
+    for (int k = 0; k < 3; ++k) l[k] = F[3 * k] * x + F[3 * k + 1] * y + F[3 * k + 2];
+}
+
+// Rules 3 and 4 of the gate for candidate (xj, yj) of scale s = scale[octave_j]; rules 1 and 2 (group, Hamming) are integer tests of
+// the caller.  A comparison with a NaN fails: such a candidate does not pass.
+LP_TRI_FN bool gate_geometry(const double* l, bool either_stereo, const Epipolar& e, double xj, double yj, double s)
+{
+    if (!either_stereo && e.has_epipole) {
+        const double dx = xj - e.ex, dy = yj - e.ey;
+        if (!(dx * dx + dy * dy >= 100.0 * s)) return false;
+    }
+    const double nn = l[0] * l[0] + l[1] * l[1];
+    if (!(nn > 0.0)) return false;
+    const double num = l[0] * xj + l[1] * yj + l[2];
+    return num * num <= 3.84 * (s * s) * nn;
+}
+
+// Cyclic Jacobi on a symmetric 4 x 4 matrix with the arithmetic of sym_eigen_jacobi (lpslam_amd/host/two_view.cpp), fully unrolled so
+// that every index is a constant (registers on the device); a, v row major, v receives the eigenvectors as columns.
+LP_TRI_FN void jacobi4(double* a, double* v)
+{
+    for (int i = 0; i < 16; ++i) v[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        double off = 0, diag = 0;
+        LP_TRI_UNROLL
+        for (int i = 0; i < 4; ++i)
+            LP_TRI_UNROLL
+            for (int j = 0; j < 4; ++j) { if (i == j) diag += a[i * 4 + j] * a[i * 4 + j]; else off += a[i * 4 + j] * a[i * 4 + j]; }
+        if (off <= 1e-30 * (diag + 1e-300)) break;
+        LP_TRI_UNROLL
+        for (int p = 0; p < 3; ++p)
+            LP_TRI_UNROLL
+            for (int q = p + 1; q < 4; ++q) {
+                const double apq = a[p * 4 + q];
+                if (apq == 0.0) continue;
+                const double theta = (a[q * 4 + q] - a[p * 4 + p]) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                LP_TRI_UNROLL
+                for (int k = 0; k < 4; ++k) {                   // columns p, q
+                    const double akp = a[k * 4 + p], akq = a[k * 4 + q];
+                    a[k * 4 + p] = c * akp - s * akq; a[k * 4 + q] = s * akp + c * akq;
+                }
+                LP_TRI_UNROLL
+                for (int k = 0; k < 4; ++k) {                   // rows p, q
+                    const double apk = a[p * 4 + k], aqk = a[q * 4 + k];
+                    a[p * 4 + k] = c * apk - s * aqk; a[q * 4 + k] = s * apk + c * aqk;
+                }
+                LP_TRI_UNROLL
+                for (int k = 0; k < 4; ++k) {
+                    const double vkp = v[k * 4 + p], vkq = v[k * 4 + q];
+                    v[k * 4 + p] = c * vkp - s * vkq; v[k * 4 + q] = s * vkp + c * vkq;
+                }
+            }
+    }
+}
+
+// P = K [R | t], row major 3 x 4
+LP_TRI_FN void projection(const Camera& cam, const View& v, double* P)
+{
+    for (int c = 0; c < 3; ++c) { P[c] = cam.fx * v.R[c] + cam.cx * v.R[6 + c]; P[4 + c] = cam.fy * v.R[3 + c] + cam.cy * v.R[6 + c]; P[8 + c] = v.R[6 + c]; }
+    P[3] = cam.fx * v.t[0] + cam.cx * v.t[2]; P[7] = cam.fy * v.t[1] + cam.cy * v.t[2]; P[11] = v.t[2];
+}
+
+// triangulate_point of lpslam_amd/host/two_view.cpp: rows, A^T A, Jacobi, the eigenvector of the smallest eigenvalue (the first
+// among equal ones), false when its last component is 0
+LP_TRI_FN bool triangulate_linear(const double* P1, const double* P2, double x1, double y1, double x2, double y2, double* X)
+{
+    double A[16];
+    LP_TRI_UNROLL
+    for (int c = 0; c < 4; ++c) {
+        A[c] = x1 * P1[8 + c] - P1[c];
+        A[4 + c] = y1 * P1[8 + c] - P1[4 + c];
+        A[8 + c] = x2 * P2[8 + c] - P2[c];
+        A[12 + c] = y2 * P2[8 + c] - P2[4 + c];
+    }
+    double AtA[16], evec[16];
+    LP_TRI_UNROLL
+    for (int a = 0; a < 4; ++a)
+        LP_TRI_UNROLL
+        for (int b = 0; b < 4; ++b) {
+            double s = 0;
+            LP_TRI_UNROLL
+            for (int r = 0; r < 4; ++r) s += A[r * 4 + a] * A[r * 4 + b];
+            AtA[a * 4 + b] = s;
+        }
+    jacobi4(AtA, evec);
+    // the column of the smallest diagonal entry, selected without a variable index
+    double best = AtA[0], e0 = evec[0], e1 = evec[4], e2 = evec[8], e3 = evec[12];
+    LP_TRI_UNROLL
+    for (int c = 1; c < 4; ++c)
+        if (AtA[c * 5] < best) { best = AtA[c * 5]; e0 = evec[c]; e1 = evec[4 + c]; e2 = evec[8 + c]; e3 = evec[12 + c]; }
+    if (e3 == 0.0) return false;
+    X[0] = e0 / e3; X[1] = e1 / e3; X[2] = e2 / e3;
+    return true;
+}
+
+// X_w = R^T (X_c - t) of the keypoint at its stereo depth
+LP_TRI_FN void back_project(const Camera& cam, const View& v, const Keypoint& k, double* X)
+{
+    const double z = (double)k.depth;
+    const double xc = ((double)k.x - cam.cx) * z / cam.fx, yc = ((double)k.y - cam.cy) * z / cam.fy;
+    const double d0 = xc - v.t[0], d1 = yc - v.t[1], d2 = z - v.t[2];
+    for (int a = 0; a < 3; ++a) X[a] = v.R[a] * d0 + v.R[3 + a] * d1 + v.R[6 + a] * d2;
+}
+
+// One view's checks of a landmark: positive depth, reprojection error within the chi-square bound of the keypoint's level (with the
+// right-image term for a stereo keypoint), positive distance to the camera centre (*dist).
+LP_TRI_FN bool view_accepts(const Camera& cam, const View& v, const Keypoint& k, bool stereo, double s, const double* X, double* dist)
+{
+    double Xc[3];
+    for (int r = 0; r < 3; ++r) Xc[r] = v.R[r * 3] * X[0] + v.R[r * 3 + 1] * X[1] + v.R[r * 3 + 2] * X[2] + v.t[r];
+    if (!(Xc[2] > 0.0)) return false;
+    const double sigma2 = s * s;
+    const double ex = cam.fx * Xc[0] / Xc[2] + cam.cx - (double)k.x, ey = cam.fy * Xc[1] / Xc[2] + cam.cy - (double)k.y;
+    if (stereo) {
+        const double er = cam.fx * Xc[0] / Xc[2] + cam.cx - cam.fxb / Xc[2] - (double)k.x_right;
+        if (!(ex * ex + ey * ey + er * er <= 7.81473 * sigma2)) return false;
+    } else if (!(ex * ex + ey * ey <= 5.991 * sigma2)) return false;
+    double C[3];
+    for (int a = 0; a < 3; ++a) C[a] = -(v.R[a] * v.t[0] + v.R[3 + a] * v.t[1] + v.R[6 + a] * v.t[2]);
+    const double dx = X[0] - C[0], dy = X[1] - C[1], dz = X[2] - C[2];
+    *dist = sqrt(dx * dx + dy * dy + dz * dz);
+    return *dist > 0.0;
+}
+
+LP_TRI_FN double cos_stereo(const Camera& cam, bool stereo, float depth)
+{
+    return stereo ? cos(2.0 * atan2(cam.fxb / cam.fx / 2.0, (double)depth)) : 2.0;
+}
+
+// The landmark of pair (k1 in view v1 = c, k2 in view v2 = n).  scale[octave] is the pyramid's scale table (octaves are the caller's to
+// keep inside it).  Returns 0 (no landmark; X is not written), 1 (triangulated), 2 (back-projection of k1), 3 (back-projection of k2).
+LP_TRI_FN int tri_pair(const Camera& cam, const float* scale, const View& v1, const View& v2, const Keypoint& k1, const Keypoint& k2, double* X_out)
+{
+    const bool st1 = is_stereo(cam, k1.depth), st2 = is_stereo(cam, k2.depth);
+    const double a1[2] = {((double)k1.x - cam.cx) / cam.fx, ((double)k1.y - cam.cy) / cam.fy};
+    const double a2[2] = {((double)k2.x - cam.cx) / cam.fx, ((double)k2.y - cam.cy) / cam.fy};
+    double r1[3], r2[3];
+    for (int a = 0; a < 3; ++a) { r1[a] = v1.R[a] * a1[0] + v1.R[3 + a] * a1[1] + v1.R[6 + a]; r2[a] = v2.R[a] * a2[0] + v2.R[3 + a] * a2[1] + v2.R[6 + a]; }
+    const double cos_rays = (r1[0] * r2[0] + r1[1] * r2[1] + r1[2] * r2[2]) / (sqrt(r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2]) * sqrt(r2[0] * r2[0] + r2[1] * r2[1] + r2[2] * r2[2]));
+    const double cs1 = cos_stereo(cam, st1, k1.depth), cs2 = cos_stereo(cam, st2, k2.depth);
+    const double cs = cs1 < cs2 ? cs1 : cs2;
+    int code = 0;
+    double X[3] = {0, 0, 0};
+    if (cos_rays < cs && cos_rays > 0.0 && (st1 || st2 || cos_rays < 0.9998)) {
+        double P1[12], P2[12];
+        projection(cam, v1, P1); projection(cam, v2, P2);
+        if (!triangulate_linear(P1, P2, (double)k1.x, (double)k1.y, (double)k2.x, (double)k2.y, X)) return 0;
+        code = 1;
+    } else if (st1 && cs1 < cs2) { back_project(cam, v1, k1, X); code = 2; }
+    else if (st2 && cs2 < cs1) { back_project(cam, v2, k2, X); code = 3; }
+    else return 0;
+    const double s1 = (double)scale[k1.octave], s2 = (double)scale[k2.octave];
+    double d1, d2;
+    if (!view_accepts(cam, v1, k1, st1, s1, X, &d1)) return 0;
+    if (!view_accepts(cam, v2, k2, st2, s2, X, &d2)) return 0;
+    // the distances agree with the pyramid levels the keypoints were found at
+    const double ratio_d = d1 / d2, ratio_o = s2 / s1, rf = 1.5 * cam.scale_factor;
+    if (ratio_d * rf < ratio_o || ratio_d > ratio_o * rf) return 0;
+    X_out[0] = X[0]; X_out[1] = X[1]; X_out[2] = X[2];
+    return code;
+}
+
+// ---- host only from here on (plain inline functions) ------------------------------------------------------------------------------
+#if !defined(__HIP_DEVICE_COMPILE__)
+// The candidate lists of n1 queries against one neighbour: keys[8 * i + r] = distance << 32 | j, ascending (kNoKey: empty), count[i]
+// = how many candidates passed.  stereo1 / stereo2: per keypoint "is a stereo keypoint" (may be null: none).
+inline void candidates_host(const Keypoint* kp1, const uint8_t* desc1, const int32_t* group1, int n1, const Keypoint* kp2, const uint8_t* desc2,
+                            const int32_t* group2, int n2, const Camera& cam, const Epipolar& e, const float* scale, unsigned long long* keys, int32_t* count)
+{
+    for (int i = 0; i < n1; ++i) {
+        unsigned long long* top = keys + (size_t)kListed * i;
+        for (int r = 0; r < kListed; ++r) top[r] = kNoKey;
+        count[i] = 0;
+        if (group1[i] < 0) continue;
+        double l[3];
+        epipolar_line(e.F, (double)kp1[i].x, (double)kp1[i].y, l);
+        const bool st1 = is_stereo(cam, kp1[i].depth);
+        uint32_t a[8], b[8];
+        for (int w = 0; w < 8; ++w) a[w] = (uint32_t)desc1[32 * (size_t)i + 4 * w] | (uint32_t)desc1[32 * (size_t)i + 4 * w + 1] << 8 | (uint32_t)desc1[32 * (size_t)i + 4 * w + 2] << 16 | (uint32_t)desc1[32 * (size_t)i + 4 * w + 3] << 24;
+        for (int j = 0; j < n2; ++j) {
+            if (group2[j] < 0 || group2[j] != group1[i]) continue;
+            if (!gate_geometry(l, st1 || is_stereo(cam, kp2[j].depth), e, (double)kp2[j].x, (double)kp2[j].y, (double)scale[kp2[j].octave])) continue;
+            for (int w = 0; w < 8; ++w) b[w] = (uint32_t)desc2[32 * (size_t)j + 4 * w] | (uint32_t)desc2[32 * (size_t)j + 4 * w + 1] << 8 | (uint32_t)desc2[32 * (size_t)j + 4 * w + 2] << 16 | (uint32_t)desc2[32 * (size_t)j + 4 * w + 3] << 24;
+            const int h = hamming(a, b);
+            if (h > kHammingMax) continue;
+            ++count[i];
+            unsigned long long key = (unsigned long long)h << 32 | (unsigned long long)j;
+            for (int r = 0; r < kListed; ++r) if (key < top[r]) { const unsigned long long tmp = top[r]; top[r] = key; key = tmp; }
+        }
+    }
+}
+
+// The ordered replay of one neighbour: queries in ascending i, the first listed candidate not yet taken in n is the match and takes j.
+// match[i] = j or -1 and rank[i] = its position in the list; a query whose list is used up while more than kListed candidates passed
+// adds one to *exhausted.  `skip` (may be null): queries that are not served.
+inline void replay_host(const unsigned long long* keys, const int32_t* count, int n1, int n2, const uint8_t* skip, int32_t* match, int32_t* rank, int* exhausted)
+{
+    std::vector<uint8_t> taken((size_t)(n2 > 0 ? n2 : 0), 0);
+    for (int i = 0; i < n1; ++i) {
+        match[i] = -1; rank[i] = -1;
+        if ((skip && skip[i]) || count[i] <= 0) continue;
+        for (int r = 0; r < kListed; ++r) {
+            const unsigned long long key = keys[(size_t)kListed * i + r];
+            if (key == kNoKey) break;
+            const int j = (int)(key & 0xffffffffu);
+            if (j < 0 || j >= n2 || taken[(size_t)j]) continue;
+            taken[(size_t)j] = 1; match[i] = j; rank[i] = r;
+            break;
+        }
+        if (match[i] < 0 && count[i] > kListed && exhausted) ++*exhausted;
+    }
+}
+
+// The neighbour gate: true when the camera centres of c and n are at least `min_distance` apart (stereo: the true baseline;
+// monocular: baselineDistThresh x the median depth of n's landmarks in n's frame).
+inline bool baseline_accepts(const View& c, const View& n, double min_distance)
+{
+    double d2 = 0;
+    for (int a = 0; a < 3; ++a) {
+        const double cc = -(c.R[a] * c.t[0] + c.R[3 + a] * c.t[1] + c.R[6 + a] * c.t[2]);
+        const double cn = -(n.R[a] * n.t[0] + n.R[3 + a] * n.t[1] + n.R[6 + a] * n.t[2]);
+        d2 += (cc - cn) * (cc - cn);
+    }
+    return !(sqrt(d2) < min_distance);
+}
+
+// F with x_n^T F x_c = 0 (pixels) and the epipole of c in n, from the two views -- the arithmetic of monoTriangulate's essential
+// matrix, with the intrinsics folded in: F = K^-T [t]x R K^-1, R, t the pose of n relative to c.
+inline Epipolar epipolar_from_views(const Camera& cam, const View& c, const View& n)
+{
+    double R[9], t[3];
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) R[r * 3 + k] = n.R[r * 3] * c.R[k * 3] + n.R[r * 3 + 1] * c.R[k * 3 + 1] + n.R[r * 3 + 2] * c.R[k * 3 + 2];
+    for (int r = 0; r < 3; ++r) t[r] = n.t[r] - (R[r * 3] * c.t[0] + R[r * 3 + 1] * c.t[1] + R[r * 3 + 2] * c.t[2]);
+    const double tx[9] = {0, -t[2], t[1], t[2], 0, -t[0], -t[1], t[0], 0};
+    double E[9];
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) E[r * 3 + k] = tx[r * 3] * R[k] + tx[r * 3 + 1] * R[3 + k] + tx[r * 3 + 2] * R[6 + k];
+    // K^-T E K^-1 with K^-1 = [1/fx 0 -cx/fx; 0 1/fy -cy/fy; 0 0 1]
+    const double ki[9] = {1.0 / cam.fx, 0, -cam.cx / cam.fx, 0, 1.0 / cam.fy, -cam.cy / cam.fy, 0, 0, 1};
+    double EK[9];
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) EK[r * 3 + k] = E[r * 3] * ki[k] + E[r * 3 + 1] * ki[3 + k] + E[r * 3 + 2] * ki[6 + k];
+    Epipolar e{};
+    for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) e.F[r * 3 + k] = ki[r] * EK[k] + ki[3 + r] * EK[3 + k] + ki[6 + r] * EK[6 + k];
+    // c's centre in n's frame is t
+    e.has_epipole = t[2] != 0.0 ? 1 : 0;
+    if (e.has_epipole) { e.ex = cam.fx * t[0] / t[2] + cam.cx; e.ey = cam.fy * t[1] / t[2] + cam.cy; }
+    return e;
+}
+#endif
+
+}  // namespace lpslam_tri

@@ -20,6 +20,7 @@ BA_OBS_DTYPE = np.dtype([("pose", "<i4"), ("point", "<i4"), ("u", "<f8"), ("v", 
 SIM3_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("meas", "<f8", (8,))])
 SIM3_PAIR_DTYPE = np.dtype([("p1c", "<f8", (3,)), ("p2c", "<f8", (3,)), ("obs1", "<f8", (2,)), ("obs2", "<f8", (2,)),
                             ("inv_sigma2_1", "<f8"), ("inv_sigma2_2", "<f8")])
+TRI_KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("x_right", "<f4"), ("depth", "<f4")])      # lpslam_hip_tri_keypoint
 PROJ_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("x_right", "<f4"), ("radius", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
 SCAN_POSE_DTYPE = np.dtype([("key", "<i4"), ("pad", "<i4"), ("origin", "<f8", (2,)), ("fwd", "<f8", (2,)), ("left", "<f8", (2,))])
 BA_LOG_DTYPE = np.dtype([("chi2_before", "<f8"), ("chi2_after", "<f8"), ("lambda", "<f8"),
@@ -49,6 +50,7 @@ SYMBOLS = [
     "lpslam_hip_adjust_intensity", "lpslam_hip_upload_raw_image_adjusted", "lpslam_hip_front_end_images_adjusted", "lpslam_hip_adjust_intensity_last",
     "lpslam_hip_upload_pixels", "lpslam_hip_upload_raw_pixels", "lpslam_hip_front_end_pixels",
     "lpslam_hip_set_keypoint_camera", "lpslam_hip_stage_undistort", "lpslam_hip_undistort_dropped", "lpslam_hip_undistort_points",
+    "lpslam_hip_triangulate_neighbours", "lpslam_hip_triangulate_pairs",
 ]
 
 
@@ -75,6 +77,20 @@ class Fisheye(C.Structure):
 
     def __init__(self, fx, fy, cx, cy, k=(0.0, 0.0, 0.0, 0.0), max_angle_deg=70.0):
         super().__init__(float(fx), float(fy), float(cx), float(cy), (C.c_double * 4)(*[float(v) for v in k]), float(np.deg2rad(max_angle_deg)))
+
+
+class TriCamera(C.Structure):
+    """lpslam_hip_tri_camera: focal_x_baseline 0 = a monocular camera"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("focal_x_baseline", C.c_double), ("scale_factor", C.c_double)]
+
+    def __init__(self, fx, fy, cx, cy, focal_x_baseline=0.0, scale_factor=1.2):
+        super().__init__(float(fx), float(fy), float(cx), float(cy), float(focal_x_baseline), float(scale_factor))
+
+
+class TriSet(C.Structure):
+    """lpslam_hip_tri_set: one neighbour keyframe in host memory"""
+    _fields_ = [("kpts", C.c_void_p), ("desc32", C.c_void_p), ("group", C.c_void_p), ("x_right", C.c_void_p), ("depth", C.c_void_p), ("n", C.c_int32),
+                ("pose", C.c_double * 7), ("F", C.c_double * 9), ("epipole", C.c_double * 2), ("has_epipole", C.c_int32)]
 
 
 class BaCamera(C.Structure):
@@ -486,6 +502,54 @@ class Context:
         out = np.full(xy.shape, np.nan, np.float32); valid = np.zeros(len(xy), np.uint8)
         _check(f(self.h, C.byref(model), _p(xy), len(xy), _p(out), _p(valid)))
         return out, valid.astype(bool)
+
+    def triangulate_neighbours(self, image, group1, pose1, cam, sets, scale=None, capacity=None):
+        """lpslam_hip_triangulate_neighbours: the keypoints of slot `image` (view pose1, 7 doubles) against `sets`, a list of dicts with
+        kpts (KP_DTYPE), desc (n, 32), group (int32), optional x_right / depth (float32), pose (7), F (3, 3), epipole ((x, y) or None).
+        Returns a dict of arrays per (set, query): j, dist, code (n_sets, nq, 8), X (n_sets, nq, 8, 3), count (n_sets, nq)."""
+        f = self.lib.lpslam_hip_triangulate_neighbours
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TriCamera), C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                      C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        scale = np.ascontiguousarray(self.scale if scale is None else scale, np.float32)
+        cap = self.max_kp if capacity is None else int(capacity)
+        ns = len(sets)
+        keep, arr = [], (TriSet * max(ns, 1))()
+        for k, s in enumerate(sets):
+            kp = np.ascontiguousarray(s["kpts"], KP_DTYPE); desc = np.ascontiguousarray(s["desc"], np.uint8); grp = np.ascontiguousarray(s["group"], np.int32)
+            xr = None if s.get("x_right") is None else np.ascontiguousarray(s["x_right"], np.float32)
+            dep = None if s.get("depth") is None else np.ascontiguousarray(s["depth"], np.float32)
+            keep += [kp, desc, grp, xr, dep]
+            t = arr[k]
+            t.kpts, t.desc32, t.group = kp.ctypes.data, desc.ctypes.data, grp.ctypes.data
+            t.x_right = None if xr is None else xr.ctypes.data; t.depth = None if dep is None else dep.ctypes.data
+            t.n = int(s.get("n", len(kp)))
+            t.pose = (C.c_double * 7)(*[float(v) for v in s["pose"]]); t.F = (C.c_double * 9)(*[float(v) for v in np.asarray(s["F"], np.float64).reshape(9)])
+            ep = s.get("epipole")
+            t.has_epipole = 0 if ep is None else 1
+            t.epipole = (C.c_double * 2)(*([0.0, 0.0] if ep is None else [float(ep[0]), float(ep[1])]))
+        group1 = None if group1 is None else np.ascontiguousarray(group1, np.int32)
+        pose1 = np.ascontiguousarray(pose1, np.float64)
+        j = np.full((ns, cap, 8), -1, np.int32); dist = np.full((ns, cap, 8), 256, np.int32); code = np.zeros((ns, cap, 8), np.int32)
+        X = np.full((ns, cap, 8, 3), np.nan, np.float64); count = np.zeros((ns, cap), np.int32)
+        nq = C.c_int32(0)
+        _check(f(self.h, int(image), _p(group1), _p(pose1), C.byref(cam), arr if ns else None, ns, _p(scale), len(scale), cap,
+                 C.byref(nq), _p(j), _p(dist), _p(code), _p(X), _p(count)))
+        n = nq.value
+        return {"j": j[:, :n], "dist": dist[:, :n], "code": code[:, :n], "X": X[:, :n], "count": count[:, :n]}
+
+    def triangulate_pairs(self, cam, pose1, pose2, kp1, kp2, scale=None):
+        """tri_pair on caller pairs (TRI_KP_DTYPE arrays): (code (n,) int32, X (n, 3) float64, NaN where the code is 0)"""
+        f = self.lib.lpslam_hip_triangulate_pairs
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.POINTER(TriCamera), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        scale = np.ascontiguousarray(self.scale if scale is None else scale, np.float32)
+        kp1 = np.ascontiguousarray(kp1, TRI_KP_DTYPE); kp2 = np.ascontiguousarray(kp2, TRI_KP_DTYPE)
+        assert len(kp1) == len(kp2)
+        pose1 = np.ascontiguousarray(pose1, np.float64); pose2 = np.ascontiguousarray(pose2, np.float64)
+        code = np.zeros(len(kp1), np.int32); X = np.full((len(kp1), 3), np.nan, np.float64)
+        _check(f(self.h, C.byref(cam), _p(scale), len(scale), _p(pose1), _p(pose2), _p(kp1), _p(kp2), len(kp1), _p(code), _p(X)))
+        return code, X
 
     def keypoints(self, image):
         kp = np.zeros(self.max_kp, KP_DTYPE); desc = np.zeros((self.max_kp, 32), np.uint8)

@@ -34,6 +34,8 @@ HipVslamTrackerBase::HipVslamTrackerBase()
     o.optional("device", 0); o.optional("keyframeInterval", 6); o.optional("localWindow", 10); o.optional("asyncMapping", true); o.optional("prefetch", true); o.optional("mapCulling", true); o.optional("mappingReserve", 0);
     // monocular fisheye cameras: keypoints whose ray lies further than this from the optical axis are dropped (degrees, (0, 89])
     o.optional("fisheyeMaxAngleDeg", 70.0);
+    // new landmarks by triangulation against this many covisible keyframes (0 .. 32; 0 = off)
+    o.optional("triangulateNeighbours", 0);
 }
 
 HipVslamTrackerBase::~HipVslamTrackerBase() { stop(); }
@@ -59,6 +61,7 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_mappingReserve = std::min(16, std::max(0, o.getInteger("mappingReserve")));
     m_prefetch = o.getBool("prefetch"); m_mapCulling = o.getBool("mapCulling");
     m_fisheyeMaxAngleDeg = o.getDouble("fisheyeMaxAngleDeg");
+    m_triangulateNeighbours = o.getInteger("triangulateNeighbours");
 }
 
 // The keypoint camera of a monocular session: the fisheye model from the camera configuration (f_x, f_y, c_x, c_y, dist[0..3]) with
@@ -160,6 +163,10 @@ bool HipVslamTrackerBase::startContext(bool stereo)
             logMessage(LpSlamLogLevel_Error, "OpenVSLAM config file " + m_configFromFile + ": Feature.* values out of range");
             return false;
         }
+    }
+    if (!triangulateNeighboursOk(m_triangulateNeighbours)) {
+        logMessage(LpSlamLogLevel_Error, "triangulateNeighbours " + std::to_string(m_triangulateNeighbours) + " outside 0 .. " + std::to_string(lpslam_tri::kMaxSets));
+        return false;
     }
     // ImageProcessing::Undistort (reference: src/Utils/ImageProcessing.h:134-250): the maps are built once from the camera
     // pair and every frame is remapped -- here on the device (lpslam_hip_upload_raw_image).  The reference does this for the
@@ -381,12 +388,14 @@ int HipVslamTrackerBase::resolve(int id) const
 
 // [UPSTREAM] graph_node::get_top_n_covisibilities: the keyframes that share landmarks with `kf`, by weight (number of shared
 // landmarks) descending, ties to the newer keyframe; at most top_n with weight >= min_weight, returned in ascending id order
-std::vector<int> HipVslamTrackerBase::covisible(int kf, int top_n, int min_weight) const
+std::vector<int> HipVslamTrackerBase::covisible(int kf, int top_n, int min_weight) const { return covisibleOf(m_kfs[(size_t)kf].landmark, kf, top_n, min_weight); }
+
+std::vector<int> HipVslamTrackerBase::covisibleOf(const std::vector<int>& landmark, int kf, int top_n, int min_weight) const
 {
     IdMarks& w = m_marksKf;                              // shared observations per keyframe
     w.begin(m_kfs.size());
     std::vector<int> touched;
-    for (int id : m_kfs[(size_t)kf].landmark) {
+    for (int id : landmark) {
         const Landmark* l = lm(id);
         if (!l) continue;
         for (auto& o : l->obs) if (o.first != kf) { if (!w.has(o.first)) touched.push_back(o.first); w.at(o.first)++; }
@@ -540,6 +549,14 @@ bool HipVslamTrackerBase::frameNodes(const FrameData& f, std::vector<int32_t>& n
     return true;
 }
 
+namespace {
+struct ScopedSeconds {                                   // adds the scope's wall time to a statistics field
+    double& acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    explicit ScopedSeconds(double& a) : acc(a) {}
+    ~ScopedSeconds() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+};
+}  // namespace
+
 int HipVslamTrackerBase::insertKeyframe(FrameData& f)
 {
     const int c = (int)m_kfs.size();
@@ -585,12 +602,19 @@ int HipVslamTrackerBase::insertKeyframe(FrameData& f)
             else f.landmark[i] = -1;
         }
     }
-    if (!m_stereo && c > m_segmentStart) monoTriangulate(c - 1, kf, f);
+    bool bow_done = false;
+    if (m_triangulateNeighbours > 0) {
+        ScopedSeconds timed(m_stats.t_kf_triangulate);
+        // with a vocabulary the candidates' groups are the tree nodes: the keyframe's walk comes first (the descriptors are still in its slot)
+        if (m_vocab) { kf.kpts = f.kpts; kf.desc = f.desc; if (!frameNodes(f, kf.node, &kf.bow)) computeBow(kf); bow_done = true; }
+        if (c > m_segmentStart) triangulateNeighbours(kf, f);
+    }
+    else if (!m_stereo && c > m_segmentStart) monoTriangulate(c - 1, kf, f);
     kf.kpts = f.kpts; kf.desc = f.desc; kf.x_right = f.x_right; kf.depth = f.depth; kf.landmark = f.landmark;
     if (m_vocab) {
         static const bool trace = getenv("LPSLAM_HIP_MATCH_TRACE") != nullptr;
         const auto t0 = std::chrono::steady_clock::now();
-        if (!frameNodes(f, kf.node, &kf.bow)) computeBow(kf);      // the frame's descriptors are still in its slot: no upload
+        if (!bow_done && !frameNodes(f, kf.node, &kf.bow)) computeBow(kf);      // the frame's descriptors are still in its slot: no upload
         const auto t1 = std::chrono::steady_clock::now();
         m_bowDb.add(c, kf.bow);
         if (trace) fprintf(stderr, "kf_bow: transform %.1f us, database %.1f us\n", 1e6 * std::chrono::duration<double>(t1 - t0).count(), 1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count());
@@ -621,13 +645,6 @@ int HipVslamTrackerBase::insertKeyframe(FrameData& f)
 }
 
 // motion-only pose optimisation ([UPSTREAM] optimize::pose_optimizer) over keypoint <-> landmark associations
-namespace {
-struct ScopedSeconds {                                   // adds the scope's wall time to a statistics field
-    double& acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    explicit ScopedSeconds(double& a) : acc(a) {}
-    ~ScopedSeconds() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-};
-}  // namespace
 
 // the bundle adjuster's camera: chi-square bounds of 2 (monocular) and 3 (stereo) degrees of freedom at 95 %
 lpslam_hip_ba_camera HipVslamTrackerBase::baCamera(bool with_baseline) const
@@ -1274,6 +1291,119 @@ void HipVslamTrackerBase::monoTriangulate(int prev_kf, Keyframe& kf, FrameData& 
     (void)kf;
 }
 
+std::vector<int> triangulationNeighbourList(const std::vector<int>& covisible, int prev, int n)
+{
+    std::vector<int> out(covisible);
+    if (prev >= 0 && std::find(out.begin(), out.end(), prev) == out.end()) out.insert(out.begin(), prev);
+    if ((int)out.size() > n) out.resize((size_t)std::max(n, 0));
+    return out;
+}
+
+double medianDepth(std::vector<double> depths)
+{
+    if (depths.empty()) return -1.0;
+    std::sort(depths.begin(), depths.end());
+    return depths[(depths.size() - 1) / 2];
+}
+
+// New landmarks for the keyframe being inserted, triangulateNeighbours > 0 ([UPSTREAM] mapping_module::create_new_landmarks; the rule
+// is this project's own, csrc/triangulate_math.h).  The neighbours: covisible(c, N, 15), a monocular session's previous keyframe in
+// front; one whose camera centre is closer than the true baseline (stereo) or baselineDistThresh x the median depth of its landmarks
+// (monocular) is skipped.  The device returns, per (neighbour, keypoint without a landmark), the eight nearest candidates that pass
+// the gate and the landmark each would make; the order-dependent part is replayed here, neighbour by neighbour.
+void HipVslamTrackerBase::triangulateNeighbours(Keyframe& kf, FrameData& f)
+{
+    const int c = (int)m_kfs.size();
+    const int n1 = (int)f.kpts.size();
+    if (n1 == 0) return;
+    const bool use_nodes = m_vocab && kf.node.size() == f.kpts.size();
+    const int prev = (!m_stereo && c - 1 >= m_segmentStart && m_kfs[(size_t)c - 1].segment == m_segment) ? c - 1 : -1;
+    const std::vector<int> listed = triangulationNeighbourList(covisibleOf(f.landmark, c, m_triangulateNeighbours, 15), prev, m_triangulateNeighbours);
+    const lpslam_tri::Camera cam{m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y, m_stereo ? m_cam.focal_x_baseline : 0.0, m_scaleFactor};
+    double pose_c[7] = {f.pose.q[0], f.pose.q[1], f.pose.q[2], f.pose.q[3], f.pose.t[0], f.pose.t[1], f.pose.t[2]};
+    const lpslam_tri::View view_c = lpslam_tri::view_from_pose(pose_c);
+    std::vector<int> nbs;
+    std::vector<lpslam_hip_tri_set> sets;
+    std::vector<std::vector<int32_t>> groups;
+    for (int k : listed) {
+        if (k < 0 || k >= c) continue;
+        const Keyframe& nb = m_kfs[(size_t)k];
+        if (nb.erased || nb.kpts.empty() || (use_nodes && nb.node.size() != nb.kpts.size())) continue;
+        lpslam_hip_tri_set s{};
+        const double pose_n[7] = {nb.pose.q[0], nb.pose.q[1], nb.pose.q[2], nb.pose.q[3], nb.pose.t[0], nb.pose.t[1], nb.pose.t[2]};
+        std::copy(pose_n, pose_n + 7, s.pose);
+        const lpslam_tri::View view_n = lpslam_tri::view_from_pose(pose_n);
+        double min_distance = m_cam.focal_x_baseline / m_cam.f_x;
+        if (!m_stereo) {
+            const Mat3 R = quatToRot(nb.pose.q);
+            std::vector<double> depths;
+            for (int id : nb.landmark) if (const Landmark* l = lm(id)) depths.push_back(R.m[6] * l->p[0] + R.m[7] * l->p[1] + R.m[8] * l->p[2] + nb.pose.t[2]);
+            const double median = medianDepth(std::move(depths));
+            if (!(median > 0)) continue;
+            min_distance = m_baselineDistThresh * median;
+        }
+        if (!lpslam_tri::baseline_accepts(view_c, view_n, min_distance)) continue;
+        const lpslam_tri::Epipolar e = lpslam_tri::epipolar_from_views(cam, view_c, view_n);
+        std::copy(e.F, e.F + 9, s.F); s.epipole[0] = e.ex; s.epipole[1] = e.ey; s.has_epipole = e.has_epipole;
+        std::vector<int32_t> g(nb.kpts.size());
+        for (size_t j = 0; j < g.size(); ++j) g[j] = nb.landmark[j] >= 0 ? -1 : (use_nodes ? std::max(nb.node[j], 0) : 0);
+        groups.push_back(std::move(g));
+        s.kpts = nb.kpts.data(); s.desc32 = nb.desc.data(); s.n = (int32_t)nb.kpts.size();
+        const bool stereo_cols = m_stereo && nb.x_right.size() == nb.kpts.size() && nb.depth.size() == nb.kpts.size();
+        s.x_right = stereo_cols ? nb.x_right.data() : nullptr; s.depth = stereo_cols ? nb.depth.data() : nullptr;
+        sets.push_back(s); nbs.push_back(k);
+    }
+    if (sets.empty()) return;
+    for (size_t i = 0; i < sets.size(); ++i) sets[i].group = groups[i].data();
+    std::vector<int32_t> group1((size_t)n1);
+    for (int i = 0; i < n1; ++i) group1[(size_t)i] = f.landmark[(size_t)i] >= 0 ? -1 : (use_nodes ? std::max(kf.node[(size_t)i], 0) : 0);
+    const size_t rows = sets.size() * (size_t)n1;
+    std::vector<int32_t> out_j(rows * 8), out_dist(rows * 8), out_code(rows * 8), out_count(rows);
+    std::vector<double> out_X(rows * 24);
+    int32_t nq = 0;
+    const lpslam_hip_tri_camera dev_cam{cam.fx, cam.fy, cam.cx, cam.cy, cam.fxb, cam.scale_factor};
+    if (lpslam_hip_triangulate_neighbours(m_ctx, f.slot, group1.data(), pose_c, &dev_cam, sets.data(), (int32_t)sets.size(), m_scales, m_numLevels, n1, &nq,
+                                          out_j.data(), out_dist.data(), out_code.data(), out_X.data(), out_count.data()) != LPSLAM_HIP_OK || nq != n1) {
+        logMessage(LpSlamLogLevel_Error, std::string("triangulateNeighbours: ") + lpslam_hip_last_error());
+        return;
+    }
+    const std::vector<float> angle_c = keypointAngles(f.kpts);
+    std::vector<uint8_t> skip((size_t)n1);
+    std::vector<int32_t> match((size_t)n1), rank((size_t)n1);
+    std::vector<unsigned long long> keys((size_t)n1 * 8);
+    for (size_t s = 0; s < sets.size(); ++s) {
+        Keyframe& nb = m_kfs[(size_t)nbs[s]];
+        const size_t row0 = s * (size_t)n1;
+        for (int i = 0; i < n1; ++i) {
+            skip[(size_t)i] = f.landmark[(size_t)i] >= 0;            // carries a landmark by now (an earlier neighbour made it)
+            for (int r = 0; r < 8; ++r) { const int32_t j = out_j[(row0 + (size_t)i) * 8 + (size_t)r]; keys[(size_t)i * 8 + (size_t)r] = j < 0 ? lpslam_tri::kNoKey : ((unsigned long long)out_dist[(row0 + (size_t)i) * 8 + (size_t)r] << 32 | (unsigned long long)j); }
+        }
+        int exhausted = 0;
+        lpslam_tri::replay_host(keys.data(), out_count.data() + row0, n1, (int)nb.kpts.size(), skip.data(), match.data(), rank.data(), &exhausted);
+        m_stats.tri_exhausted += exhausted;
+        ++m_stats.tri_pairs;
+        const std::vector<float> angle_n = keypointAngles(nb.kpts);
+        int32_t kept = 0;
+        (void)lpslam_hip_match_orientation_filter(angle_c.data(), angle_n.data(), match.data(), n1, &kept);
+        for (int i = 0; i < n1; ++i) {
+            const int j = match[(size_t)i];
+            if (j < 0 || nb.landmark[(size_t)j] >= 0) continue;
+            const size_t ent = (row0 + (size_t)i) * 8 + (size_t)rank[(size_t)i];
+            if (out_code[ent] == 0) continue;
+            Landmark lmk;
+            lmk.p[0] = out_X[3 * ent]; lmk.p[1] = out_X[3 * ent + 1]; lmk.p[2] = out_X[3 * ent + 2];
+            initLandmarkView(lmk, f.pose, f.kpts[(size_t)i], f.desc.data() + 32 * (size_t)i);
+            lmk.ref_kf = c;
+            lmk.obs.emplace_back(nbs[s], j); lmk.obs.emplace_back(c, i);
+            const int id = m_nextLandmarkId++;
+            m_landmarks[id] = std::move(lmk); indexLandmark(id);
+            m_freshLandmarks.push_back(id);
+            f.landmark[(size_t)i] = id; nb.landmark[(size_t)j] = id;
+            ++m_stats.triangulated;
+        }
+    }
+}
+
 // ---- relocalisation ([UPSTREAM] module::relocalizer, reached while the tracker state is Lost) -----------------------------------
 // Candidates: the keyframes nearest to the last pose that was tracked (the reference picks them from the BoW database; with
 // relocWithNavigation the navigation prior moves that pose along).  Each candidate's descriptors are matched against the frame
@@ -1871,14 +2001,15 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
                   s.ba_failed, (long)dev[LPSLAM_HIP_BA_COUNTER_SIGNATURES], (long)dev[LPSLAM_HIP_BA_COUNTER_GRAPHS], (long)dev[LPSLAM_HIP_BA_COUNTER_REPLAYS],
                   (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted, s.color_converted, s.fisheye_dropped,
                   s.t_total * per, s.t_front * per, s.t_track * per, s.t_local * per, s.t_keyframe * per,
-                  s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per);
+                  s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per,
+                  s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per);
     m_lastStatistics = buf;
     logMessage(LpSlamLogLevel_Info, buf);
 }

@@ -12,6 +12,7 @@
 #include "pose_math.h"
 #include "map_file.h"
 #include "../csrc/fisheye_math.h"
+#include "../csrc/triangulate_math.h"
 #include "../../include/lpslam_hip.h"
 
 #include <array>
@@ -98,11 +99,13 @@ protected:
         long ba_failed = 0;                           // windows whose solve failed on the device (result dropped)
         long local_ba = 0, loops_closed = 0, loop_fused = 0, global_ba = 0, lost = 0, relocalised = 0, reinitialised = 0, nav_priors = 0, prefetched = 0;
         long color_converted = 0;                     // frames whose colour / YUV source was converted to grey on the device
+        long triangulated = 0, tri_pairs = 0, tri_exhausted = 0;      // triangulateNeighbours: landmarks made, (keyframe, neighbour) pairs served, queries whose eight candidates were all taken while more had passed
         long fisheye_dropped = 0;                     // fisheye session: keypoints the undistort stage removed (beyond the angle limit or 90 degrees, not converged), summed
         long intensity_adjusted = 0;                  // frames whose intensity adjustment ran on the device (a request the host had applied already does not count)
         // where the frames' time went (seconds, summed): front end (upload, extraction, stereo, read-back), tracking against the
         // previous frame, local-map tracking, keyframe work on the tracking thread (insertion, fusion, loop search, BA set-up / wait)
         double t_front = 0, t_track = 0, t_local = 0, t_keyframe = 0, t_total = 0;
+        double t_kf_triangulate = 0;                  // inside t_kf_insert: the triangulation step
         double t_kf_wait = 0, t_kf_apply = 0, t_kf_insert = 0, t_kf_loop = 0, t_kf_prepare = 0, t_map_solve = 0;      // keyframe path: waiting for the previous window's solve, applying it, the new keyframe, the next window's set-up; the mapping thread's solve
         double t_prefetch_wait = 0, t_prefetch_busy = 0;       // this thread waiting for the prefetch thread at the end of a frame / that thread's own time per frame
         double t_dev_match = 0, t_dev_pose = 0, t_dev_upload = 0, t_dev_extract = 0, t_dev_get = 0;      // inside the above: device calls
@@ -151,6 +154,11 @@ protected:
     // by triangulation between consecutive keyframes ([UPSTREAM] mapping_module::create_new_landmarks, previous keyframe only)
     bool monoInitialize(FrameData& cur);
     void monoTriangulate(int prev_kf, Keyframe& kf, FrameData& f);
+    // triangulateNeighbours > 0: the keypoints of the keyframe being inserted (id = m_kfs.size(), keypoints in f.slot) that carry no
+    // landmark against those of its best covisible keyframes -- candidate lists and tri_pair on the device
+    // (lpslam_hip_triangulate_neighbours), ordered replay and orientation filter here
+    void triangulateNeighbours(Keyframe& kf, FrameData& f);
+    std::vector<int> covisibleOf(const std::vector<int>& landmark, int kf, int top_n, int min_weight) const;      // covisible() of a keyframe that is not stored yet
     bool detectAndCloseLoop(FrameData& cur, int c);
     void initLandmarkView(Landmark& lm, const Pose& pose, const lpslam_hip_keypoint& kp, const uint8_t* desc32) const;
     int insertKeyframe(FrameData& f);
@@ -221,7 +229,8 @@ protected:
     int m_mappingReserve = 0;                      // compute units of every XCD the front end leaves to the mapping thread's solves
     std::string m_configFromFile, m_cameraSetup = "monocular", m_vocabFile = "orb_vocab.dbow2", m_mapFilename = "map.db";
     int m_slamKeypoints = 1200, m_viewerFps = 10;
-    double m_baselineDistThresh = 0.1, m_maxLaserAge = 1.0;
+    double m_baselineDistThresh = 0.1, m_maxLaserAge = 1.0;      // baselineDistThresh: read by the triangulateNeighbours step only
+    int m_triangulateNeighbours = 0;                  // 0: as before (monocular: the previous keyframe by brute force; stereo: nothing); 1 .. 32: that many covisible keyframes
     // MI355X additions: the generated reference config hard-codes these
     int m_numLevels = 3, m_iniFastThr = 20, m_minFastThr = 7, m_device = 0, m_keyframeInterval = 6, m_localWindow = 10;
     double m_scaleFactor = 1.2;
@@ -330,6 +339,13 @@ protected:
 int resolveFisheyeModel(const LpSlamCameraConfiguration& cam, const std::unordered_map<std::string, std::string>& yaml, double max_angle_deg,
                         lpslam_fisheye::Model* out, std::string* why);
 bool loadFlatYaml(const std::string& path, std::unordered_map<std::string, std::string>& yaml, std::string* bad_line);
+// the triangulateNeighbours step's host rules (hip_tracker.cpp; also reached through the C shim, for tests without a device):
+// the option's range; the neighbour list -- the covisible keyframes in their order, for a monocular session the previous keyframe of the
+// segment (prev >= 0) in front when it is absent, cut to n; the median of a keyframe's landmark depths (the lower one of an even count,
+// -1 without landmarks)
+inline bool triangulateNeighboursOk(int n) { return n >= 0 && n <= lpslam_tri::kMaxSets; }
+std::vector<int> triangulationNeighbourList(const std::vector<int>& covisible, int prev, int n);
+double medianDepth(std::vector<double> depths);
 
 class HipStereoTracker : public HipVslamTrackerBase {
 public:

@@ -214,6 +214,55 @@ LPS_API void lpslam_fisheye_forward(const double* model, const double* xyz, size
         visible[i] = lpslam_fisheye::visible(m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], width, height) ? 1 : 0;
     }
 }
+// ---- the triangulation step's host forms (csrc/triangulate_math.h), for tests without a device; cam = {fx, fy, cx, cy, focal_x_baseline,
+// scale_factor}, poses = qw qx qy qz tx ty tz, keypoints = lpslam_hip_tri_keypoint ----
+static lpslam_tri::Camera tri_camera_of(const double* c) { return lpslam_tri::Camera{c[0], c[1], c[2], c[3], c[4], c[5]}; }
+static_assert(sizeof(lpslam_hip_tri_keypoint) == sizeof(lpslam_tri::Keypoint), "keypoint layout");
+// the candidate lists of n1 queries against one neighbour: keys[8 i + r] = distance << 32 | j (all ones: empty), count[i]
+LPS_API void lpslam_tri_candidates_host(const double* cam, const float* scale, const lpslam_hip_tri_keypoint* kp1, const uint8_t* desc1, const int32_t* group1, int n1,
+                                        const lpslam_hip_tri_keypoint* kp2, const uint8_t* desc2, const int32_t* group2, int n2, const double* F, const double* epipole,
+                                        int has_epipole, unsigned long long* keys, int32_t* count) {
+    lpslam_tri::Epipolar e{};
+    std::copy(F, F + 9, e.F);
+    e.has_epipole = has_epipole ? 1 : 0; e.ex = has_epipole ? epipole[0] : 0.0; e.ey = has_epipole ? epipole[1] : 0.0;
+    lpslam_tri::candidates_host(reinterpret_cast<const lpslam_tri::Keypoint*>(kp1), desc1, group1, n1, reinterpret_cast<const lpslam_tri::Keypoint*>(kp2), desc2, group2, n2,
+                                tri_camera_of(cam), e, scale, keys, count);
+}
+// tri_pair on n pairs: code[k], X[3 k ..] (NaN with code 0)
+LPS_API void lpslam_tri_pair_host(const double* cam, const float* scale, const double* pose1, const double* pose2, const lpslam_hip_tri_keypoint* kp1,
+                                  const lpslam_hip_tri_keypoint* kp2, int n, int32_t* code, double* X) {
+    const lpslam_tri::Camera c = tri_camera_of(cam);
+    const lpslam_tri::View v1 = lpslam_tri::view_from_pose(pose1), v2 = lpslam_tri::view_from_pose(pose2);
+    for (int k = 0; k < n; ++k) {
+        double x[3] = {std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::quiet_NaN(), std::numeric_limits<double>::quiet_NaN()};
+        code[k] = lpslam_tri::tri_pair(c, scale, v1, v2, reinterpret_cast<const lpslam_tri::Keypoint*>(kp1)[k], reinterpret_cast<const lpslam_tri::Keypoint*>(kp2)[k], x);
+        std::copy(x, x + 3, X + 3 * (size_t)k);
+    }
+}
+// the ordered replay of one neighbour; returns the number of exhausted queries
+LPS_API int lpslam_tri_replay_host(const unsigned long long* keys, const int32_t* count, int n1, int n2, const uint8_t* skip, int32_t* match, int32_t* rank) {
+    int exhausted = 0;
+    lpslam_tri::replay_host(keys, count, n1, n2, skip, match, rank, &exhausted);
+    return exhausted;
+}
+// F (9, row major), the epipole (2) and whether it exists, as the tracker derives them from the two poses
+LPS_API int lpslam_tri_epipolar(const double* cam, const double* pose_c, const double* pose_n, double* F, double* epipole) {
+    const lpslam_tri::Epipolar e = lpslam_tri::epipolar_from_views(tri_camera_of(cam), lpslam_tri::view_from_pose(pose_c), lpslam_tri::view_from_pose(pose_n));
+    std::copy(e.F, e.F + 9, F); epipole[0] = e.ex; epipole[1] = e.ey;
+    return e.has_epipole;
+}
+// the neighbour gate and list of the tracker: the option's range; the covisible keyframes with the previous keyframe (prev >= 0) in front,
+// cut to n (returns how many, out holds at most n); the camera-centre test; the median landmark depth
+LPS_API int lpslam_tri_option_ok(int n) { return LpSlam::triangulateNeighboursOk(n) ? 1 : 0; }
+LPS_API int lpslam_tri_neighbour_list(const int32_t* covisible, int n_covisible, int prev, int n, int32_t* out) {
+    const std::vector<int> v = LpSlam::triangulationNeighbourList(std::vector<int>(covisible, covisible + n_covisible), prev, n);
+    std::copy(v.begin(), v.end(), out);
+    return (int)v.size();
+}
+LPS_API int lpslam_tri_baseline_accepts(const double* pose_c, const double* pose_n, double min_distance) {
+    return lpslam_tri::baseline_accepts(lpslam_tri::view_from_pose(pose_c), lpslam_tri::view_from_pose(pose_n), min_distance) ? 1 : 0;
+}
+LPS_API double lpslam_tri_median_depth(const double* depths, int n) { return LpSlam::medianDepth(std::vector<double>(depths, depths + n)); }
 // the keypoint camera a monocular tracker of this manager would start with: camera 0 of its registry (the configuration file's
 // cameras[]), the YAML file of configFromFile (NULL or "": none) and fisheyeMaxAngleDeg.  1: model[9] filled; 0: not a fisheye camera;
 // -1: refused (the start would fail), why says it

@@ -528,3 +528,97 @@ def fisheye_session_model(mgr, yaml_path=None, max_angle_deg=70.0):
     model = np.zeros(9, np.float64); why = C.create_string_buffer(512)
     rc = int(f(mgr.h, (str(yaml_path).encode() if yaml_path else None), float(max_angle_deg), model.ctypes.data, why, 512))
     return (rc, model) if rc == 1 else (rc, why.value.decode() if rc < 0 else None)
+
+
+TRI_KP_DTYPE = [("x", "<f4"), ("y", "<f4"), ("octave", "<i4"), ("x_right", "<f4"), ("depth", "<f4")]      # lpslam_hip_tri_keypoint
+
+
+def tri_candidates_host(cam, scale, kp1, desc1, group1, kp2, desc2, group2, F, epipole):
+    """the host form of the triangulation step's candidate gate (csrc/triangulate_math.h), CPU only: cam = 6 numbers {fx, fy, cx, cy,
+    focal_x_baseline, scale_factor}, kp1 / kp2 arrays of TRI_KP_DTYPE, epipole (x, y) or None.  Returns (j (n1, 8) with -1, dist (n1, 8)
+    with 256, count (n1,), keys (n1, 8) uint64)"""
+    import numpy as np
+    f = load().lpslam_tri_candidates_host
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    f.restype = None
+    cam = np.ascontiguousarray(cam, np.float64); scale = np.ascontiguousarray(scale, np.float32)
+    kp1 = np.ascontiguousarray(kp1, np.dtype(TRI_KP_DTYPE)); kp2 = np.ascontiguousarray(kp2, np.dtype(TRI_KP_DTYPE))
+    desc1 = np.ascontiguousarray(desc1, np.uint8); desc2 = np.ascontiguousarray(desc2, np.uint8)
+    group1 = np.ascontiguousarray(group1, np.int32); group2 = np.ascontiguousarray(group2, np.int32)
+    F = np.ascontiguousarray(F, np.float64).reshape(9); ep = np.array([0.0, 0.0] if epipole is None else [epipole[0], epipole[1]], np.float64)
+    n1, n2 = len(kp1), len(kp2)
+    keys = np.full((n1, 8), 2 ** 64 - 1, np.uint64); count = np.zeros(n1, np.int32)
+    f(cam.ctypes.data, scale.ctypes.data, kp1.ctypes.data, desc1.ctypes.data, group1.ctypes.data, n1, kp2.ctypes.data, desc2.ctypes.data, group2.ctypes.data, n2,
+      F.ctypes.data, ep.ctypes.data, 0 if epipole is None else 1, keys.ctypes.data, count.ctypes.data)
+    empty = keys == np.uint64(2 ** 64 - 1)
+    j = np.where(empty, -1, (keys & np.uint64(0xffffffff)).astype(np.int64)).astype(np.int32)
+    dist = np.where(empty, 256, (keys >> np.uint64(32)).astype(np.int64)).astype(np.int32)
+    return j, dist, count, keys
+
+
+def tri_pair_host(cam, scale, pose1, pose2, kp1, kp2):
+    """the host form of tri_pair on n pairs: (code (n,) int32, X (n, 3) float64 with NaN where the code is 0)"""
+    import numpy as np
+    f = load().lpslam_tri_pair_host
+    f.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_void_p]; f.restype = None
+    cam = np.ascontiguousarray(cam, np.float64); scale = np.ascontiguousarray(scale, np.float32)
+    pose1 = np.ascontiguousarray(pose1, np.float64); pose2 = np.ascontiguousarray(pose2, np.float64)
+    kp1 = np.ascontiguousarray(kp1, np.dtype(TRI_KP_DTYPE)); kp2 = np.ascontiguousarray(kp2, np.dtype(TRI_KP_DTYPE))
+    n = len(kp1)
+    code = np.zeros(n, np.int32); X = np.full((n, 3), np.nan, np.float64)
+    f(cam.ctypes.data, scale.ctypes.data, pose1.ctypes.data, pose2.ctypes.data, kp1.ctypes.data, kp2.ctypes.data, n, code.ctypes.data, X.ctypes.data)
+    return code, X
+
+
+def tri_replay_host(keys, count, n2, skip=None):
+    """the ordered replay of one neighbour over candidate lists (keys (n1, 8) uint64): (match (n1,), rank (n1,), exhausted)"""
+    import numpy as np
+    f = load().lpslam_tri_replay_host
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = C.c_int
+    keys = np.ascontiguousarray(keys, np.uint64); count = np.ascontiguousarray(count, np.int32)
+    n1 = len(count)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    match = np.zeros(n1, np.int32); rank = np.zeros(n1, np.int32)
+    ex = f(keys.ctypes.data, count.ctypes.data, n1, int(n2), None if skip is None else skip.ctypes.data, match.ctypes.data, rank.ctypes.data)
+    return match, rank, int(ex)
+
+
+def tri_epipolar(cam, pose_c, pose_n):
+    """F (3, 3) with x_n^T F x_c = 0 and the epipole of c in n ((x, y) or None), as the tracker derives them"""
+    import numpy as np
+    f = load().lpslam_tri_epipolar
+    f.argtypes = [C.c_void_p] * 5; f.restype = C.c_int
+    cam = np.ascontiguousarray(cam, np.float64); pc = np.ascontiguousarray(pose_c, np.float64); pn = np.ascontiguousarray(pose_n, np.float64)
+    F = np.zeros(9, np.float64); ep = np.zeros(2, np.float64)
+    has = f(cam.ctypes.data, pc.ctypes.data, pn.ctypes.data, F.ctypes.data, ep.ctypes.data)
+    return F.reshape(3, 3), (float(ep[0]), float(ep[1])) if has else None
+
+
+def tri_option_ok(n):
+    """whether the tracker accepts triangulateNeighbours = n"""
+    f = load().lpslam_tri_option_ok; f.argtypes = [C.c_int]; f.restype = C.c_int
+    return bool(f(int(n)))
+
+
+def tri_neighbour_list(covisible, prev, n):
+    """the tracker's neighbour list: the covisible keyframes in their order, the previous keyframe (prev >= 0) in front when absent, cut to n"""
+    import numpy as np
+    f = load().lpslam_tri_neighbour_list; f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]; f.restype = C.c_int
+    cov = np.ascontiguousarray(covisible, np.int32)
+    out = np.zeros(len(cov) + 1, np.int32)
+    k = f(cov.ctypes.data, len(cov), int(prev), int(n), out.ctypes.data)
+    return [int(v) for v in out[:k]]
+
+
+def tri_baseline_accepts(pose_c, pose_n, min_distance):
+    import numpy as np
+    f = load().lpslam_tri_baseline_accepts; f.argtypes = [C.c_void_p, C.c_void_p, C.c_double]; f.restype = C.c_int
+    pc = np.ascontiguousarray(pose_c, np.float64); pn = np.ascontiguousarray(pose_n, np.float64)
+    return bool(f(pc.ctypes.data, pn.ctypes.data, float(min_distance)))
+
+
+def tri_median_depth(depths):
+    import numpy as np
+    f = load().lpslam_tri_median_depth; f.argtypes = [C.c_void_p, C.c_int]; f.restype = C.c_double
+    d = np.ascontiguousarray(depths, np.float64)
+    return float(f(d.ctypes.data, len(d)))
