@@ -19,16 +19,16 @@ _HOST = os.path.join("..", "host")
 UNIT_DEPS = {
     "api.hip": ["fisheye_math.h"],
     "frontend.hip": ["orb_pattern.inc", "fisheye_math.h"],
-    "match.hip": [],
+    "match.hip": ["desc_wave.h"],
     "ba.hip": ["ba_common.h", "chol_panel.inl", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl", "ba_host.inl", "ba_partitioned.inl"],
     "pose_opt.hip": ["ba_common.h"],
     "sim3.hip": ["ba_common.h"],
-    "bow.hip": [],
+    "bow.hip": ["desc_wave.h"],
     "share.hip": [],
     "occupancy.hip": [],
     "intensity.hip": [],
     "ingest.hip": ["ingest_math.h"],
-    "triangulate.hip": ["triangulate_math.h"],
+    "triangulate.hip": ["desc_wave.h", "triangulate_math.h"],
     "jpeg.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_tables.h")],
     "jpeg_dec.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_header.h"), os.path.join(_HOST, "jpeg_tables.h")],
 }

@@ -1404,14 +1404,7 @@ __global__ __launch_bounds__(256) void k_frame_to_host_req(DeliverBatch b, int o
     const int n_blocks = r.blocks;
     if ((int)blockIdx.x >= n_blocks) return;
     frame_to_host_body(r.d_count, r.kp, r.desc, r.xr, r.dep, r.st, o_kp, o_desc, o_xr, o_dep, slots, n_blocks);
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (n_blocks == 1 || atomicAdd(r.counter, 1u) == (unsigned)n_blocks - 1) {
-            if (n_blocks > 1) { *r.counter = 0; __threadfence(); }
-            __hip_atomic_store(r.flag, r.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    lp_signal_done_of(r.counter, r.flag, r.seq, (unsigned)n_blocks);
 }
 }  // namespace
 

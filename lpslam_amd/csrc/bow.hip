@@ -17,6 +17,7 @@
 // as the window matchers do (match.hip).
 #include <chrono>
 #include "internal.h"
+#include "desc_wave.h"
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -66,8 +67,7 @@ __global__ __launch_bounds__(256) void k_bow_transform16(const uint8_t* __restri
                 const int id = child_list[c];
                 const uint4* d4 = reinterpret_cast<const uint4*>(node_desc + 32 * (size_t)id);
                 const uint4 da = d4[0], db = d4[1];
-                const int d = __popc(qa.x ^ da.x) + __popc(qa.y ^ da.y) + __popc(qa.z ^ da.z) + __popc(qa.w ^ da.w) +
-                              __popc(qb.x ^ db.x) + __popc(qb.y ^ db.y) + __popc(qb.z ^ db.z) + __popc(qb.w ^ db.w);
+                const int d = hamming256(qa, qb, da, db);
                 best = min(best, ((unsigned)d << 16) | (unsigned)(c - c0));
             }
 #pragma unroll
@@ -81,12 +81,6 @@ __global__ __launch_bounds__(256) void k_bow_transform16(const uint8_t* __restri
     lp_signal_done(counter, flag, seq);
 }
 
-__device__ __forceinline__ unsigned long long wave_min_u64b(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
-
 // one wavefront per query: the 4 nearest free targets among positions [seg_lo, seg_hi) of the node-sorted target order;
 // key = distance << 32 | position (position order = target keypoint order inside a node: the first minimum wins)
 __device__ __forceinline__ void bow_topk_body(int bx, const uint8_t* __restrict__ q_desc, const int2* __restrict__ q_seg, const int* __restrict__ q_ids, int nq,
@@ -97,33 +91,21 @@ __device__ __forceinline__ void bow_topk_body(int bx, const uint8_t* __restrict_
     if (qslot >= nq) return;
     const int qi = q_ids ? q_ids[qslot] : qslot;
     const int2 seg = q_seg[qi];
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(q_desc + 32 * (size_t)qi);
     uint32_t a[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = qd[k];
-    const unsigned long long NONE = ~0ull;
-    unsigned long long top[4] = {NONE, NONE, NONE, NONE};
+    desc_load8(q_desc + 32 * (size_t)qi, a);
+    unsigned long long top[4] = {kNoKey, kNoKey, kNoKey, kNoKey};
     int cnt = 0;
     for (int s = seg.x + lane; s < seg.y; s += 64) {
         const int t = t_order ? t_order[s] : s;          // (no order table: the targets were sent down in node order)
         if (t_taken[t]) continue;
-        const uint32_t* d = reinterpret_cast<const uint32_t*>(t_desc + 32 * (size_t)t);
-        int dist = 0;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) dist += __popc(a[w] ^ d[w]);
+        const int dist = hamming256(a, reinterpret_cast<const uint32_t*>(t_desc + 32 * (size_t)t));
         unsigned long long key = ((unsigned long long)dist << 32) | (unsigned)s;
         ++cnt;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) if (key < top[r]) { const unsigned long long tmp = top[r]; top[r] = key; key = tmp; }
+        topk_insert(top, key);
     }
-    for (int o2 = 32; o2 > 0; o2 >>= 1) cnt += __shfl_xor(cnt, o2);
+    cnt = wave_sum_i32(cnt);
     unsigned long long res[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const unsigned long long m = wave_min_u64b(top[0]);
-        res[r] = m;
-        if (top[0] == m && m != NONE) { top[0] = top[1]; top[1] = top[2]; top[2] = top[3]; top[3] = NONE; }
-    }
+    wave_topk_pop(top, [&](int r, unsigned long long m) { res[r] = m; });
     if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) out_keys[4 * (size_t)qslot + r] = res[r];

@@ -333,20 +333,23 @@ int lp_launch_deliver_batch(hipStream_t s, const LpDeliverReq* reqs, int n, int 
 // A small read-back through the copy engines costs a packet round trip per transfer plus the wait for the stream (15 - 25 us for
 // the three or five copies of a tracker call).  The kernels that end such a call instead write their results into page-locked host
 // memory and release a sequence number into a flag there as their very last store; the calling thread polls the flag.
-// lp_signal_done: every thread of every workgroup calls it at the end of the kernel (after its last store to host memory).
+// The signal: every thread of each of the `total` workgroups that deliver under one flag calls it at the end of the kernel, after its
+// last store to host memory.  Each workgroup makes its stores visible to the host and arrives at the counter; the last to arrive zeroes
+// the counter for the next launch and releases the flag.  One workgroup (total == 1) needs no counter: it may be null.  lp_signal_done_of
+// takes the total (a request's own row of workgroups in a launch that serves several requests), lp_signal_done is the whole grid.
 #ifdef __HIPCC__
-__device__ __forceinline__ void lp_signal_done(unsigned* counter, int* flag, int seq)
+__device__ __forceinline__ void lp_signal_done_of(unsigned* counter, int* flag, int seq, unsigned total)
 {
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0) {
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
         if (total == 1 || atomicAdd(counter, 1u) == total - 1) {
             if (total > 1) { *counter = 0; __threadfence(); }
             __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
+__device__ __forceinline__ void lp_signal_done(unsigned* counter, int* flag, int seq) { lp_signal_done_of(counter, flag, seq, gridDim.x * gridDim.y * gridDim.z); }
 #endif
 inline void lp_pf_invalidate(lpslam_hip_ctx* c, int first, int n) { const int p = c->pf_image.load(std::memory_order_relaxed); if (p >= first && p < first + n) c->pf_image.store(-1, std::memory_order_relaxed); }      // the slot's results are being rewritten
 unsigned* lp_done_counter(lpslam_hip_ctx* c, int which);      // arrival counter number `which` (0 .. 7) of the context, nullptr on failure

@@ -6,6 +6,7 @@
 // stereo parameters: focal_x_baseline (src/Trackers/OpenVSLAMTrackerBase.cpp:188-190, src/Interface/LpSlamTypes.h:219-222).
 // Integer work (xor + popcount + argmin) is bit-exact; the few float operations are written without contraction.
 #include "internal.h"
+#include "desc_wave.h"
 #include <chrono>
 #include <vector>
 #include <algorithm>
@@ -45,10 +46,9 @@ __device__ __forceinline__ void bf_knn2_body(const uint8_t* __restrict__ qdesc, 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ql = lane & 15, sub = lane >> 4;
     const int q = blockIdx.x * BF_QPW + ql;
     if (blockIdx.x * BF_QPW >= nq) return;                              // block-uniform
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(qdesc + (size_t)min(q, nq - 1) * 32);
     uint32_t a[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = qd[k];
+    desc_load8(qdesc + (size_t)min(q, nq - 1) * 32, a);
+    const uint4 a0 = make_uint4(a[0], a[1], a[2], a[3]), a1 = make_uint4(a[4], a[5], a[6], a[7]);
     const uint4* td = reinterpret_cast<const uint4*>(tdesc);
     int best = 257, second = 257, bidx = -1;
     for (int base = 0; base < nt; base += BF_TILE) {
@@ -60,10 +60,7 @@ __device__ __forceinline__ void bf_knn2_body(const uint8_t* __restrict__ qdesc, 
         for (int j = jb; j < je; ++j) {
             const uint4 b0 = *reinterpret_cast<const uint4*>(&tile[j * 8]);
             const uint4 b1 = *reinterpret_cast<const uint4*>(&tile[j * 8 + 4]);
-            int d = __popc(a[0] ^ b0.x) + __popc(a[1] ^ b0.y) + __popc(a[2] ^ b0.z) + __popc(a[3] ^ b0.w) +
-                    __popc(a[4] ^ b1.x) + __popc(a[5] ^ b1.y) + __popc(a[6] ^ b1.z) + __popc(a[7] ^ b1.w);
-            if (d < best) { second = best; best = d; bidx = base + j; }
-            else if (d < second) second = d;
+            knn2_update(hamming256(a0, a1, b0, b1), base + j, best, second, bidx);
         }
     }
     // the four subs of a wavefront (lanes ql, ql + 16, ql + 32, ql + 48), then the four wavefronts
@@ -196,7 +193,6 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_stereo(const uint8_t* __restr
     if (i >= nl) return;                                  // wave-uniform
     const lpslam_hip_keypoint kl = kpts[(size_t)left * slots_per_image + i];
     const lpslam_hip_keypoint* kr = kpts + (size_t)right * slots_per_image;
-    const uint32_t* dl = reinterpret_cast<const uint32_t*>(desc + ((size_t)left * slots_per_image + i) * 32);
     const uint8_t* dr = desc + (size_t)right * slots_per_image * 32;
     float* o_xr = out_f + (size_t)left * 2 * slots_per_image;
     float* o_depth = o_xr + slots_per_image;
@@ -204,8 +200,7 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_stereo(const uint8_t* __restr
     int32_t* o_corr = out_corr + (size_t)left * slots_per_image;
 
     uint32_t a[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = dl[k];
+    desc_load8(desc + ((size_t)left * slots_per_image + i) * 32, a);
     const int row = (int)kl.y;
     const float min_xr = kl.x - max_disp, max_xr = kl.x - 0.0f;
     unsigned best = 0xFFFFFFFFu;                          // (distance << 16) | index
@@ -219,10 +214,7 @@ __global__ __launch_bounds__(64 * ST_WAVES) void k_stereo(const uint8_t* __restr
             const lpslam_hip_keypoint r = kr[j];
             if (r.octave < kl.octave - 1 || r.octave > kl.octave + 1) continue;
             if (r.x < min_xr || max_xr < r.x) continue;
-            const uint32_t* b = reinterpret_cast<const uint32_t*>(dr + (size_t)j * 32);
-            unsigned d = 0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) d += __popc(a[k] ^ b[k]);
+            const unsigned d = (unsigned)hamming256(a, reinterpret_cast<const uint32_t*>(dr + (size_t)j * 32));
             best = min(best, (d << 16) | (unsigned)j);
         }
     }
@@ -381,12 +373,6 @@ struct ProjQuery { float x, y, x_right, radius; int min_level, max_level; };
 // mode 0: window + right-image window (projection / area matching); mode 1: chi-square gate of the keypoint's level (match::fuse)
 struct ProjGate { int mode; float inv_sigma_sq[LPSLAM_HIP_MAX_LEVELS]; };
 
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
-
 // (a device function: launched as k_proj_topk for one call and as k_proj_topk_req, blockIdx.y = request, for the pending calls of
 // several sessions at once)
 __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc,
@@ -400,13 +386,10 @@ __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __rest
     if (qslot < nq) {
     const int qi = q_ids ? q_ids[qslot] : qslot;
     const ProjQuery q = queries[qi];
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(q_desc + 32 * (size_t)qi);
     uint32_t a[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = qd[k];
+    desc_load8(q_desc + 32 * (size_t)qi, a);
     const int n = *kp_count;
-    const unsigned long long NONE = ~0ull;
-    unsigned long long top[4] = {NONE, NONE, NONE, NONE};
+    unsigned long long top[4] = {kNoKey, kNoKey, kNoKey, kNoKey};
     int cnt = 0;
     // Two passes, so that a wavefront waits for memory a handful of times instead of once per keypoint and once per candidate (2000
     // keypoints: 32 + up to 32 waits in a row, 19 us for a kernel that computes next to nothing).  Pass 1: sixteen keypoints of a lane in
@@ -425,10 +408,8 @@ __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __rest
             struct { float x, y; int octave; } k{kpi->x, kpi->y, kpi->octave};
             const float xr_i = stereo_xr ? stereo_xr[i] : -1.0f;
             const int bsf_i = best_so_far ? (int)best_so_far[i] : 32767;
-            const uint32_t* d = reinterpret_cast<const uint32_t*>(desc + 32 * (size_t)i);
             uint32_t dw[8];
-#pragma unroll
-            for (int w = 0; w < 8; ++w) dw[w] = d[w];
+            desc_load8(desc + 32 * (size_t)i, dw);
             if (gate.mode == 0) {
                 if (stereo_xr) { const float xr = xr_i; if (0 < xr && q.x_right >= 0 && q.radius < fabsf(q.x_right - xr)) continue; }
             } else {
@@ -440,9 +421,7 @@ __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __rest
                 if (0 <= xr && q.x_right >= 0) { const float er = q.x_right - xr; if ((ex * ex + ey * ey + er * er) * isq > 7.81473f) continue; }
                 else if ((ex * ex + ey * ey) * isq > 5.99146f) continue;
             }
-            int dist = 0;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) dist += __popc(a[w] ^ dw[w]);
+            const int dist = hamming256(a, dw);
             if (bsf_i <= dist) continue;                                // taken (0), or already matched at an equal or smaller distance
             // the cell as the oracle's proj_cell computes it: a double product (a float one rounds x * 64 / w below the integer it
             // equals at widths such as 752, x = 47 k, and ranks the keypoint one cell column early among equal distances)
@@ -450,8 +429,7 @@ __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __rest
             cx = min(max(cx, 0), 63); cy = min(max(cy, 0), 47);
             unsigned long long key = ((unsigned long long)dist << 32) | ((unsigned long long)(cx * 48 + cy) << 20) | ((unsigned long long)i << 4) | (unsigned)k.octave;
             ++cnt;
-#pragma unroll
-            for (int t = 0; t < 4; ++t) if (key < top[t]) { const unsigned long long tmp = top[t]; top[t] = key; key = tmp; }     // sorted insert
+            topk_insert(top, key);
         }
         __builtin_amdgcn_wave_barrier();
         n_list = 0;
@@ -470,20 +448,13 @@ __device__ __forceinline__ void proj_topk_body(const lpslam_hip_keypoint* __rest
             bool pass = i < n && fabsf(kxs[u] - q.x) < q.radius && fabsf(kys[u] - q.y) < q.radius;
             if (q.min_level >= 0 && ocs[u] < q.min_level) pass = false;
             if (q.max_level >= 0 && ocs[u] > q.max_level) pass = false;
-            const unsigned long long b = __ballot(pass);
-            if (pass) list[n_list + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u))] = (uint16_t)i;
-            n_list += __popcll(b);
+            wave_append(list, n_list, pass, i);
         }
     }
     second_pass();
-    for (int o2 = 32; o2 > 0; o2 >>= 1) cnt += __shfl_xor(cnt, o2);
+    cnt = wave_sum_i32(cnt);
     unsigned long long res[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const unsigned long long m = wave_min_u64(top[0]);
-        res[r] = m;
-        if (top[0] == m && m != NONE) { top[0] = top[1]; top[1] = top[2]; top[2] = top[3]; top[3] = NONE; }      // keys are unique (index bits)
-    }
+    wave_topk_pop(top, [&](int r, unsigned long long m) { res[r] = m; });      // keys are unique (index bits)
     if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) out_keys[4 * (size_t)qslot + r] = res[r];
@@ -514,15 +485,7 @@ __global__ __launch_bounds__(256) void k_proj_topk_req(const LpProjReq* __restri
     const ProjGate& gate = *reinterpret_cast<const ProjGate*>(&r->gate);
     proj_topk_body((const lpslam_hip_keypoint*)r->kp, r->desc, r->stereo_xr, r->kp_count, (const ProjQuery*)r->queries, r->q_desc, (const int*)nullptr, r->nq,
                    r->best_so_far, r->inv_w, r->inv_h, gate, r->out_keys, r->out_count);
-    // lp_signal_done with this request's own row of workgroups as the total
-    __threadfence_system();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (grid_x == 1 || atomicAdd(r->done_counter, 1u) == (unsigned)grid_x - 1) {
-            if (grid_x > 1) { *r->done_counter = 0; __threadfence(); }
-            __hip_atomic_store(r->done_flag, r->done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    lp_signal_done_of(r->done_counter, r->done_flag, r->done_seq, (unsigned)grid_x);
 }
 
 extern "C" {
@@ -1049,10 +1012,8 @@ __device__ __forceinline__ uint32_t rk_step(const uint4& a0, const uint4& a1, co
 {
     const uint4 b0 = *reinterpret_cast<const uint4*>(&tile[j * 8]);
     const uint4 b1 = *reinterpret_cast<const uint4*>(&tile[j * 8 + 4]);
-    const int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-                  __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-    if (d < best) { second = best; best = d; bidx = idx; }          // the per-lane loop of bf_knn2_body
-    else if (d < second) second = d;
+    const int d = hamming256(a0, a1, b0, b1);
+    knn2_update(d, idx, best, second, bidx);
     return rk_wave_min_shift((uint32_t)d << 16 | qpack, acc);
 }
 

@@ -446,11 +446,7 @@ __global__ __launch_bounds__(PO_T) void k_pose_optimize(double* pose7, const dou
         n_inliers[0] = n - n_bad_last;
         n_inliers[1] = passes;
     }
-    if (done_flag) {
-        __threadfence_system();
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(done_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (done_flag) lp_signal_done_of(nullptr, done_flag, seq, 1u);
 }
 
 // ---- the same flow with ONE observation per lane, for up to 256 observations (what a tracked frame has) ---------------------------------
@@ -636,11 +632,7 @@ __device__ __forceinline__ void po_wn_body(double* pose7, const PoObs* packed, i
         n_inliers[0] = n - n_bad_last;
         n_inliers[1] = passes;
     }
-    if (done_flag) {
-        __threadfence_system();
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(done_flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (done_flag) lp_signal_done_of(nullptr, done_flag, seq, 1u);
 }
 
 // One workgroup per request.  A request is a page-locked block of the caller: pose (in / out) at 0, inlier count and passes at 56 / 60,

@@ -7,6 +7,7 @@
 // One upload, the two launches and one wait per keyframe.  The order-dependent part (a neighbour's keypoint taken by an earlier
 // query is invisible to later ones) is the caller's replay over these lists (lpslam_tri::replay_host).
 #include "internal.h"
+#include "desc_wave.h"
 #include "triangulate_math.h"
 #include <algorithm>
 #include <cmath>
@@ -24,12 +25,7 @@ struct TriSetDev { tri::Epipolar e; tri::View v; unsigned o_gate, o_desc, o_xr, 
 struct TriHead { tri::Camera cam; tri::View v1; float scale[LPSLAM_HIP_MAX_LEVELS]; unsigned o_sets, o_group1; int32_t nq, n_sets; };
 
 constexpr unsigned long long NONE = tri::kNoKey;
-
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
+static_assert(NONE == kNoKey, "the empty list entry of the host definition and of the wavefront top-K");
 
 // (depth1: the slot's depth column, nullptr for a camera without a baseline)
 __global__ __launch_bounds__(256) void k_epi_topk(const uint8_t* __restrict__ blk, const lpslam_hip_keypoint* __restrict__ kp1, const uint8_t* __restrict__ desc1,
@@ -48,10 +44,8 @@ __global__ __launch_bounds__(256) void k_epi_topk(const uint8_t* __restrict__ bl
     const bool q_stereo = depth1 ? tri::is_stereo(head->cam, depth1[q]) : false;
     double l[3];
     tri::epipolar_line(e.F, (double)qx, (double)qy, l);
-    const uint32_t* qd = reinterpret_cast<const uint32_t*>(desc1 + 32 * (size_t)q);
     uint32_t a[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = qd[k];
+    desc_load8(desc1 + 32 * (size_t)q, a);
     const GateRec* gate = reinterpret_cast<const GateRec*>(blk + set->o_gate);
     const uint8_t* desc2 = blk + set->o_desc;
     const float* scale = head->scale;
@@ -59,9 +53,9 @@ __global__ __launch_bounds__(256) void k_epi_topk(const uint8_t* __restrict__ bl
 #pragma unroll
     for (int r = 0; r < tri::kListed; ++r) top[r] = NONE;
     int cnt = 0;
-    // Two passes, as the window matcher's scan (match.hip, proj_topk_body): pass 1 keeps eight gate records of a lane in flight and
-    // appends the survivors of the gate to the wavefront's list in LDS (ballot + prefix count); pass 2 gives every listed keypoint a
-    // lane, which loads its descriptor.  Keys are unique and the eight smallest are wanted: the order candidates are met in is free.
+    // Two passes, in the shape of the window matcher's scan (match.hip, proj_topk_body; list and top-K steps: desc_wave.h): pass 1 keeps
+    // eight gate records of a lane in flight and appends the survivors of the gate to the wavefront's list in LDS; pass 2 gives every
+    // listed keypoint a lane, which loads its descriptor.  Keys are unique and the eight smallest are wanted: their order is free.
     constexpr int PT_U = 8, PT_CAP = 2048;
     __shared__ uint16_t s_list[4][PT_CAP];
     uint16_t* list = s_list[threadIdx.x >> 6];
@@ -77,8 +71,7 @@ __global__ __launch_bounds__(256) void k_epi_topk(const uint8_t* __restrict__ bl
             if (h > tri::kHammingMax) continue;
             ++cnt;
             unsigned long long key = ((unsigned long long)h << 32) | (unsigned long long)j;
-#pragma unroll
-            for (int t = 0; t < tri::kListed; ++t) if (key < top[t]) { const unsigned long long tmp = top[t]; top[t] = key; key = tmp; }     // sorted insert
+            topk_insert(top, key);
         }
         __builtin_amdgcn_wave_barrier();
         n_list = 0;
@@ -96,23 +89,12 @@ __global__ __launch_bounds__(256) void k_epi_topk(const uint8_t* __restrict__ bl
                 const int oct = rec[u].z & 255;
                 pass = tri::gate_geometry(l, q_stereo || (rec[u].z >> 8) != 0, e, (double)__int_as_float(rec[u].x), (double)__int_as_float(rec[u].y), (double)scale[oct & (LPSLAM_HIP_MAX_LEVELS - 1)]);
             }
-            const unsigned long long b = __ballot(pass);
-            if (pass) list[n_list + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u))] = (uint16_t)j;
-            n_list += __popcll(b);
+            wave_append(list, n_list, pass, j);
         }
     }
     second_pass();
-    for (int o2 = 32; o2 > 0; o2 >>= 1) cnt += __shfl_xor(cnt, o2);
-#pragma unroll
-    for (int r = 0; r < tri::kListed; ++r) {
-        const unsigned long long m = wave_min_u64(top[0]);
-        if (lane == 0) out_keys[tri::kListed * oq + r] = m;
-        if (top[0] == m && m != NONE) {                                 // keys are unique (index bits): one lane
-#pragma unroll
-            for (int t = 0; t + 1 < tri::kListed; ++t) top[t] = top[t + 1];
-            top[tri::kListed - 1] = NONE;
-        }
-    }
+    cnt = wave_sum_i32(cnt);
+    wave_topk_pop(top, [&](int r, unsigned long long m) { if (lane == 0) out_keys[tri::kListed * oq + r] = m; });      // keys are unique (index bits)
     if (lane == 0) out_count[oq] = cnt;
 }
 

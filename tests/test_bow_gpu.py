@@ -324,6 +324,30 @@ def test_bow_tree_match_rescan_is_needed_and_runs(hiplib, oracle, small_ctx):
     assert gn == 12 and gi.tolist() == list(range(12)) and gd.tolist() == list(range(1, 13))
 
 
+def test_bow_tree_match_four_nearest_targets_on_one_lane(hiplib, oracle, small_ctx):
+    """One query and 64 * 4 + 1 = 257 targets under one node: lane l of the query's wavefront meets targets l, l + 64, l + 128, ...
+    The four nearest (8, 9, 10 and 11 bits from the query, every other target 60) are targets 5, 69, 133 and 197 -- all lane 5 -- so
+    the wavefront's four answers are one lane's whole list, popped four times.  8 against 9 fails a ratio of 0.8, 8 against a lost
+    second (60) would pass; with the successive bests marked taken every entry becomes the head in turn, and only 11 against 60
+    passes."""
+    rng = np.random.default_rng(46)
+    one = rng.integers(0, 256, (1, 32), dtype=np.uint8)
+    best4 = [5, 69, 133, 197]
+    td = _noisy(rng, np.repeat(one, 257, axis=0), 60)
+    for r, t in enumerate(best4):
+        td[t] = _noisy(rng, one, 8 + r)
+    tn = np.full(257, 31, np.int32); qn = np.full(1, 31, np.int32)
+    for stage in range(5):
+        taken = np.zeros(257, np.uint8); taken[best4[:stage]] = 1
+        gi, gd, gn = _match_both(hiplib, oracle, small_ctx, one, qn, td, tn, 256, 0.8, taken if stage else None)
+        assert gi.tolist() == ([best4[3]] if stage == 3 else [-1]), (stage, gi)        # 8 : 9, 9 : 10, 10 : 11 fail, 11 : 60 passes, 60 : 60 fails
+        gi, gd, gn = _match_both(hiplib, oracle, small_ctx, one, qn, td, tn, 256, 1.0, taken if stage else None)
+        if stage < 4:
+            assert gi.tolist() == [best4[stage]] and gd.tolist() == [8 + stage], (stage, gi, gd)
+        else:
+            assert gn == 1 and gd.tolist() == [60] and gi[0] not in best4
+
+
 def test_bow_tree_match_taken_masks(hiplib, oracle, small_ctx):
     rng = np.random.default_rng(44)
     td = rng.integers(0, 256, (6, 32), dtype=np.uint8); tn = np.full(6, 9, np.int32)

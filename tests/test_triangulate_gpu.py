@@ -123,6 +123,28 @@ def test_candidate_edge_cases(hiplib, ctx):
     assert ref_m[0][2].sum() <= ref_s[0][2].sum()
 
 
+def test_eight_nearest_candidates_on_one_lane(hiplib, ctx):
+    """One query and 64 * 8 + 1 = 513 keypoints of one neighbour that all pass the gate (every one a copy of the query's partner, half a
+    pixel around it): candidate j is met by lane j % 64.  The eight nearest (1 .. 8 bits from the query, every other one 40) are
+    keypoints 5, 69, ..., 453 -- all lane 5 -- so the wavefront's eight answers are one lane's whole list, popped eight times."""
+    cam, q, sets = tc.planted_sets(1, 513, 1)
+    q = {k: v.copy() for k, v in q.items()}
+    s = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in sets[0].items()}
+    rng = np.random.default_rng(47)
+    X = np.array([[0.4, -0.3, 7.0]])
+    u, v, _ = tr.project(cam, tc.ORIGIN, X); pu, pv, _ = tr.project(cam, s["pose"], X)
+    q["kp"]["x"] = u; q["kp"]["y"] = v; q["kp"]["octave"] = 0; q["group"][:] = 0
+    s["kpts"]["x"] = pu + rng.uniform(-0.5, 0.5, 513); s["kpts"]["y"] = pv + rng.uniform(-0.5, 0.5, 513); s["kpts"]["octave"] = 0; s["group"][:] = 0
+    best8 = 5 + 64 * np.arange(8)
+    for j in range(513):
+        s["desc"][j] = tc._flip(rng, q["desc"][0], 40)
+    for r, j in enumerate(best8):
+        s["desc"][j] = tc._flip(rng, q["desc"][0], 1 + r)
+    out, ref = run_lists(hiplib, ctx, 0, cam, q, [s])
+    j, dist, count = ref[0]
+    assert count[0] == 513 and j[0].tolist() == best8.tolist() and dist[0].tolist() == list(range(1, 9))
+
+
 # ---- 3. through extraction -------------------------------------------------------------------------------------------------------
 def seq_pose(seq, k):
     R, t = seq.pose(k)

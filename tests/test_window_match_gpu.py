@@ -136,6 +136,49 @@ def test_equal_distances_are_ranked_by_the_oracles_cell(wide, oracle):
             assert on > len(lattice) and len(np.unique(m)) == len(m)
 
 
+def test_four_nearest_candidates_on_one_lane(wide, oracle):
+    """One query, level 0 only, a window that holds exactly 64 * 4 + 1 = 257 keypoints: candidate r of the wavefront's list is met by
+    lane r % 64.  The four nearest (8, 9, 10 and 11 bits from the query, every other candidate 60) sit at list positions 5, 69, 133
+    and 197 -- all lane 5 -- so the wavefront's four answers are one lane's whole list, popped four times.  8 against 9 fails a Lowe
+    ratio of 0.8, 8 against a lost second (60) would pass; with the successive bests marked `taken` every entry becomes the head
+    in turn, and only 11 against 60 passes."""
+    fr = wide
+    lvl0 = np.flatnonzero(fr.kp["octave"] == 0)
+    cx, cy = np.float32(fr.w / 2), np.float32(fr.h / 2)
+    cheb = np.maximum(np.abs(fr.kp["x"][lvl0] - cx), np.abs(fr.kp["y"][lvl0] - cy))          # float32, as the kernel's window test
+    order = np.sort(cheb)
+    assert len(lvl0) > 257 and order[257] - order[256] > 1e-3
+    radius = np.float32(0.5) * (order[256] + order[257])
+    cand = lvl0[cheb < radius]                                        # in index order: the order the wavefront lists them in
+    assert len(cand) == 257
+    best4 = cand[[5, 69, 133, 197]]
+
+    def ones(bits):
+        return np.packbits(np.arange(256) < bits)
+
+    desc = fr.desc0.copy()
+    desc[cand] = ones(60)
+    for r, i in enumerate(best4):
+        desc[i] = ones(8 + r)
+    fr.set_descriptors(desc)
+    q, qd = M.queries([cx], cy, radius, -1, 0), np.zeros((1, 32), np.uint8)
+    try:
+        for stage in range(5):
+            taken = np.zeros(len(fr.kp), np.uint8); taken[best4[:stage]] = 1
+            for ratio in (0.8, 1.0):
+                why, (oi, od, on), rescans = M.compare(oracle, fr, "projection", q, qd, 256, ratio, taken if stage else None)
+                assert not why, (stage, ratio, why)
+                assert rescans == 0
+                if ratio == 0.8:                                      # 8 : 9, 9 : 10, 10 : 11 fail, 11 : 60 passes, 60 : 60 fails
+                    assert (on, oi[0]) == ((1, best4[3]) if stage == 3 else (0, -1)), (stage, oi)
+                elif stage < 4:
+                    assert on == 1 and oi[0] == best4[stage] and od[0] == 8 + stage, (stage, oi, od)
+                else:
+                    assert on == 1 and od[0] == 60 and oi[0] not in best4
+    finally:
+        fr.set_descriptors(fr.desc0)
+
+
 # ---- 320 x 240 stereo pair: odd queries, rescans ------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def small(hiplib, oracle):
