@@ -4,10 +4,9 @@ import numpy as np
 import pytest
 
 import occupancy_ref as R
+from occupancy_cases import RES, Session, edge_beam_case, pose_array, pose_rec, window_case
 
 pytestmark = pytest.mark.gpu
-
-RES = 0.05
 
 
 @pytest.fixture(scope="module")
@@ -15,45 +14,6 @@ def ctx(hiplib):
     c = hiplib.Context(320, 240, 500, 1.2, 3, max_images=2)
     yield c
     c.close()
-
-
-def pose_rec(hip, key, origin, yaw):
-    """a horizontal laser at `origin` (map plane) looking along yaw (counter-clockwise from map +y... any convention: fwd/left
-    orthonormal and right-handed seen from above)"""
-    p = np.zeros(1, hip.SCAN_POSE_DTYPE)
-    p["key"] = key
-    p["origin"] = origin
-    fwd = np.array([np.sin(yaw), np.cos(yaw)])
-    p["fwd"] = fwd
-    p["left"] = [-fwd[1], fwd[0]]
-    return p
-
-
-class Session:
-    """what was put into the store, mirrored for the reference"""
-
-    def __init__(self, hip, ctx):
-        self.hip, self.ctx, self.scans, self.geo = hip, ctx, {}, {}
-
-    def put(self, key, cs, ranges, rmin, rmax, rthr):
-        gkey = cs.tobytes()
-        if gkey not in self.geo:
-            self.geo[gkey] = self.ctx.scan_geometry_put(cs)
-        self.ctx.scan_store_put(key, self.geo[gkey], ranges, rmin, rmax, rthr)
-        self.scans[key] = (cs, np.asarray(ranges, np.float32), rmin, rmax, rthr)
-
-    def drop(self, key):
-        self.ctx.scan_store_drop(key)
-        self.scans.pop(key, None)
-
-    def check(self, poses, max_side=4096, res=RES):
-        ref_grid, ref_info = R.build(self.scans, [(int(p["key"]), p["origin"], p["fwd"], p["left"]) for p in poses], res, max_side)
-        grid, info = self.ctx.occupancy_build(poses, res, max_side)
-        assert info == ref_info, (info, ref_info)
-        assert grid.shape == ref_grid.shape
-        bad = np.argwhere(grid != ref_grid)
-        assert len(bad) == 0, "%d cells differ, first %s: %d vs %d" % (len(bad), bad[0], grid[tuple(bad[0])], ref_grid[tuple(bad[0])])
-        return grid, info
 
 
 def room_ranges(origin, yaw, cs, walls):
@@ -90,37 +50,20 @@ def test_room_scans(hiplib, ctx):
 
 def test_edge_beams(hiplib, ctx):
     s = Session(hiplib, ctx)
-    # exact axis and 45-degree directions (ties of the closed form), beams that end in the origin cell, negative coordinates
-    ang = np.array([0, np.pi / 4, np.pi / 2, 3 * np.pi / 4, np.pi, -np.pi / 4, -np.pi / 2, -3 * np.pi / 4] * 4)
-    cs = np.stack([np.cos(ang), np.sin(ang)], 1)
-    cs[0::8] = [1, 0]; cs[2::8] = [0, 1]; cs[4::8] = [-1, 0]; cs[6::8] = [0, -1]
-    h = np.sqrt(0.5); cs[1::8] = [h, h]; cs[3::8] = [-h, h]; cs[5::8] = [h, -h]; cs[7::8] = [-h, -h]
-    r = np.array([np.nan, np.inf, -np.inf, -1.0, 0.05, 0.01, 3.0, 3.0001,     # NaN, +-inf, negative, below range_min (0.1)...
-                  5.0, 5.5, 6.0, 4.99, 0.2, 0.12, 1.0, 2.0,                   # at / above range_threshold (5.0), above range_max (6.0)
-                  1.17, 2.33, 0.35, 4.2, 3.3, 0.11, 1.55, 0.64,
-                  2.0, 2.0, 2.0, 2.0, 2.0, 2.0, 2.0, 2.0], np.float32)
-    s.put(7, cs, r, 0.1, 6.0, 5.0)
-    s.put(8, cs, r[::-1].copy(), 0.1, 6.0, 5.0)
-    poses = np.concatenate([pose_rec(hiplib, 7, (-3.2, -7.9), 0.0), pose_rec(hiplib, 8, (0.025, -0.025), 0.3),
-                            pose_rec(hiplib, 7, (-0.05, -0.05), np.pi / 2)])
-    # a right-angle laser frame exactly on the axes: fwd = (0, 1), left = (-1, 0)
-    poses[0]["fwd"] = [0.0, 1.0]; poses[0]["left"] = [-1.0, 0.0]
-    poses[2]["fwd"] = [1.0, 0.0]; poses[2]["left"] = [0.0, 1.0]
-    s.check(poses)
+    puts, poses = edge_beam_case()
+    poses = pose_array(hiplib, poses)
+    s.load(puts[:2])
+    s.check(poses[:3])
     # range_threshold above range_max, and a beam length of exactly zero
-    s.put(9, cs, np.where(np.isfinite(r), np.abs(r), 0).astype(np.float32), 0.0, 4.0, 9.0)
-    s.check(np.concatenate([poses, pose_rec(hiplib, 9, (-1.23, 2.71), -1.0)]))
+    s.load(puts[2:])
+    s.check(poses)
 
 
 def test_max_side_window_cuts_rays(hiplib, ctx):
     s = Session(hiplib, ctx)
-    cs = R.beam_table(360, -np.pi, np.pi / 180)
-    rng = np.random.default_rng(2)
-    poses = []
-    for key in range(6):
-        s.put(100 + key, cs, rng.uniform(2.0, 20.0, 360).astype(np.float32), 0.1, 25.0, 18.0)
-        poses.append(pose_rec(hiplib, 100 + key, (key * 3.0 - 7.0, 1.0 - key), key * 0.7))
-    grid, info = s.check(np.concatenate(poses), max_side=256)
+    puts, poses = window_case()
+    s.load(puts)
+    grid, info = s.check(pose_array(hiplib, poses), max_side=256)
     assert info["width"] == 256 and info["height"] == 256
 
 
