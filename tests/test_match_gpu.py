@@ -54,7 +54,7 @@ def test_bf_one_call_keyframe_comparison(ctx, oracle, nq, nt):
             assert np.array_equal(one[0], o[0]) and np.array_equal(one[1], o[1])
 
 
-def test_bf_against_stored_descriptor_sets(ctx):
+def test_bf_against_stored_descriptor_sets(ctx, oracle):
     """lpslam_hip_match_bf_stored: an image slot against many descriptor sets kept on the device, one launch and one wait -- per set
     the matches of lpslam_hip_match_bf_descriptors; sets of different sizes, an empty one, a replaced one, a dropped one"""
     rng = np.random.default_rng(77)
@@ -73,6 +73,7 @@ def test_bf_against_stored_descriptor_sets(ctx):
         for key, g in zip(keys, got):
             want = ctx.match_bf_descriptors(2, 3, sets[key], 60, ratio, cross)
             assert all(np.array_equal(a, b) for a, b in zip(g, want)), key
+            assert all(np.array_equal(a, b) for a, b in zip(g, oracle.match_bf(q, sets[key], 60, ratio, cross))), key      # and what the CPU oracle returns
     assert sum(len(g[0]) for g in got) > 100
     ctx.desc_store_drop(5)
     with pytest.raises(Exception):

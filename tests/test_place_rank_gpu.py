@@ -4,6 +4,8 @@ top K keys by (votes desc, key asc).  The reference here is exactly that: match_
 import numpy as np
 import pytest
 
+import store_cases
+
 pytestmark = pytest.mark.gpu
 
 MAX_DIST, RATIO = 50, 0.75
@@ -91,10 +93,11 @@ def test_rank_other_thresholds_and_key_order(ctx):
     nd = 700
     q = rng.integers(0, 256, (nd, 32), dtype=np.uint8)
     ctx.set_descriptors(1, q)
-    keys, masks, _ = _make_map(ctx, rng, q, 130, nd, twins=10)
+    keys, masks, sets = _make_map(ctx, rng, q, 130, nd, twins=10)
     try:
         for max_dist, ratio in ((80, 0.0), (30, 0.9), (256, 0.75)):
-            want_k, want_v, _ = _reference(ctx, 1, keys, masks, 40, max_dist, ratio)
+            want_k, want_v, votes = _reference(ctx, 1, keys, masks, 40, max_dist, ratio)
+            assert votes == store_cases.reference_votes(q, sets, masks, max_dist, ratio)       # the chunked device reference against the CPU oracle
             got_k, got_v = ctx.rank_stored(1, keys[::-1], max_dist, ratio, 40)
             assert np.array_equal(got_k, want_k) and np.array_equal(got_v, want_v), (max_dist, ratio)
     finally:
