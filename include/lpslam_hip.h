@@ -90,6 +90,10 @@ const char* lpslam_hip_last_error(void);
 int lpslam_hip_device_count(int* count);
 
 /* ---- context ------------------------------------------------------------------------------------------- */
+/* Accepted configurations: an image of at least 64 x 64; every pyramid level larger than 45 px and smaller than 4134 px on both axes,
+ * with fewer than 2048 FAST cells; a per-level keypoint quota of 0 .. 2000; thresholds >= 0 in either order; and, per level, at most
+ * 256 quad-tree root columns and 256 root rows (the rounded aspect ratio of the level inside its 19-px border: no level beyond
+ * 256 : 1) with fewer than 511 roots in all.  Anything else: LPSLAM_HIP_ERR_INVALID, the message names the level. */
 int lpslam_hip_create(const lpslam_hip_frontend_config* cfg, lpslam_hip_ctx** out);
 void lpslam_hip_destroy(lpslam_hip_ctx* ctx);
 /* hipStream_t all work of this context is enqueued on (for event timing / interop). */

@@ -116,6 +116,11 @@ static int build_level_table(const lpslam_hip_frontend_config& cfg, LevelTable& 
             set_error("per-level keypoint quota %d exceeds the supported %d", lt.quota[l], kQuotaMax);
             return LPSLAM_HIP_ERR_INVALID;
         }
+        // k_distribute tabulates every pixel's root column and row in bytes: a level beyond 256 : 1 would put its far corners into root 255
+        if (lt.nxg[l] > 256 || lt.nyg[l] > 256) {
+            set_error("level %d (%dx%d) has %d x %d quad-tree roots; at most 256 columns and 256 rows are supported", l, lt.w[l], lt.h[l], lt.nxg[l], lt.nyg[l]);
+            return LPSLAM_HIP_ERR_INVALID;
+        }
         if (cx * cy * kCellSlots >= (1 << 21) || lt.w[l] >= 4096 + 2 * kEdge || lt.h[l] >= 4096 + 2 * kEdge) {
             set_error("level %d (%dx%d) exceeds the supported image size", l, lt.w[l], lt.h[l]);
             return LPSLAM_HIP_ERR_INVALID;

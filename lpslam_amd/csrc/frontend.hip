@@ -385,7 +385,9 @@ __device__ __forceinline__ void fast_cells_body(int cell_arg, int image_arg, con
             const int e = queue[wave][i], r = e >> 6, x = e & 63;
             const uint8_t* q = &smap[(r + 1) * SMAP_PITCH + x + 1];
             const int sc = q[0];
-            if (sc > 0 && sc > q[-1] && sc > q[1] && sc > q[-SMAP_PITCH - 1] && sc > q[-SMAP_PITCH] && sc > q[-SMAP_PITCH + 1] &&
+            // cv::FAST suppresses on cornerScore = S - 1 against 0 for a pixel that is no corner: at threshold 0 a corner of strength 1
+            // has score 0 and never survives (at any other threshold S > thr >= 1 says the same as before)
+            if (sc > 1 && sc > q[-1] && sc > q[1] && sc > q[-SMAP_PITCH - 1] && sc > q[-SMAP_PITCH] && sc > q[-SMAP_PITCH + 1] &&
                 sc > q[SMAP_PITCH - 1] && sc > q[SMAP_PITCH] && sc > q[SMAP_PITCH + 1]) {
                 // the threshold fallback looks at what FAST found; a corner whose own position is masked out is dropped afterwards
                 if (!mask || !masked(min_y + r + 3, min_x + x + 3)) atomicOr(&m_sel[r], 1ull << x);

@@ -174,11 +174,13 @@ def extract(img, p, want_pyramid=False, mask=None):
         assert mask.shape == img.shape
     # a level returns up to max(quota + 3, 4 * roots) corners, roots = the aspect ratio of the level's BORDERED area (19 px each side):
     # a 1531 x 97 image has 23-30 root cells per level, not 16
-    roots = max(1, int(round((w - 32) / max(h - 32, 1))) + 1, int(round((h - 32) / max(w - 32, 1))) + 1)
+    # (taken per level: level 1 of a 2873 x 64 image at scale 1.38 is 2082 x 46 and has 256 roots, the image itself 109)
+    lw, lh = pyramid_sizes(w, h, p)
+    roots = max([1, int(round((w - 32) / max(h - 32, 1))) + 1, int(round((h - 32) / max(w - 32, 1))) + 1] +
+                [int(round(max(a - 38, 1) / max(b - 38, 1))) + int(round(max(b - 38, 1) / max(a - 38, 1))) + 1 for a, b in zip(lw, lh)])
     cap = p.max_num_keypts + (4 * roots + 8) * p.num_levels + 64
     kp = np.zeros(cap, KP_DTYPE); desc = np.zeros((cap, 32), np.uint8)
     cc = np.zeros(p.num_levels, np.int32)
-    lw, lh = pyramid_sizes(w, h, p)
     pyr = np.zeros(sum(a * b for a, b in zip(lw, lh)), np.uint8) if want_pyramid else None
     n = lib().ora_orb_extract_masked(_p(img), w, h, w, C.byref(p), _p(mask), w, _p(kp), _p(desc), cap, _p(pyr), _p(cc))
     assert n <= cap
