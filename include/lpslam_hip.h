@@ -306,6 +306,22 @@ int lpslam_hip_undistort_dropped(lpslam_hip_ctx* ctx, int image, int32_t* droppe
 /* The stage's arithmetic on caller points (host memory): xy = n pairs in, xy_out = n pairs out, valid = n bytes (1 / 0; the pair of
  * an invalid point is left as NaN).  The same device function, no compaction.  Synchronising. */
 int lpslam_hip_undistort_points(lpslam_hip_ctx* ctx, const lpslam_hip_fisheye* model, const float* xy, int32_t n, float* xy_out, uint8_t* valid);
+/* The radial-tangential ("perspective") camera model of a monocular session: the reference hands its configuration file, with
+ * Camera.model = perspective and k1, k2, p1, p2, k3, to its tracker unchanged (src/Trackers/OpenVSLAMTrackerBase.cpp:114-123), which
+ * undistorts every keypoint ([UPSTREAM] camera::perspective::undistort_keypoints = cv::undistortPoints with R = I, P = K: five
+ * fixed-point steps).  A keypoint whose denominator is not positive in one of the steps, or whose result does not map back to within
+ * half a pixel of it, is REMOVED (lpslam_amd/csrc/radtan_math.h holds the definition, DESIGN.md section 32 the reasons). */
+typedef struct lpslam_hip_radtan {
+    double fx, fy, cx, cy;
+    double k1, k2, p1, p2, k3;
+} lpslam_hip_radtan;
+/* As lpslam_hip_set_keypoint_camera, for this model: every image slot of the context, synchronising, the same stage and the same
+ * stereo refusals.  Non-finite values or fx, fy <= 0: LPSLAM_HIP_ERR_INVALID and the context keeps what it had.  NULL, or all five
+ * coefficients exactly 0, clears the model.  A context has ONE model: either setter replaces whatever the other one set.
+ * lpslam_hip_stage_undistort and lpslam_hip_undistort_dropped serve both kinds. */
+int lpslam_hip_set_keypoint_camera_radtan(lpslam_hip_ctx* ctx, const lpslam_hip_radtan* model);
+/* As lpslam_hip_undistort_points, for this model (zero coefficients are evaluated like any others: the identity). */
+int lpslam_hip_undistort_points_radtan(lpslam_hip_ctx* ctx, const lpslam_hip_radtan* model, const float* xy, int32_t n, float* xy_out, uint8_t* valid);
 
 /* Synchronising readbacks (device -> caller memory). */
 int lpslam_hip_keypoint_count(lpslam_hip_ctx* ctx, int image, int32_t* count);

@@ -17,8 +17,8 @@ OBJ_DIR = os.path.join(CSRC, "_obj")
 # only the units that list it.  tests/test_abi_cpu.py follows the #include lines and fails when an entry is missing.
 _HOST = os.path.join("..", "host")
 UNIT_DEPS = {
-    "api.hip": ["fisheye_math.h"],
-    "frontend.hip": ["orb_pattern.inc", "fisheye_math.h"],
+    "api.hip": ["fisheye_math.h", "radtan_math.h"],
+    "frontend.hip": ["orb_pattern.inc", "fisheye_math.h", "radtan_math.h"],
     "match.hip": ["desc_wave.h"],
     "ba.hip": ["ba_common.h", "chol_panel.inl", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl", "ba_host.inl", "ba_partitioned.inl"],
     "pose_opt.hip": ["ba_common.h"],
@@ -84,7 +84,7 @@ def host_library(force=False, verbose=False):
     """C++ host mirror of the reference interface (g++), linked against the HIP C-ABI library next to it."""
     hdir = os.path.join(HERE, "host")
     srcs = [os.path.join(hdir, s) for s in HOST_SOURCES]
-    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "triangulate_math.h"))] + \
+    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "radtan_math.h"), os.path.join("..", "csrc", "triangulate_math.h"))] + \
         [os.path.join(HERE, "..", "include", h) for h in ("lpslam_types.h", "lpslam_manager.h", "lpslam_hip.h")] + [LIB]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps if os.path.exists(d)):
         return HOST_LIB

@@ -2,6 +2,7 @@
 // readbacks.  Declarations and the reference interfaces they replace: include/lpslam_hip.h.
 #include "internal.h"
 #include "fisheye_math.h"
+#include "radtan_math.h"
 #include <cstring>
 #include <vector>
 #include <cmath>
@@ -376,16 +377,16 @@ static int ctx_alloc(lpslam_hip_ctx* c)
         LP_HIP(hipMemsetAsync(c->d_cand_count, 0, B * L * sizeof(int32_t), c->stream));
         // the slots may have belonged to a fisheye session that left: no model until this one sets its own
         if (p->d_fe_model) {
-            LP_HIP(hipMemsetAsync(p->d_fe_model + f, 0, B * sizeof(LpFisheyeEntry), c->stream));
+            LP_HIP(hipMemsetAsync(p->d_fe_model + f, 0, B * sizeof(LpKpCamEntry), c->stream));
             LP_HIP(hipMemsetAsync(p->d_fe_dropped + f, 0, B * sizeof(int32_t), c->stream));
             std::lock_guard<std::mutex> lock(c->sess_pool->pool_mutex);
             for (size_t i = f; i < f + B && i < c->sess_pool->fe_model_on.size(); ++i) c->sess_pool->fe_model_on[i] = 0;
         }
         return LPSLAM_HIP_OK;
     }
-    LP_HIP(hipMalloc((void**)&c->d_fe_model, B * sizeof(LpFisheyeEntry)));
+    LP_HIP(hipMalloc((void**)&c->d_fe_model, B * sizeof(LpKpCamEntry)));
     LP_HIP(hipMalloc((void**)&c->d_fe_dropped, B * sizeof(int32_t)));
-    LP_HIP(hipMemsetAsync(c->d_fe_model, 0, B * sizeof(LpFisheyeEntry), c->stream));
+    LP_HIP(hipMemsetAsync(c->d_fe_model, 0, B * sizeof(LpKpCamEntry), c->stream));
     LP_HIP(hipMemsetAsync(c->d_fe_dropped, 0, B * sizeof(int32_t), c->stream));
     c->fe_model_on.assign(B, 0);
     LP_HIP(hipMalloc((void**)&c->d_pyr, B * c->image_slab));
@@ -1218,39 +1219,62 @@ int lpslam_hip_extract_range(lpslam_hip_ctx* c, int first, int n)
     if ((rc = lp_launch_fast(c, first, n))) return rc;
     if ((rc = lp_launch_distribute(c, first, n))) return rc;
     if ((rc = lp_launch_describe(c, first, n))) return rc;
-    return c->has_fisheye ? lp_launch_undistort(c, first, n) : LPSLAM_HIP_OK;
+    return c->has_kp_camera ? lp_launch_undistort(c, first, n) : LPSLAM_HIP_OK;
 }
 
-// ---- fisheye keypoints (frontend.hip: k_undistort_compact; the definition is fisheye_math.h) --------------------------------
-static bool fisheye_entry(const lpslam_hip_fisheye* m, LpFisheyeEntry* e)
+// ---- keypoint cameras (frontend.hip: k_undistort_compact; the definitions are fisheye_math.h and radtan_math.h) -------------
+static bool fisheye_entry(const lpslam_hip_fisheye* m, LpKpCamEntry* e)
 {
     const lpslam_fisheye::Model mm{m->fx, m->fy, m->cx, m->cy, {m->k[0], m->k[1], m->k[2], m->k[3]}, m->max_angle};
     if (!lpslam_fisheye::model_ok(mm)) { set_error("fisheye model: values must be finite, fx and fy positive, max_angle in (0, 89 degrees]"); return false; }
-    *e = LpFisheyeEntry{m->fx, m->fy, m->cx, m->cy, {m->k[0], m->k[1], m->k[2], m->k[3]}, m->max_angle, 1, 0};
+    *e = LpKpCamEntry{m->fx, m->fy, m->cx, m->cy, {m->k[0], m->k[1], m->k[2], m->k[3], m->max_angle}, LP_KPCAM_FISHEYE, 0};
+    return true;
+}
+// (all five coefficients exactly 0: no model -- *e stays kind 0)
+static bool radtan_entry(const lpslam_hip_radtan* m, LpKpCamEntry* e)
+{
+    const lpslam_radtan::Model mm{m->fx, m->fy, m->cx, m->cy, m->k1, m->k2, m->p1, m->p2, m->k3};
+    if (!lpslam_radtan::model_ok(mm)) { set_error("radial-tangential model: values must be finite, fx and fy positive"); return false; }
+    *e = LpKpCamEntry{};
+    if (!lpslam_radtan::is_identity(mm)) *e = LpKpCamEntry{m->fx, m->fy, m->cx, m->cy, {m->k1, m->k2, m->p1, m->p2, m->k3}, LP_KPCAM_RADTAN, 0};
     return true;
 }
 
-int lpslam_hip_set_keypoint_camera(lpslam_hip_ctx* c, const lpslam_hip_fisheye* model)
+// writes e (kind 0: clears) into every slot of the context; synchronising
+static int set_keypoint_camera_entry(lpslam_hip_ctx* c, const LpKpCamEntry& e)
 {
-    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
-    LpFisheyeEntry e{};
-    if (model && !fisheye_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
     LP_HIP(hipSetDevice(c->cfg.device));
     lpslam_hip_ctx* const o = lp_slot_owner(c);
     const size_t off = c->sess_pool ? (size_t)c->pool_first : 0, B = (size_t)c->cfg.max_images;
     if (!o->d_fe_model || off + B > o->fe_model_on.size()) { set_error("set_keypoint_camera: the context has no model table"); return LPSLAM_HIP_ERR_DEVICE; }
     // a launch that reads the entries may be in flight on any stream of the device (a session's chain runs on its pool's): all of it first
     LP_HIP(hipDeviceSynchronize());
-    const std::vector<LpFisheyeEntry> entries(B, e);
-    LP_HIP(hipMemcpy(o->d_fe_model + off, entries.data(), B * sizeof(LpFisheyeEntry), hipMemcpyHostToDevice));
+    const std::vector<LpKpCamEntry> entries(B, e);
+    LP_HIP(hipMemcpy(o->d_fe_model + off, entries.data(), B * sizeof(LpKpCamEntry), hipMemcpyHostToDevice));
     LP_HIP(hipMemset(o->d_fe_dropped + off, 0, B * sizeof(int32_t)));
     LP_HIP(hipDeviceSynchronize());
     {
         std::lock_guard<std::mutex> lock(o->pool_mutex);
-        for (size_t i = off; i < off + B; ++i) o->fe_model_on[i] = model ? 1 : 0;
+        for (size_t i = off; i < off + B; ++i) o->fe_model_on[i] = (uint8_t)e.kind;
     }
-    c->has_fisheye = model != nullptr;
+    c->has_kp_camera = e.kind != LP_KPCAM_NONE;
     return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_set_keypoint_camera(lpslam_hip_ctx* c, const lpslam_hip_fisheye* model)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    LpKpCamEntry e{};
+    if (model && !fisheye_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
+    return set_keypoint_camera_entry(c, e);
+}
+
+int lpslam_hip_set_keypoint_camera_radtan(lpslam_hip_ctx* c, const lpslam_hip_radtan* model)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    LpKpCamEntry e{};
+    if (model && !radtan_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
+    return set_keypoint_camera_entry(c, e);
 }
 
 int lpslam_hip_stage_undistort(lpslam_hip_ctx* c, int n) { int rc = check_batch(c, n); return rc ? rc : lp_launch_undistort(c, 0, n); }
@@ -1260,18 +1284,15 @@ int lpslam_hip_undistort_dropped(lpslam_hip_ctx* c, int image, int32_t* dropped)
     int rc = check_image(c, image); if (rc) return rc;
     if (!dropped) { set_error("null argument"); return LPSLAM_HIP_ERR_INVALID; }
     *dropped = 0;
-    if (!c->has_fisheye) return LPSLAM_HIP_OK;
+    if (!c->has_kp_camera) return LPSLAM_HIP_OK;
     LP_HIP(hipSetDevice(c->cfg.device));
     LP_HIP(hipMemcpy(dropped, lp_slot_owner(c)->d_fe_dropped + (c->sess_pool ? c->pool_first : 0) + image, sizeof(int32_t), hipMemcpyDeviceToHost));
     return LPSLAM_HIP_OK;
 }
 
-int lpslam_hip_undistort_points(lpslam_hip_ctx* c, const lpslam_hip_fisheye* model, const float* xy, int32_t n, float* xy_out, uint8_t* valid)
+// the parity hooks' common part: the stage's device function on n caller points with entry e
+static int undistort_points_entry(lpslam_hip_ctx* c, const LpKpCamEntry& e, const float* xy, int32_t n, float* xy_out, uint8_t* valid)
 {
-    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
-    if (!model || n < 0 || (n && (!xy || !xy_out || !valid))) { set_error("undistort_points: null argument or negative count"); return LPSLAM_HIP_ERR_INVALID; }
-    LpFisheyeEntry e{};
-    if (!fisheye_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
     if (n == 0) return LPSLAM_HIP_OK;
     LP_HIP(hipSetDevice(c->cfg.device));
     // one block of the cache: points in | points out | flags
@@ -1287,6 +1308,26 @@ int lpslam_hip_undistort_points(lpslam_hip_ctx* c, const lpslam_hip_fisheye* mod
     const hipError_t err = hipStreamSynchronize(s);
     if (err != hipSuccess) { blk.leak(); return hip_fail(err, "undistort_points"); }
     return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_undistort_points(lpslam_hip_ctx* c, const lpslam_hip_fisheye* model, const float* xy, int32_t n, float* xy_out, uint8_t* valid)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    if (!model || n < 0 || (n && (!xy || !xy_out || !valid))) { set_error("undistort_points: null argument or negative count"); return LPSLAM_HIP_ERR_INVALID; }
+    LpKpCamEntry e{};
+    if (!fisheye_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
+    return undistort_points_entry(c, e, xy, n, xy_out, valid);
+}
+
+int lpslam_hip_undistort_points_radtan(lpslam_hip_ctx* c, const lpslam_hip_radtan* model, const float* xy, int32_t n, float* xy_out, uint8_t* valid)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    if (!model || n < 0 || (n && (!xy || !xy_out || !valid))) { set_error("undistort_points_radtan: null argument or negative count"); return LPSLAM_HIP_ERR_INVALID; }
+    LpKpCamEntry e{};
+    if (!radtan_entry(model, &e)) return LPSLAM_HIP_ERR_INVALID;
+    // (the hook evaluates the model it is given: zero coefficients are the identity of the same five steps, not "no model")
+    e = LpKpCamEntry{model->fx, model->fy, model->cx, model->cy, {model->k1, model->k2, model->p1, model->p2, model->k3}, LP_KPCAM_RADTAN, 0};
+    return undistort_points_entry(c, e, xy, n, xy_out, valid);
 }
 
 int lpslam_hip_extract(lpslam_hip_ctx* c, int n) { return lpslam_hip_extract_range(c, 0, n); }
@@ -1526,7 +1567,7 @@ int lpslam_hip_front_end(lpslam_hip_ctx* c, int image, int32_t stereo, float fxb
 {
     int rc = check_image(c, image); if (rc) return rc;
     if (stereo && (rc = check_image(c, image + 1))) return rc;
-    if (stereo && c->has_fisheye) { set_error("stereo front end on a context with a fisheye keypoint camera (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
+    if (stereo && c->has_kp_camera) { set_error("stereo front end on a context with a keypoint camera model (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
     if (stereo && (!(baseline > 0.f) || !(fxb > 0.f))) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
     LP_HIP(hipSetDevice(c->cfg.device));
     const int shared = lp_share_front_end(c, image, stereo ? 1 : 0, fxb, baseline);
@@ -1546,7 +1587,7 @@ static int front_end_images_impl(lpslam_hip_ctx* c, int image, const lpslam_hip_
     if (stereo && (rc = check_image(c, image + 1))) return rc;
     if ((rc = lp_ingest_check(c, left))) return rc;
     if (stereo && (rc = lp_ingest_check(c, right))) return rc;
-    if (stereo && c->has_fisheye) { set_error("stereo front end on a context with a fisheye keypoint camera (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
+    if (stereo && c->has_kp_camera) { set_error("stereo front end on a context with a keypoint camera model (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
     if (stereo && (!(baseline > 0.f) || !(fxb > 0.f))) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
     if (adjust && (rc = lp_adjust_check(c, adjust))) return rc;
     LP_HIP(hipSetDevice(c->cfg.device));

@@ -11,6 +11,7 @@
 // batch back to back; FAST results in fixed 1024-entry slots per 64x64 cell; keypoints/descriptors per image.
 #include "internal.h"
 #include "fisheye_math.h"
+#include "radtan_math.h"
 
 #pragma clang fp contract(off)
 
@@ -1170,10 +1171,11 @@ __global__ __launch_bounds__(256) void k_remap(const uint8_t* __restrict__ raw, 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// K5: fisheye keypoints.  The monocular tracker of the reference undistorts every keypoint of a fisheye camera
-// and works in undistorted pinhole coordinates (src/Trackers/OpenVSLAMTrackerBase.cpp:170-175 hands the model over; [UPSTREAM]
-// camera::fisheye::undistort_keypoints).  Here: x, y of every keypoint of a slot with a model become the undistorted position
-// (fisheye_math.h, FP64), keypoints without one are removed by a STABLE compaction of keypoints and descriptors in place, and the
+// K5: keypoint cameras (DESIGN.md sections 30 and 32).  The monocular tracker of the reference undistorts every keypoint of a fisheye
+// or a perspective (radial-tangential) camera and works in undistorted pinhole coordinates (src/Trackers/OpenVSLAMTrackerBase.cpp:
+// 114-123 and 170-175 hand the model over; [UPSTREAM] camera::fisheye::undistort_keypoints, camera::perspective::undistort_keypoints).
+// Here: x, y of every keypoint of a slot with a model become the undistorted position (fisheye_math.h or radtan_math.h by the kind of
+// the slot's table entry, FP64), keypoints without one are removed by a STABLE compaction of keypoints and descriptors in place, and the
 // slot's count is rewritten -- whatever reads the slot afterwards (window matchers, read-back, delivery, descriptor stores) sees a
 // dense slot in undistorted coordinates.
 // One 1024-thread workgroup per image, chunks of 1024 slots in index order.  Per chunk a thread loads its keypoint (7 words) and
@@ -1183,14 +1185,21 @@ __global__ __launch_bounds__(256) void k_remap(const uint8_t* __restrict__ raw, 
 // Destinations of a chunk lie below the chunk's first slot, so later chunks' sources are never touched; the wave totals are double
 // buffered by chunk parity (a wave two chunks ahead has passed the barrier every reader of the buffer it overwrites arrived at).
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void k_undistort_compact(const LpFisheyeEntry* __restrict__ models, lpslam_hip_keypoint* kpts, uint8_t* desc,
+// the one dispatch on the kind of a table entry (kind != LP_KPCAM_NONE; the branch is uniform wherever the entry is)
+__device__ __forceinline__ bool lp_kpcam_undistort(const LpKpCamEntry& e, bool radtan, double px, double py, float* ux, float* uy)
+{
+    if (radtan) return lpslam_radtan::undistort(lpslam_radtan::Model{e.fx, e.fy, e.cx, e.cy, e.c[0], e.c[1], e.c[2], e.c[3], e.c[4]}, px, py, ux, uy);
+    return lpslam_fisheye::undistort(lpslam_fisheye::Model{e.fx, e.fy, e.cx, e.cy, {e.c[0], e.c[1], e.c[2], e.c[3]}, e.c[4]}, px, py, ux, uy);
+}
+
+__global__ __launch_bounds__(1024) void k_undistort_compact(const LpKpCamEntry* __restrict__ models, lpslam_hip_keypoint* kpts, uint8_t* desc,
                                                             int32_t* kp_count, int32_t* __restrict__ dropped, int slots_per_image, ImgSel image0)
 {
     const int image = lp_image(image0, blockIdx.x);
-    const LpFisheyeEntry e = models[image];
-    if (!e.on) return;                                   // (uniform: the whole workgroup leaves)
+    const LpKpCamEntry e = models[image];
+    if (e.kind == LP_KPCAM_NONE) return;                 // (uniform: the whole workgroup leaves)
     __shared__ int wave_total[2][16];
-    const lpslam_fisheye::Model m{e.fx, e.fy, e.cx, e.cy, {e.k[0], e.k[1], e.k[2], e.k[3]}, e.max_angle};
+    const bool radtan = e.kind == LP_KPCAM_RADTAN;       // (uniform: one image, one kind)
     const int n = min(max(kp_count[image], 0), slots_per_image);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint32_t* const kw = reinterpret_cast<uint32_t*>(kpts + (size_t)image * slots_per_image);
@@ -1206,7 +1215,7 @@ __global__ __launch_bounds__(1024) void k_undistort_compact(const LpFisheyeEntry
             for (int q = 0; q < 7; ++q) k[q] = kw[(size_t)i * 7 + q];
             d0 = dw[(size_t)i * 2]; d1 = dw[(size_t)i * 2 + 1];
             float ux, uy;
-            valid = lpslam_fisheye::undistort(m, (double)__uint_as_float(k[0]), (double)__uint_as_float(k[1]), &ux, &uy);
+            valid = lp_kpcam_undistort(e, radtan, (double)__uint_as_float(k[0]), (double)__uint_as_float(k[1]), &ux, &uy);
             if (valid) { k[0] = __float_as_uint(ux); k[1] = __float_as_uint(uy); }
         }
         const unsigned long long b = __ballot(valid);
@@ -1227,13 +1236,12 @@ __global__ __launch_bounds__(1024) void k_undistort_compact(const LpFisheyeEntry
 }
 
 // the same device function on caller points, no compaction (lpslam_hip_undistort_points)
-__global__ __launch_bounds__(256) void k_undistort_points(LpFisheyeEntry e, const float* __restrict__ xy, int n, float* __restrict__ xy_out, uint8_t* __restrict__ valid)
+__global__ __launch_bounds__(256) void k_undistort_points(LpKpCamEntry e, const float* __restrict__ xy, int n, float* __restrict__ xy_out, uint8_t* __restrict__ valid)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const lpslam_fisheye::Model m{e.fx, e.fy, e.cx, e.cy, {e.k[0], e.k[1], e.k[2], e.k[3]}, e.max_angle};
     float ux = __uint_as_float(0x7fc00000u), uy = ux;
-    const bool ok = lpslam_fisheye::undistort(m, (double)xy[2 * (size_t)i], (double)xy[2 * (size_t)i + 1], &ux, &uy);
+    const bool ok = lp_kpcam_undistort(e, e.kind == LP_KPCAM_RADTAN, (double)xy[2 * (size_t)i], (double)xy[2 * (size_t)i + 1], &ux, &uy);
     xy_out[2 * (size_t)i] = ux; xy_out[2 * (size_t)i + 1] = uy; valid[i] = ok ? 1 : 0;
 }
 
@@ -1410,7 +1418,7 @@ int lp_launch_undistort(lpslam_hip_ctx* c, int first, int n_images, const uint16
         std::lock_guard<std::mutex> lock(o->pool_mutex);
         for (int k = 0; k < n_images && !any; ++k) { const size_t i = (size_t)(off + (list ? (int)list[k] : first + k)); any = i < o->fe_model_on.size() && o->fe_model_on[i]; }
     }
-    if (!any || !o->d_fe_model) return LPSLAM_HIP_OK;    // grey and pinhole sessions: nothing is enqueued
+    if (!any || !o->d_fe_model) return LPSLAM_HIP_OK;    // grey, pinhole and zero-coefficient sessions: nothing is enqueued
     if (!list) {
         for (int i = first; i < first + n_images && (size_t)i < c->h_kp_valid.size(); ++i) c->h_kp_valid[(size_t)i] = 0;      // counts are rewritten
         lp_pf_invalidate(c, first, n_images);
@@ -1422,7 +1430,7 @@ int lp_launch_undistort(lpslam_hip_ctx* c, int first, int n_images, const uint16
     return LPSLAM_HIP_OK;
 }
 
-int lp_launch_undistort_points(lpslam_hip_ctx* c, const LpFisheyeEntry& e, const float* d_xy, int n, float* d_out, uint8_t* d_valid, hipStream_t s)
+int lp_launch_undistort_points(lpslam_hip_ctx* c, const LpKpCamEntry& e, const float* d_xy, int n, float* d_out, uint8_t* d_valid, hipStream_t s)
 {
     if (n <= 0) return LPSLAM_HIP_OK;
     hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, s, e, d_xy, n, d_out, d_valid);

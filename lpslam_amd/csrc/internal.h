@@ -185,12 +185,13 @@ struct lpslam_hip_ctx {
     lpslam_hip_keypoint* d_kpts = nullptr;  // [max_images][slots_per_image]
     uint8_t* d_desc = nullptr;              // [max_images][slots_per_image][32]
     int32_t* d_kp_count = nullptr;          // [max_images]
-    // fisheye keypoints (k_undistort_compact, frontend.hip): the model of every image slot, kept by the context that OWNS the slots -- a
-    // session writes entries pool_first .. of its pool's table -- so that one listed launch carries fisheye and pinhole sessions together
-    struct LpFisheyeEntry* d_fe_model = nullptr;   // [max_images], on == 0: the slot has no model (owner only; nullptr in a session)
+    // keypoint cameras (k_undistort_compact, frontend.hip): the model of every image slot, kept by the context that OWNS the slots -- a
+    // session writes entries pool_first .. of its pool's table -- so that one listed launch carries fisheye, radial-tangential and
+    // pinhole sessions together
+    struct LpKpCamEntry* d_fe_model = nullptr;     // [max_images], kind == 0: the slot has no model (owner only; nullptr in a session)
     int32_t* d_fe_dropped = nullptr;               // [max_images] keypoints the stage's last run removed from the slot (owner only)
-    std::vector<uint8_t> fe_model_on;              // owner: host mirror of `on` per slot, under pool_mutex (a launch with no model among its images is not made)
-    bool has_fisheye = false;                      // this context (a session: its own slots) has a model
+    std::vector<uint8_t> fe_model_on;              // owner: host mirror of `kind` per slot, under pool_mutex (a launch with no model among its images is not made)
+    bool has_kp_camera = false;                    // this context (a session: its own slots) has a model
     // matching results
     int32_t* d_bf = nullptr;           // [max_images][3][slots_per_image] best idx, best dist, second dist
     float* d_stereo = nullptr;         // [max_images][2][slots_per_image] x_right, depth
@@ -269,12 +270,15 @@ void lp_ingest_free(lpslam_hip_ctx* c);
 int lp_launch_fast(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
 int lp_launch_distribute(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
 int lp_launch_describe(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
-// fisheye keypoints: launches k_undistort_compact when one of the images has a model, nothing otherwise (c: the context the slots are
-// counted in -- for a list, the pool)
-struct LpFisheyeEntry { double fx, fy, cx, cy, k[4], max_angle; int32_t on, pad; };
+// keypoint cameras: launches k_undistort_compact when one of the images has a model, nothing otherwise (c: the context the slots are
+// counted in -- for a list, the pool).  The entry of a slot: its kind and the coefficients of that kind -- fisheye: c = k1 .. k4,
+// max_angle (fisheye_math.h); radial-tangential: c = k1, k2, p1, p2, k3 (radtan_math.h).  Either set is five doubles: 80 bytes as before.
+enum { LP_KPCAM_NONE = 0, LP_KPCAM_FISHEYE = 1, LP_KPCAM_RADTAN = 2 };
+struct LpKpCamEntry { double fx, fy, cx, cy, c[5]; int32_t kind, pad; };
+static_assert(sizeof(LpKpCamEntry) == 80, "keypoint-camera table entry");
 inline lpslam_hip_ctx* lp_slot_owner(lpslam_hip_ctx* c) { return c->sess_pool ? c->sess_pool : c; }
 int lp_launch_undistort(lpslam_hip_ctx* c, int first, int n_images, const uint16_t* list = nullptr);
-int lp_launch_undistort_points(lpslam_hip_ctx* c, const LpFisheyeEntry& e, const float* d_xy, int n, float* d_out, uint8_t* d_valid, hipStream_t s);
+int lp_launch_undistort_points(lpslam_hip_ctx* c, const LpKpCamEntry& e, const float* d_xy, int n, float* d_out, uint8_t* d_valid, hipStream_t s);
 int lp_launch_bf_strided(lpslam_hip_ctx* c, int q0, int t0, int stride, int n_pairs);
 int lp_launch_stereo_strided(lpslam_hip_ctx* c, int left0, int right0, int stride, int n_pairs, float fxb, float baseline, const uint16_t* pair_list = nullptr);
 size_t lp_distribute_lds_bytes(int qcap_max, int ncell_max);

@@ -745,7 +745,7 @@ int lpslam_hip_match_bf_stored(lpslam_hip_ctx* c, int query, const int32_t* keys
 int lpslam_hip_match_stereo(lpslam_hip_ctx* c, int left, int right, float fxb, float baseline)
 {
     int rc = chk(c, left, right); if (rc) return rc;
-    if (c->has_fisheye) { set_error("stereo matching on a context with a fisheye keypoint camera (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
+    if (c->has_kp_camera) { set_error("stereo matching on a context with a keypoint camera model (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
     if (!(baseline > 0.f) || !(fxb > 0.f)) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
     return lp_launch_stereo_strided(c, left, right, 0, 1, fxb, baseline);
 }
@@ -755,7 +755,7 @@ int lpslam_hip_match_stereo_strided(lpslam_hip_ctx* c, int left0, int right0, in
     if (n_pairs < 1) { set_error("n_pairs < 1"); return LPSLAM_HIP_ERR_INVALID; }
     int rc = chk(c, left0, right0); if (rc) return rc;
     if ((rc = chk(c, left0 + (n_pairs - 1) * stride, right0 + (n_pairs - 1) * stride))) return rc;
-    if (c->has_fisheye) { set_error("stereo matching on a context with a fisheye keypoint camera (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
+    if (c->has_kp_camera) { set_error("stereo matching on a context with a keypoint camera model (stereo frames are rectified)"); return LPSLAM_HIP_ERR_INVALID; }
     if (!(baseline > 0.f) || !(fxb > 0.f)) { set_error("focal_x_baseline and baseline must be positive"); return LPSLAM_HIP_ERR_INVALID; }
     return lp_launch_stereo_strided(c, left0, right0, stride, n_pairs, fxb, baseline);
 }

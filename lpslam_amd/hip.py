@@ -50,6 +50,7 @@ SYMBOLS = [
     "lpslam_hip_adjust_intensity", "lpslam_hip_upload_raw_image_adjusted", "lpslam_hip_front_end_images_adjusted", "lpslam_hip_adjust_intensity_last",
     "lpslam_hip_upload_pixels", "lpslam_hip_upload_raw_pixels", "lpslam_hip_front_end_pixels",
     "lpslam_hip_set_keypoint_camera", "lpslam_hip_stage_undistort", "lpslam_hip_undistort_dropped", "lpslam_hip_undistort_points",
+    "lpslam_hip_set_keypoint_camera_radtan", "lpslam_hip_undistort_points_radtan",
     "lpslam_hip_triangulate_neighbours", "lpslam_hip_triangulate_pairs",
 ]
 
@@ -77,6 +78,15 @@ class Fisheye(C.Structure):
 
     def __init__(self, fx, fy, cx, cy, k=(0.0, 0.0, 0.0, 0.0), max_angle_deg=70.0):
         super().__init__(float(fx), float(fy), float(cx), float(cy), (C.c_double * 4)(*[float(v) for v in k]), float(np.deg2rad(max_angle_deg)))
+
+
+class Radtan(C.Structure):
+    """lpslam_hip_radtan: intrinsics and the radial-tangential coefficients k1, k2, p1, p2, k3"""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double), ("p2", C.c_double), ("k3", C.c_double)]
+
+    def __init__(self, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+        super().__init__(float(fx), float(fy), float(cx), float(cy), float(k1), float(k2), float(p1), float(p2), float(k3))
 
 
 class TriCamera(C.Structure):
@@ -480,6 +490,21 @@ class Context:
         f = self.lib.lpslam_hip_set_keypoint_camera
         f.restype = C.c_int; f.argtypes = [C.c_void_p, C.POINTER(Fisheye)]
         _check(f(self.h, None if model is None else C.byref(model)))
+
+    def set_keypoint_camera_radtan(self, model):
+        """radial-tangential model of every slot (a Radtan; None or all-zero coefficients clear it); replaces a fisheye model"""
+        f = self.lib.lpslam_hip_set_keypoint_camera_radtan
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.POINTER(Radtan)]
+        _check(f(self.h, None if model is None else C.byref(model)))
+
+    def undistort_points_radtan(self, model, xy):
+        """undistort_points for a Radtan model"""
+        f = self.lib.lpslam_hip_undistort_points_radtan
+        f.restype = C.c_int; f.argtypes = [C.c_void_p, C.POINTER(Radtan), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.full(xy.shape, np.nan, np.float32); valid = np.zeros(len(xy), np.uint8)
+        _check(f(self.h, C.byref(model), _p(xy), len(xy), _p(out), _p(valid)))
+        return out, valid.astype(bool)
 
     def stage_undistort(self, n_images):
         f = self.lib.lpslam_hip_stage_undistort

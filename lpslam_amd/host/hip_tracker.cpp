@@ -92,6 +92,33 @@ int resolveFisheyeModel(const LpSlamCameraConfiguration& cam, const std::unorder
     return 1;
 }
 
+// The radial-tangential keypoint camera of a monocular session (hip_tracker.h has the rule): the intrinsics of cam with the file's
+// Camera.fx .. cy on top, and the file's five coefficients.
+int resolveRadtanModel(const LpSlamCameraConfiguration& cam, const std::unordered_map<std::string, std::string>& yaml, lpslam_radtan::Model* out, std::string* why)
+{
+    if (yaml.empty()) return 0;                          // no file: a Pinhole camera of the JSON configuration keeps getting no coefficients
+    auto it = yaml.find("Camera.model");
+    if (it != yaml.end() ? it->second != "perspective" : cam.distortion_function == LpSlamCameraDistortionFunction_Fisheye) return 0;
+    double v[9] = {cam.f_x, cam.f_y, cam.c_x, cam.c_y, 0, 0, 0, 0, 0};
+    const char* keys[9] = {"Camera.fx", "Camera.fy", "Camera.cx", "Camera.cy", "Camera.k1", "Camera.k2", "Camera.p1", "Camera.p2", "Camera.k3"};
+    for (int i = 0; i < 9; ++i) {
+        it = yaml.find(keys[i]);
+        if (it == yaml.end()) continue;
+        char* e = nullptr; const double x = std::strtod(it->second.c_str(), &e);
+        if (e == it->second.c_str()) {
+            if (i < 4) continue;                         // (the intrinsics: startContext ignores a value that is no number, as before)
+            if (why) *why = std::string(keys[i]) + " is not a number";
+            return -1;
+        }
+        v[i] = x;
+    }
+    const lpslam_radtan::Model m{v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]};
+    if (!lpslam_radtan::model_ok(m)) { if (why) *why = "perspective camera: intrinsics and coefficients must be finite, fx and fy positive"; return -1; }
+    if (lpslam_radtan::is_identity(m)) return 0;
+    *out = m;
+    return 1;
+}
+
 bool loadFlatYaml(const std::string& path, std::unordered_map<std::string, std::string>& yaml, std::string* bad_line)
 {
     std::ifstream f(path);
@@ -122,7 +149,8 @@ bool HipVslamTrackerBase::startContext(bool stereo)
     // (src/Trackers/OpenVSLAMTrackerBase.cpp:114-123: a file that cannot be loaded fails the start).  The keys this path has a use for
     // are read -- Camera.{fx, fy, cx, cy, cols, rows, focal_x_baseline}, Feature.{max_num_keypoints, scale_factor, num_levels,
     // ini_fast_threshold, min_fast_threshold}, Initializer.{num_min_triangulated_pts, parallax_deg_threshold}, time_to_relocalize,
-    // relocalize_with_nav_data, and for a monocular session Camera.model (fisheye) with Camera.k1 .. k4 -- nested ("Camera:" + indented "fx: ...") or flat ("Camera.fx: ..."); the rest is ignored.
+    // relocalize_with_nav_data, and for a monocular session Camera.model with its coefficients (fisheye: Camera.k1 .. k4; perspective, or
+    // no model named: Camera.k1, k2, p1, p2, k3) -- nested ("Camera:" + indented "fx: ...") or flat ("Camera.fx: ..."); the rest is ignored.
     std::unordered_map<std::string, std::string> yaml;
     if (!m_configFromFile.empty()) {
         std::string bad_line;
@@ -180,6 +208,14 @@ bool HipVslamTrackerBase::startContext(bool stereo)
         if (r < 0) { logMessage(LpSlamLogLevel_Error, "Fisheye camera refused: " + why); return false; }
         m_fisheye = r == 1;
     }
+    // ... and of a perspective camera whose configuration file carries radial-tangential coefficients (:114-123 pass the file on unchanged)
+    m_radtan = false;
+    if (!stereo && !m_fisheye) {
+        std::string why;
+        const int r = resolveRadtanModel(m_cam, yaml, &m_radtanModel, &why);
+        if (r < 0) { logMessage(LpSlamLogLevel_Error, "Perspective camera refused: " + why); return false; }
+        m_radtan = r == 1;
+    }
     m_rectify = stereo && m_cam.distortion_function != LpSlamCameraDistortionFunction_NoDistortion;
     RectifyMaps maps[2];
     if (m_rectify) {
@@ -193,6 +229,11 @@ bool HipVslamTrackerBase::startContext(bool stereo)
     }
     if (m_cam.resolution_x <= 0 || m_cam.resolution_y <= 0 || !(m_cam.f_x > 0) || (stereo && !(m_cam.focal_x_baseline > 0))) {
         logMessage(LpSlamLogLevel_Error, "Camera configuration incomplete (resolution, focal length, focal_x_baseline)");
+        return false;
+    }
+    long radtan_border_invalid = 0, radtan_border = 0;
+    if (m_radtan && !lpslam_radtan::bounds(m_radtanModel, m_cam.resolution_x, m_cam.resolution_y, &m_radtanBounds, &radtan_border_invalid, &radtan_border)) {
+        logMessage(LpSlamLogLevel_Error, "Perspective camera refused: no border pixel of the image has an undistorted position (Camera.k1, k2, p1, p2, k3)");
         return false;
     }
     lpslam_hip_frontend_config cfg{};
@@ -218,6 +259,21 @@ bool HipVslamTrackerBase::startContext(bool stereo)
             return false;
         }
         logMessage(LpSlamLogLevel_Info, "Fisheye camera: keypoints are undistorted on the device, angle limit " + std::to_string(m_fisheyeMaxAngleDeg) + " degrees");
+    }
+    if (m_radtan) {
+        const lpslam_radtan::Model& rm = m_radtanModel;
+        const lpslam_hip_radtan model{rm.fx, rm.fy, rm.cx, rm.cy, rm.k1, rm.k2, rm.p1, rm.p2, rm.k3};
+        if (lpslam_hip_set_keypoint_camera_radtan(m_ctx, &model) != LPSLAM_HIP_OK) {
+            logMessage(LpSlamLogLevel_Error, std::string("Cannot set the perspective keypoint camera: ") + lpslam_hip_last_error());
+            lpslam_hip_destroy(m_ctx); m_ctx = nullptr;
+            return false;
+        }
+        char buf[320];
+        std::snprintf(buf, sizeof(buf), "Perspective camera: keypoints are undistorted on the device (k1 %g k2 %g p1 %g p2 %g k3 %g), undistorted image x %.1f .. %.1f, y %.1f .. %.1f",
+                      rm.k1, rm.k2, rm.p1, rm.p2, rm.k3, m_radtanBounds.min_x, m_radtanBounds.max_x, m_radtanBounds.min_y, m_radtanBounds.max_y);
+        std::string line = buf;
+        if (radtan_border_invalid > 0) line += ", " + std::to_string(100.0 * (double)radtan_border_invalid / (double)radtan_border) + " % of the border pixels have no undistorted position";
+        logMessage(LpSlamLogLevel_Info, line);
     }
     for (int eye = 0; m_rectify && eye < 2; ++eye)
         if (lpslam_hip_set_rectify_map(m_ctx, eye, maps[eye].map_x.data(), maps[eye].map_y.data()) != LPSLAM_HIP_OK) {
@@ -1877,6 +1933,7 @@ MapFileCamera HipVslamTrackerBase::sessionMapCamera() const
     c.fx = m_cam.f_x; c.fy = m_cam.f_y; c.cx = m_cam.c_x; c.cy = m_cam.c_y; c.focal_x_baseline = m_cam.focal_x_baseline;
     c.num_levels = m_numLevels; c.scale_factor = m_scaleFactor;
     if (m_fisheye) { c.model = kMapFileModelFisheye; std::copy(m_fisheyeModel.k, m_fisheyeModel.k + 4, c.k); c.max_angle = m_fisheyeModel.max_angle; }
+    if (m_radtan) { c.model = kMapFileModelRadtan; const double d[5] = {m_radtanModel.k1, m_radtanModel.k2, m_radtanModel.p1, m_radtanModel.p2, m_radtanModel.k3}; std::copy(d, d + 5, c.d); }
     return c;
 }
 
@@ -1949,7 +2006,7 @@ void HipVslamTrackerBase::saveMap()
 {
     const auto t0 = std::chrono::steady_clock::now();
     MapData d;
-    d.cam = sessionMapCamera();      // (a fisheye session: the version-2 record)
+    d.cam = sessionMapCamera();      // (a fisheye session: the version-2 record; a radial-tangential one: version 3)
     d.next_landmark_id = m_nextLandmarkId; d.segment = m_segment;
     d.kfs.resize(m_kfs.size());
     long live = 0;
@@ -2001,7 +2058,7 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
@@ -2009,7 +2066,7 @@ void HipVslamTrackerBase::logStatistics()
                   (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted, s.color_converted, s.fisheye_dropped,
                   s.t_total * per, s.t_front * per, s.t_track * per, s.t_local * per, s.t_keyframe * per,
                   s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per,
-                  s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per);
+                  s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per, s.perspective_dropped);
     m_lastStatistics = buf;
     logMessage(LpSlamLogLevel_Info, buf);
 }
@@ -2182,6 +2239,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     cur.landmark.assign((size_t)n, -1);
     cur.scan = std::move(scan);
     if (m_fisheye) { int32_t dropped = 0; if (lpslam_hip_undistort_dropped(m_ctx, cur.slot, &dropped) == LPSLAM_HIP_OK) m_stats.fisheye_dropped += dropped; }      // (the slot's frame is collected: its stage has run)
+    if (m_radtan) { int32_t dropped = 0; if (lpslam_hip_undistort_dropped(m_ctx, cur.slot, &dropped) == LPSLAM_HIP_OK) m_stats.perspective_dropped += dropped; }
     dev_lap(m_stats.t_dev_get);
     ++m_imageTracked; ++m_stats.frames;
     if (cam.adjust) ++m_stats.intensity_adjusted;

@@ -12,6 +12,7 @@
 #include "pose_math.h"
 #include "map_file.h"
 #include "../csrc/fisheye_math.h"
+#include "../csrc/radtan_math.h"
 #include "../csrc/triangulate_math.h"
 #include "../../include/lpslam_hip.h"
 
@@ -101,6 +102,7 @@ protected:
         long color_converted = 0;                     // frames whose colour / YUV source was converted to grey on the device
         long triangulated = 0, tri_pairs = 0, tri_exhausted = 0;      // triangulateNeighbours: landmarks made, (keyframe, neighbour) pairs served, queries whose eight candidates were all taken while more had passed
         long fisheye_dropped = 0;                     // fisheye session: keypoints the undistort stage removed (beyond the angle limit or 90 degrees, not converged), summed
+        long perspective_dropped = 0;                 // radial-tangential session: keypoints the undistort stage removed (a denominator not positive, or the result more than half a pixel off its pixel), summed
         long intensity_adjusted = 0;                  // frames whose intensity adjustment ran on the device (a request the host had applied already does not count)
         // where the frames' time went (seconds, summed): front end (upload, extraction, stereo, read-back), tracking against the
         // previous frame, local-map tracking, keyframe work on the tracking thread (insertion, fusion, loop search, BA set-up / wait)
@@ -129,6 +131,8 @@ protected:
         // a fisheye session matches at the pinhole (u, v) -- its keypoints are undistorted -- but what the SENSOR sees decides visibility:
         // inside the angle limit and the distorted pixel inside the image (fisheye_math.h)
         if (m_fisheye) return lpslam_fisheye::visible(m_fisheyeModel, pc[0], pc[1], pc[2], m_cam.resolution_x, m_cam.resolution_y);
+        // a radial-tangential session likewise: (u, v) inside the bounds of the undistorted image and the distorted pixel inside the image (radtan_math.h)
+        if (m_radtan) return lpslam_radtan::visible(m_radtanModel, m_radtanBounds, pc[0], pc[1], pc[2], m_cam.resolution_x, m_cam.resolution_y);
         return !(u < 0 || v < 0 || u >= m_cam.resolution_x || v >= m_cam.resolution_y);
     }
     lpslam_hip_proj_query projQuery(double u, double v, double z, float radius, int min_level, int max_level, bool stereo) const
@@ -244,6 +248,12 @@ protected:
     bool m_fisheye = false;
     lpslam_fisheye::Model m_fisheyeModel{};
     double m_fisheyeMaxAngleDeg = 70.0;
+    // monocular radial-tangential session (a configFromFile with Camera.model = perspective and k1, k2, p1, p2, k3, which the reference
+    // hands to its tracker unchanged, OpenVSLAMTrackerBase.cpp:114-123): lpslam_hip_set_keypoint_camera_radtan; the bounds of the
+    // undistorted image are computed once at start
+    bool m_radtan = false;
+    lpslam_radtan::Model m_radtanModel{};
+    lpslam_radtan::Bounds m_radtanBounds{};
     MapFileCamera sessionMapCamera() const;           // the camera record a map file of this session carries
     TrackerState m_state = TrackerState::NotInitialized;
     std::optional<TimeStamp> m_firstImageTimestamp;
@@ -338,6 +348,11 @@ protected:
 // through the C shim, for tests without a device)
 int resolveFisheyeModel(const LpSlamCameraConfiguration& cam, const std::unordered_map<std::string, std::string>& yaml, double max_angle_deg,
                         lpslam_fisheye::Model* out, std::string* why);
+// the radial-tangential model of a monocular session: only from a YAML file (Camera.model = perspective, or no Camera.model and a camera
+// that is not a fisheye one) with at least one of Camera.k1, k2, p1, p2, k3 a non-zero number.  1: *out is the model; 0: none (no file,
+// another model, all coefficients zero or absent -- a Pinhole camera of the JSON configuration gets none whatever its dist[] holds, as
+// in the reference, OpenVSLAMTrackerBase.cpp:161-169); -1: refused, *why says it (names the key that is not a number).
+int resolveRadtanModel(const LpSlamCameraConfiguration& cam, const std::unordered_map<std::string, std::string>& yaml, lpslam_radtan::Model* out, std::string* why);
 bool loadFlatYaml(const std::string& path, std::unordered_map<std::string, std::string>& yaml, std::string* bad_line);
 // the triangulateNeighbours step's host rules (hip_tracker.cpp; also reached through the C shim, for tests without a device):
 // the option's range; the neighbour list -- the covisible keyframes in their order, for a monocular session the previous keyframe of the

@@ -176,7 +176,7 @@ LPS_API int lpslam_map_file_rewrite(const char* in, const char* out, char* why, 
     return ok ? 1 : 0;
 }
 // compares the camera record of a map file with a session's: session = {stereo, width, height, fx, fy, cx, cy, focal_x_baseline,
-// num_levels, scale_factor, model (0 / 1 = fisheye), k1 .. k4, max_angle in radians}.  1: they agree; 0: why = what differs, as the tracker
+// num_levels, scale_factor, model (0 / 1 = fisheye / 2 = radial-tangential), k1 .. k4, max_angle in radians -- model 2: k1, k2, p1, p2, k3}.  1: they agree; 0: why = what differs, as the tracker
 // logs it ("camera model", ...); -1: the file itself was rejected, why = the reader's reason
 LPS_API int lpslam_map_file_camera_check(const char* path, const double* session, char* why, size_t why_cap) {
     LpSlam::MapData d; std::string err;
@@ -186,8 +186,8 @@ LPS_API int lpslam_map_file_camera_check(const char* path, const double* session
         s.stereo = session[0] != 0 ? 1 : 0; s.width = (int32_t)session[1]; s.height = (int32_t)session[2];
         s.fx = session[3]; s.fy = session[4]; s.cx = session[5]; s.cy = session[6]; s.focal_x_baseline = session[7];
         s.num_levels = (int32_t)session[8]; s.scale_factor = session[9]; s.model = (uint32_t)session[10];
-        for (int i = 0; i < 4; ++i) s.k[i] = session[11 + i];
-        s.max_angle = session[15];
+        if (s.model == LpSlam::kMapFileModelRadtan) std::copy(session + 11, session + 16, s.d);      // model 2: k1, k2, p1, p2, k3 in the same five places
+        else { for (int i = 0; i < 4; ++i) s.k[i] = session[11 + i]; s.max_angle = session[15]; }
         err = LpSlam::map_camera_mismatch(d.cam, s);
         rc = err.empty() ? 1 : 0;
     }
@@ -212,6 +212,39 @@ LPS_API void lpslam_fisheye_forward(const double* model, const double* xyz, size
     for (size_t i = 0; i < n; ++i) {
         lpslam_fisheye::forward(m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &sensor_xy[2 * i], &sensor_xy[2 * i + 1], &theta[i]);
         visible[i] = lpslam_fisheye::visible(m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], width, height) ? 1 : 0;
+    }
+}
+// ---- the radial-tangential model's host forms (csrc/radtan_math.h), for tests without a device; model = {fx, fy, cx, cy, k1, k2, p1, p2, k3} ----
+static lpslam_radtan::Model radtan_model_of(const double* m) { return lpslam_radtan::Model{m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8]}; }
+// n pixels (x, y as doubles) -> out (2 floats each, NaN where invalid), valid (bytes); res2 and min_den (may be NULL): the squared
+// residual in pixels and the smallest denominator of the five steps
+LPS_API void lpslam_radtan_undistort(const double* model, const double* xy, size_t n, float* out, uint8_t* valid, double* res2, double* min_den) {
+    const lpslam_radtan::Model m = radtan_model_of(model);
+    for (size_t i = 0; i < n; ++i) {
+        float ux = std::numeric_limits<float>::quiet_NaN(), uy = ux; double r = 0, d = 0;
+        valid[i] = lpslam_radtan::undistort(m, xy[2 * i], xy[2 * i + 1], &ux, &uy, &r, &d) ? 1 : 0;
+        out[2 * i] = ux; out[2 * i + 1] = uy;
+        if (res2) res2[i] = r;
+        if (min_den) min_den[i] = d;
+    }
+}
+// the bounds of the undistorted width x height image: bounds = {min_x, max_x, min_y, max_y}; invalid_share (may be NULL): the share of
+// border pixels without an undistorted position.  0: no border pixel is valid (a start with this model is refused)
+LPS_API int lpslam_radtan_bounds(const double* model, int width, int height, double* bounds, double* invalid_share) {
+    lpslam_radtan::Bounds b{};
+    long bad = 0, all = 0;
+    const bool ok = lpslam_radtan::bounds(radtan_model_of(model), width, height, &b, &bad, &all);
+    if (invalid_share) *invalid_share = all > 0 ? (double)bad / (double)all : 0.0;
+    if (ok) { bounds[0] = b.min_x; bounds[1] = b.max_x; bounds[2] = b.min_y; bounds[3] = b.max_y; }
+    return ok ? 1 : 0;
+}
+// n camera-frame points (X, Y, Z) -> the sensor pixel and the visibility rule of the tracker's projection, given the bounds and the size
+LPS_API void lpslam_radtan_forward(const double* model, const double* xyz, size_t n, const double* bounds, int width, int height, double* sensor_xy, uint8_t* visible) {
+    const lpslam_radtan::Model m = radtan_model_of(model);
+    const lpslam_radtan::Bounds b{bounds[0], bounds[1], bounds[2], bounds[3]};
+    for (size_t i = 0; i < n; ++i) {
+        lpslam_radtan::forward(m, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], &sensor_xy[2 * i], &sensor_xy[2 * i + 1]);
+        visible[i] = lpslam_radtan::visible(m, b, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], width, height) ? 1 : 0;
     }
 }
 // ---- the triangulation step's host forms (csrc/triangulate_math.h), for tests without a device; cam = {fx, fy, cx, cy, focal_x_baseline,
@@ -278,6 +311,24 @@ LPS_API int lpslam_manager_fisheye_session_model(lpslam_c_manager* m, const char
         lpslam_fisheye::Model fm{};
         rc = LpSlam::resolveFisheyeModel(*cam, yaml, max_angle_deg, &fm, &err);
         if (rc == 1) { const double v[9] = {fm.fx, fm.fy, fm.cx, fm.cy, fm.k[0], fm.k[1], fm.k[2], fm.k[3], fm.max_angle}; std::copy(v, v + 9, model); }
+    }
+    if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
+    return rc;
+}
+// likewise the radial-tangential model a monocular tracker of this manager would start with (a camera that resolves as fisheye gets none:
+// the two rules exclude each other).  1: model[9] filled; 0: no model; -1: refused, why says it
+LPS_API int lpslam_manager_radtan_session_model(lpslam_c_manager* m, const char* yaml_path, double* model, char* why, size_t why_cap) {
+    LpSlam::SlamManager* impl = *reinterpret_cast<LpSlam::SlamManager**>(&m->mgr);
+    std::string err;
+    int rc = -1;
+    std::unordered_map<std::string, std::string> yaml;
+    const auto cam = impl ? impl->cameraRegistry().getConfiguration((LpSlamCameraNumber)0) : std::nullopt;
+    if (!cam) err = "no camera 0";
+    else if (yaml_path && *yaml_path && !LpSlam::loadFlatYaml(yaml_path, yaml, &err)) { if (err.empty()) err = "cannot load the YAML file"; }
+    else {
+        lpslam_radtan::Model rm{};
+        rc = LpSlam::resolveRadtanModel(*cam, yaml, &rm, &err);
+        if (rc == 1) { const double v[9] = {rm.fx, rm.fy, rm.cx, rm.cy, rm.k1, rm.k2, rm.p1, rm.p2, rm.k3}; std::copy(v, v + 9, model); }
     }
     if (why && why_cap) { const size_t n = std::min(err.size(), why_cap - 1); memcpy(why, err.data(), n); why[n] = 0; }
     return rc;

@@ -44,13 +44,14 @@ bool write_map_file(const std::string& path, const MapData& m, std::string* err)
 {
     Out o;
     o.raw(kMagic, 8);
-    const bool fisheye = m.cam.model == kMapFileModelFisheye;
-    if (m.cam.model != 0 && !fisheye) { if (err) *err = "camera model " + std::to_string(m.cam.model) + " cannot be written"; return false; }
-    o.v<uint32_t>(fisheye ? kMapFileVersionFisheye : kMapFileVersion);
+    const bool fisheye = m.cam.model == kMapFileModelFisheye, radtan = m.cam.model == kMapFileModelRadtan;
+    if (m.cam.model != 0 && !fisheye && !radtan) { if (err) *err = "camera model " + std::to_string(m.cam.model) + " cannot be written"; return false; }
+    o.v<uint32_t>(fisheye ? kMapFileVersionFisheye : radtan ? kMapFileVersionRadtan : kMapFileVersion);
     o.v<uint32_t>(m.cam.stereo); o.v<int32_t>(m.cam.width); o.v<int32_t>(m.cam.height);
     o.v<double>(m.cam.fx); o.v<double>(m.cam.fy); o.v<double>(m.cam.cx); o.v<double>(m.cam.cy); o.v<double>(m.cam.focal_x_baseline);
     o.v<int32_t>(m.cam.num_levels); o.v<double>(m.cam.scale_factor);
     if (fisheye) { o.v<uint32_t>(m.cam.model); for (double x : m.cam.k) o.v<double>(x); o.v<double>(m.cam.max_angle); }
+    if (radtan) { o.v<uint32_t>(m.cam.model); for (double x : m.cam.d) o.v<double>(x); }
     o.v<uint32_t>((uint32_t)m.kfs.size()); o.v<uint32_t>((uint32_t)m.lms.size()); o.v<int32_t>(m.next_landmark_id); o.v<int32_t>(m.segment);
     for (const auto& k : m.kfs) {
         o.v<uint8_t>(k.erased ? 1 : 0);
@@ -102,8 +103,8 @@ bool read_map_file(const std::string& path, MapData& m, std::string* err)
     uint32_t version = 0;
     if (b.size() < 12) return fail("truncated: no version");
     std::memcpy(&version, b.data() + 8, 4);
-    if (version != kMapFileVersion && version != kMapFileVersionFisheye)
-        return fail("unsupported format version " + std::to_string(version) + " (this build reads " + std::to_string(kMapFileVersion) + " and " + std::to_string(kMapFileVersionFisheye) + ")");
+    if (version != kMapFileVersion && version != kMapFileVersionFisheye && version != kMapFileVersionRadtan)
+        return fail("unsupported format version " + std::to_string(version) + " (this build reads " + std::to_string(kMapFileVersion) + ", " + std::to_string(kMapFileVersionFisheye) + " and " + std::to_string(kMapFileVersionRadtan) + ")");
     if (b.size() < 20) return fail("truncated: no checksum");
     // the records first (a file cut short runs out of bytes: "truncated"), the checksum over all of it last
     In in{b.data(), b.size() - 8, 12};
@@ -117,6 +118,13 @@ bool read_map_file(const std::string& path, MapData& m, std::string* err)
         if (ok && m.cam.model != kMapFileModelFisheye)
             return fail("unsupported format version 2 with camera model " + std::to_string(m.cam.model) + " (this build reads model " + std::to_string(kMapFileModelFisheye) + ", fisheye)");
         ok = ok && in.raw(m.cam.k, sizeof(m.cam.k)) && in.v(m.cam.max_angle);
+    }
+    if (ok && version == kMapFileVersionRadtan) {
+        ok = in.v(m.cam.model);
+        // version 3 exists for the radial-tangential model alone
+        if (ok && m.cam.model != kMapFileModelRadtan)
+            return fail("unsupported format version 3 with camera model " + std::to_string(m.cam.model) + " (this build reads model " + std::to_string(kMapFileModelRadtan) + ", radial-tangential)");
+        ok = ok && in.raw(m.cam.d, sizeof(m.cam.d));
     }
     ok = ok && in.v(nk) && in.v(nl) && in.v(m.next_landmark_id) && in.v(m.segment);
     if (!ok) return fail("truncated: header");
@@ -177,6 +185,7 @@ std::string map_camera_mismatch(const MapFileCamera& c, const MapFileCamera& s)
     if (s.stereo && !close_to(c.focal_x_baseline, s.focal_x_baseline)) return "focal_x_baseline";
     if (c.num_levels != s.num_levels || !close_to(c.scale_factor, s.scale_factor)) return "numLevels / scaleFactor";
     if (c.model != s.model) return "camera model";
+    for (int i = 0; i < 5; ++i) if (!close_to(c.d[i], s.d[i])) return "camera model";      // (all zero but in a radial-tangential record)
     if (c.model != 0 && !(close_to(c.k[0], s.k[0]) && close_to(c.k[1], s.k[1]) && close_to(c.k[2], s.k[2]) && close_to(c.k[3], s.k[3]) && close_to(c.max_angle, s.max_angle))) return "camera model";
     return std::string();
 }

@@ -20,6 +20,8 @@ struct MapFileCamera {
     // radians.  model = 0: a version-1 record, which has none of the three.
     uint32_t model = 0;
     double k[4] = {0, 0, 0, 0}, max_angle = 0;
+    // version 3 only (a monocular radial-tangential session): model = 2, then k1, k2, p1, p2, k3
+    double d[5] = {0, 0, 0, 0, 0};
 };
 
 struct MapFileKeyframe {
@@ -50,9 +52,11 @@ struct MapData {
     std::vector<MapFileLandmark> lms;
 };
 
-constexpr uint32_t kMapFileVersion = 1;              // every session but a fisheye one writes it, byte for byte as before
+constexpr uint32_t kMapFileVersion = 1;              // every session without a keypoint-camera model writes it, byte for byte as before
 constexpr uint32_t kMapFileVersionFisheye = 2;       // version 1 with model, k[4], max_angle behind the camera record
 constexpr uint32_t kMapFileModelFisheye = 1;
+constexpr uint32_t kMapFileVersionRadtan = 3;        // version 1 with model, k1, k2, p1, p2, k3 behind the camera record
+constexpr uint32_t kMapFileModelRadtan = 2;
 
 // <path>.tmp, then rename: a crash never leaves half a map under the name.  false + *err on failure.
 bool write_map_file(const std::string& path, const MapData& m, std::string* err);
@@ -60,7 +64,8 @@ bool write_map_file(const std::string& path, const MapData& m, std::string* err)
 bool read_map_file(const std::string& path, MapData& m, std::string* err);
 // What differs between the camera a file was made with and the session's ("camera setup", "resolution", "intrinsics",
 // "focal_x_baseline", "numLevels / scaleFactor", "camera model"), or an empty string.  A version-1 file in a fisheye session, a
-// version-2 file in any other, other coefficients or another angle limit: "camera model".
+// version-2 file in any other, other coefficients or another angle limit: "camera model".  Likewise a version-1 or version-2 file in a
+// radial-tangential session, a version-3 file in any other, other coefficients.
 std::string map_camera_mismatch(const MapFileCamera& file, const MapFileCamera& session);
 
 }  // namespace LpSlam

@@ -481,7 +481,7 @@ def map_file_rewrite(src, dst):
 
 def map_file_camera_check(path, session):
     """compares a map file's camera record with a session's (lpslam_map_file_camera_check): session = 16 numbers {stereo, width, height,
-    fx, fy, cx, cy, focal_x_baseline, num_levels, scale_factor, model, k1 .. k4, max_angle}.  (1, "") they agree; (0, what differs);
+    fx, fy, cx, cy, focal_x_baseline, num_levels, scale_factor, model, k1 .. k4, max_angle -- model 2: k1, k2, p1, p2, k3}.  (1, "") they agree; (0, what differs);
     (-1, why the file itself was rejected)"""
     import numpy as np
     lib = load()
@@ -527,6 +527,56 @@ def fisheye_session_model(mgr, yaml_path=None, max_angle_deg=70.0):
     f.argtypes = [C.c_void_p, C.c_char_p, C.c_double, C.c_void_p, C.c_char_p, C.c_size_t]; f.restype = C.c_int
     model = np.zeros(9, np.float64); why = C.create_string_buffer(512)
     rc = int(f(mgr.h, (str(yaml_path).encode() if yaml_path else None), float(max_angle_deg), model.ctypes.data, why, 512))
+    return (rc, model) if rc == 1 else (rc, why.value.decode() if rc < 0 else None)
+
+
+def radtan_undistort(model, xy):
+    """the host form of the radial-tangential undistortion (csrc/radtan_math.h), CPU only: model = 9 numbers {fx, fy, cx, cy, k1, k2, p1,
+    p2, k3}, xy (n, 2) float64 pixels.  Returns (out (n, 2) float32 with NaN where invalid, valid (n,) bool, squared residual in pixels
+    (n,), smallest denominator of the five steps (n,))"""
+    import numpy as np
+    lib = load()
+    f = lib.lpslam_radtan_undistort; f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]; f.restype = None
+    m = np.ascontiguousarray(model, np.float64); xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    n = len(xy)
+    out = np.zeros((n, 2), np.float32); valid = np.zeros(n, np.uint8); res2 = np.zeros(n, np.float64); den = np.zeros(n, np.float64)
+    f(m.ctypes.data, xy.ctypes.data, n, out.ctypes.data, valid.ctypes.data, res2.ctypes.data, den.ctypes.data)
+    return out, valid.astype(bool), res2, den
+
+
+def radtan_bounds(model, width, height):
+    """the bounds of the undistorted image as the tracker computes them at start, CPU only: ((min_x, max_x, min_y, max_y), share of
+    invalid border pixels), or (None, share) when no border pixel is valid (the start is refused)"""
+    import numpy as np
+    lib = load()
+    f = lib.lpslam_radtan_bounds; f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_double)]; f.restype = C.c_int
+    m = np.ascontiguousarray(model, np.float64); b = np.zeros(4, np.float64); share = C.c_double()
+    ok = f(m.ctypes.data, int(width), int(height), b.ctypes.data, C.byref(share))
+    return (tuple(b) if ok else None), share.value
+
+
+def radtan_forward(model, xyz, bounds, width, height):
+    """the host form of the forward model and the tracker's visibility rule, CPU only: xyz (n, 3) camera-frame points, bounds as
+    radtan_bounds gives them.  Returns (sensor pixel (n, 2), visible (n,) bool)"""
+    import numpy as np
+    lib = load()
+    f = lib.lpslam_radtan_forward; f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]; f.restype = None
+    m = np.ascontiguousarray(model, np.float64); xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+    b = np.ascontiguousarray(bounds, np.float64)
+    n = len(xyz)
+    s = np.zeros((n, 2), np.float64); vis = np.zeros(n, np.uint8)
+    f(m.ctypes.data, xyz.ctypes.data, n, b.ctypes.data, int(width), int(height), s.ctypes.data, vis.ctypes.data)
+    return s, vis.astype(bool)
+
+
+def radtan_session_model(mgr, yaml_path=None):
+    """the radial-tangential keypoint camera a monocular tracker of Manager `mgr` would start with (camera 0 of its configuration, the
+    YAML file of configFromFile), without a device: (1, 9 numbers), (0, None) for no model, (-1, reason)"""
+    import numpy as np
+    f = mgr.lib.lpslam_manager_radtan_session_model
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_size_t]; f.restype = C.c_int
+    model = np.zeros(9, np.float64); why = C.create_string_buffer(512)
+    rc = int(f(mgr.h, (str(yaml_path).encode() if yaml_path else None), model.ctypes.data, why, 512))
     return (rc, model) if rc == 1 else (rc, why.value.decode() if rc < 0 else None)
 
 
