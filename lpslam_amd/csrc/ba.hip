@@ -981,26 +981,45 @@ __device__ __forceinline__ void pose_oplus(const double* pose, const double* d, 
 // Launch m factors panel columns j = 2m and j1 = 2m + 1 and applies the previous pair (kb0 = 2m - 2, kb1 = 2m - 1) to the rest of
 // the trailing matrix: one kernel boundary per two panels on the critical path.  A panel workgroup (row block i, or
 // Minv row block e) keeps its five blocks  D_j, X = A_j1,j, D_j1, B0 = A_i,j, B1 = A_i,j1  in LDS:
-//   1. lookahead with the previous pair (K = 64, matrix cores): D_j, X, B0 on all four wavefronts;
+//   1. lookahead with the previous pair (K = 64, matrix cores): the LEFT halves of D_j, X, B0 on all four wavefronts;
 //   2. wavefront 0 factors [D_j; X] -> L_jj, L_j1,j and wavefront 1 [D_j; B0] -> L_i,j in registers, while
-//      wavefronts 2 and 3 finish the lookahead of D_j1 and B1;
-//   3. D_j1 -= L_j1,j L_j1,j^T, B1 -= L_i,j L_j1,j^T (matrix cores);
-//   4. wavefront 0 factors [D_j1; B1] -> L_j1,j1, L_i,j1.
+//      wavefronts 2 and 3 finish the right halves, announce them, and go on with the lookahead of D_j1 and B1;
+//   3. D_j1 -= L_j1,j L_j1,j^T, B1 -= L_i,j L_j1,j^T (matrix cores), left halves;
+//   4. wavefront 0 factors [D_j1; B1] -> L_j1,j1, L_i,j1 while wavefronts 1-3 finish the right halves, announce them and store
+//      step 2's blocks.
+// A panel starts strip A on the left halves alone and takes the right ones behind the announcement (chol_panel_split).
 // D_j, X and D_j1 are factored redundantly by every panel workgroup; nobody overwrites them in S during the launch (the
 // diagonal workgroup publishes L_jj, L_j1,j1 into Ldiag; L_j1,j is needed by no later launch).  With an odd number of panels
 // the last launch is `single`: only column j, factored by wavefront 0 alone.
 // The LAST panel column of a system (step 4 of its last launch, or step 2 of a `single` one) stops after its dim - 32 (nb - 1) real
 // columns (chol_panel_trim): what follows them -- the rhs row's diagonal, the identity padding -- is read by nobody.
 constexpr int CP_BLK = NB * (NB + 1);                  // one padded 32x32 block in LDS
-constexpr int CP_LDS_BYTES = (11 * CP_BLK + 2 * (64 * 17 + 64 * 17)) * (int)sizeof(double);      // 11 blocks + the factor scratch of two wavefronts
+// 11 blocks + the factor scratch of two wavefronts + the two announcement counters (chol_panel_split)
+constexpr int CP_LDS_BYTES = (11 * CP_BLK + 2 * (64 * 17 + 64 * 17) + 2) * (int)sizeof(double);
 
 constexpr int CH_SCR = 64 * 17 + 64 * 17;              // doubles of scratch per factoring wavefront: L1 [64][17] and U [64][17]
 // the strips, the panel [D; B] in registers and the 32-wide tile product: shared with tools/dev/panel_bench.hip
 #include "chol_panel.inl"
 
-__global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ views, int m, int pin, int skip_small)
+#ifdef LPSLAM_PAIR_STAMPS
+// development: shader-clock stamps of the diagonal workgroup, the first row workgroup and the first Minv workgroup of launches
+// m = 0 .. 7 of view 0, 24 slots each (tools/dev/pair_stamps.py names them)
+__device__ unsigned long long g_pair_stamps[8 * 3 * 24];
+#define PAIR_STAMP(k, cond) do { if (stamp_kind >= 0 && (cond) && lane == 0) g_pair_stamps[(m * 3 + stamp_kind) * 24 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
+// wait start, wait end (chol_panel_split) and panel written out
+#define PAIR_PANEL_STAMPS(k, p) do { if (stamp_kind >= 0 && lane == 0) { unsigned long long* g = g_pair_stamps + (m * 3 + stamp_kind) * 24 + (k); \
+        g[0] = (p).clk[0]; g[1] = (p).clk[1]; g[2] = __builtin_amdgcn_s_memtime(); } } while (0)
+#else
+#define PAIR_STAMP(k, cond) do {} while (0)
+#define PAIR_PANEL_STAMPS(k, p) do {} while (0)
+#endif
+
+__global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__ views, int m, int pin, int skip_small)
 {
     if (pin && (blockIdx.x & 7)) return;                 // small launches: XCD 0 only (see above); large ones use the whole chip
+#ifdef LPSLAM_PAIR_STAMPS
+    const unsigned long long t_entry = __builtin_amdgcn_s_memtime();
+#endif
     // Everything this kernel reads of its view, fetched in ONE round trip: left to itself the compiler loads each member where it
     // is first used, and the prologue becomes a chain of dependent round trips (measured: 3 us of an 18 us launch went into ten
     // of them -- arguments, sizes, control block, pointers, four passes of block loads).
@@ -1094,6 +1113,10 @@ __global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ vi
     const size_t rj = (size_t)j * NB, rj1 = (size_t)j1 * NB, ri = (size_t)i * NB;
     const bool has_b = !diag;
     const double* Bsrc = extra ? M : S;
+#ifdef LPSLAM_PAIR_STAMPS
+    const int stamp_kind = (blockIdx.y != 0 || m >= 8) ? -1 : (diag ? 0 : (bid == 1 && n_rows > 0 ? 1 : (bid == n_rows + 1 ? 2 : -1)));
+    if (stamp_kind >= 0 && tid == 0) g_pair_stamps[(m * 3 + stamp_kind) * 24] = t_entry;
+#endif
     double* Dj = cp_lds;               double* X = cp_lds + CP_BLK;        double* Dj1 = cp_lds + 2 * CP_BLK;
     double* B0 = cp_lds + 3 * CP_BLK;  double* B1 = cp_lds + 4 * CP_BLK;
     double* Ljk0 = cp_lds + 5 * CP_BLK; double* Ljk1 = cp_lds + 6 * CP_BLK;      // row j of the previous pair (later: L_j1,j and L_i,j)
@@ -1129,23 +1152,37 @@ __global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ vi
             }
         }
     }
+    // the announcements of the right halves (chol_panel_split): [0] step 1's, two wavefronts; [1] step 3's, three
+    int* const gate = reinterpret_cast<int*>(cp_lds + 11 * CP_BLK + 2 * CH_SCR);
+    if (tid == 0) { gate[0] = 0; gate[1] = 0; }
+    PAIR_STAMP(1, wave == 0);
     __syncthreads();
-    if (prev) {                                          // 1. lookahead of the blocks the first factorisations need
+    // One 16x16 tile (r, c) of a block, D -= A0 Bk0^T + A1 Bk1^T (K = 64) or D -= A0 Bk0^T (K = 32): a chain of mfma_tile32 calls of
+    // its own, so its bits do not depend on the wavefront that runs it or on when.  Tile (0, 1) of D_j and D_j1 is never computed:
+    // panel loads read the lower triangle of a diagonal block and panel_to_lds writes zeros above it.
+    auto tile64 = [&](double* D, const double* A0, const double* A1, const double* Bk0, const double* Bk1, int r, int c) __attribute__((always_inline)) {
         f64x4 acc = {0, 0, 0, 0};
-        acc = mfma_tile32(Ljk0, Ljk0, tr, tc, lr, lk, acc); acc = mfma_tile32(Ljk1, Ljk1, tr, tc, lr, lk, acc);
-        tile_sub(Dj, tr, tc, lr, lk, acc);
-        if (!single) {
-            f64x4 ax = {0, 0, 0, 0};
-            ax = mfma_tile32(Lj1k0, Ljk0, tr, tc, lr, lk, ax); ax = mfma_tile32(Lj1k1, Ljk1, tr, tc, lr, lk, ax);
-            tile_sub(X, tr, tc, lr, lk, ax);
-        }
-        if (has_b) {
-            f64x4 ab = {0, 0, 0, 0};
-            ab = mfma_tile32(Lik0, Ljk0, tr, tc, lr, lk, ab); ab = mfma_tile32(Lik1, Ljk1, tr, tc, lr, lk, ab);
-            tile_sub(B0, tr, tc, lr, lk, ab);
-        }
+        acc = mfma_tile32(A0, Bk0, 16 * r, 16 * c, lr, lk, acc); acc = mfma_tile32(A1, Bk1, 16 * r, 16 * c, lr, lk, acc);
+        tile_sub(D, 16 * r, 16 * c, lr, lk, acc);
+    };
+    auto tile32 = [&](double* D, const double* A0, const double* Bk0, int r, int c) __attribute__((always_inline)) {
+        f64x4 acc = {0, 0, 0, 0};
+        acc = mfma_tile32(A0, Bk0, 16 * r, 16 * c, lr, lk, acc);
+        tile_sub(D, 16 * r, 16 * c, lr, lk, acc);
+    };
+    // 1. lookahead of the blocks the first factorisations need, LEFT halves first (strip A of a panel reads columns 0-15 only):
+    //      round 1   D_j (0,0) | D_j (1,0) | X (0,0) | X (1,0)          round 2   B0 (0,0) | B0 (1,0) | D_j (1,1) | X (0,1)
+    //    The right halves that remain -- X (1,1) on wavefront 2, B0 (0,1) and (1,1) on wavefront 3 -- run beside strip A (step 2).
+    if (prev) {
+        if (wave < 2) tile64(Dj, Ljk0, Ljk1, Ljk0, Ljk1, wave, 0);
+        else if (!single) tile64(X, Lj1k0, Lj1k1, Ljk0, Ljk1, wave - 2, 0);
+        if (wave < 2) { if (has_b) tile64(B0, Lik0, Lik1, Ljk0, Ljk1, wave, 0); }
+        else if (wave == 2) tile64(Dj, Ljk0, Ljk1, Ljk0, Ljk1, 1, 1);
+        else if (!single) tile64(X, Lj1k0, Lj1k1, Ljk0, Ljk1, 0, 1);
     }
     __syncthreads();
+    PAIR_STAMP(2, wave == 0);
+    const int want1 = prev ? 2 : 0;                      // wavefronts 2 and 3 announce step 1's right halves
     bool fail = false;
     const int need = min(max(dim - NB * (nb - 1), 0), NB);       // real columns of the system's last panel column (chol_panel_trim)
     // The factored blocks leave the registers through LDS (every lane owns a ROW there): the workgroup then stores them to memory
@@ -1172,69 +1209,92 @@ __global__ __launch_bounds__(256) void k_chol_pair(const BaView* __restrict__ vi
             dst[(size_t)r * pitch + c] = L[r * (NB + 1) + c];
         }
     };
-    if (single) {                                        // 2. the system's last panel column alone: [D_j; B0] -> L_jj / L_i,j, cut short
-        if (wave == 0) {
-            PanelRegs p;
-            fail = chol_panel_trim(p, Dj, has_b ? B0 : nullptr, lane, cp_lds + 11 * CP_BLK, need);
+    auto block_to_memory3 = [&](const double* L, double* dst, size_t pitch) {      // wavefronts 1-3, six rows a pass
+#pragma unroll
+        for (int it = 0; it < 6; ++it) {
+            const int t = tid - 64 + it * 192, r = t / NB, c = t % NB;
+            if (t < NB * NB) dst[(size_t)r * pitch + c] = L[r * (NB + 1) + c];
+        }
+    };
+    // Every factoring wavefront passes the announcement before it writes its panel out (panel_to_lds overwrites X, Ljk0 and Ljk1,
+    // which the right-half tiles read): chol_panel_split waits in all of its paths.
+    if (wave == 0) {
+        PanelRegs p;
+        PAIR_STAMP(3, true);
+        if (single) {                                    // 2. the system's last panel column alone: [D_j; B0] -> L_jj / L_i,j, cut short
+            fail = chol_panel_split<true>(p, Dj, has_b ? B0 : nullptr, lane, cp_lds + 11 * CP_BLK, gate, want1, need);
             panel_to_lds(p, diag ? X : nullptr, has_b ? Ljk1 : nullptr);
-            if (diag && fail && lane == 0) scal[5] = 1.0;
+        } else {                                         // 2a. [D_j; X] -> L_jj, L_j1,j
+            fail = chol_panel_split<false>(p, Dj, X, lane, cp_lds + 11 * CP_BLK, gate, want1, NB);
+            panel_to_lds(p, diag ? X : nullptr, Ljk0);                                 // L_j1,j for step 3
         }
-    } else if (wave == 0) {                              // 2a. [D_j; X] -> L_jj, L_j1,j
-        PanelRegs p;
-        fail = chol_panel_dpp(p, Dj, X, lane, cp_lds + 11 * CP_BLK);
-        panel_to_lds(p, diag ? X : nullptr, Ljk0);                                     // L_j1,j for step 3
+        PAIR_PANEL_STAMPS(4, p);
         if (diag && fail && lane == 0) scal[5] = 1.0;
-    } else if (wave == 1 && has_b) {                     // 2b. [D_j; B0] -> L_i,j
-        PanelRegs p;
-        chol_panel_dpp(p, Dj, B0, lane, cp_lds + 11 * CP_BLK + CH_SCR);
-        panel_to_lds(p, nullptr, Ljk1);
-    } else if (prev && wave >= 2) {                      // 2c. the rest of the lookahead, beside the factorisations
-        if (wave == 2) {
+    } else if (wave == 1) {
+        if (!single && has_b) {                          // 2b. [D_j; B0] -> L_i,j
+            PanelRegs p;
+            PAIR_STAMP(7, true);
+            chol_panel_split<false>(p, Dj, B0, lane, cp_lds + 11 * CP_BLK + CH_SCR, gate, want1, NB);
+            panel_to_lds(p, nullptr, Ljk1);
+            PAIR_PANEL_STAMPS(8, p);
+        }
+    } else if (prev) {
+        // the right halves step 1 left over, then 2c, the rest of the lookahead: D_j1 (0,0) (1,0) (1,1) and B1 (0,0) on wavefront 2,
+        // B1 (0,1) (1,0) (1,1) on wavefront 3 -- five tiles each behind step 1's barrier, 80 MFMAs against the ~118 a panel has room for
+        if (wave == 2) { if (!single) tile64(X, Lj1k0, Lj1k1, Ljk0, Ljk1, 1, 1); }
+        else if (has_b) { tile64(B0, Lik0, Lik1, Ljk0, Ljk1, 0, 1); tile64(B0, Lik0, Lik1, Ljk0, Ljk1, 1, 1); }
+        panel_gate_open(gate, lane);
+        PAIR_STAMP(15 + wave, true);
+        if (!single) {
             for (int t4 = 0; t4 < 4; ++t4) {
-                const int r2 = (t4 >> 1) * 16, c2 = (t4 & 1) * 16;
-                f64x4 acc = {0, 0, 0, 0};
-                acc = mfma_tile32(Lj1k0, Lj1k0, r2, c2, lr, lk, acc); acc = mfma_tile32(Lj1k1, Lj1k1, r2, c2, lr, lk, acc);
-                tile_sub(Dj1, r2, c2, lr, lk, acc);
-            }
-        } else if (has_b) {
-            for (int t4 = 0; t4 < 4; ++t4) {
-                const int r2 = (t4 >> 1) * 16, c2 = (t4 & 1) * 16;
-                f64x4 acc = {0, 0, 0, 0};
-                acc = mfma_tile32(Lik0, Lj1k0, r2, c2, lr, lk, acc); acc = mfma_tile32(Lik1, Lj1k1, r2, c2, lr, lk, acc);
-                tile_sub(B1, r2, c2, lr, lk, acc);
+                const bool d = wave == 2 && t4 < 3;      // a tile of D_j1
+                if (!d && (!has_b || (wave == 3 && t4 == 0))) continue;
+                const int r2 = d ? (t4 + 1) >> 1 : (wave == 2 ? 0 : t4 >> 1), c2 = d ? t4 >> 1 : (wave == 2 ? 0 : t4 & 1);
+                tile64(d ? Dj1 : B1, d ? Lj1k0 : Lik0, d ? Lj1k1 : Lik1, Lj1k0, Lj1k1, r2, c2);
             }
         }
+        PAIR_STAMP(17 + wave, true);
     }
     __syncthreads();
-    if (diag) {
-        block_to_memory(X, Ldiag + (size_t)j * NB * NB, NB);
-        // L_j1,j for k_chol_xsolve when the rhs row lives in block j1.  Not into S: the other panel workgroups read A_j1,j.
-        if (!single) block_to_memory(Ljk0, Lsub + (size_t)j1 * NB * NB, NB);
-    } else {
-        block_to_memory(Ljk1, (extra ? M : S) + ri * n + rj, n);
+    PAIR_STAMP(11, wave == 0);
+    if (single) {
+        if (diag) block_to_memory(X, Ldiag + (size_t)j * NB * NB, NB);
+        else block_to_memory(Ljk1, (extra ? M : S) + ri * n + rj, n);
+        PAIR_STAMP(23, wave == 0);
+        return;
     }
-    if (single) return;
-    {                                                    // 3. the second column sees the first: K = 32
-        f64x4 acc = {0, 0, 0, 0};
-        acc = mfma_tile32(Ljk0, Ljk0, tr, tc, lr, lk, acc);
-        tile_sub(Dj1, tr, tc, lr, lk, acc);
-        if (has_b) {
-            f64x4 ab = {0, 0, 0, 0};
-            ab = mfma_tile32(Ljk1, Ljk0, tr, tc, lr, lk, ab);
-            tile_sub(B1, tr, tc, lr, lk, ab);
-        }
-    }
+    // 3. the second column sees the first (K = 32), left halves first:  D_j1 (0,0) | D_j1 (1,0) | B1 (0,0) | B1 (1,0)
+    if (wave < 2) tile32(Dj1, Ljk0, Ljk0, wave, 0);
+    else if (has_b) tile32(B1, Ljk1, Ljk0, wave - 2, 0);
     __syncthreads();
+    PAIR_STAMP(12, wave == 0);
     if (wave == 0) {                                     // 4. [D_j1; B1] -> L_j1,j1, L_i,j1
         PanelRegs p;
-        fail = j1 == nb - 1 ? chol_panel_trim(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK, need)
-                            : chol_panel_dpp(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK);
+        PAIR_STAMP(13, true);
+        fail = j1 == nb - 1 ? chol_panel_split<true>(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK, gate + 1, 3, need)
+                            : chol_panel_split<false>(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK, gate + 1, 3, NB);
         panel_to_lds(p, diag ? Dj1 : nullptr, has_b ? B1 : nullptr);
+        PAIR_PANEL_STAMPS(14, p);
         if (diag && fail && lane == 0) scal[5] = 1.0;
+    } else {
+        // beside strip A: D_j1 (1,1) | B1 (0,1) | B1 (1,1), announced; then step 2's blocks leave for memory in the panel's shadow
+        // (step 4 touches none of X, Ljk0, Ljk1)
+        if (wave == 1) tile32(Dj1, Ljk0, Ljk0, 1, 1);
+        else if (has_b) tile32(B1, Ljk1, Ljk0, wave - 2, 1);
+        panel_gate_open(gate + 1, lane);
+        if (diag) {
+            block_to_memory3(X, Ldiag + (size_t)j * NB * NB, NB);
+            // L_j1,j for k_chol_xsolve when the rhs row lives in block j1.  Not into S: the other panel workgroups read A_j1,j.
+            block_to_memory3(Ljk0, Lsub + (size_t)j1 * NB * NB, NB);
+        } else {
+            block_to_memory3(Ljk1, (extra ? M : S) + ri * n + rj, n);
+        }
+        PAIR_STAMP(21, wave == 1);
     }
     __syncthreads();
     if (diag) block_to_memory(Dj1, Ldiag + (size_t)j1 * NB * NB, NB);
     else block_to_memory(B1, (extra ? M : S) + ri * n + rj1, n);
+    PAIR_STAMP(23, wave == 0);
 }
 
 // the whole factorisation + L^-T rows: ceil(nb / 2) launches
@@ -1448,6 +1508,9 @@ __global__ __launch_bounds__(256) void k_ba_obs_chi2(const BaView* __restrict__ 
 
 #ifdef LPSLAM_SCHUR_STAMPS
 extern "C" __attribute__((visibility("default"))) int lpslam_hip_debug_schur_stamps(unsigned long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_schur_stamps), (size_t)n * sizeof(unsigned long long)); }
+#endif
+#ifdef LPSLAM_PAIR_STAMPS
+extern "C" __attribute__((visibility("default"))) int lpslam_hip_debug_pair_stamps(unsigned long long* out, int n) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pair_stamps), (size_t)n * sizeof(unsigned long long)); }
 #endif
 #ifdef LPSLAM_UPD_STAMPS
 extern "C" __attribute__((visibility("default"))) int lpslam_hip_debug_upd_stamps(double* out32) { return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_upd_stamps), 32 * sizeof(double)); }

@@ -84,7 +84,14 @@ __device__ __forceinline__ bool strip_factor(double (&d)[16], double (&x)[16])
 // block of each strip, and in x / y its own row of the stack  [D rows 16..31 (lanes 0-15); B rows 0..31 (lanes 16-47)]:
 //   dA = L00, x = [L10; L_B,0], dB = L11, y = [L11; L_B,1]  (lanes 48-63 idle along with zeros)
 // On entry dB holds row 16 + (l & 15) of D, columns 16 .. 31: what lanes 0-15 carry in y, in every DPP row.
+#ifdef LPSLAM_PAIR_STAMPS
+struct PanelRegs { double dA[16], x[16], dB[16], y[16]; unsigned long long clk[2]; };     // development: the wait of chol_panel_split
+// (the clock is a scalar instruction and the strips are plain inline assembly: without the barriers it is read ahead of strip A)
+#define LP_PANEL_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); p.clk[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#else
 struct PanelRegs { double dA[16], x[16], dB[16], y[16]; };
+#define LP_PANEL_STAMP(k) do {} while (0)
+#endif
 // ---- the block product between the strips ----------------------------------------------------------------------------------
 // y -= U, U = X (X[0..15, :])^T (K = 16, matrix cores, through this wavefront's scratch: Ls takes x one row per lane, Us the
 // product), and dB, which the caller loaded with the rows of the second diagonal block that lanes 0-15 carry in y, -= U as well:
@@ -207,6 +214,65 @@ __device__ __forceinline__ bool chol_panel_trim(PanelRegs& p, const double* Dblk
     } else {                                             // the second strip's columns stay as loaded
 #pragma unroll
         for (int c = 0; c < 16; ++c) p.dB[c] = 0.0;
+    }
+    return fail;
+}
+// ---- a panel whose right half arrives while strip A runs (k_chol_pair) ------------------------------------------
+// Strip A reads columns 0-15 of its two blocks only (dA, x); columns 16-31 (y, dB) are first needed by the block product, a load and
+// a strip later.  So the panel starts on the left halves, and the wavefronts that produce the right halves announce them on a
+// counter in LDS: release fence + relaxed add there, relaxed load + acquire fence here, all at workgroup scope (s_diag in k_chol_wg
+// works the same way).  Every wavefront of a workgroup is resident and the announcers wait for nothing, so the wait is bounded by
+// work that is already running.  The wait stands in EVERY path, also where the right half is not factored (need <= 16): whoever
+// returns from here may overwrite the blocks the announcers read.
+// The right half is loaded without a condition around the load (lanes that carry no row read the diagonal block and drop the
+// value): a guarded load is awaited on its own, 1132 cycles for a split load against 668.  The left half keeps
+// panel_load's guarded form: unconditional there as well, the kernel needs 271 registers and falls to one wavefront per SIMD.
+__device__ __forceinline__ void panel_gate_open(int* gate, int lane)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (lane == 0) __hip_atomic_fetch_add(gate, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void panel_gate_wait(int* gate, int want)
+{
+    while (__hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) __builtin_amdgcn_s_sleep(1);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// TRIM: the system's last panel column, `need` real columns (chol_panel_trim); otherwise the full panel (chol_panel_dpp), need unused.
+// want == 0: nothing is announced (no previous pair), the gate is not read.
+template <bool TRIM>
+__device__ __forceinline__ bool chol_panel_split(PanelRegs& p, const double* Dblk, const double* Bblk, int lane, double* scr, int* gate, int want, int need)
+{
+    const int r = lane & 15;
+    const bool has = lane < 16 || (Bblk != nullptr && lane < 48);
+    const double* own = lane < 16 ? Dblk + (16 + lane) * (NB + 1) : (has ? Bblk + (lane - 16) * (NB + 1) : Dblk);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        p.dA[c] = Dblk[r * (NB + 1) + c];
+        p.x[c] = has ? own[c] : 0.0;
+    }
+    bool fail = false;
+    if constexpr (TRIM) { if (need > 0) strip_step_n<0>(p.dA, p.x, dpp_bcast<0>(p.dA[0]), fail, min(need, 16)); }
+    else fail = strip_factor(p.dA, p.x);
+    LP_PANEL_STAMP(0);
+    if (want > 0) panel_gate_wait(gate, want);
+    LP_PANEL_STAMP(1);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        const double v = own[16 + c];
+        p.y[c] = has ? v : 0.0;
+        p.dB[c] = Dblk[(16 + r) * (NB + 1) + 16 + c];    // the rows lanes 0-15 carry in y, in every DPP row
+    }
+    if constexpr (TRIM) {
+        if (need > 16) {
+            panel_between<64>(p, lane, scr);
+            strip_step_n<0>(p.dB, p.y, dpp_bcast<0>(p.dB[0]), fail, need - 16);
+        } else {                                         // the second strip's columns stay as loaded
+#pragma unroll
+            for (int c = 0; c < 16; ++c) p.dB[c] = 0.0;
+        }
+    } else {
+        panel_between<64>(p, lane, scr);
+        fail |= strip_factor(p.dB, p.y);
     }
     return fail;
 }

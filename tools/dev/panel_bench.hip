@@ -8,6 +8,8 @@
 //   parts   load | strip A | between | strip B             panel_load, strip_factor, panel_between, strip_factor
 //   chol_panel_dpp                                         the panel of k_chol_pair, no stamps inside
 //   chol_panel_core<48>                                    the panel of k_chol_wg behind a loader of this file's, no stamps inside
+//   chol_panel_split                                       the panel of k_chol_pair that loads its right half behind strip A (nothing to
+//                                                          wait for here: want = 0), no stamps inside
 // A stamp waits for the LDS queue first (s_waitcnt lgkmcnt(0)), so a part owns the reads and writes it issued; the rows without
 // stamps inside are the ones to compare.  Ten launches of REPS panels each: minimum / median / maximum of the launch means.
 #include <hip/hip_runtime.h>
@@ -21,7 +23,7 @@
 
 constexpr int PB_BLK = NB * (NB + 1);
 constexpr int PB_SCR = 2 * 64 * 17;
-enum { PB_PARTS, PB_DPP, PB_CORE48, PB_MODES };
+enum { PB_PARTS, PB_DPP, PB_CORE48, PB_SPLIT, PB_MODES };
 
 // all four register sets of a panel, as k_chol_wg's own loader hands them to chol_panel_core
 __device__ __forceinline__ void pb_load_all(PanelRegs& p, const double* Dblk, const double* Bblk, int lane)
@@ -79,6 +81,7 @@ __global__ __launch_bounds__(64) void k_panel(const double* A, double* out, int 
             part[0] += t1 - t0; part[1] += t2 - t1; part[2] += t3 - t2; part[3] += t4 - t3;
         } else {
             if (MODE == PB_DPP) fail |= chol_panel_dpp(p, Dblk, Bblk, lane, scr);
+            else if (MODE == PB_SPLIT) fail |= chol_panel_split<false>(p, Dblk, Bblk, lane, scr, nullptr, 0, NB);
             else { pb_load_all(p, Dblk, Bblk, lane); fail |= chol_panel_core<48>(p, lane, scr); }
         }
         carry = p.dB[0] * 1e-300;                        // L11[r][0]: a number every lane owns (the wavefront issues in order)
@@ -105,6 +108,7 @@ static void launch(int mode, const double* dA, double* dO, int reps, long long* 
     switch (mode) {
     case PB_PARTS: hipLaunchKernelGGL(k_panel<PB_PARTS>, 1, 64, 0, 0, dA, dO, reps, dC, dF); break;
     case PB_DPP: hipLaunchKernelGGL(k_panel<PB_DPP>, 1, 64, 0, 0, dA, dO, reps, dC, dF); break;
+    case PB_SPLIT: hipLaunchKernelGGL(k_panel<PB_SPLIT>, 1, 64, 0, 0, dA, dO, reps, dC, dF); break;
     default: hipLaunchKernelGGL(k_panel<PB_CORE48>, 1, 64, 0, 0, dA, dO, reps, dC, dF); break;
     }
 }
@@ -136,7 +140,7 @@ int main()
     double *dA, *dO; long long* dC; int* dF;
     PB_CHECK(hipMalloc(&dA, 8 * rows * n)); PB_CHECK(hipMalloc(&dO, 8 * rows * n)); PB_CHECK(hipMalloc(&dC, 8 * 5)); PB_CHECK(hipMalloc(&dF, 4));
     PB_CHECK(hipMemcpy(dA, A.data(), 8 * rows * n, hipMemcpyHostToDevice));
-    const char* names[PB_MODES] = {"parts", "chol_panel_dpp", "chol_panel_core<48>"};
+    const char* names[PB_MODES] = {"parts", "chol_panel_dpp", "chol_panel_core<48>", "chol_panel_split"};
     int bad = 0;
     printf("cycles per panel (s_memtime), %d launches of %d panels: min / median / max\n", launches, reps);
     for (int mode = 0; mode < PB_MODES; ++mode) {
