@@ -709,6 +709,26 @@ int lpslam_hip_triangulate_neighbours(lpslam_hip_ctx* ctx, int image, const int3
 int lpslam_hip_triangulate_pairs(lpslam_hip_ctx* ctx, const lpslam_hip_tri_camera* cam, const float* scale, int32_t n_levels, const double* pose1, const double* pose2,
                                  const lpslam_hip_tri_keypoint* kp1, const lpslam_hip_tri_keypoint* kp2, int32_t n, int32_t* code, double* X);
 
+/* ---- PnP RANSAC for a batch of match sets (relocalisation) ---------------------------------------------------------
+ * Replaces the loop of LpSlam::pnp_solve_ransac calls (lpslam_amd/host/two_view.h) the relocaliser makes, one per candidate keyframe:
+ * [UPSTREAM] solve::pnp_solver -- the pose from landmark / keypoint matches alone, EPnP on 4-match samples inside a RANSAC, then EPnP
+ * once more over the inliers of the best sample.  DESIGN.md section 34; the arithmetic is lpslam_amd/csrc/epnp_math.h.
+ * Set s holds matches offsets[s] .. offsets[s + 1] of pw (3 doubles each, world), obs (2 doubles, pixels) and inv_sigma2 (1 / scale^2
+ * of the keypoint's level); cam4 = fx fy cx cy; every set is sampled with the same seed (xorshift32 from seed ? seed : 1) and
+ * `iterations` samples.  Per set: pose7 = qw qx qy qz tx ty tz (world -> camera), n_inliers, the per-match flags in `inlier`
+ * (indexed like the matches) and, where best_iteration is not NULL, the winning sample (-1: none).  A set with fewer than four matches,
+ * one whose every sample fails (coplanar landmarks) and one whose best sample explains fewer than four matches answer n_inliers 0,
+ * flags cleared, best_iteration -1 and the identity pose.  The results are those of pnp_solve_ransac on each set.  One upload, two
+ * launches, one wait; the refit calls LpSlam::epnp_solve of liblpslam.so, which must lie beside this library (or be in the process).
+ * n_sets == 0: LPSLAM_HIP_OK, nothing done.  n_sets < 0, offsets that start below 0 or do not ascend, iterations outside
+ * 1 .. LPSLAM_HIP_PNP_MAX_ITERATIONS, a camera that is no number or NULL where an array is needed (best_iteration alone may be NULL):
+ * LPSLAM_HIP_ERR_INVALID with nothing written. */
+#define LPSLAM_HIP_PNP_MAX_ITERATIONS 1024
+int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* ctx, int32_t n_sets, const int32_t* offsets /* n_sets + 1 */, const double* pw, const double* obs,
+                                const double* inv_sigma2, const double* cam4, int32_t iterations, uint32_t seed,
+                                double* pose7 /* 7 per set */, int32_t* n_inliers /* per set */, uint8_t* inlier /* per match */,
+                                int32_t* best_iteration /* per set, may be NULL */);
+
 /* ---- Sim3 pose graph ---------------------------------------------------------------------------------------------
  * Replaces what openvslam::system runs on its global-optimisation thread after a loop closure while the loop detector
  * is enabled (reference: src/Trackers/OpenVSLAMTrackerBase.cpp:250-255): [UPSTREAM] optimize::graph_optimizer on

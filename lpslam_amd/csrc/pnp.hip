@@ -1,0 +1,265 @@
+// pnp.hip -- the relocaliser's pose solver for a batch of match sets ([UPSTREAM] solve::pnp_solver, the host
+// form is LpSlam::pnp_solve_ransac in lpslam_amd/host/two_view.cpp).  One call takes S sets of landmark / keypoint matches:
+//   host            the sample table (the 4-match samples pnp_solve_ransac would draw, epnp_math.h) and ONE upload of it with the matches
+//   k_pnp_hypotheses  sixteen lanes per (set, iteration): EPnP on the four sampled matches (epnp4 of epnp_math.h, bit for bit the host's
+//                   epnp_solve at n = 4); the 12 x 12 matrix and its eigenvectors live in LDS (2.3 KB a hypothesis, four a wave) and
+//                   the lanes divide each Jacobi rotation's elements among them
+//   k_pnp_score     one workgroup per set, a wave per hypothesis in turn: inliers counted with the host's expression, the winner by the
+//                   key count << 32 | ~iteration (the lowest iteration among equal counts, the host's `count > best`), its flags and
+//                   pose written to page-locked memory, then the done flag (internal.h)
+//   host            one wait; per set the refit of pnp_solve_ransac: LpSlam::epnp_solve over the winner's inliers -- the host library's
+//                   own function, found at run time (liblpslam.so links against this library, not the other way round)
+#include "internal.h"
+#include "epnp_math.h"
+#include "../host/pose_math.h"
+#include <dlfcn.h>
+#include <cmath>
+
+using namespace lpslam;
+namespace ep = lpslam_epnp;
+
+namespace {
+
+constexpr int kHypLanes = 16;          // lanes that solve one hypothesis together (12 of them carry a row / column of the 12 x 12 matrix)
+constexpr int kHypPerWg = 64 / kHypLanes;      // one wave per workgroup
+constexpr int kHypLds = ep::kWorkspace + 2;    // doubles of LDS per hypothesis: the four workspaces of a wave start on different banks
+
+struct PnpHead { double cam[4]; int32_t n_sets, iterations; uint32_t o_offsets, o_table, o_pw, o_obs, o_w, pad; };
+struct PnpResult { int32_t best_iteration, count; double R[9], t[3]; };
+static_assert(sizeof(PnpResult) == 104, "result record");
+
+__global__ __launch_bounds__(64) void k_pnp_hypotheses(const uint8_t* __restrict__ base, double* __restrict__ hyp, int* __restrict__ valid)
+{
+    __shared__ double ws[kHypLds * kHypPerWg];
+    const PnpHead& head = *(const PnpHead*)base;
+    const int group = threadIdx.x / kHypLanes, ln = threadIdx.x % kHypLanes;
+    const int h = blockIdx.x * kHypPerWg + group;
+    if (h >= head.n_sets * head.iterations) return;           // (the sixteen lanes of a hypothesis together; no workgroup barrier in this kernel)
+    const int s = h / head.iterations;
+    const int32_t* off = (const int32_t*)(base + head.o_offsets);
+    const int o = off[s], n = off[s + 1] - o;
+    if (n < 4) { if (ln == 0) valid[h] = 0; return; }
+    const int32_t* idx = (const int32_t*)(base + head.o_table) + 4 * (size_t)h;
+    const double* pw = (const double*)(base + head.o_pw);
+    const double* obs = (const double*)(base + head.o_obs);
+    double p4[12], u4[8], cam[4], R[9], t[3];
+    for (int k = 0; k < 4; ++k) {
+        const size_t m = (size_t)o + (size_t)min(max(idx[k], 0), n - 1);
+        for (int a = 0; a < 3; ++a) p4[3 * k + a] = pw[3 * m + a];
+        u4[2 * k] = obs[2 * m]; u4[2 * k + 1] = obs[2 * m + 1];
+    }
+    for (int k = 0; k < 4; ++k) cam[k] = head.cam[k];
+    const bool ok = ep::epnp4(p4, u4, cam, ws + kHypLds * group, 1, R, t, ln, kHypLanes);
+    if (ln != 0) return;
+    valid[h] = ok ? 1 : 0;
+    if (ok) { for (int k = 0; k < 9; ++k) hyp[12 * (size_t)h + k] = R[k]; for (int k = 0; k < 3; ++k) hyp[12 * (size_t)h + 9 + k] = t[k]; }
+}
+
+__global__ __launch_bounds__(256) void k_pnp_score(const uint8_t* __restrict__ base, const double* __restrict__ hyp, const int* __restrict__ valid,
+                                                   PnpResult* __restrict__ res, uint8_t* __restrict__ flags, unsigned* counter, int* flag, int seq)
+{
+    __shared__ unsigned long long wkey[4];
+    const PnpHead& head = *(const PnpHead*)base;
+    const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t* off = (const int32_t*)(base + head.o_offsets);
+    const int o = off[s], n = off[s + 1] - o;
+    const double* pw = (const double*)(base + head.o_pw) + 3 * (size_t)o;
+    const double* obs = (const double*)(base + head.o_obs) + 2 * (size_t)o;
+    const double* w = (const double*)(base + head.o_w) + (size_t)o;
+    double cam[4];
+    for (int k = 0; k < 4; ++k) cam[k] = head.cam[k];
+    unsigned long long best = 0;
+    if (n >= 4)
+        for (int it = wave; it < head.iterations; it += 4) {              // the same for every lane of a wave
+            const size_t h = (size_t)s * (size_t)head.iterations + (size_t)it;
+            if (!valid[h]) continue;
+            double Rt[12];
+            for (int k = 0; k < 12; ++k) Rt[k] = hyp[12 * h + k];
+            int count = 0;
+            for (int i0 = 0; i0 < n; i0 += 64) {
+                const int i = i0 + lane;
+                const bool in = i < n && ep::pnp_inlier(Rt, Rt + 9, cam, pw + 3 * (size_t)i, obs[2 * (size_t)i], obs[2 * (size_t)i + 1], w[i]);
+                count += __popcll(__ballot(in));
+            }
+            const unsigned long long key = (unsigned long long)count << 32 | (unsigned long long)(~(uint32_t)it);
+            if (count > 0 && key > best) best = key;
+        }
+    if (lane == 0) wkey[wave] = best;
+    __syncthreads();
+    best = wkey[0];
+    for (int k = 1; k < 4; ++k) if (wkey[k] > best) best = wkey[k];
+    const int count = (int)(best >> 32);
+    const int it = (int)(~(uint32_t)(best & 0xffffffffu));
+    uint8_t* fl = flags + o;
+    if (count < 4) {                                                      // the host's `best < 4`: no pose, the flags cleared
+        for (int i = threadIdx.x; i < n; i += 256) fl[i] = 0;
+        if (threadIdx.x == 0) {
+            PnpResult r{};
+            r.best_iteration = -1; r.count = 0; r.R[0] = r.R[4] = r.R[8] = 1.0;
+            res[s] = r;
+        }
+    } else {
+        const size_t h = (size_t)s * (size_t)head.iterations + (size_t)it;
+        double Rt[12];
+        for (int k = 0; k < 12; ++k) Rt[k] = hyp[12 * h + k];
+        for (int i = threadIdx.x; i < n; i += 256)
+            fl[i] = ep::pnp_inlier(Rt, Rt + 9, cam, pw + 3 * (size_t)i, obs[2 * (size_t)i], obs[2 * (size_t)i + 1], w[i]) ? 1 : 0;
+        if (threadIdx.x == 0) {
+            PnpResult r{};
+            r.best_iteration = it; r.count = count;
+            for (int k = 0; k < 9; ++k) r.R[k] = Rt[k];
+            for (int k = 0; k < 3; ++k) r.t[k] = Rt[9 + k];
+            res[s] = r;
+        }
+    }
+    lp_signal_done(counter, flag, seq);
+}
+
+size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+// LpSlam::epnp_solve through its C shim lpslam_epnp_solve of the host library: already in the process (a client linked against
+// liblpslam.so), or loaded from the directory this library lies in.  nullptr: not found.
+typedef int (*EpnpSolveFn)(const double*, const double*, int, const double*, double*, double*);
+EpnpSolveFn host_epnp_solve()
+{
+    static const EpnpSolveFn fn = []() -> EpnpSolveFn {
+        if (void* f = dlsym(RTLD_DEFAULT, "lpslam_epnp_solve")) return (EpnpSolveFn)f;
+        Dl_info info{};
+        if (!dladdr((const void*)&lpslam_hip_pnp_ransac_batch, &info) || !info.dli_fname) return nullptr;
+        std::string path(info.dli_fname);
+        const size_t slash = path.rfind('/');
+        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "liblpslam.so";
+        void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        return lib ? (EpnpSolveFn)dlsym(lib, "lpslam_epnp_solve") : nullptr;
+    }();
+    return fn;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const int32_t* offsets, const double* pw, const double* obs, const double* inv_sigma2,
+                                const double* cam4, int32_t iterations, uint32_t seed, double* pose7, int32_t* n_inliers, uint8_t* inlier, int32_t* best_iteration)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    if (n_sets < 0) { set_error("pnp_ransac_batch: %d sets", n_sets); return LPSLAM_HIP_ERR_INVALID; }
+    if (iterations < 1 || iterations > LPSLAM_HIP_PNP_MAX_ITERATIONS) { set_error("pnp_ransac_batch: %d iterations outside 1 .. %d", iterations, LPSLAM_HIP_PNP_MAX_ITERATIONS); return LPSLAM_HIP_ERR_INVALID; }
+    if (!offsets || !cam4 || (n_sets > 0 && (!pose7 || !n_inliers))) { set_error("pnp_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    if (offsets[0] < 0) { set_error("pnp_ransac_batch: offsets[0] = %d is negative", offsets[0]); return LPSLAM_HIP_ERR_INVALID; }
+    for (int s = 0; s < n_sets; ++s) if (offsets[s + 1] < offsets[s]) { set_error("pnp_ransac_batch: offsets do not ascend at set %d", s); return LPSLAM_HIP_ERR_INVALID; }
+    const int first = offsets[0], total = offsets[n_sets] - first;
+    if (total > 0 && (!pw || !obs || !inv_sigma2 || !inlier)) { set_error("pnp_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(cam4[k])) { set_error("pnp_ransac_batch: the camera is no number"); return LPSLAM_HIP_ERR_INVALID; }
+    if (n_sets == 0) return LPSLAM_HIP_OK;
+    const size_t n_hyp = (size_t)n_sets * (size_t)iterations;
+    if (n_hyp > (size_t)0x7fffffff / 4) { set_error("pnp_ransac_batch: %d sets x %d iterations do not fit one launch", n_sets, iterations); return LPSLAM_HIP_ERR_CAPACITY; }
+    const EpnpSolveFn epnp_solve = host_epnp_solve();
+    if (!epnp_solve) { set_error("pnp_ransac_batch: the host library (liblpslam.so, for the refit's LpSlam::epnp_solve) is not beside this library"); return LPSLAM_HIP_ERR_INVALID; }
+    LP_HIP(hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    const LpMatchTrace tr;
+    // page-locked block: flag | input (head, offsets rebased to 0, sample table, landmarks, keypoints, weights) | results (a record per
+    // set, a flag per match); device block: the input, then the hypotheses (R, t) and their valid flags
+    const size_t o_in = 64;
+    size_t at = al64(sizeof(PnpHead));
+    const size_t o_offsets = at; at += al64((size_t)(n_sets + 1) * 4);
+    const size_t o_table = at; at += al64(n_hyp * 16);
+    const size_t o_pw = at; at += al64((size_t)std::max(total, 1) * 24);
+    const size_t o_obs = at; at += al64((size_t)std::max(total, 1) * 16);
+    const size_t o_w = at; at += al64((size_t)std::max(total, 1) * 8);
+    const size_t in_bytes = at;
+    const size_t d_hyp = at; at += al64(n_hyp * 96);
+    const size_t d_valid = at; at += al64(n_hyp * 4);
+    const size_t dev_bytes = at;
+    const size_t h_res = o_in + in_bytes, h_flags = h_res + al64((size_t)n_sets * sizeof(PnpResult));
+    const size_t host_bytes = h_flags + al64((size_t)std::max(total, 1));
+    if (dev_bytes >= (size_t)0xffffffffu) { set_error("pnp_ransac_batch: the sets do not fit one block"); return LPSLAM_HIP_ERR_CAPACITY; }
+    uint8_t* hb = lp_match_staging(c, host_bytes, host_bytes + host_bytes / 2, s);
+    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
+    LpPoolBlock blk(c);
+    if (int rc = blk.alloc(dev_bytes)) return rc;
+    uint8_t* base = (uint8_t*)blk.ptr;
+    uint8_t* in = hb + o_in;
+    PnpHead head{};
+    for (int k = 0; k < 4; ++k) head.cam[k] = cam4[k];
+    head.n_sets = n_sets; head.iterations = iterations;
+    head.o_offsets = (uint32_t)o_offsets; head.o_table = (uint32_t)o_table; head.o_pw = (uint32_t)o_pw; head.o_obs = (uint32_t)o_obs; head.o_w = (uint32_t)o_w;
+    memcpy(in, &head, sizeof head);
+    int32_t* off0 = (int32_t*)(in + o_offsets);
+    for (int i = 0; i <= n_sets; ++i) off0[i] = offsets[i] - first;
+    int32_t* table = (int32_t*)(in + o_table);
+    {
+        int max_n = 0;
+        for (int i = 0; i < n_sets; ++i) max_n = std::max(max_n, off0[i + 1] - off0[i]);
+        std::vector<int> avail((size_t)std::max(max_n, 1));
+        for (int i = 0; i < n_sets; ++i) {
+            const int n = off0[i + 1] - off0[i];
+            int32_t* tb = table + 4 * (size_t)i * (size_t)iterations;
+            if (n >= 4) ep::sample_table(n, iterations, seed, tb, avail.data());
+            else memset(tb, 0, (size_t)iterations * 16);
+        }
+    }
+    if (total > 0) {
+        memcpy(in + o_pw, pw + 3 * (size_t)first, (size_t)total * 24);
+        memcpy(in + o_obs, obs + 2 * (size_t)first, (size_t)total * 16);
+        memcpy(in + o_w, inv_sigma2 + (size_t)first, (size_t)total * 8);
+    }
+    const double tr_staged = tr.us();
+    LpDone done{};
+    if (int rc = lp_done_arm(c, 6, (int*)hb, c->done_seq, &done)) return rc;
+    LP_HIP(hipMemcpyAsync(base, in, in_bytes, hipMemcpyHostToDevice, s));
+    double* hyp = (double*)(base + d_hyp); int* valid = (int*)(base + d_valid);
+    hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)((n_hyp + kHypPerWg - 1) / kHypPerWg)), dim3(64), 0, s, (const uint8_t*)base, hyp, valid);
+    hipLaunchKernelGGL(k_pnp_score, dim3((unsigned)n_sets), dim3(256), 0, s, (const uint8_t*)base, (const double*)hyp, (const int*)valid,
+                       (PnpResult*)(hb + h_res), hb + h_flags, done.counter, done.flag, done.seq);
+    LP_HIP(hipGetLastError());
+    if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("pnp_ransac_batch: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+    const double tr_back = tr.us();
+    // the refit of pnp_solve_ransac (two_view.cpp:755-775), per set: EPnP over the winner's inliers, kept when it explains at least as many
+    const PnpResult* res = (const PnpResult*)(hb + h_res);
+    const uint8_t* fl = hb + h_flags;
+    std::vector<double> pi, ui;
+    std::vector<uint8_t> cur;
+    for (int i = 0; i < n_sets; ++i) {
+        const int o = off0[i], n = off0[i + 1] - o;
+        const double* spw = pw + 3 * (size_t)(first + o); const double* sob = obs + 2 * (size_t)(first + o); const double* sw = inv_sigma2 + (size_t)(first + o);
+        uint8_t* out_fl = inlier + (size_t)(first + o);
+        double* p7 = pose7 + 7 * (size_t)i;
+        int best = res[i].count;
+        if (best_iteration) best_iteration[i] = best >= 4 ? res[i].best_iteration : -1;
+        if (best < 4) {
+            for (int k = 0; k < n; ++k) out_fl[k] = 0;
+            n_inliers[i] = 0;
+            p7[0] = 1; for (int k = 1; k < 7; ++k) p7[k] = 0;
+            continue;
+        }
+        double bestR[9], bestT[3];
+        for (int k = 0; k < 9; ++k) bestR[k] = res[i].R[k];
+        for (int k = 0; k < 3; ++k) bestT[k] = res[i].t[k];
+        for (int k = 0; k < n; ++k) out_fl[k] = fl[o + k];
+        pi.clear(); ui.clear();
+        for (int k = 0; k < n; ++k) if (out_fl[k]) { for (int a = 0; a < 3; ++a) pi.push_back(spw[3 * (size_t)k + a]); ui.push_back(sob[2 * (size_t)k]); ui.push_back(sob[2 * (size_t)k + 1]); }
+        double R[9], t[3];
+        if (epnp_solve(pi.data(), ui.data(), (int)(ui.size() / 2), cam4, R, t)) {
+            cur.assign((size_t)n, 0);
+            int count = 0;
+            for (int k = 0; k < n; ++k) { cur[(size_t)k] = ep::pnp_inlier(R, t, cam4, spw + 3 * (size_t)k, sob[2 * (size_t)k], sob[2 * (size_t)k + 1], sw[k]) ? 1 : 0; count += cur[(size_t)k]; }
+            if (count >= best) {
+                best = count;
+                for (int k = 0; k < n; ++k) out_fl[k] = cur[(size_t)k];
+                for (int k = 0; k < 9; ++k) bestR[k] = R[k];
+                for (int k = 0; k < 3; ++k) bestT[k] = t[k];
+            }
+        }
+        double q[4];
+        LpSlam::rotToQuat(bestR, q);
+        for (int k = 0; k < 4; ++k) p7[k] = q[k];
+        for (int k = 0; k < 3; ++k) p7[4 + k] = bestT[k];
+        n_inliers[i] = best;
+    }
+    if (tr.on()) fprintf(stderr, "pnp_ransac_batch: %d sets, %d matches, %d iterations; us: staged %.1f, results back %.1f, refitted %.1f\n", n_sets, total, iterations, tr_staged, tr_back, tr.us());
+    return LPSLAM_HIP_OK;
+}
+
+}  // extern "C"

@@ -52,6 +52,7 @@ SYMBOLS = [
     "lpslam_hip_set_keypoint_camera", "lpslam_hip_stage_undistort", "lpslam_hip_undistort_dropped", "lpslam_hip_undistort_points",
     "lpslam_hip_set_keypoint_camera_radtan", "lpslam_hip_undistort_points_radtan",
     "lpslam_hip_triangulate_neighbours", "lpslam_hip_triangulate_pairs",
+    "lpslam_hip_pnp_ransac_batch",
 ]
 
 
@@ -940,6 +941,68 @@ def match_bow_tree_multi(ctx, q_desc, q_node, t_descs, t_nodes, hamming_thr=50, 
     f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     _check(f(ctx.h, _p(qd), _p(qn), len(qn), ns, arr(tds), arr(tns), nts, arr(tks) if t_takens is not None else None, int(hamming_thr), float(lowe_ratio), arr(idx), arr(dist), nm))
     return [(idx[i][:len(qn)], dist[i][:len(qn)], int(nm[i])) for i in range(ns)]
+
+PNP_MAX_ITERATIONS = 1024          # LPSLAM_HIP_PNP_MAX_ITERATIONS
+_PNP_ARGS = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def _pnp_arrays(offsets, pw, obs, inv_sigma2, cam4):
+    off = np.ascontiguousarray(offsets, np.int32)
+    n_sets = len(off) - 1
+    total = int(off[-1]) if n_sets >= 0 else 0
+    out = (np.zeros((max(n_sets, 1), 7)), np.zeros(max(n_sets, 1), np.int32), np.zeros(max(total, 1), np.uint8), np.full(max(n_sets, 1), -1, np.int32))
+    return off, n_sets, total, np.ascontiguousarray(pw, np.float64), np.ascontiguousarray(obs, np.float64), np.ascontiguousarray(inv_sigma2, np.float64), np.ascontiguousarray(cam4, np.float64), out
+
+
+def pnp_ransac_batch(ctx, offsets, pw, obs, inv_sigma2, cam4, iterations=100, seed=0x9E3779B9, want_iteration=True):
+    """lpslam_hip_pnp_ransac_batch: the sets are matches offsets[s] .. offsets[s + 1] of pw (n, 3), obs (n, 2), inv_sigma2 (n);
+    returns pose7 (S, 7), n_inliers (S), the per-match flags (n) and the winning iteration per set (-1: none; None when not asked for)"""
+    off, n_sets, total, pw, obs, w, cam, (pose, cnt, fl, best) = _pnp_arrays(offsets, pw, obs, inv_sigma2, cam4)
+    f = ctx.lib.lpslam_hip_pnp_ransac_batch
+    f.argtypes = [C.c_void_p] + _PNP_ARGS
+    _check(f(ctx.h, n_sets, _p(off), _p(pw), _p(obs), _p(w), _p(cam), int(iterations), int(seed) & 0xffffffff, _p(pose), _p(cnt), _p(fl), _p(best) if want_iteration else None))
+    return pose[:n_sets], cnt[:n_sets], fl[:total], (best[:n_sets] if want_iteration else None)
+
+
+_host_lib = None
+
+
+def host_lib():
+    """the host library (lpslam_amd/liblpslam.so): the CPU definitions behind the shims below, no device needed"""
+    global _host_lib
+    if _host_lib is None:
+        _host_lib = C.CDLL(os.path.join(_HERE, "liblpslam.so"))
+    return _host_lib
+
+
+def pnp_ransac_batch_host(offsets, pw, obs, inv_sigma2, cam4, iterations=100, seed=0x9E3779B9, want_iteration=True):
+    """lpslam_pnp_ransac_batch_host: LpSlam::pnp_solve_ransac on each set, the CPU definition of pnp_ransac_batch (same results)"""
+    off, n_sets, total, pw, obs, w, cam, (pose, cnt, fl, best) = _pnp_arrays(offsets, pw, obs, inv_sigma2, cam4)
+    f = host_lib().lpslam_pnp_ransac_batch_host
+    f.argtypes = _PNP_ARGS; f.restype = C.c_int
+    if f(n_sets, _p(off), _p(pw), _p(obs), _p(w), _p(cam), int(iterations), int(seed) & 0xffffffff, _p(pose), _p(cnt), _p(fl), _p(best) if want_iteration else None):
+        raise LpslamHipError("lpslam_pnp_ransac_batch_host refused its arguments")
+    return pose[:n_sets], cnt[:n_sets], fl[:total], (best[:n_sets] if want_iteration else None)
+
+
+def pnp_sample_table(n, iterations, seed):
+    """lpslam_pnp_sample_table: the (iterations, 4) match indices pnp_solve_ransac draws for a set of n >= 4 matches"""
+    f = host_lib().lpslam_pnp_sample_table
+    f.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p]; f.restype = C.c_int
+    table = np.full((max(int(iterations), 1), 4), -1, np.int32)
+    if not f(int(n), int(iterations), int(seed) & 0xffffffff, _p(table)):
+        raise LpslamHipError("lpslam_pnp_sample_table: n < 4 or iterations < 1")
+    return table
+
+
+def epnp4_host(p4, u4, cam4):
+    """lpslam_epnp4_host: the host form of epnp4 (csrc/epnp_math.h) on four matches; (R (3, 3), t (3)) or None"""
+    f = host_lib().lpslam_epnp4_host
+    f.argtypes = [C.c_void_p] * 5; f.restype = C.c_int
+    p4 = np.ascontiguousarray(p4, np.float64); u4 = np.ascontiguousarray(u4, np.float64); cam = np.ascontiguousarray(cam4, np.float64)
+    assert p4.size == 12 and u4.size == 8 and cam.size == 4
+    R = np.zeros(9); t = np.zeros(3)
+    return (R.reshape(3, 3), t) if f(_p(p4), _p(u4), _p(cam), _p(R), _p(t)) else None
 
 
 class RcclComm:

@@ -36,6 +36,8 @@ HipVslamTrackerBase::HipVslamTrackerBase()
     o.optional("fisheyeMaxAngleDeg", 70.0);
     // new landmarks by triangulation against this many covisible keyframes (0 .. 32; 0 = off)
     o.optional("triangulateNeighbours", 0);
+    // relocalisation: the candidates' PnP RANSAC in one call on the device; false: one host solve per candidate
+    o.optional("relocaliseOnDevice", false);
 }
 
 HipVslamTrackerBase::~HipVslamTrackerBase() { stop(); }
@@ -62,6 +64,7 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_prefetch = o.getBool("prefetch"); m_mapCulling = o.getBool("mapCulling");
     m_fisheyeMaxAngleDeg = o.getDouble("fisheyeMaxAngleDeg");
     m_triangulateNeighbours = o.getInteger("triangulateNeighbours");
+    m_relocaliseOnDevice = o.getBool("relocaliseOnDevice");
 }
 
 // The keypoint camera of a monocular session: the fisheye model from the camera configuration (f_x, f_y, c_x, c_y, dist[0..3]) with
@@ -1501,10 +1504,8 @@ bool HipVslamTrackerBase::relocalise(FrameData& cur)
     }
     const int scratch = previousSlot(cur.slot);                    // the previous frame's slot pair: its device data is not needed while lost
     std::vector<int32_t> mq((size_t)m_maxKp), mt((size_t)m_maxKp), md((size_t)m_maxKp);
-    for (auto& nc : near) {
-        const Keyframe& kf = m_kfs[(size_t)nc.second];
-        if (kf.kpts.empty()) continue;
-        std::vector<int> cur_idx, lm_ids;
+    // one candidate's matches on the device: the frame's keypoints and the landmarks they would observe; false: too few (or the call failed)
+    auto matchCandidate = [&](const Keyframe& kf, std::vector<int>& cur_idx, std::vector<int>& lm_ids) -> bool {
         if (use_bow && kf.node.size() == kf.kpts.size()) {
             // [UPSTREAM] match::bow_tree::match_frame_and_keyframe: the keyframe's keypoints that carry a landmark against the
             // frame's keypoints under the same vocabulary node (Hamming <= 50, ratio 0.75), then the orientation check
@@ -1513,44 +1514,93 @@ bool HipVslamTrackerBase::relocalise(FrameData& cur)
             std::vector<int32_t> idx(kf.kpts.size(), -1);
             int32_t nm = 0;
             if (lpslam_hip_match_bow_tree(m_ctx, kf.desc.data(), qn.data(), (int32_t)qn.size(), cur.desc.data(), cur_node.data(), (int32_t)cur_node.size(), nullptr, 50, 0.75f,
-                                          idx.data(), nullptr, &nm) != LPSLAM_HIP_OK) continue;
+                                          idx.data(), nullptr, &nm) != LPSLAM_HIP_OK) return false;
             int32_t kept = 0;
             (void)lpslam_hip_match_orientation_filter(keypointAngles(kf.kpts).data(), keypointAngles(cur.kpts).data(), idx.data(), (int32_t)idx.size(), &kept);
             associate(idx.data(), nullptr, (int)idx.size(), kf.landmark, cur_idx, lm_ids);     // (a keypoint whose landmark is gone was no query: qn above)
         } else {
             int32_t nm = 0;
-            if (lpslam_hip_match_bf_descriptors(m_ctx, cur.slot, scratch, kf.desc.data(), (int32_t)kf.kpts.size(), 50, 0.75f, 1, mq.data(), mt.data(), md.data(), m_maxKp, &nm) != LPSLAM_HIP_OK) continue;
+            if (lpslam_hip_match_bf_descriptors(m_ctx, cur.slot, scratch, kf.desc.data(), (int32_t)kf.kpts.size(), 50, 0.75f, 1, mq.data(), mt.data(), md.data(), m_maxKp, &nm) != LPSLAM_HIP_OK) return false;
             associate(mq.data(), mt.data(), nm, kf.landmark, cur_idx, lm_ids);
         }
-        if (cur_idx.size() < 15) continue;
-        // [UPSTREAM] solve::pnp_solver: the pose from the matches alone -- no prior, the camera may be anywhere that sees these
-        // landmarks -- refined by the pose optimiser ([UPSTREAM] min_num_inliers 10 for the solver)
-        Pose seed = kf.pose;
-        {
+        return cur_idx.size() >= 15;
+    };
+    // [UPSTREAM] solve::pnp_solver: the pose from the matches alone -- no prior, the camera may be anywhere that sees these
+    // landmarks -- refined by the pose optimiser ([UPSTREAM] min_num_inliers 10 for the solver).  The solver's input:
+    auto solverInput = [&](const std::vector<int>& cur_idx, const std::vector<int>& lm_ids, std::vector<double>& pw, std::vector<double>& ob, std::vector<double>& w) {
+        for (size_t k = 0; k < cur_idx.size(); ++k) {
+            auto it = m_landmarks.find(lm_ids[k]);
+            if (it == m_landmarks.end()) continue;               // culled since the keyframe saw it (poseFromMatches skips it too)
+            const lpslam_hip_keypoint& kp = cur.kpts[(size_t)cur_idx[k]];
+            pw.insert(pw.end(), it->second.p, it->second.p + 3);
+            ob.push_back(kp.x); ob.push_back(kp.y);
+            const double sc = m_scales[kp.octave];
+            w.push_back(1.0 / (sc * sc));
+        }
+    };
+    // the solver's pose seeds the pose optimiser; 30 inliers bring the tracker back
+    auto refine = [&](int kf_index, const std::vector<int>& cur_idx, const std::vector<int>& lm_ids, const double* p7) -> bool {
+        Pose seed = m_kfs[(size_t)kf_index].pose;
+        for (int a = 0; a < 4; ++a) seed.q[a] = p7[a];
+        for (int a = 0; a < 3; ++a) seed.t[a] = p7[4 + a];
+        int inl = 0;
+        FrameData trial = cur;
+        if (!poseFromMatches(trial, cur_idx, lm_ids, seed, inl, 30)) return false;
+        cur.pose = trial.pose; cur.landmark = trial.landmark;
+        logMessage(LpSlamLogLevel_Info, "VSLAM relocalised against keyframe " + std::to_string(kf_index) + " with " + std::to_string(inl) + " inliers");
+        return true;
+    };
+    const double cam4[4] = {m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y};
+    if (!m_relocaliseOnDevice) {
+        for (auto& nc : near) {
+            const Keyframe& kf = m_kfs[(size_t)nc.second];
+            if (kf.kpts.empty()) continue;
+            std::vector<int> cur_idx, lm_ids;
+            if (!matchCandidate(kf, cur_idx, lm_ids)) continue;
             std::vector<double> pw, ob, w;
-            for (size_t k = 0; k < cur_idx.size(); ++k) {
-                auto it = m_landmarks.find(lm_ids[k]);
-                if (it == m_landmarks.end()) continue;               // culled since the keyframe saw it (poseFromMatches skips it too)
-                const lpslam_hip_keypoint& kp = cur.kpts[(size_t)cur_idx[k]];
-                pw.insert(pw.end(), it->second.p, it->second.p + 3);
-                ob.push_back(kp.x); ob.push_back(kp.y);
-                const double sc = m_scales[kp.octave];
-                w.push_back(1.0 / (sc * sc));
-            }
+            solverInput(cur_idx, lm_ids, pw, ob, w);
             const size_t nm2 = w.size();
-            const double cam4[4] = {m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y};
             double p7[7];
             std::vector<uint8_t> pnp_inl(std::max<size_t>(nm2, 1));
             if (nm2 < 4 || pnp_solve_ransac(pw.data(), ob.data(), w.data(), (int)nm2, cam4, 100, 0x9E3779B9u, p7, pnp_inl.data()) < 10) continue;
-            for (int a = 0; a < 4; ++a) seed.q[a] = p7[a];
-            for (int a = 0; a < 3; ++a) seed.t[a] = p7[4 + a];
+            if (refine(nc.second, cur_idx, lm_ids, p7)) return true;
         }
-        int inl = 0;
-        FrameData trial = cur;
-        if (!poseFromMatches(trial, cur_idx, lm_ids, seed, inl, 30)) continue;
-        cur.pose = trial.pose; cur.landmark = trial.landmark;
-        logMessage(LpSlamLogLevel_Info, "VSLAM relocalised against keyframe " + std::to_string(nc.second) + " with " + std::to_string(inl) + " inliers");
-        return true;
+        return false;
+    }
+    // relocaliseOnDevice: the match sets of all candidates first, ONE solver call for them (lpslam_hip_pnp_ransac_batch, the results of
+    // pnp_solve_ransac on each), then the candidates in their order as above -- the outcome is the serial loop's; only solves that loop
+    // would have skipped after an earlier success are wasted
+    struct Candidate { int kf; std::vector<int> cur_idx, lm_ids; };
+    std::vector<Candidate> cands;
+    std::vector<double> pw, ob, w;
+    std::vector<int32_t> offsets{0};
+    for (auto& nc : near) {
+        const Keyframe& kf = m_kfs[(size_t)nc.second];
+        if (kf.kpts.empty()) continue;
+        Candidate cd; cd.kf = nc.second;
+        if (!matchCandidate(kf, cd.cur_idx, cd.lm_ids)) continue;
+        solverInput(cd.cur_idx, cd.lm_ids, pw, ob, w);
+        offsets.push_back((int32_t)w.size());
+        cands.push_back(std::move(cd));
+    }
+    if (cands.empty()) return false;
+    const int32_t ns = (int32_t)cands.size();
+    std::vector<double> p7((size_t)ns * 7);
+    std::vector<int32_t> n_inl((size_t)ns, 0);
+    std::vector<uint8_t> pnp_inl(std::max<size_t>(w.size(), 1));
+    if (lpslam_hip_pnp_ransac_batch(m_ctx, ns, offsets.data(), pw.data(), ob.data(), w.data(), cam4, 100, 0x9E3779B9u, p7.data(), n_inl.data(), pnp_inl.data(), nullptr) == LPSLAM_HIP_OK)
+        ++m_stats.pnp_batches;
+    else {
+        logMessage(LpSlamLogLevel_Error, std::string("VSLAM relocalisation: the solver batch failed (") + lpslam_hip_last_error() + "); this frame's candidates are solved on the host");
+        for (int32_t i = 0; i < ns; ++i) {
+            const size_t o = (size_t)offsets[(size_t)i];
+            const int n = offsets[(size_t)i + 1] - offsets[(size_t)i];
+            n_inl[(size_t)i] = n < 4 ? 0 : pnp_solve_ransac(pw.data() + 3 * o, ob.data() + 2 * o, w.data() + o, n, cam4, 100, 0x9E3779B9u, p7.data() + 7 * (size_t)i, pnp_inl.data() + o);
+        }
+    }
+    for (int32_t i = 0; i < ns; ++i) {
+        if (n_inl[(size_t)i] < 10) continue;
+        if (refine(cands[(size_t)i].kf, cands[(size_t)i].cur_idx, cands[(size_t)i].lm_ids, p7.data() + 7 * (size_t)i)) return true;
     }
     return false;
 }
@@ -2058,7 +2108,7 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld pnp_batches=%ld reloc_frames=%ld ms_reloc_frame=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
@@ -2066,7 +2116,8 @@ void HipVslamTrackerBase::logStatistics()
                   (long)(dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_BAND] + dev[LPSLAM_HIP_BA_COUNTER_TIMEOUTS_UPDATE]), s.intensity_adjusted, s.color_converted, s.fisheye_dropped,
                   s.t_total * per, s.t_front * per, s.t_track * per, s.t_local * per, s.t_keyframe * per,
                   s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per,
-                  s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per, s.perspective_dropped);
+                  s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per, s.perspective_dropped,
+                  s.pnp_batches, s.reloc_frames, s.reloc_frames > 0 ? 1e3 * s.t_relocalise / (double)s.reloc_frames : 0.0);
     m_lastStatistics = buf;
     logMessage(LpSlamLogLevel_Info, buf);
 }
@@ -2260,7 +2311,10 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
         Pose nav_step;
         if (m_lostSinceUnset) { m_lostSince = cam.timestamp; m_lostSinceUnset = false; }
         if (m_relocWithNavigation && navDelta(nav_step)) m_lastGoodPose = compose(nav_step, m_lastGoodPose);
-        if (relocalise(cur)) {
+        const auto t_reloc = std::chrono::steady_clock::now();
+        const bool relocalised = relocalise(cur);
+        m_stats.t_relocalise += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_reloc).count(); ++m_stats.reloc_frames;
+        if (relocalised) {
             m_state = TrackerState::Tracking;
             ++m_stats.relocalised;
             m_relocByRank = false;

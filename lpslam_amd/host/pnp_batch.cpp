@@ -1,0 +1,58 @@
+// pnp_batch.cpp -- the CPU side of the batched PnP RANSAC: C shims for the tests and the timing tool.
+//   lpslam_pnp_sample_table        the 4-match samples pnp_solve_ransac draws for a set of n matches (csrc/epnp_math.h)
+//   lpslam_epnp4_host              the host form of the header's epnp4, bit for bit epnp_solve at n = 4
+//   lpslam_pnp_ransac_batch_host   lpslam_hip_pnp_ransac_batch without the context: pnp_solve_ransac on each set -- the CPU definition
+#include "two_view.h"
+#include "../csrc/epnp_math.h"
+#include <vector>
+
+#define LP_EXPORT extern "C" __attribute__((visibility("default")))
+
+// 1: table holds iterations x 4 indices; 0: n < 4 or iterations < 1, table untouched
+LP_EXPORT int lpslam_pnp_sample_table(int n, int iterations, uint32_t seed, int32_t* table)
+{
+    if (n < 4 || iterations < 1 || !table) return 0;
+    std::vector<int> avail((size_t)n);
+    lpslam_epnp::sample_table(n, iterations, seed, table, avail.data());
+    return 1;
+}
+
+LP_EXPORT int lpslam_epnp4_host(const double* p4, const double* u4, const double* cam, double* R9, double* t3)
+{
+    double ws[lpslam_epnp::kWorkspace];
+    return lpslam_epnp::epnp4(p4, u4, cam, ws, 1, R9, t3) ? 1 : 0;
+}
+
+// 0: done; 1: refused (the argument rules of lpslam_hip_pnp_ransac_batch), nothing written
+LP_EXPORT int lpslam_pnp_ransac_batch_host(int32_t n_sets, const int32_t* offsets, const double* pw, const double* obs, const double* inv_sigma2, const double* cam4,
+                                           int32_t iterations, uint32_t seed, double* pose7, int32_t* n_inliers, uint8_t* inlier, int32_t* best_iteration)
+{
+    if (n_sets < 0 || iterations < 1 || !offsets || !cam4 || (n_sets > 0 && (!pose7 || !n_inliers)) || offsets[0] < 0) return 1;
+    for (int s = 0; s < n_sets; ++s) if (offsets[s + 1] < offsets[s]) return 1;
+    if (offsets[n_sets] > offsets[0] && (!pw || !obs || !inv_sigma2 || !inlier)) return 1;
+    std::vector<int32_t> table;
+    for (int s = 0; s < n_sets; ++s) {
+        const size_t o = (size_t)offsets[s];
+        const int n = offsets[s + 1] - offsets[s];
+        const double* spw = pw + 3 * o; const double* sob = obs + 2 * o; const double* sw = inv_sigma2 + o;
+        double* p7 = pose7 + 7 * (size_t)s;
+        p7[0] = 1; for (int k = 1; k < 7; ++k) p7[k] = 0;                       // (pnp_solve_ransac leaves the pose alone when it finds none)
+        n_inliers[s] = LpSlam::pnp_solve_ransac(spw, sob, sw, n, cam4, iterations, seed, p7, inlier + o);
+        if (!best_iteration) continue;
+        // which sample won: the loop of pnp_solve_ransac over the table, first maximum
+        best_iteration[s] = -1;
+        if (n < 4 || n_inliers[s] == 0) continue;
+        table.resize((size_t)iterations * 4);
+        lpslam_pnp_sample_table(n, iterations, seed, table.data());
+        int best = 0;
+        for (int it = 0; it < iterations; ++it) {
+            double p4[12], u4[8], R[9], t[3];
+            for (int k = 0; k < 4; ++k) { const size_t m = (size_t)table[(size_t)4 * it + k]; for (int a = 0; a < 3; ++a) p4[3 * k + a] = spw[3 * m + a]; u4[2 * k] = sob[2 * m]; u4[2 * k + 1] = sob[2 * m + 1]; }
+            if (!LpSlam::epnp_solve(p4, u4, 4, cam4, R, t)) continue;
+            int count = 0;
+            for (int i = 0; i < n; ++i) count += lpslam_epnp::pnp_inlier(R, t, cam4, spw + 3 * (size_t)i, sob[2 * (size_t)i], sob[2 * (size_t)i + 1], sw[i]) ? 1 : 0;
+            if (count > best) { best = count; best_iteration[s] = it; }
+        }
+    }
+    return 0;
+}

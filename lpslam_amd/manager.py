@@ -154,6 +154,8 @@ class Manager:
         return bool(self.lib.lpslam_manager_read_configuration_file(self.h, path.encode()))
 
     def add_tracker(self, name, cfg=""):
+        """cfg: the tracker's JSON object as text; every key goes to the plugin as written (INTEGRATION.md lists them, e.g.
+        "triangulateNeighbours": 10, "relocaliseOnDevice": true)"""
         return bool(self.lib.lpslam_manager_add_tracker(self.h, name.encode(), cfg.encode()))
 
     def add_processor(self, name, cfg=""):
