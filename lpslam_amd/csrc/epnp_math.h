@@ -1,34 +1,45 @@
-// epnp_math.h -- the pose of a camera from exactly four landmark / keypoint matches, once, for the device
-// kernels (pnp.hip), the host shims (lpslam_amd/host/pnp_batch.cpp) and the CPU tests: FP64 throughout.
-//   epnp4          the fixed-size form of LpSlam::epnp_solve (lpslam_amd/host/two_view.cpp) at n = 4: the same operations in the same
-//                  order with the same thresholds, so that -- both sides built with -ffp-contract=off, + - * / sqrt correctly
-//                  rounded on both -- its R, t and return value are those of epnp_solve to the last bit
-//   pnp_inlier     the scoring rule of pnp_solve_ransac's count_inliers
-//   sample_table   the 4-match samples pnp_solve_ransac draws (host only: the draw is sequential by definition)
-// [UPSTREAM] solve::pnp_solver; EPnP: Lepetit, Moreno-Noguer, Fua, IJCV 2009 (see the comment in front of epnp_solve).
-// No heap, every array of fixed size, every loop with the host's own fixed bound.  The 12 x 12 matrix M^T M and its eigenvectors
-// (288 doubles) live in a workspace of the caller: element e of it is ws[e * stride] -- stride 1 on the host, the number of
-// workspace's element stride on the device.  There sixteen lanes of a wave solve one hypothesis together: they share the workspace (LDS)
-// and divide the independent elements of each Jacobi rotation of the 12 x 12 matrix among them (jacobi, below); everything else each
-// of them computes for itself, with the same result.
+// epnp_math.h -- the pose of a camera from landmark / keypoint matches (DESIGN.md sections 34 and 35), once, for the device kernels
+// (pnp.hip), the host library (lpslam_amd/host/two_view.cpp, pnp_batch.cpp) and the CPU tests: FP64 throughout, + - * / sqrt only, so
+// that -- every side built with -ffp-contract=off -- all of them return the same bits.
+//   epnp           EPnP on n >= 4 matches; epnp<4> is its instance at n = 4 with the per-match arrays as locals (the device's form)
+//   horn           Horn's absolute orientation of n >= 3 matched points, with or without a free scale
+//   lsq_small      the small least-squares solves of EPnP's betas
+//   pnp_inlier     the scoring rule of the RANSAC around EPnP, pnp_score its count over a set
+//   host only:     sample_table (the 4-match samples of LpSlam::pnp_solve_ransac; the draw is sequential by definition),
+//                  pnp_solve_sample (one sample's hypothesis) and pnp_refit (EPnP once more over the winner's inliers)
+// No heap: every array is of fixed size or the caller's.  The 12 x 12 matrix M^T M and its eigenvectors (288 doubles) live in a
+// workspace of the caller: element e of it is ws[e * stride].  On the device sixteen lanes of a wave solve one hypothesis together:
+// they share the workspace (LDS) and divide the independent elements of each Jacobi rotation of the 12 x 12 matrix among them
+// (jacobi_math.h); everything else each of them computes for itself, with the same result.
+//
+// [UPSTREAM] solve::pnp_solver (relocalisation without a pose prior).
+// EPnP (Lepetit, Moreno-Noguer, Fua: "EPnP: An Accurate O(n) Solution to the PnP Problem", IJCV 2009) inside a RANSAC over 4-match
+// samples, then a refit on the inliers of the best sample -- the structure of OpenVSLAM's solver (which follows ORB-SLAM's PnPsolver,
+// itself the authors' reference implementation).  The algorithm, as published:
+//   1. four control points in the world: the centroid and the centroid plus the principal directions scaled by sqrt(eigenvalue / n);
+//   2. every landmark as a barycentric combination of them (alphas, they sum to one);
+//   3. the projection equations are linear in the 12 camera-frame coordinates of the control points: M x = 0 (2 n x 12); the solution is
+//      a combination x = sum beta_k v_k of the eigenvectors of M^T M with the four smallest eigenvalues;
+//   4. the betas from the six pairwise distances of the control points, which the camera frame must preserve (L_6x10 beta_ij = rho):
+//      three linearised guesses (N = 1 .. 3 null vectors: approx_1 / _2 / _3), each refined by five Gauss-Newton steps;
+//   5. per guess the camera-frame landmarks, the sign that puts them in front of the camera, the rigid motion world -> camera (Horn's
+//      absolute orientation here; the reference implementation takes the SVD form), and its mean reprojection error: the best wins.
+// Inliers are counted by the reprojection error (chi-square 5.991 at the keypoint's level).  The pose optimiser on the device refines
+// the result, as upstream refines EPnP's.  The linear algebra is the Jacobi eigen-solver of jacobi_math.h and small Gaussian
+// eliminations, written so that the tests' numpy restatement can follow it operation by operation (both sides then test the same
+// hypotheses).
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
+#include "jacobi_math.h"
 
 #if defined(__HIPCC__)
 #define LP_EPNP_FN __host__ __device__ inline
-#define LP_EPNP_PRAGMA(x) _Pragma(#x)
-#define LP_EPNP_UNROLL(n) LP_EPNP_PRAGMA(unroll n)      // constant indices: the small matrices stay in registers on the device
+#define LP_EPNP_UNROLL(n) LP_JACOBI_UNROLL(n)
 #else
 #define LP_EPNP_FN inline
 #define LP_EPNP_UNROLL(n)
-#endif
-// Lanes of one wave that work on one workspace together (below): what a lane wrote to it is read by its neighbours from here on.  A
-// wave's LDS instructions execute in their order; this keeps the compiler from moving or caching accesses across the point.
-#if defined(__HIP_DEVICE_COMPILE__)
-#define LP_EPNP_LANES_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-#else
-#define LP_EPNP_LANES_SYNC() do { } while (0)
 #endif
 
 namespace lpslam_epnp {
@@ -37,74 +48,7 @@ constexpr int kWorkspace = 288;       // doubles of workspace per hypothesis: M^
 
 LP_EPNP_FN bool finite(double x) { return __builtin_isfinite(x); }
 
-// sym_eigen_jacobi of lpslam_amd/host/two_view.cpp on an N x N matrix, in place: a (row major, element (i, j) at a[(i * N + j) * st])
-// ends with the eigenvalues on its diagonal, v receives the eigenvectors as columns; at most 64 sweeps.  order[c] = the column of the
-// c-th smallest eigenvalue: the host sorts with std::sort, which for 16 elements or fewer is libstdc++'s insertion sort -- the first
-// among equal eigenvalues stays first -- and that sort is written out here comparison by comparison.
-// UNROLL: the loop bodies are expanded so that every index is a constant (N = 3, 4); the 12 x 12 matrix keeps its loops.
-// ln, nl: lane ln of nl lanes of one wave that call this together on one (shared) a and v with the same values: the elements of a
-// rotation -- independent of each other -- are divided among them (k = ln, ln + nl, ...), everything else every lane computes for
-// itself.  Each element is computed by the same operations either way; the host and the small matrices run with one lane.
-template <int N, int UNROLL>
-LP_EPNP_FN void jacobi(double* a, double* v, int st, int* order, int ln = 0, int nl = 1)
-{
-    for (int i = ln; i < N * N; i += nl) v[i * st] = 0.0;
-    LP_EPNP_LANES_SYNC();
-    for (int i = ln; i < N; i += nl) v[(i * N + i) * st] = 1.0;
-    LP_EPNP_LANES_SYNC();
-    for (int sweep = 0; sweep < 64; ++sweep) {
-        double off = 0, diag = 0;
-        LP_EPNP_UNROLL(UNROLL)
-        for (int i = 0; i < N; ++i)
-            LP_EPNP_UNROLL(UNROLL)
-            for (int j = 0; j < N; ++j) { const double x = a[(i * N + j) * st]; if (i == j) diag += x * x; else off += x * x; }
-        if (off <= 1e-30 * (diag + 1e-300)) break;
-        LP_EPNP_UNROLL(UNROLL)
-        for (int p = 0; p < N - 1; ++p)
-            LP_EPNP_UNROLL(UNROLL)
-            for (int q = p + 1; q < N; ++q) {
-                const double apq = a[(p * N + q) * st];
-                if (apq == 0.0) continue;
-                const double theta = (a[(q * N + q) * st] - a[(p * N + p) * st]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                LP_EPNP_LANES_SYNC();                           // (every lane has read a_pp, a_qq, a_pq)
-                LP_EPNP_UNROLL(UNROLL)
-                for (int k = ln; k < N; k += nl) {              // columns p, q
-                    const double akp = a[(k * N + p) * st], akq = a[(k * N + q) * st];
-                    a[(k * N + p) * st] = c * akp - s * akq; a[(k * N + q) * st] = s * akp + c * akq;
-                }
-                LP_EPNP_LANES_SYNC();
-                LP_EPNP_UNROLL(UNROLL)
-                for (int k = ln; k < N; k += nl) {              // rows p, q
-                    const double apk = a[(p * N + k) * st], aqk = a[(q * N + k) * st];
-                    a[(p * N + k) * st] = c * apk - s * aqk; a[(q * N + k) * st] = s * apk + c * aqk;
-                }
-                LP_EPNP_UNROLL(UNROLL)
-                for (int k = ln; k < N; k += nl) {
-                    const double vkp = v[(k * N + p) * st], vkq = v[(k * N + q) * st];
-                    v[(k * N + p) * st] = c * vkp - s * vkq; v[(k * N + q) * st] = s * vkp + c * vkq;
-                }
-                LP_EPNP_LANES_SYNC();
-            }
-    }
-    for (int i = 0; i < N; ++i) order[i] = i;
-    for (int i = 1; i < N; ++i) {
-        const int val = order[i];
-        const double dv = a[(val * N + val) * st];
-        if (dv < a[(order[0] * N + order[0]) * st]) {
-            for (int j = i; j > 0; --j) order[j] = order[j - 1];
-            order[0] = val;
-        } else {
-            int j = i;
-            while (dv < a[(order[j - 1] * N + order[j - 1]) * st]) { order[j] = order[j - 1]; --j; }      // (stops at j = 1 at the latest: the test above failed)
-            order[j] = val;
-        }
-    }
-}
-
-// lsq_small of two_view.cpp: least squares A x = b (m x k, k <= 5) by the normal equations and Gaussian elimination with partial
-// pivoting; false when singular
+// least squares A x = b (m x k, k <= 5) by the normal equations and Gaussian elimination with partial pivoting; false when singular
 LP_EPNP_FN bool lsq_small(const double* A, const double* b, int m, int k, double* x)
 {
     double N[5 * 6];
@@ -132,10 +76,14 @@ LP_EPNP_FN bool lsq_small(const double* A, const double* b, int m, int k, double
     return true;
 }
 
-// horn_absolute_orientation of two_view.cpp for four points and a fixed scale: x1 = R x2 + t
-LP_EPNP_FN bool horn4(const double* x1, const double* x2, double* R, double* t)
+// Horn's absolute orientation of n >= 3 matched points: x1 = s R x2 + t (R row major; fix_scale: s = 1).  false: fewer than three
+// points, no rotation, or no positive scale -- nothing is written then.  NFIX: the number of points when it is a constant of the
+// caller (epnp<4>), 0: it is the argument n_points.
+template <int NFIX = 0>
+LP_EPNP_FN bool horn(const double* x1, const double* x2, int n_points, bool fix_scale, double* R, double* t, double* s_out)
 {
-    const int n = 4;
+    const int n = NFIX > 0 ? NFIX : n_points;
+    if (n < 3) return false;
     double o1[3] = {0, 0, 0}, o2[3] = {0, 0, 0};
     for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) { o1[a] += x1[3 * i + a]; o2[a] += x2[3 * i + a]; }
     for (int a = 0; a < 3; ++a) { o1[a] /= n; o2[a] /= n; }
@@ -148,7 +96,7 @@ LP_EPNP_FN bool horn4(const double* x1, const double* x2, double* R, double* t)
                     M[1] - M[3], M[6] + M[2], M[5] + M[7], -M[0] - M[4] + M[8]};
     double evec[16];
     int order[4];
-    jacobi<4, 4>(N, evec, 1, order);                     // ascending: the last column belongs to the largest eigenvalue
+    lpslam_jacobi::jacobi<4, 4>(N, evec, 1, order);                    // ascending: the last column belongs to the largest eigenvalue
     double q[4];
     q[0] = evec[0]; q[1] = evec[4]; q[2] = evec[8]; q[3] = evec[12];
     LP_EPNP_UNROLL(3)
@@ -160,20 +108,43 @@ LP_EPNP_FN bool horn4(const double* x1, const double* x2, double* R, double* t)
     const double Rm[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
                           2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
                           2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
-    const double sc = 1.0;
+    double sc = 1.0;
+    if (!fix_scale) {
+        double nom = 0, den = 0;
+        for (int i = 0; i < n; ++i) {
+            double p3[3];
+            for (int r = 0; r < 3; ++r) p3[r] = Rm[r * 3] * (x2[3 * i] - o2[0]) + Rm[r * 3 + 1] * (x2[3 * i + 1] - o2[1]) + Rm[r * 3 + 2] * (x2[3 * i + 2] - o2[2]);
+            for (int r = 0; r < 3; ++r) { nom += (x1[3 * i + r] - o1[r]) * p3[r]; den += p3[r] * p3[r]; }
+        }
+        if (!(den > 0) || !(nom > 0)) return false;
+        sc = nom / den;
+    }
     for (int k = 0; k < 9; ++k) R[k] = Rm[k];
     for (int r = 0; r < 3; ++r) t[r] = o1[r] - sc * (Rm[r * 3] * o2[0] + Rm[r * 3 + 1] * o2[1] + Rm[r * 3 + 2] * o2[2]);
+    *s_out = sc;
     return true;
 }
 
 LP_EPNP_FN double dot3(const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; }
 
-// epnp_solve of two_view.cpp (lines 587-717) for n = 4.  pw: 4 x 3 landmarks (world), uv: 4 x 2 keypoints (pixels), cam: fx fy cx cy;
-// ws: kWorkspace doubles, element e at ws[e * stride].  true: R (row major, world -> camera) and t are written.
-// ln, nl: as for jacobi -- nl lanes of a wave call this together with the same arguments and one workspace; each returns the result.
-LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, double* ws, int stride, double* R, double* t, int ln = 0, int nl = 1)
+// EPnP (the steps in the comment at the top).  pw: n x 3 landmarks (world), uv: n x 2 keypoints (pixels), cam: fx fy cx cy; ws:
+// kWorkspace doubles, element e at ws[e * stride].  true: R (row major, world -> camera) and t are written; false: fewer than four
+// matches or degenerate input.
+// NFIX: the number of matches when it is a constant of the caller -- the RANSAC's 4, on the device and on the host -- 0: it is the
+// argument n_matches.  The per-match arrays, the alphas al (4 n doubles) and the camera-frame landmarks pc (3 n), are locals at a
+// constant n (al and pc are not read, pass null) and the caller's scratch otherwise.  (The kernel calls epnp<4> itself, and the
+// arrays are declared here, because k_pnp_hypotheses was found to keep its code only so: a wrapper in between, or arrays handed in,
+// moved its register allocation.)
+// ln, nl: as for jacobi_sweeps (jacobi_math.h) -- nl lanes of a wave call this together with the same arguments and one workspace; each
+// returns the result.
+template <int NFIX = 0>
+LP_EPNP_FN bool epnp(const double* pw, const double* uv, int n_matches, const double* cam, double* al, double* pc, double* ws, int stride, double* R, double* t,
+                     int ln = 0, int nl = 1)
 {
-    const int n = 4;
+    const int n = NFIX > 0 ? NFIX : n_matches;
+    double al_fixed[NFIX > 0 ? 4 * NFIX : 1], pc_fixed[NFIX > 0 ? 3 * NFIX : 1];
+    if (NFIX > 0) { al = al_fixed; pc = pc_fixed; }
+    if (n < 4) return false;
     const double fu = cam[0], fv = cam[1], uc = cam[2], vc = cam[3];
     // 1. control points
     double cws[4][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
@@ -184,7 +155,7 @@ LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, dou
         for (int a = 0; a < 3; ++a) for (int b2 = 0; b2 < 3; ++b2) C[a * 3 + b2] += (pw[3 * i + a] - cws[0][a]) * (pw[3 * i + b2] - cws[0][b2]);
     double evec[9];
     int ord3[3];
-    jacobi<3, 3>(C, evec, 1, ord3);                         // ascending; the principal direction first, as the published code orders them
+    lpslam_jacobi::jacobi<3, 3>(C, evec, 1, ord3);                       // ascending; the principal direction first, as the published code orders them
     for (int j = 1; j <= 3; ++j) {
         const int col = ord3[3 - j];
         const double e = C[col * 4];
@@ -199,7 +170,6 @@ LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, dou
     CI[0] = (CC[4] * CC[8] - CC[5] * CC[7]) / det; CI[1] = (CC[2] * CC[7] - CC[1] * CC[8]) / det; CI[2] = (CC[1] * CC[5] - CC[2] * CC[4]) / det;
     CI[3] = (CC[5] * CC[6] - CC[3] * CC[8]) / det; CI[4] = (CC[0] * CC[8] - CC[2] * CC[6]) / det; CI[5] = (CC[2] * CC[3] - CC[0] * CC[5]) / det;
     CI[6] = (CC[3] * CC[7] - CC[4] * CC[6]) / det; CI[7] = (CC[1] * CC[6] - CC[0] * CC[7]) / det; CI[8] = (CC[0] * CC[4] - CC[1] * CC[3]) / det;
-    double al[16];
     for (int i = 0; i < n; ++i) {
         const double d0 = pw[3 * i] - cws[0][0], d1 = pw[3 * i + 1] - cws[0][1], d2 = pw[3 * i + 2] - cws[0][2];
         for (int j = 0; j < 3; ++j) al[4 * i + 1 + j] = CI[j * 3] * d0 + CI[j * 3 + 1] * d1 + CI[j * 3 + 2] * d2;
@@ -209,7 +179,7 @@ LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, dou
     double* MtM = ws;
     double* mvec = ws + 144 * stride;
     for (int e = ln; e < 144; e += nl) MtM[e * stride] = 0;
-    LP_EPNP_LANES_SYNC();
+    LP_JACOBI_LANES_SYNC();
     for (int i = 0; i < n; ++i) {
         double r1[12], r2[12];
         for (int j = 0; j < 4; ++j) {
@@ -219,9 +189,9 @@ LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, dou
         }
         for (int a = ln; a < 12; a += nl) for (int b2 = 0; b2 < 12; ++b2) MtM[(a * 12 + b2) * stride] += r1[a] * r1[b2] + r2[a] * r2[b2];      // (a lane's rows are its own)
     }
-    LP_EPNP_LANES_SYNC();
+    LP_JACOBI_LANES_SYNC();
     int ord12[12];
-    jacobi<12, 1>(MtM, mvec, stride, ord12, ln, nl);        // ascending: columns 0 .. 3 span the (approximate) null space
+    lpslam_jacobi::jacobi<12, 1>(MtM, mvec, stride, ord12, ln, nl);       // ascending: columns 0 .. 3 span the (approximate) null space
     double v[4][12];
     for (int k = 0; k < 4; ++k) for (int a = 0; a < 12; ++a) v[k][a] = mvec[(a * 12 + ord12[k]) * stride];
     // 4. distance constraints
@@ -240,7 +210,6 @@ LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, dou
     }
     double best_err = 1e300;
     bool found = false;
-    double pc[12];
     for (int guess = 0; guess < 3; ++guess) {
         double be[4] = {0, 0, 0, 0};
         if (guess == 0) {                                   // betas 11 12 13 14 (columns 0, 1, 3, 6): N = 4 with the cross terms of beta_1 only
@@ -287,9 +256,9 @@ LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, dou
         for (int j = 0; j < 4; ++j) for (int a = 0; a < 3; ++a) ccs[j][a] = be[0] * v[0][3 * j + a] + be[1] * v[1][3 * j + a] + be[2] * v[2][3 * j + a] + be[3] * v[3][3 * j + a];
         for (int i = 0; i < n; ++i)
             for (int a = 0; a < 3; ++a) pc[3 * i + a] = al[4 * i] * ccs[0][a] + al[4 * i + 1] * ccs[1][a] + al[4 * i + 2] * ccs[2][a] + al[4 * i + 3] * ccs[3][a];
-        if (pc[2] < 0) for (int k = 0; k < 12; ++k) pc[k] = -pc[k];      // the first landmark in front of the camera
-        double Rg[9], tg[3];
-        if (!horn4(pc, pw, Rg, tg)) continue;
+        if (pc[2] < 0) for (int k = 0; k < 3 * n; ++k) pc[k] = -pc[k];      // the first landmark in front of the camera
+        double Rg[9], tg[3], unit;
+        if (!horn<NFIX>(pc, pw, n, true, Rg, tg, &unit)) continue;
         double err = 0;
         bool fin = true;
         for (int i = 0; i < n; ++i) {
@@ -307,7 +276,7 @@ LP_EPNP_FN bool epnp4(const double* pw, const double* uv, const double* cam, dou
     return found;
 }
 
-// count_inliers of pnp_solve_ransac for one match: landmark X, keypoint (u, v) with weight inv_sigma2 = 1 / scale^2 of its level
+// The RANSAC's inlier rule for one match: landmark X, keypoint (u, v) with weight inv_sigma2 = 1 / scale^2 of its level
 LP_EPNP_FN bool pnp_inlier(const double* R, const double* t, const double* cam, const double* X, double u, double v, double inv_sigma2)
 {
     const double xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0], yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
@@ -316,8 +285,8 @@ LP_EPNP_FN bool pnp_inlier(const double* R, const double* t, const double* cam, 
     return z > 0 && (du * du + dv * dv) * inv_sigma2 < 5.991;
 }
 
-// ---- host only from here on (a plain inline function) ---------------------------------------------------------------------------
-// The samples of pnp_solve_ransac for a set of n >= 4 matches: xorshift32 from seed ? seed : 1, four draws per iteration (whether
+// ---- host only from here on (plain inline functions) ---------------------------------------------------------------------------
+// The samples of LpSlam::pnp_solve_ransac for a set of n >= 4 matches: xorshift32 from seed ? seed : 1, four draws per iteration (whether
 // or not the solve succeeds), each a step of a partial Fisher-Yates over avail[0 .. n) that is rebuilt every iteration.  table
 // receives iterations x 4 match indices; avail is n ints of scratch.
 inline void sample_table(int n, int iterations, uint32_t seed, int32_t* table, int* avail)
@@ -332,6 +301,41 @@ inline void sample_table(int n, int iterations, uint32_t seed, int32_t* table, i
             table[4 * it + k] = avail[r]; avail[r] = avail[left - 1]; --left;
         }
     }
+}
+
+// The hypothesis of one sample: EPnP on the four matches idx names
+inline bool pnp_solve_sample(const double* pw, const double* obs, const int32_t* idx, const double* cam, double* R, double* t)
+{
+    double p4[12], u4[8], ws[kWorkspace];
+    for (int k = 0; k < 4; ++k) { const size_t m = (size_t)idx[k]; for (int a = 0; a < 3; ++a) p4[3 * k + a] = pw[3 * m + a]; u4[2 * k] = obs[2 * m]; u4[2 * k + 1] = obs[2 * m + 1]; }
+    return epnp<4>(p4, u4, 4, cam, nullptr, nullptr, ws, 1, R, t);
+}
+
+// The inliers of a pose among n matches: their number, flags[i] = 1 for each
+inline int pnp_score(const double* R, const double* t, const double* cam, const double* pw, const double* obs, const double* inv_sigma2, int n, uint8_t* flags)
+{
+    int count = 0;
+    for (int i = 0; i < n; ++i) { flags[i] = pnp_inlier(R, t, cam, pw + 3 * (size_t)i, obs[2 * (size_t)i], obs[2 * (size_t)i + 1], inv_sigma2[i]) ? 1 : 0; count += flags[i]; }
+    return count;
+}
+
+// The refit on the inliers of the best sample ([UPSTREAM] refine): EPnP over all of them, kept when it explains at least as many
+// matches as the sample's `best` -- then inlier, R and t are replaced and the new count is returned; `best` otherwise.
+// scratch: 12 n doubles (the inliers' landmarks and keypoints, EPnP's alphas and camera-frame landmarks), cur: n flags.
+inline int pnp_refit(const double* pw, const double* obs, const double* inv_sigma2, int n, const double* cam, int best, uint8_t* inlier, double* R, double* t,
+                     double* scratch, uint8_t* cur)
+{
+    double* pi = scratch; double* ui = pi + 3 * (size_t)n; double* al = ui + 2 * (size_t)n; double* pc = al + 4 * (size_t)n;
+    int m = 0;
+    for (int i = 0; i < n; ++i) if (inlier[i]) { for (int a = 0; a < 3; ++a) pi[3 * (size_t)m + a] = pw[3 * (size_t)i + a]; ui[2 * (size_t)m] = obs[2 * (size_t)i]; ui[2 * (size_t)m + 1] = obs[2 * (size_t)i + 1]; ++m; }
+    double ws[kWorkspace], Rr[9], tr[3];
+    if (!epnp(pi, ui, m, cam, al, pc, ws, 1, Rr, tr)) return best;
+    const int count = pnp_score(Rr, tr, cam, pw, obs, inv_sigma2, n, cur);
+    if (count < best) return best;
+    for (int i = 0; i < n; ++i) inlier[i] = cur[i];
+    for (int k = 0; k < 9; ++k) R[k] = Rr[k];
+    for (int k = 0; k < 3; ++k) t[k] = tr[k];
+    return count;
 }
 
 }  // namespace lpslam_epnp

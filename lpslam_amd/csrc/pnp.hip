@@ -1,18 +1,16 @@
 // pnp.hip -- the relocaliser's pose solver for a batch of match sets ([UPSTREAM] solve::pnp_solver, the host
 // form is LpSlam::pnp_solve_ransac in lpslam_amd/host/two_view.cpp).  One call takes S sets of landmark / keypoint matches:
 //   host            the sample table (the 4-match samples pnp_solve_ransac would draw, epnp_math.h) and ONE upload of it with the matches
-//   k_pnp_hypotheses  sixteen lanes per (set, iteration): EPnP on the four sampled matches (epnp4 of epnp_math.h, bit for bit the host's
-//                   epnp_solve at n = 4); the 12 x 12 matrix and its eigenvectors live in LDS (2.3 KB a hypothesis, four a wave) and
+//   k_pnp_hypotheses  sixteen lanes per (set, iteration): EPnP on the four sampled matches (epnp<4> of epnp_math.h, the function the host
+//                   solver calls); the 12 x 12 matrix and its eigenvectors live in LDS (2.3 KB a hypothesis, four a wave) and
 //                   the lanes divide each Jacobi rotation's elements among them
 //   k_pnp_score     one workgroup per set, a wave per hypothesis in turn: inliers counted with the host's expression, the winner by the
 //                   key count << 32 | ~iteration (the lowest iteration among equal counts, the host's `count > best`), its flags and
 //                   pose written to page-locked memory, then the done flag (internal.h)
-//   host            one wait; per set the refit of pnp_solve_ransac: LpSlam::epnp_solve over the winner's inliers -- the host library's
-//                   own function, found at run time (liblpslam.so links against this library, not the other way round)
+//   host            one wait; per set the refit of pnp_solve_ransac (pnp_refit of epnp_math.h): EPnP over the winner's inliers
 #include "internal.h"
 #include "epnp_math.h"
 #include "../host/pose_math.h"
-#include <dlfcn.h>
 #include <cmath>
 
 using namespace lpslam;
@@ -49,7 +47,7 @@ __global__ __launch_bounds__(64) void k_pnp_hypotheses(const uint8_t* __restrict
         u4[2 * k] = obs[2 * m]; u4[2 * k + 1] = obs[2 * m + 1];
     }
     for (int k = 0; k < 4; ++k) cam[k] = head.cam[k];
-    const bool ok = ep::epnp4(p4, u4, cam, ws + kHypLds * group, 1, R, t, ln, kHypLanes);
+    const bool ok = ep::epnp<4>(p4, u4, 4, cam, nullptr, nullptr, ws + kHypLds * group, 1, R, t, ln, kHypLanes);
     if (ln != 0) return;
     valid[h] = ok ? 1 : 0;
     if (ok) { for (int k = 0; k < 9; ++k) hyp[12 * (size_t)h + k] = R[k]; for (int k = 0; k < 3; ++k) hyp[12 * (size_t)h + 9 + k] = t[k]; }
@@ -117,24 +115,6 @@ __global__ __launch_bounds__(256) void k_pnp_score(const uint8_t* __restrict__ b
 
 size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
 
-// LpSlam::epnp_solve through its C shim lpslam_epnp_solve of the host library: already in the process (a client linked against
-// liblpslam.so), or loaded from the directory this library lies in.  nullptr: not found.
-typedef int (*EpnpSolveFn)(const double*, const double*, int, const double*, double*, double*);
-EpnpSolveFn host_epnp_solve()
-{
-    static const EpnpSolveFn fn = []() -> EpnpSolveFn {
-        if (void* f = dlsym(RTLD_DEFAULT, "lpslam_epnp_solve")) return (EpnpSolveFn)f;
-        Dl_info info{};
-        if (!dladdr((const void*)&lpslam_hip_pnp_ransac_batch, &info) || !info.dli_fname) return nullptr;
-        std::string path(info.dli_fname);
-        const size_t slash = path.rfind('/');
-        path = (slash == std::string::npos ? std::string() : path.substr(0, slash + 1)) + "liblpslam.so";
-        void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        return lib ? (EpnpSolveFn)dlsym(lib, "lpslam_epnp_solve") : nullptr;
-    }();
-    return fn;
-}
-
 }  // namespace
 
 extern "C" {
@@ -154,8 +134,6 @@ int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const int32_t
     if (n_sets == 0) return LPSLAM_HIP_OK;
     const size_t n_hyp = (size_t)n_sets * (size_t)iterations;
     if (n_hyp > (size_t)0x7fffffff / 4) { set_error("pnp_ransac_batch: %d sets x %d iterations do not fit one launch", n_sets, iterations); return LPSLAM_HIP_ERR_CAPACITY; }
-    const EpnpSolveFn epnp_solve = host_epnp_solve();
-    if (!epnp_solve) { set_error("pnp_ransac_batch: the host library (liblpslam.so, for the refit's LpSlam::epnp_solve) is not beside this library"); return LPSLAM_HIP_ERR_INVALID; }
     LP_HIP(hipSetDevice(c->cfg.device));
     hipStream_t s = c->stream;
     const LpMatchTrace tr;
@@ -216,10 +194,10 @@ int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const int32_t
     LP_HIP(hipGetLastError());
     if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("pnp_ransac_batch: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
     const double tr_back = tr.us();
-    // the refit of pnp_solve_ransac (two_view.cpp:755-775), per set: EPnP over the winner's inliers, kept when it explains at least as many
+    // the refit of pnp_solve_ransac, per set (pnp_refit of epnp_math.h): EPnP over the winner's inliers, kept when it explains at least as many
     const PnpResult* res = (const PnpResult*)(hb + h_res);
     const uint8_t* fl = hb + h_flags;
-    std::vector<double> pi, ui;
+    std::vector<double> scratch;
     std::vector<uint8_t> cur;
     for (int i = 0; i < n_sets; ++i) {
         const int o = off0[i], n = off0[i + 1] - o;
@@ -238,20 +216,8 @@ int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const int32_t
         for (int k = 0; k < 9; ++k) bestR[k] = res[i].R[k];
         for (int k = 0; k < 3; ++k) bestT[k] = res[i].t[k];
         for (int k = 0; k < n; ++k) out_fl[k] = fl[o + k];
-        pi.clear(); ui.clear();
-        for (int k = 0; k < n; ++k) if (out_fl[k]) { for (int a = 0; a < 3; ++a) pi.push_back(spw[3 * (size_t)k + a]); ui.push_back(sob[2 * (size_t)k]); ui.push_back(sob[2 * (size_t)k + 1]); }
-        double R[9], t[3];
-        if (epnp_solve(pi.data(), ui.data(), (int)(ui.size() / 2), cam4, R, t)) {
-            cur.assign((size_t)n, 0);
-            int count = 0;
-            for (int k = 0; k < n; ++k) { cur[(size_t)k] = ep::pnp_inlier(R, t, cam4, spw + 3 * (size_t)k, sob[2 * (size_t)k], sob[2 * (size_t)k + 1], sw[k]) ? 1 : 0; count += cur[(size_t)k]; }
-            if (count >= best) {
-                best = count;
-                for (int k = 0; k < n; ++k) out_fl[k] = cur[(size_t)k];
-                for (int k = 0; k < 9; ++k) bestR[k] = R[k];
-                for (int k = 0; k < 3; ++k) bestT[k] = t[k];
-            }
-        }
+        scratch.resize((size_t)12 * n); cur.resize((size_t)n);
+        best = ep::pnp_refit(spw, sob, sw, n, cam4, best, out_fl, bestR, bestT, scratch.data(), cur.data());
         double q[4];
         LpSlam::rotToQuat(bestR, q);
         for (int k = 0; k < 4; ++k) p7[k] = q[k];

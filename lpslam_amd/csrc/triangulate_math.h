@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <vector>
+#include "jacobi_math.h"
 
 #if defined(__HIPCC__)
 #define LP_TRI_FN __host__ __device__ __forceinline__
@@ -79,46 +80,6 @@ LP_TRI_FN bool gate_geometry(const double* l, bool either_stereo, const Epipolar
     return num * num <= 3.84 * (s * s) * nn;
 }
 
-// Cyclic Jacobi on a symmetric 4 x 4 matrix with the arithmetic of sym_eigen_jacobi (lpslam_amd/host/two_view.cpp), fully unrolled so
-// that every index is a constant (registers on the device); a, v row major, v receives the eigenvectors as columns.
-LP_TRI_FN void jacobi4(double* a, double* v)
-{
-    for (int i = 0; i < 16; ++i) v[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 64; ++sweep) {
-        double off = 0, diag = 0;
-        LP_TRI_UNROLL
-        for (int i = 0; i < 4; ++i)
-            LP_TRI_UNROLL
-            for (int j = 0; j < 4; ++j) { if (i == j) diag += a[i * 4 + j] * a[i * 4 + j]; else off += a[i * 4 + j] * a[i * 4 + j]; }
-        if (off <= 1e-30 * (diag + 1e-300)) break;
-        LP_TRI_UNROLL
-        for (int p = 0; p < 3; ++p)
-            LP_TRI_UNROLL
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = a[p * 4 + q];
-                if (apq == 0.0) continue;
-                const double theta = (a[q * 4 + q] - a[p * 4 + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                LP_TRI_UNROLL
-                for (int k = 0; k < 4; ++k) {                   // columns p, q
-                    const double akp = a[k * 4 + p], akq = a[k * 4 + q];
-                    a[k * 4 + p] = c * akp - s * akq; a[k * 4 + q] = s * akp + c * akq;
-                }
-                LP_TRI_UNROLL
-                for (int k = 0; k < 4; ++k) {                   // rows p, q
-                    const double apk = a[p * 4 + k], aqk = a[q * 4 + k];
-                    a[p * 4 + k] = c * apk - s * aqk; a[q * 4 + k] = s * apk + c * aqk;
-                }
-                LP_TRI_UNROLL
-                for (int k = 0; k < 4; ++k) {
-                    const double vkp = v[k * 4 + p], vkq = v[k * 4 + q];
-                    v[k * 4 + p] = c * vkp - s * vkq; v[k * 4 + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-}
-
 // P = K [R | t], row major 3 x 4
 LP_TRI_FN void projection(const Camera& cam, const View& v, double* P)
 {
@@ -126,8 +87,8 @@ LP_TRI_FN void projection(const Camera& cam, const View& v, double* P)
     P[3] = cam.fx * v.t[0] + cam.cx * v.t[2]; P[7] = cam.fy * v.t[1] + cam.cy * v.t[2]; P[11] = v.t[2];
 }
 
-// triangulate_point of lpslam_amd/host/two_view.cpp: rows, A^T A, Jacobi, the eigenvector of the smallest eigenvalue (the first
-// among equal ones), false when its last component is 0
+// Linear triangulation (LpSlam::triangulate_point of lpslam_amd/host/two_view.cpp is this function): rows, A^T A, Jacobi
+// (jacobi_math.h), the eigenvector of the smallest eigenvalue (the first among equal ones), false when its last component is 0
 LP_TRI_FN bool triangulate_linear(const double* P1, const double* P2, double x1, double y1, double x2, double y2, double* X)
 {
     double A[16];
@@ -148,8 +109,8 @@ LP_TRI_FN bool triangulate_linear(const double* P1, const double* P2, double x1,
             for (int r = 0; r < 4; ++r) s += A[r * 4 + a] * A[r * 4 + b];
             AtA[a * 4 + b] = s;
         }
-    jacobi4(AtA, evec);
-    // the column of the smallest diagonal entry, selected without a variable index
+    lpslam_jacobi::jacobi_sweeps<4, 4, false>(AtA, evec, 1);
+    // the column of the smallest diagonal entry (the first among equal ones, as the shared sort orders them), selected without a variable index
     double best = AtA[0], e0 = evec[0], e1 = evec[4], e2 = evec[8], e3 = evec[12];
     LP_TRI_UNROLL
     for (int c = 1; c < 4; ++c)

@@ -1,6 +1,6 @@
 // pnp_batch.cpp -- the CPU side of the batched PnP RANSAC: C shims for the tests and the timing tool.
 //   lpslam_pnp_sample_table        the 4-match samples pnp_solve_ransac draws for a set of n matches (csrc/epnp_math.h)
-//   lpslam_epnp4_host              the host form of the header's epnp4, bit for bit epnp_solve at n = 4
+//   lpslam_epnp4_host              the header's epnp<4> on the host (LpSlam::epnp_solve at n = 4 runs the same template at a run-time n)
 //   lpslam_pnp_ransac_batch_host   lpslam_hip_pnp_ransac_batch without the context: pnp_solve_ransac on each set -- the CPU definition
 #include "two_view.h"
 #include "../csrc/epnp_math.h"
@@ -20,7 +20,7 @@ LP_EXPORT int lpslam_pnp_sample_table(int n, int iterations, uint32_t seed, int3
 LP_EXPORT int lpslam_epnp4_host(const double* p4, const double* u4, const double* cam, double* R9, double* t3)
 {
     double ws[lpslam_epnp::kWorkspace];
-    return lpslam_epnp::epnp4(p4, u4, cam, ws, 1, R9, t3) ? 1 : 0;
+    return lpslam_epnp::epnp<4>(p4, u4, 4, cam, nullptr, nullptr, ws, 1, R9, t3) ? 1 : 0;
 }
 
 // 0: done; 1: refused (the argument rules of lpslam_hip_pnp_ransac_batch), nothing written
@@ -31,6 +31,7 @@ LP_EXPORT int lpslam_pnp_ransac_batch_host(int32_t n_sets, const int32_t* offset
     for (int s = 0; s < n_sets; ++s) if (offsets[s + 1] < offsets[s]) return 1;
     if (offsets[n_sets] > offsets[0] && (!pw || !obs || !inv_sigma2 || !inlier)) return 1;
     std::vector<int32_t> table;
+    std::vector<uint8_t> cur;
     for (int s = 0; s < n_sets; ++s) {
         const size_t o = (size_t)offsets[s];
         const int n = offsets[s + 1] - offsets[s];
@@ -45,12 +46,11 @@ LP_EXPORT int lpslam_pnp_ransac_batch_host(int32_t n_sets, const int32_t* offset
         table.resize((size_t)iterations * 4);
         lpslam_pnp_sample_table(n, iterations, seed, table.data());
         int best = 0;
+        cur.resize((size_t)n);
         for (int it = 0; it < iterations; ++it) {
-            double p4[12], u4[8], R[9], t[3];
-            for (int k = 0; k < 4; ++k) { const size_t m = (size_t)table[(size_t)4 * it + k]; for (int a = 0; a < 3; ++a) p4[3 * k + a] = spw[3 * m + a]; u4[2 * k] = sob[2 * m]; u4[2 * k + 1] = sob[2 * m + 1]; }
-            if (!LpSlam::epnp_solve(p4, u4, 4, cam4, R, t)) continue;
-            int count = 0;
-            for (int i = 0; i < n; ++i) count += lpslam_epnp::pnp_inlier(R, t, cam4, spw + 3 * (size_t)i, sob[2 * (size_t)i], sob[2 * (size_t)i + 1], sw[i]) ? 1 : 0;
+            double R[9], t[3];
+            if (!lpslam_epnp::pnp_solve_sample(spw, sob, table.data() + (size_t)4 * it, cam4, R, t)) continue;
+            const int count = lpslam_epnp::pnp_score(R, t, cam4, spw, sob, sw, n, cur.data());
             if (count > best) { best = count; best_iteration[s] = it; }
         }
     }

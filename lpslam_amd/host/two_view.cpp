@@ -1,6 +1,8 @@
 // two_view.cpp -- see two_view.h
 #include "two_view.h"
 #include "pose_math.h"
+#include "../csrc/epnp_math.h"
+#include "../csrc/triangulate_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -257,37 +259,17 @@ bool hypotheses_from_homography(const M3& H21, const double* K, std::vector<Hypo
 
 }  // namespace
 
+// the shared solver (csrc/jacobi_math.h) on a copy of A, its columns read through the order it returns
 void sym_eigen_jacobi(const double* A, int n, double* eigval, double* eigvec)
 {
-    std::vector<double> a(A, A + n * n), v((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i) v[(size_t)i * n + i] = 1.0;
-    for (int sweep = 0; sweep < 64; ++sweep) {
-        double off = 0, diag = 0;
-        for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) (i == j ? diag : off) += a[(size_t)i * n + j] * a[(size_t)i * n + j];
-        if (off <= 1e-30 * (diag + 1e-300)) break;
-        for (int p = 0; p < n - 1; ++p) for (int q = p + 1; q < n; ++q) {
-            const double apq = a[(size_t)p * n + q];
-            if (apq == 0.0) continue;
-            const double theta = (a[(size_t)q * n + q] - a[(size_t)p * n + p]) / (2.0 * apq);
-            const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-            const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-            for (int k = 0; k < n; ++k) {                   // columns p, q
-                const double akp = a[(size_t)k * n + p], akq = a[(size_t)k * n + q];
-                a[(size_t)k * n + p] = c * akp - s * akq; a[(size_t)k * n + q] = s * akp + c * akq;
-            }
-            for (int k = 0; k < n; ++k) {                   // rows p, q
-                const double apk = a[(size_t)p * n + k], aqk = a[(size_t)q * n + k];
-                a[(size_t)p * n + k] = c * apk - s * aqk; a[(size_t)q * n + k] = s * apk + c * aqk;
-            }
-            for (int k = 0; k < n; ++k) {
-                const double vkp = v[(size_t)k * n + p], vkq = v[(size_t)k * n + q];
-                v[(size_t)k * n + p] = c * vkp - s * vkq; v[(size_t)k * n + q] = s * vkp + c * vkq;
-            }
-        }
-    }
+    std::vector<double> a(A, A + n * n), v((size_t)n * n);
     std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](int x, int y) { return a[(size_t)x * n + x] < a[(size_t)y * n + y]; });
+    lpslam_jacobi::jacobi_sweeps<0, 1>(a.data(), v.data(), 1, 0, 1, n);
+    if (n <= 16) lpslam_jacobi::jacobi_order<0>(a.data(), 1, order.data(), n);
+    else {                                                   // (no caller: beyond 16 elements std::sort is no insertion sort, and equal eigenvalues get the order it gives them)
+        for (int i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return a[(size_t)x * n + x] < a[(size_t)y * n + y]; });
+    }
     for (int c = 0; c < n; ++c) {
         eigval[c] = a[(size_t)order[c] * n + order[c]];
         for (int r = 0; r < n; ++r) eigvec[(size_t)r * n + c] = v[(size_t)r * n + order[c]];
@@ -333,21 +315,7 @@ void fundamental_from_matches(const double* x1, const double* x2, int n, double*
 
 bool triangulate_point(const double* P1, const double* P2, const double* x1, const double* x2, double* X)
 {
-    double A[16];
-    for (int c = 0; c < 4; ++c) {
-        A[c] = x1[0] * P1[8 + c] - P1[c];
-        A[4 + c] = x1[1] * P1[8 + c] - P1[4 + c];
-        A[8 + c] = x2[0] * P2[8 + c] - P2[c];
-        A[12 + c] = x2[1] * P2[8 + c] - P2[4 + c];
-    }
-    double AtA[16] = {0};
-    for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) for (int r = 0; r < 4; ++r) AtA[a * 4 + b] += A[r * 4 + a] * A[r * 4 + b];
-    double ev[4], evec[16];
-    sym_eigen_jacobi(AtA, 4, ev, evec);
-    const double w = evec[12];
-    if (w == 0.0) return false;
-    X[0] = evec[0] / w; X[1] = evec[4] / w; X[2] = evec[8] / w;
-    return true;
+    return lpslam_tri::triangulate_linear(P1, P2, x1[0], x1[1], x2[0], x2[1], X);
 }
 
 bool two_view_initialize(const double* K, const float* kp_ref, const float* kp_cur, const int32_t* matches, int n_matches,
@@ -461,42 +429,7 @@ bool two_view_initialize(const double* K, const float* kp_ref, const float* kp_c
 
 bool horn_absolute_orientation(const double* x1, const double* x2, int n, bool fix_scale, double* R, double* t, double* s_out)
 {
-    if (n < 3) return false;
-    double o1[3] = {0, 0, 0}, o2[3] = {0, 0, 0};
-    for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) { o1[a] += x1[3 * i + a]; o2[a] += x2[3 * i + a]; }
-    for (int a = 0; a < 3; ++a) { o1[a] /= n; o2[a] /= n; }
-    double M[9] = {0};                                   // M[a][b] = sum (x2 - o2)[a] (x1 - o1)[b]
-    for (int i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) M[a * 3 + b] += (x2[3 * i + a] - o2[a]) * (x1[3 * i + b] - o1[b]);
-    const double N[16] = {M[0] + M[4] + M[8], M[5] - M[7], M[6] - M[2], M[1] - M[3],
-                          M[5] - M[7], M[0] - M[4] - M[8], M[1] + M[3], M[6] + M[2],
-                          M[6] - M[2], M[1] + M[3], -M[0] + M[4] - M[8], M[5] + M[7],
-                          M[1] - M[3], M[6] + M[2], M[5] + M[7], -M[0] - M[4] + M[8]};
-    double ev[4], evec[16];
-    sym_eigen_jacobi(N, 4, ev, evec);                    // ascending: the last column belongs to the largest eigenvalue
-    double q[4] = {evec[3], evec[7], evec[11], evec[15]};
-    const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (!(qn > 0)) return false;
-    for (double& v : q) v /= qn;
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double Rm[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
-                          2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
-                          2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
-    double sc = 1.0;
-    if (!fix_scale) {
-        double nom = 0, den = 0;
-        for (int i = 0; i < n; ++i) {
-            double p3[3];
-            for (int r = 0; r < 3; ++r) p3[r] = Rm[r * 3] * (x2[3 * i] - o2[0]) + Rm[r * 3 + 1] * (x2[3 * i + 1] - o2[1]) + Rm[r * 3 + 2] * (x2[3 * i + 2] - o2[2]);
-            for (int r = 0; r < 3; ++r) { nom += (x1[3 * i + r] - o1[r]) * p3[r]; den += p3[r] * p3[r]; }
-        }
-        if (!(den > 0) || !(nom > 0)) return false;
-        sc = nom / den;
-    }
-    for (int k = 0; k < 9; ++k) R[k] = Rm[k];
-    for (int r = 0; r < 3; ++r) t[r] = o1[r] - sc * (Rm[r * 3] * o2[0] + Rm[r * 3 + 1] * o2[1] + Rm[r * 3 + 2] * o2[2]);
-    *s_out = sc;
-    return true;
+    return lpslam_epnp::horn(x1, x2, n, fix_scale, R, t, s_out);
 }
 
 int sim3_solve_ransac(const double* p1c, const double* p2c, const double* obs1, const double* obs2, const double* inv_sigma2_1, const double* inv_sigma2_2,
@@ -513,7 +446,7 @@ int sim3_solve_ransac(const double* p1c, const double* p2c, const double* obs1, 
         for (int k = 0; k < 3; ++k) { const int r = (int)(rng.next() % (uint32_t)left); idx[k] = avail[(size_t)r]; avail[(size_t)r] = avail[(size_t)left - 1]; --left; }
         double a1[9], a2[9], R[9], t[3], sc;
         for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) { a1[3 * k + a] = p1c[3 * idx[k] + a]; a2[3 * k + a] = p2c[3 * idx[k] + a]; }
-        if (!horn_absolute_orientation(a1, a2, 3, fix_scale, R, t, &sc)) continue;
+        if (!lpslam_epnp::horn(a1, a2, 3, fix_scale, R, t, &sc)) continue;
         int count = 0;
         for (int i = 0; i < n; ++i) {
             cur[(size_t)i] = 0;
@@ -539,212 +472,30 @@ int sim3_solve_ransac(const double* p1c, const double* p2c, const double* obs1, 
 }
 
 
-// ---- [UPSTREAM] solve::pnp_solver (relocalisation without a pose prior) -------------------------------------------------------------
-// EPnP (Lepetit, Moreno-Noguer, Fua: "EPnP: An Accurate O(n) Solution to the PnP Problem", IJCV 2009) inside a RANSAC over 4-match
-// samples, then a refit on the inliers of the best sample -- the structure of OpenVSLAM's solver (which follows ORB-SLAM's PnPsolver,
-// itself the authors' reference implementation).  The algorithm, as published:
-//   1. four control points in the world: the centroid and the centroid plus the principal directions scaled by sqrt(eigenvalue / n);
-//   2. every landmark as a barycentric combination of them (alphas, they sum to one);
-//   3. the projection equations are linear in the 12 camera-frame coordinates of the control points: M x = 0 (2 n x 12); the solution is
-//      a combination x = sum beta_k v_k of the eigenvectors of M^T M with the four smallest eigenvalues;
-//   4. the betas from the six pairwise distances of the control points, which the camera frame must preserve (L_6x10 beta_ij = rho):
-//      three linearised guesses (N = 1 .. 3 null vectors: approx_1 / _2 / _3), each refined by five Gauss-Newton steps;
-//   5. per guess the camera-frame landmarks, the sign that puts them in front of the camera, the rigid motion world -> camera (Horn's
-//      absolute orientation here; the reference implementation takes the SVD form), and its mean reprojection error: the best wins.
-// Inliers are counted by the reprojection error (chi-square 5.991 at the keypoint's level).  The pose optimiser on the device refines
-// the result, as upstream refines EPnP's.  The linear algebra is this file's Jacobi eigen-solver and small Gaussian eliminations,
-// written so that the tests' numpy restatement can follow it operation by operation (both sides then test the same hypotheses).
-namespace {
-// least squares A x = b (m x k, k <= 5) by the normal equations and Gaussian elimination with partial pivoting; false when singular
-bool lsq_small(const double* A, const double* b, int m, int k, double* x)
-{
-    double N[5 * 6];
-    for (int i = 0; i < k; ++i) {
-        for (int j = 0; j < k; ++j) { double s = 0; for (int r = 0; r < m; ++r) s += A[r * k + i] * A[r * k + j]; N[i * (k + 1) + j] = s; }
-        double s = 0;
-        for (int r = 0; r < m; ++r) s += A[r * k + i] * b[r];
-        N[i * (k + 1) + k] = s;
-    }
-    for (int c = 0; c < k; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < k; ++r) if (std::fabs(N[r * (k + 1) + c]) > std::fabs(N[piv * (k + 1) + c])) piv = r;
-        if (!(std::fabs(N[piv * (k + 1) + c]) > 1e-300)) return false;
-        if (piv != c) for (int j = 0; j <= k; ++j) std::swap(N[c * (k + 1) + j], N[piv * (k + 1) + j]);
-        for (int r = c + 1; r < k; ++r) {
-            const double f = N[r * (k + 1) + c] / N[c * (k + 1) + c];
-            for (int j = c; j <= k; ++j) N[r * (k + 1) + j] -= f * N[c * (k + 1) + j];
-        }
-    }
-    for (int i = k - 1; i >= 0; --i) {
-        double s2 = N[i * (k + 1) + k];
-        for (int j = i + 1; j < k; ++j) s2 -= N[i * (k + 1) + j] * x[j];
-        x[i] = s2 / N[i * (k + 1) + i];
-    }
-    return true;
-}
-}  // namespace
-
+// ---- [UPSTREAM] solve::pnp_solver (relocalisation without a pose prior): the algorithm and its arithmetic are csrc/epnp_math.h ------------
 bool epnp_solve(const double* pw, const double* uv, int n, const double* cam, double* R, double* t)
 {
     if (n < 4) return false;
-    const double fu = cam[0], fv = cam[1], uc = cam[2], vc = cam[3];
-    // 1. control points
-    double cws[4][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    for (int i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) cws[0][a] += pw[3 * i + a];
-    for (int a = 0; a < 3; ++a) cws[0][a] /= n;
-    double C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) for (int b2 = 0; b2 < 3; ++b2) C[a * 3 + b2] += (pw[3 * i + a] - cws[0][a]) * (pw[3 * i + b2] - cws[0][b2]);
-    double ev[3], evec[9];
-    sym_eigen_jacobi(C, 3, ev, evec);                       // ascending; the principal direction first, as the published code orders them
-    for (int j = 1; j <= 3; ++j) {
-        const int col = 3 - j;
-        const double k = std::sqrt(std::max(ev[col], 0.0) / n);
-        for (int a = 0; a < 3; ++a) cws[j][a] = cws[0][a] + k * evec[a * 3 + col];
-    }
-    // 2. barycentric coordinates: [c1 - c0, c2 - c0, c3 - c0] a = p - c0
-    double CC[9], CI[9];
-    for (int a = 0; a < 3; ++a) for (int j = 1; j <= 3; ++j) CC[a * 3 + (j - 1)] = cws[j][a] - cws[0][a];
-    const double det = CC[0] * (CC[4] * CC[8] - CC[5] * CC[7]) - CC[1] * (CC[3] * CC[8] - CC[5] * CC[6]) + CC[2] * (CC[3] * CC[7] - CC[4] * CC[6]);
-    if (!(std::fabs(det) > 1e-300)) return false;           // landmarks in a plane or on a line: no volume to span
-    CI[0] = (CC[4] * CC[8] - CC[5] * CC[7]) / det; CI[1] = (CC[2] * CC[7] - CC[1] * CC[8]) / det; CI[2] = (CC[1] * CC[5] - CC[2] * CC[4]) / det;
-    CI[3] = (CC[5] * CC[6] - CC[3] * CC[8]) / det; CI[4] = (CC[0] * CC[8] - CC[2] * CC[6]) / det; CI[5] = (CC[2] * CC[3] - CC[0] * CC[5]) / det;
-    CI[6] = (CC[3] * CC[7] - CC[4] * CC[6]) / det; CI[7] = (CC[1] * CC[6] - CC[0] * CC[7]) / det; CI[8] = (CC[0] * CC[4] - CC[1] * CC[3]) / det;
-    std::vector<double> al((size_t)4 * n);
-    for (int i = 0; i < n; ++i) {
-        const double d0 = pw[3 * i] - cws[0][0], d1 = pw[3 * i + 1] - cws[0][1], d2 = pw[3 * i + 2] - cws[0][2];
-        for (int j = 0; j < 3; ++j) al[4 * (size_t)i + 1 + j] = CI[j * 3] * d0 + CI[j * 3 + 1] * d1 + CI[j * 3 + 2] * d2;
-        al[4 * (size_t)i] = 1.0 - al[4 * (size_t)i + 1] - al[4 * (size_t)i + 2] - al[4 * (size_t)i + 3];
-    }
-    // 3. M^T M, accumulated row pair by row pair
-    double MtM[144];
-    for (double& v : MtM) v = 0;
-    for (int i = 0; i < n; ++i) {
-        double r1[12], r2[12];
-        for (int j = 0; j < 4; ++j) {
-            const double a = al[4 * (size_t)i + j];
-            r1[3 * j] = a * fu; r1[3 * j + 1] = 0.0;    r1[3 * j + 2] = a * (uc - uv[2 * i]);
-            r2[3 * j] = 0.0;    r2[3 * j + 1] = a * fv; r2[3 * j + 2] = a * (vc - uv[2 * i + 1]);
-        }
-        for (int a = 0; a < 12; ++a) for (int b2 = 0; b2 < 12; ++b2) MtM[a * 12 + b2] += r1[a] * r1[b2] + r2[a] * r2[b2];
-    }
-    double mev[12], mvec[144];
-    sym_eigen_jacobi(MtM, 12, mev, mvec);                   // ascending: columns 0 .. 3 span the (approximate) null space
-    double v[4][12];
-    for (int k = 0; k < 4; ++k) for (int a = 0; a < 12; ++a) v[k][a] = mvec[a * 12 + k];
-    // 4. distance constraints
-    static const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {1, 2, 3, 2, 3, 3};
-    double dv[4][6][3], L[60], rho[6];
-    for (int k = 0; k < 4; ++k) for (int p = 0; p < 6; ++p) for (int a = 0; a < 3; ++a) dv[k][p][a] = v[k][3 * pa[p] + a] - v[k][3 * pb[p] + a];
-    auto dot3 = [](const double* x, const double* y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2]; };
-    for (int p = 0; p < 6; ++p) {
-        double* row = L + 10 * p;
-        row[0] = dot3(dv[0][p], dv[0][p]); row[1] = 2.0 * dot3(dv[0][p], dv[1][p]); row[2] = dot3(dv[1][p], dv[1][p]);
-        row[3] = 2.0 * dot3(dv[0][p], dv[2][p]); row[4] = 2.0 * dot3(dv[1][p], dv[2][p]); row[5] = dot3(dv[2][p], dv[2][p]);
-        row[6] = 2.0 * dot3(dv[0][p], dv[3][p]); row[7] = 2.0 * dot3(dv[1][p], dv[3][p]); row[8] = 2.0 * dot3(dv[2][p], dv[3][p]);
-        row[9] = dot3(dv[3][p], dv[3][p]);
-        double d2 = 0;
-        for (int a = 0; a < 3; ++a) { const double d = cws[pa[p]][a] - cws[pb[p]][a]; d2 += d * d; }
-        rho[p] = d2;
-    }
-    double best_err = 1e300;
-    bool found = false;
-    std::vector<double> pc((size_t)3 * n);
-    for (int guess = 0; guess < 3; ++guess) {
-        double be[4] = {0, 0, 0, 0};
-        if (guess == 0) {                                   // betas 11 12 13 14 (columns 0, 1, 3, 6): N = 4 with the cross terms of beta_1 only
-            double A[24], x4[4];
-            for (int p = 0; p < 6; ++p) { A[4 * p] = L[10 * p]; A[4 * p + 1] = L[10 * p + 1]; A[4 * p + 2] = L[10 * p + 3]; A[4 * p + 3] = L[10 * p + 6]; }
-            if (!lsq_small(A, rho, 6, 4, x4)) continue;
-            if (x4[0] < 0) { be[0] = std::sqrt(-x4[0]); be[1] = -x4[1] / be[0]; be[2] = -x4[2] / be[0]; be[3] = -x4[3] / be[0]; }
-            else { be[0] = std::sqrt(x4[0]); be[1] = x4[1] / be[0]; be[2] = x4[2] / be[0]; be[3] = x4[3] / be[0]; }
-        } else if (guess == 1) {                            // betas 11 12 22 (columns 0, 1, 2): N = 2
-            double A[18], x3[3];
-            for (int p = 0; p < 6; ++p) { A[3 * p] = L[10 * p]; A[3 * p + 1] = L[10 * p + 1]; A[3 * p + 2] = L[10 * p + 2]; }
-            if (!lsq_small(A, rho, 6, 3, x3)) continue;
-            if (x3[0] < 0) { be[0] = std::sqrt(-x3[0]); be[1] = x3[2] < 0 ? std::sqrt(-x3[2]) : 0.0; }
-            else { be[0] = std::sqrt(x3[0]); be[1] = x3[2] > 0 ? std::sqrt(x3[2]) : 0.0; }
-            if (x3[1] < 0) be[0] = -be[0];
-        } else {                                            // betas 11 12 22 13 23 (columns 0 .. 4): N = 3
-            double A[30], x5[5];
-            for (int p = 0; p < 6; ++p) for (int c = 0; c < 5; ++c) A[5 * p + c] = L[10 * p + c];
-            if (!lsq_small(A, rho, 6, 5, x5)) continue;
-            if (x5[0] < 0) { be[0] = std::sqrt(-x5[0]); be[1] = x5[2] < 0 ? std::sqrt(-x5[2]) : 0.0; }
-            else { be[0] = std::sqrt(x5[0]); be[1] = x5[2] > 0 ? std::sqrt(x5[2]) : 0.0; }
-            if (x5[1] < 0) be[0] = -be[0];
-            be[2] = x5[3] / be[0];
-        }
-        if (!(be[0] == be[0]) || !std::isfinite(be[0]) || !std::isfinite(be[1]) || !std::isfinite(be[2]) || !std::isfinite(be[3])) continue;
-        bool gn_ok = true;
-        for (int it = 0; it < 5 && gn_ok; ++it) {           // Gauss-Newton on the six distance equations
-            double A[24], r6[6], dx[4];
-            for (int p = 0; p < 6; ++p) {
-                const double* l = L + 10 * p;
-                A[4 * p] = 2 * l[0] * be[0] + l[1] * be[1] + l[3] * be[2] + l[6] * be[3];
-                A[4 * p + 1] = l[1] * be[0] + 2 * l[2] * be[1] + l[4] * be[2] + l[7] * be[3];
-                A[4 * p + 2] = l[3] * be[0] + l[4] * be[1] + 2 * l[5] * be[2] + l[8] * be[3];
-                A[4 * p + 3] = l[6] * be[0] + l[7] * be[1] + l[8] * be[2] + 2 * l[9] * be[3];
-                r6[p] = rho[p] - (l[0] * be[0] * be[0] + l[1] * be[0] * be[1] + l[2] * be[1] * be[1] + l[3] * be[0] * be[2] + l[4] * be[1] * be[2] +
-                                  l[5] * be[2] * be[2] + l[6] * be[0] * be[3] + l[7] * be[1] * be[3] + l[8] * be[2] * be[3] + l[9] * be[3] * be[3]);
-            }
-            if (!lsq_small(A, r6, 6, 4, dx)) { gn_ok = false; break; }
-            for (int k = 0; k < 4; ++k) be[k] += dx[k];
-        }
-        if (!gn_ok || !std::isfinite(be[0]) || !std::isfinite(be[1]) || !std::isfinite(be[2]) || !std::isfinite(be[3])) continue;
-        // 5. camera-frame control points and landmarks, sign, rigid motion, reprojection error
-        double ccs[4][3];
-        for (int j = 0; j < 4; ++j) for (int a = 0; a < 3; ++a) ccs[j][a] = be[0] * v[0][3 * j + a] + be[1] * v[1][3 * j + a] + be[2] * v[2][3 * j + a] + be[3] * v[3][3 * j + a];
-        for (int i = 0; i < n; ++i)
-            for (int a = 0; a < 3; ++a) pc[3 * (size_t)i + a] = al[4 * (size_t)i] * ccs[0][a] + al[4 * (size_t)i + 1] * ccs[1][a] + al[4 * (size_t)i + 2] * ccs[2][a] + al[4 * (size_t)i + 3] * ccs[3][a];
-        if (pc[2] < 0) for (double& x : pc) x = -x;         // the first landmark in front of the camera
-        double Rg[9], tg[3], sdummy = 1.0;
-        if (!horn_absolute_orientation(pc.data(), pw, n, true, Rg, tg, &sdummy)) continue;
-        double err = 0;
-        bool finite = true;
-        for (int i = 0; i < n; ++i) {
-            const double* X = pw + 3 * (size_t)i;
-            const double xc = Rg[0] * X[0] + Rg[1] * X[1] + Rg[2] * X[2] + tg[0], yc = Rg[3] * X[0] + Rg[4] * X[1] + Rg[5] * X[2] + tg[1], zc = Rg[6] * X[0] + Rg[7] * X[1] + Rg[8] * X[2] + tg[2];
-            const double du = uc + fu * xc / zc - uv[2 * i], dv2 = vc + fv * yc / zc - uv[2 * i + 1];
-            const double e = std::sqrt(du * du + dv2 * dv2);
-            if (!std::isfinite(e)) { finite = false; break; }
-            err += e;
-        }
-        if (!finite) continue;
-        err /= n;
-        if (err < best_err) { best_err = err; found = true; for (int k = 0; k < 9; ++k) R[k] = Rg[k]; for (int k = 0; k < 3; ++k) t[k] = tg[k]; }
-    }
-    return found;
+    std::vector<double> scratch((size_t)7 * n);              // the alphas (4 n), the camera-frame landmarks (3 n)
+    double ws[lpslam_epnp::kWorkspace];
+    return lpslam_epnp::epnp(pw, uv, n, cam, scratch.data(), scratch.data() + (size_t)4 * n, ws, 1, R, t);
 }
 
 int pnp_solve_ransac(const double* pw, const double* obs, const double* inv_sigma2, int n, const double* cam, int iterations, uint32_t seed, double* pose7, uint8_t* inlier)
 {
+    namespace ep = lpslam_epnp;
     for (int i = 0; i < n; ++i) inlier[i] = 0;
     if (n < 4) return 0;
-    Rng rng{seed ? seed : 1u};
     std::vector<int> avail((size_t)n);
+    std::vector<int32_t> table((size_t)4 * (size_t)std::max(iterations, 0));
+    ep::sample_table(n, iterations, seed, table.data(), avail.data());
     std::vector<uint8_t> cur((size_t)n);
     int best = 0;
     double bestR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, bestT[3] = {0, 0, 0};
-    auto count_inliers = [&](const double* R, const double* t, uint8_t* flags) {
-        int count = 0;
-        for (int i = 0; i < n; ++i) {
-            const double* X = pw + 3 * (size_t)i;
-            const double xc = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + t[0], yc = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + t[1];
-            const double z = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + t[2];
-            const double du = cam[0] * xc / z + cam[2] - obs[2 * i], dv = cam[1] * yc / z + cam[3] - obs[2 * i + 1];
-            flags[i] = (z > 0 && (du * du + dv * dv) * inv_sigma2[i] < 5.991) ? 1 : 0;
-            count += flags[i];
-        }
-        return count;
-    };
     for (int it = 0; it < iterations; ++it) {
-        for (int i = 0; i < n; ++i) avail[(size_t)i] = i;
-        int left = n, idx[4];
-        for (int k = 0; k < 4; ++k) { const int r = (int)(rng.next() % (uint32_t)left); idx[k] = avail[(size_t)r]; avail[(size_t)r] = avail[(size_t)left - 1]; --left; }
-        double p4[12], u4[8], R[9], t[3];
-        for (int k = 0; k < 4; ++k) { for (int a = 0; a < 3; ++a) p4[3 * k + a] = pw[3 * (size_t)idx[k] + a]; u4[2 * k] = obs[2 * (size_t)idx[k]]; u4[2 * k + 1] = obs[2 * (size_t)idx[k] + 1]; }
-        if (!epnp_solve(p4, u4, 4, cam, R, t)) continue;
-        const int count = count_inliers(R, t, cur.data());
+        double R[9], t[3];
+        if (!ep::pnp_solve_sample(pw, obs, table.data() + (size_t)4 * it, cam, R, t)) continue;
+        const int count = ep::pnp_score(R, t, cam, pw, obs, inv_sigma2, n, cur.data());
         if (count > best) {
             best = count;
             for (int i = 0; i < n; ++i) inlier[i] = cur[(size_t)i];
@@ -753,21 +504,8 @@ int pnp_solve_ransac(const double* pw, const double* obs, const double* inv_sigm
         }
     }
     if (best < 4) { for (int i = 0; i < n; ++i) inlier[i] = 0; return 0; }
-    // refit on the inliers of the best sample ([UPSTREAM] refine): EPnP over all of them, kept when it explains at least as many matches
-    {
-        std::vector<double> pi, ui;
-        for (int i = 0; i < n; ++i) if (inlier[i]) { for (int a = 0; a < 3; ++a) pi.push_back(pw[3 * (size_t)i + a]); ui.push_back(obs[2 * (size_t)i]); ui.push_back(obs[2 * (size_t)i + 1]); }
-        double R[9], t[3];
-        if (epnp_solve(pi.data(), ui.data(), (int)(ui.size() / 2), cam, R, t)) {
-            const int count = count_inliers(R, t, cur.data());
-            if (count >= best) {
-                best = count;
-                for (int i = 0; i < n; ++i) inlier[i] = cur[(size_t)i];
-                for (int k = 0; k < 9; ++k) bestR[k] = R[k];
-                for (int k = 0; k < 3; ++k) bestT[k] = t[k];
-            }
-        }
-    }
+    std::vector<double> scratch((size_t)12 * n);
+    best = ep::pnp_refit(pw, obs, inv_sigma2, n, cam, best, inlier, bestR, bestT, scratch.data(), cur.data());
     double q[4];
     rotToQuat(bestR, q);
     for (int k = 0; k < 4; ++k) pose7[k] = q[k];

@@ -3,13 +3,17 @@
 //       tools/pnp_asan.cpp lpslam_amd/host/two_view.cpp lpslam_amd/host/pnp_batch.cpp -o pnp_asan && ./pnp_asan
 // It runs the sample table, the fixed-size EPnP and the batch host path over the shapes of tests/test_pnp_cpu.py (n = 4, 5, 37, 300;
 // seeds 0 and 0x9E3779B9; 1, 7 and 100 iterations; a batch with an empty set, a set of three and a coplanar set in the middle) and
-// checks what the tests check: indices distinct and in range, epnp4 equal to epnp_solve, the batch equal to separate solver calls.
+// checks what the tests check: indices distinct and in range, the fixed-size solve equal to epnp_solve, the batch equal to separate solver calls.
+// Then the any-n EPnP of csrc/epnp_math.h at n = 5, 37 and 300 and the shared refit, each with heap scratch of exactly the documented
+// size (4 n + 3 n doubles; 12 n doubles and n flags), so that a write past it is seen: equal to epnp_solve, and a refit that returns
+// the number of flags it leaves set.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 #include "two_view.h"
+#include "../lpslam_amd/csrc/epnp_math.h"
 
 extern "C" {
 int lpslam_pnp_sample_table(int n, int iterations, uint32_t seed, int32_t* table);
@@ -101,6 +105,26 @@ int main()
         check(cnt[1] == 0 && cnt[2] == 0 && cnt[4] == 0, "degenerate sets find nothing", it, 0);
         check(lpslam_pnp_ransac_batch_host(6, off.data(), all.pw.data(), all.obs.data(), all.w.data(), kCam, 0, 1, pose.data(), cnt.data(), fl.data(), nullptr) == 1, "iterations 0 refused", it, 0);
     }
-    std::printf("pnp_asan: %ld sample tables, %ld four-match solves compared, 3 batches of 6 sets; %d failures\n", tables, solved, failures);
+    namespace ep = lpslam_epnp;
+    long refits = 0;
+    for (int n : {5, 37, 300}) for (uint64_t data = 1; data <= 3; ++data) {
+        const Set s = planted(n, 100 * (uint64_t)n + data, false);
+        std::vector<double> al((size_t)4 * n), pc((size_t)3 * n), ws((size_t)ep::kWorkspace);
+        double R1[9], t1[3], R2[9], t2[3];
+        const bool o1 = LpSlam::epnp_solve(s.pw.data(), s.obs.data(), n, kCam, R1, t1);
+        const bool o2 = ep::epnp(s.pw.data(), s.obs.data(), n, kCam, al.data(), pc.data(), ws.data(), 1, R2, t2);
+        check(o1 && o2 && !std::memcmp(R1, R2, sizeof R1) && !std::memcmp(t1, t2, sizeof t1), "any-n epnp against epnp_solve", n, (int)data);
+        if (!o2) continue;
+        // the refit from the inliers of that pose (with every third match an outlier from n = 15 on, they are a proper subset)
+        std::vector<uint8_t> inl((size_t)n), cur((size_t)n);
+        std::vector<double> scratch((size_t)12 * n);
+        const int best = ep::pnp_score(R2, t2, kCam, s.pw.data(), s.obs.data(), s.w.data(), n, inl.data());
+        const int got = ep::pnp_refit(s.pw.data(), s.obs.data(), s.w.data(), n, kCam, best, inl.data(), R2, t2, scratch.data(), cur.data());
+        int set = 0;
+        for (uint8_t f : inl) set += f;
+        check(got >= best && got == set, "refit count against its flags", n, (int)data);
+        ++refits;
+    }
+    std::printf("pnp_asan: %ld sample tables, %ld four-match solves compared, 3 batches of 6 sets, %ld any-n solves and refits; %d failures\n", tables, solved, refits, failures);
     return failures ? 1 : 0;
 }
