@@ -466,6 +466,18 @@ int lpslam_hip_ba_counters(lpslam_hip_ctx* ctx, int64_t* out, int32_t n);
 /* How many launches of the one-workgroup factorisation (k_chol_wg: batches of LPSLAM_HIP_CW_MIN_BATCH = 40 problems and more) this
  * context has enqueued.  Test hook: proves which of the two factorisations a batch went through.  No reference counterpart. */
 int64_t lpslam_hip_ba_wg_factorisations(lpslam_hip_ctx* ctx);
+/* Test hook like lpslam_hip_debug_occupy_unreserved (no reference counterpart, no product path calls it): the dense factor-and-solve
+ * on the caller's systems.  `problems`: n built problems with the dense solver selected, on one device; their observations do not
+ * matter, they fix dim_i = 6 x free keyframes.  A[i]: full symmetric dim_i x dim_i matrix, row major; it stands for S + lambda I and
+ * nothing is added to it.  b[i]: dim_i values.  Each reduced buffer is written as the product leaves it in front of a solve and the
+ * batch takes the launches an optimize of these n problems takes (alone: the panel-pair chain; 40 problems and more: k_chol_wg for the
+ * systems that fit it, the chain for the others).  x[i] receives dim_i values, pivot_flag[i] (may be NULL) 1 where the factorisation
+ * met a pivot <= 0; x[i] is the zero step then, on both kernels (what the replaced pivot left in the factor need not be finite, and
+ * none of it reaches x_p).  Finite inputs only.
+ * The call overwrites the problems' reduced systems and control blocks: lpslam_hip_ba_reset (or reset_batch) each of them before it
+ * optimises again. */
+int lpslam_hip_ba_debug_solve(lpslam_hip_ba* const* problems, int32_t n, const double* const* A, const double* const* b,
+                              double* const* x, int32_t* pivot_flag);
 /* Which linear solver a problem takes.  DENSE: Schur complement by pair lists, dense panel-pair Cholesky (any window).  BAND: when
  * no landmark of the window spans more than 10 free keyframes the reduced system is block-banded -- the shape a tracker's windows have,
  * and why the reference's local bundle adjuster solves with g2o's LinearSolverCSparse (SURVEY.md a21;

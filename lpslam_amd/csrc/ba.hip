@@ -976,8 +976,11 @@ __device__ __forceinline__ void pose_oplus(const double* pose, const double* d, 
 //   diagonal block is factored redundantly by every panel workgroup, which removes every dependence between workgroups of a launch.
 //   All working workgroups run on one XCD: the grid is launched 8x oversized and only every 8th workgroup works (workgroups go
 //   round-robin to the 8 XCDs), so the panel written by one launch is an L2 hit for the next (measured: -1 us per launch).
-// Explicit FMAs are used here (the contraction pragma only governs implicit fusing); the factorisation is not a parity
-// quantity, the solve's effect on chi2 / poses is (tolerances in DESIGN.md).
+// Explicit FMAs are used here (the contraction pragma only governs implicit fusing): the factor's bits are not a parity quantity.
+// What the factor-and-solve must deliver is x_p itself: a forward error within n kappa_2 2^-53 of the exact solution and within the
+// measured margin of a float64 Cholesky solve on the host -- the accuracy table of DESIGN.md 36 (profiles/solve_accuracy.txt),
+// held by tests/test_ba_solve_gpu.py through lpslam_hip_ba_debug_solve.  The LM trajectory (chi2 / poses, tolerances in DESIGN.md)
+// sees an error of the step only to second order.
 // Launch m factors panel columns j = 2m and j1 = 2m + 1 and applies the previous pair (kb0 = 2m - 2, kb1 = 2m - 1) to the rest of
 // the trailing matrix: one kernel boundary per two panels on the critical path.  A panel workgroup (row block i, or
 // Minv row block e) keeps its five blocks  D_j, X = A_j1,j, D_j1, B0 = A_i,j, B1 = A_i,j1  in LDS:
@@ -1325,8 +1328,11 @@ __global__ __launch_bounds__(256) void k_chol_xsolve(const BaView* __restrict__ 
 {
     if (pin && (blockIdx.x & 7)) return;  // XCD 0 only, like k_chol_pair: its inputs sit in that L2
     BA_VIEW(v);
-    BA_VIEW_HEAD("s"(v.dim), "s"(v.dim_pad), "s"(v.ctl), "s"(v.S), "s"(v.Ldiag), "s"(v.Lsub), "s"(v.Minv), "s"(v.xp), "s"(v.band_hbw));
+    BA_VIEW_HEAD("s"(v.dim), "s"(v.dim_pad), "s"(v.ctl), "s"(v.S), "s"(v.Ldiag), "s"(v.Lsub), "s"(v.Minv), "s"(v.xp), "s"(v.scal), "s"(v.band_hbw));
     if (v.band_hbw >= 0 || ba_flags(v.ctl).idle() || (skip_small && cw_fits(v.dim))) return;
+    // a flagged factorisation (a pivot <= 0 was replaced; the launches behind it may have grown that into infinities) gives the zero
+    // step: the trial is rejected on the flag, and nothing that is not finite reaches the update
+    const double flagged = v.scal[5];
     const int lane = threadIdx.x & 63;
     const int i = (pin ? blockIdx.x >> 3 : blockIdx.x) * 4 + (threadIdx.x >> 6);
     if (i >= v.dim) return;
@@ -1342,7 +1348,7 @@ __global__ __launch_bounds__(256) void k_chol_xsolve(const BaView* __restrict__ 
     double acc = 0;
     for (int c = (i / NB) * NB + lane; c < v.dim; c += 64) acc += m[c] * (c < ys0 ? y[c] : (c < yb * NB ? ys[c] : yd[c]));     // blocks left of the diagonal are empty
     acc = wave_sum(acc);
-    if (lane == 0) v.xp[i] = acc;
+    if (lane == 0) v.xp[i] = flagged != 0.0 ? 0.0 : acc;
 }
 
 void enqueue_xsolve(hipStream_t s, const BaView* d_views, int count, int dim, int skip_small = 0, bool spread = false)

@@ -187,7 +187,10 @@ __device__ __forceinline__ void lm_begin(BaView& v, double max_diag_pp, double m
 __device__ __forceinline__ int lm_decide(BaView& v, double temp_chi, double chol_failed, double scale_l, double scale_p, bool spec_ran = false, const BaCtl* preloaded = nullptr)      // returns "accepted"
 {
     BaCtl c = preloaded ? *preloaded : *v.ctl;             // (preloaded: the caller fetched the block beside its other loads -- one round trip less on the chain)
-    if (chol_failed != 0.0) temp_chi = DBL_MAX;            // factorisation failed
+    // factorisation failed: g2o's ok = 0 branch -- no step was taken, computeScale is not run (the scale is its 1e-3 alone), so rho < 0
+    // and the iteration goes on to its next trial with a larger lambda.  The scale terms of a flagged solve must not get a say: they
+    // come from whatever the factorisation left (tests/test_ba_solve_gpu.py).
+    if (chol_failed != 0.0) { temp_chi = DBL_MAX; scale_l = 0.0; scale_p = 0.0; }
     double rho = c.current_chi - temp_chi;
     const double scale = (scale_l + scale_p) + 1e-3;
     rho /= scale;

@@ -1097,6 +1097,61 @@ int lpslam_hip_ba_reset_batch(lpslam_hip_ba* const* ps, int32_t n)
     return LPSLAM_HIP_OK;
 }
 
+// Test entry into the dense factor-and-solve: the caller's systems A x = b through the launches a solve of these problems takes
+// (tests/test_ba_solve_gpu.py; no product path calls it).  Every problem's reduced buffer is written as the product leaves it in front
+// of a non-fused solve -- A (it stands for S + lambda I, nothing is added) in the dim_pad layout, b in rhs and in row `dim`, 1e200 on
+// that row's diagonal, identity padding, pivot flag cleared -- the control blocks are armed so that no kernel idles, and
+// lp_enqueue_factor_solve gets what enqueue_solve computes for the batch (wg, any_small / any_large, nb, dim, spread).
+// It overwrites the reduced system and the control block: lpslam_hip_ba_reset (or reset_batch) the problems before they optimise again.
+int lpslam_hip_ba_debug_solve(lpslam_hip_ba* const* ps, int32_t n, const double* const* A, const double* const* rhs, double* const* x, int32_t* pivot_flag)
+{
+    int rc = need_batch(ps, n, true); if (rc) return rc;
+    if (!A || !rhs || !x) { set_error("debug_solve: null matrix / right-hand side / solution array"); return LPSLAM_HIP_ERR_INVALID; }
+    for (int i = 0; i < n; ++i) {
+        if (!A[i] || !rhs[i] || !x[i]) { set_error("debug_solve: null matrix / right-hand side / solution (entry %d)", i); return LPSLAM_HIP_ERR_INVALID; }
+        if (ps[i]->h_view.band_hbw >= 0) { set_error("debug_solve: entry %d takes the band solver (lpslam_hip_ba_set_solver DENSE first)", i); return LPSLAM_HIP_ERR_INVALID; }
+        if (ps[i]->dim < 1) { set_error("debug_solve: entry %d has no free keyframe", i); return LPSLAM_HIP_ERR_INVALID; }
+    }
+    LP_HIP(hipSetDevice(ps[0]->ctx->cfg.device));
+    BatchViews bv;
+    BaLaunch L;
+    if (n == 1) L = single_launch(ps[0]);
+    else {
+        if ((rc = batch_sync_streams(ps, n, ps[0]->stream))) return rc;
+        if ((rc = batch_views(ps, n, 0, &bv))) return rc;
+        L = bv.L;
+    }
+    std::vector<std::vector<double>> stage((size_t)n);
+    std::vector<double> flags((size_t)n, 0.0);
+    for (int i = 0; i < n; ++i) {
+        const lpslam_hip_ba* b = ps[i];
+        const size_t np = (size_t)b->dim_pad, dim = (size_t)b->dim;
+        std::vector<double>& h = stage[i];
+        h.assign(np * np + np, 0.0);                                    // S | rhs
+        for (size_t r = 0; r < dim; ++r) {
+            memcpy(&h[r * np], A[i] + r * dim, dim * sizeof(double));
+            h[dim * np + r] = rhs[i][r];
+            h[np * np + r] = rhs[i][r];
+        }
+        h[dim * np + dim] = 1e200;
+        for (size_t r = dim + 1; r < np; ++r) h[r * np + r] = 1.0;
+        LP_HIP(hipMemcpyAsync(b->d_red, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, L.s));
+        LP_HIP(hipMemsetAsync(b->d_scal + 5, 0, sizeof(double), L.s));
+    }
+    hipLaunchKernelGGL(k_ba_arm, dim3(1, n), dim3(64), 0, L.s, L.d_views, 1);
+    const bool wg = L.count >= cw_min_batch();
+    if (wg && L.any_small && L.ctx) L.ctx->ba_wg_launches.fetch_add(1);
+    lp_enqueue_factor_solve(L.s, L.d_views, L.count, L.nb, L.dim, wg, L.any_small, L.any_large, L.spread);
+    LP_HIP(hipGetLastError());
+    for (int i = 0; i < n; ++i) {
+        LP_HIP(hipMemcpyAsync(x[i], (const double*)ps[i]->h_view.xp, (size_t)ps[i]->dim * sizeof(double), hipMemcpyDeviceToHost, L.s));
+        LP_HIP(hipMemcpyAsync(&flags[i], ps[i]->d_scal + 5, sizeof(double), hipMemcpyDeviceToHost, L.s));
+    }
+    LP_HIP(hipStreamSynchronize(L.s));          // the staging blocks and the view array are released on return
+    for (int i = 0; i < n; ++i) { release_stage(ps[i]); if (pivot_flag) pivot_flag[i] = flags[i] != 0.0 ? 1 : 0; }
+    return LPSLAM_HIP_OK;
+}
+
 int lpslam_hip_ba_optimize_batch(lpslam_hip_ba* const* ps, int32_t n, int32_t robust, int32_t iters, lpslam_hip_ba_iter_log* logs,
                                  int32_t log_stride, int32_t* done)
 {

@@ -281,5 +281,9 @@ __global__ __launch_bounds__(CW_THREADS) void k_chol_wg(const BaView* __restrict
         }
         __syncthreads();
     }
-    if (tid == 0 && *s_fail) v.scal[5] = 1.0;
+    // a flagged factorisation gives the zero step (as k_chol_xsolve): what the replaced pivot left behind need not be finite
+    if (*s_fail) {
+        if (tid < dim) v.xp[tid] = 0.0;
+        if (tid == 0) v.scal[5] = 1.0;
+    }
 }

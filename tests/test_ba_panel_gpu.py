@@ -7,8 +7,9 @@ ba_optimize_batch (where small systems go through k_chol_wg, chol_panel_core<48>
 
 The reduced system has six columns per free keyframe, so a last panel column holds 0, 2, 4, ... real columns: 18 and 30 are the
 one-panel windows next to 17 and 31.  S + lambda I is positive definite for every lambda > 0 an LM trial uses -- a keyframe
-without observations still has lambda on its diagonal -- so no window makes the factorisation raise its pivot flag; the strip's
-pivot guard is the parent's and tools/dev/panel_bench.hip reads the flag beside its host Cholesky."""
+without observations still has lambda on its diagonal -- so no window here makes the factorisation raise its pivot flag.  The strip's
+pivot guard, the flag and its reset have a test of their own: tests/test_ba_solve_gpu.py gives the factor-and-solve matrices that are
+not positive definite, with the first failing pivot in every kind of strip, and holds x_p itself to an exact solution."""
 import numpy as np
 import pytest
 
