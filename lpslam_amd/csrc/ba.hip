@@ -991,9 +991,11 @@ __device__ __forceinline__ void pose_oplus(const double* pose, const double* d, 
 //   4. wavefront 0 factors [D_j1; B1] -> L_j1,j1, L_i,j1 while wavefronts 1-3 finish the right halves, announce them and store
 //      step 2's blocks.
 // A panel starts strip A on the left halves alone and takes the right ones behind the announcement (chol_panel_split).
-// D_j, X and D_j1 are factored redundantly by every panel workgroup; nobody overwrites them in S during the launch (the
-// diagonal workgroup publishes L_jj, L_j1,j1 into Ldiag; L_j1,j is needed by no later launch).  With an odd number of panels
-// the last launch is `single`: only column j, factored by wavefront 0 alone.
+// D_j, X and D_j1 are factored redundantly by every panel workgroup; nobody overwrites them in S during the launch, and no later
+// launch needs L_jj, L_j1,j or L_j1,j1.  Their one reader is k_chol_xsolve, which takes the rhs row out of the system's LAST panel
+// column: the diagonal workgroup publishes the rhs row of that column's diagonal block into Ldiag and, when it is the second column of a
+// pair, L_j1,j into Lsub -- in the system's last launch and in no other.  In every other launch the diagonal workgroup
+// only raises the pivot flag.  With an odd number of panels the last launch is `single`: only column j, factored by wavefront 0 alone.
 // The LAST panel column of a system (step 4 of its last launch, or step 2 of a `single` one) stops after its dim - 32 (nb - 1) real
 // columns (chol_panel_trim): what follows them -- the rhs row's diagonal, the identity padding -- is read by nobody.
 constexpr int CP_BLK = NB * (NB + 1);                  // one padded 32x32 block in LDS
@@ -1162,7 +1164,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__
     __syncthreads();
     // One 16x16 tile (r, c) of a block, D -= A0 Bk0^T + A1 Bk1^T (K = 64) or D -= A0 Bk0^T (K = 32): a chain of mfma_tile32 calls of
     // its own, so its bits do not depend on the wavefront that runs it or on when.  Tile (0, 1) of D_j and D_j1 is never computed:
-    // panel loads read the lower triangle of a diagonal block and panel_to_lds writes zeros above it.
+    // panel loads read the lower triangle of a diagonal block, and the factored block is not written back.
     auto tile64 = [&](double* D, const double* A0, const double* A1, const double* Bk0, const double* Bk1, int r, int c) __attribute__((always_inline)) {
         f64x4 acc = {0, 0, 0, 0};
         acc = mfma_tile32(A0, Bk0, 16 * r, 16 * c, lr, lk, acc); acc = mfma_tile32(A1, Bk1, 16 * r, 16 * c, lr, lk, acc);
@@ -1188,21 +1190,36 @@ __global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__
     const int want1 = prev ? 2 : 0;                      // wavefronts 2 and 3 announce step 1's right halves
     bool fail = false;
     const int need = min(max(dim - NB * (nb - 1), 0), NB);       // real columns of the system's last panel column (chol_panel_trim)
-    // The factored blocks leave the registers through LDS (every lane owns a ROW there): the workgroup then stores them to memory
+    // Ldiag and Lsub have one reader, k_chol_xsolve, and it reads the blocks of the system's last panel column alone (the rhs row lives
+    // there): a `single` launch's column is that one, a pair's first column never is, its second column is in the system's last launch.
+    // From the view's own size, as `need`: in a batch the chain goes on behind a shorter system's last launch.
+    const bool last1 = j1 == nb - 1;
+    // The factored row blocks leave the registers through LDS (every lane owns a ROW there): the workgroup then stores them to memory
     // 32 lanes to a row, where a lane-per-row store touched one cache line per lane (2.4k cycles of the factoring wavefront).
-    // L_jj goes into X's place (wavefront 0 alone reads X, at the start of 2a), L_j1,j1 into D_j1's, L_i,j1 into B1's.
-    auto panel_to_lds = [&](const PanelRegs& p, double* Ld, double* Lb) {
-        if (lane < 16) {
-            if (Ld) {
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    Ld[lane * (NB + 1) + c] = c <= lane ? p.dA[c] : 0.0;        Ld[lane * (NB + 1) + 16 + c] = 0.0;
-                    Ld[(16 + lane) * (NB + 1) + c] = p.x[c];                     Ld[(16 + lane) * (NB + 1) + 16 + c] = c <= lane ? p.dB[c] : 0.0;
-                }
-            }
-        } else if (lane < 48 && Lb) {
+    // L_j1,j goes into Ljk0's place, L_i,j into Ljk1's, L_i,j1 into B1's.  The factored diagonal block stays in the registers.
+    auto panel_to_lds = [&](const PanelRegs& p, double* Lb) {
+        if (lane >= 16 && lane < 48 && Lb) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) { Lb[(lane - 16) * (NB + 1) + c] = p.x[c]; Lb[(lane - 16) * (NB + 1) + 16 + c] = p.y[c]; }
+        }
+    };
+    // Of the last column's diagonal block k_chol_xsolve reads ONE row: row `need`, the rhs row, columns < need.  The lane that holds it
+    // (rows 0-15 of the block: dA; rows 16-31: x | dB) stores it from its registers, two columns a store: at most 16 stores of one
+    // lane, where the whole block went through LDS (64 ds_write_b64 of the factoring wavefront) and then to memory.  With an odd `need`
+    // the last pair reaches column `need` itself, which nobody reads.  Nothing else of Ldiag is written.
+    auto rhs_row_to_memory = [&](const PanelRegs& p, double* blk) {                // wavefront 0
+        if (lane == (need & 15)) {
+            f64x2* dst = reinterpret_cast<f64x2*>(blk + (size_t)need * NB);
+            if (need < 16) {
+#pragma unroll
+                for (int c = 0; c < 16; c += 2) if (c < need) dst[c / 2] = f64x2{p.dA[c], p.dA[c + 1]};
+            } else {
+#pragma unroll
+                for (int c = 0; c < 16; c += 2) {
+                    dst[c / 2] = f64x2{p.x[c], p.x[c + 1]};
+                    if (16 + c < need) dst[8 + c / 2] = f64x2{p.dB[c], p.dB[c + 1]};
+                }
+            }
         }
     };
     auto block_to_memory = [&](const double* L, double* dst, size_t pitch) {       // all four wavefronts
@@ -1219,17 +1236,18 @@ __global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__
             if (t < NB * NB) dst[(size_t)r * pitch + c] = L[r * (NB + 1) + c];
         }
     };
-    // Every factoring wavefront passes the announcement before it writes its panel out (panel_to_lds overwrites X, Ljk0 and Ljk1,
+    // Every factoring wavefront passes the announcement before it writes its panel out (panel_to_lds overwrites Ljk0 and Ljk1,
     // which the right-half tiles read): chol_panel_split waits in all of its paths.
     if (wave == 0) {
         PanelRegs p;
         PAIR_STAMP(3, true);
         if (single) {                                    // 2. the system's last panel column alone: [D_j; B0] -> L_jj / L_i,j, cut short
             fail = chol_panel_split<true>(p, Dj, has_b ? B0 : nullptr, lane, cp_lds + 11 * CP_BLK, gate, want1, need);
-            panel_to_lds(p, diag ? X : nullptr, has_b ? Ljk1 : nullptr);
+            panel_to_lds(p, has_b ? Ljk1 : nullptr);
+            if (diag) rhs_row_to_memory(p, Ldiag + (size_t)j * NB * NB);
         } else {                                         // 2a. [D_j; X] -> L_jj, L_j1,j
             fail = chol_panel_split<false>(p, Dj, X, lane, cp_lds + 11 * CP_BLK, gate, want1, NB);
-            panel_to_lds(p, diag ? X : nullptr, Ljk0);                                 // L_j1,j for step 3
+            panel_to_lds(p, Ljk0);                                                     // L_j1,j for step 3
         }
         PAIR_PANEL_STAMPS(4, p);
         if (diag && fail && lane == 0) scal[5] = 1.0;
@@ -1238,7 +1256,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__
             PanelRegs p;
             PAIR_STAMP(7, true);
             chol_panel_split<false>(p, Dj, B0, lane, cp_lds + 11 * CP_BLK + CH_SCR, gate, want1, NB);
-            panel_to_lds(p, nullptr, Ljk1);
+            panel_to_lds(p, Ljk1);
             PAIR_PANEL_STAMPS(8, p);
         }
     } else if (prev) {
@@ -1261,8 +1279,7 @@ __global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__
     __syncthreads();
     PAIR_STAMP(11, wave == 0);
     if (single) {
-        if (diag) block_to_memory(X, Ldiag + (size_t)j * NB * NB, NB);
-        else block_to_memory(Ljk1, (extra ? M : S) + ri * n + rj, n);
+        if (!diag) block_to_memory(Ljk1, (extra ? M : S) + ri * n + rj, n);
         PAIR_STAMP(23, wave == 0);
         return;
     }
@@ -1274,9 +1291,10 @@ __global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__
     if (wave == 0) {                                     // 4. [D_j1; B1] -> L_j1,j1, L_i,j1
         PanelRegs p;
         PAIR_STAMP(13, true);
-        fail = j1 == nb - 1 ? chol_panel_split<true>(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK, gate + 1, 3, need)
+        fail = last1 ? chol_panel_split<true>(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK, gate + 1, 3, need)
                             : chol_panel_split<false>(p, Dj1, has_b ? B1 : nullptr, lane, cp_lds + 11 * CP_BLK, gate + 1, 3, NB);
-        panel_to_lds(p, diag ? Dj1 : nullptr, has_b ? B1 : nullptr);
+        panel_to_lds(p, has_b ? B1 : nullptr);
+        if (diag && last1) rhs_row_to_memory(p, Ldiag + (size_t)j1 * NB * NB);
         PAIR_PANEL_STAMPS(14, p);
         if (diag && fail && lane == 0) scal[5] = 1.0;
     } else {
@@ -1286,17 +1304,15 @@ __global__ __launch_bounds__(256, 2) void k_chol_pair(const BaView* __restrict__
         else if (has_b) tile32(B1, Ljk1, Ljk0, wave - 2, 1);
         panel_gate_open(gate + 1, lane);
         if (diag) {
-            block_to_memory3(X, Ldiag + (size_t)j * NB * NB, NB);
-            // L_j1,j for k_chol_xsolve when the rhs row lives in block j1.  Not into S: the other panel workgroups read A_j1,j.
-            block_to_memory3(Ljk0, Lsub + (size_t)j1 * NB * NB, NB);
+            // L_j1,j for k_chol_xsolve: the rhs row lives in block j1.  Not into S: the other panel workgroups read A_j1,j.
+            if (last1) block_to_memory3(Ljk0, Lsub + (size_t)j1 * NB * NB, NB);
         } else {
             block_to_memory3(Ljk1, (extra ? M : S) + ri * n + rj, n);
         }
         PAIR_STAMP(21, wave == 1);
     }
     __syncthreads();
-    if (diag) block_to_memory(Dj1, Ldiag + (size_t)j1 * NB * NB, NB);
-    else block_to_memory(B1, (extra ? M : S) + ri * n + rj1, n);
+    if (!diag) block_to_memory(B1, (extra ? M : S) + ri * n + rj1, n);
     PAIR_STAMP(23, wave == 0);
 }
 

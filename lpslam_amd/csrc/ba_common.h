@@ -77,8 +77,8 @@ struct BaView {                       // one problem, resident in device memory 
     GPTR(double) S; GPTR(double) rhs; GPTR(double) bp; GPTR(double) hppdiag; GPTR(double) chi_cur;   // reduced buffer sections (all-reduced when partitioned)
     GPTR(double) bp_loc; GPTR(double) hppdiag_loc; GPTR(double) chi_loc;                    // this rank's own sums (equal to the above on one GPU)
     GPTR(double) Minv;                                                            // L^-T row blocks (dim_pad x dim_pad)
-    GPTR(double) Ldiag;                                                           // factored diagonal blocks [nb][32][32]
-    GPTR(double) Lsub;                                                            // L_j1,j of every panel pair, stored at [j1][32][32]
+    GPTR(double) Ldiag;                                                           // [nb][32][32]; only row dim - 32 (nb - 1) of block nb - 1 is written: the rhs row inside L's last diagonal block
+    GPTR(double) Lsub;                                                            // [nb][32][32]; block nb - 1 alone, for an even nb: L_j1,j of the last pair
     GPTR(double) xp; GPTR(double) chi_pose; GPTR(double) part; GPTR(double) scal;
     GPTR(const int) blk_start; GPTR(const int4) blk_terms;        // Schur pair lists: (observation a, observation b, their landmark, -)
     GPTR(double) blk_part; GPTR(int) blk_ticket;                  // Schur partial sums [block][SCH_MAXP][SCH_PV], per-block tickets (+ the table of further parts, ba_build.inl)
