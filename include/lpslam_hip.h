@@ -741,6 +741,41 @@ int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* ctx, int32_t n_sets, const int32
                                 double* pose7 /* 7 per set */, int32_t* n_inliers /* per set */, uint8_t* inlier /* per match */,
                                 int32_t* best_iteration /* per set, may be NULL */);
 
+/* ---- Two-view initialisation: the RANSAC loop and the pose check (monocular) -----------------------------------------
+ * Steps 1 and 4 of LpSlam::two_view_initialize (lpslam_amd/host/two_view.h), what openvslam::system does inside
+ * feed_monocular_frame until a map exists (reference call site: src/Trackers/OpenVSLAMTracker.cpp:120; parameters
+ * src/Trackers/OpenVSLAMTrackerBase.cpp:161-201): [UPSTREAM] initialize::perspective -- solve::homography_solver and
+ * solve::fundamental_solver on 8-match samples of Hartley-normalised keypoints, initialize::base::check_triangulated_pts.
+ * DESIGN.md section 38; the arithmetic is lpslam_amd/csrc/two_view_math.h, the text the host function runs: the same bits.
+ *
+ * lpslam_hip_two_view_ransac_batch: set s holds matches offsets[s] .. offsets[s + 1] of p1 (reference image) and p2 (current image),
+ * two doubles (pixels) each; every set is sampled with the same seed (xorshift32 from seed ? seed : 1) and `iterations` samples of
+ * eight, each giving a homography and a fundamental matrix that are scored over all matches of the set (chi-square at `sigma`, the
+ * sum over the matches in index order).  Per set and model (0 = H, 1 = F): best_iteration[2 s + m] (the first sample with the largest
+ * score; -1: none), score[2 s + m], model[18 s + 9 m ..] (H21 / F21, reference -> current, pixels, row major) and the per-match
+ * inlier flags of the winner in inlier_h / inlier_f (indexed like the matches).  No refit.  A model answers none -- iteration -1,
+ * score 0, a zero matrix, flags cleared -- when the set has fewer than eight matches or no sample gives a valid hypothesis (H: a
+ * determinant that is not above 1e-300; either: a score that is no number, as with all matches on one point).  One upload, two
+ * launches, one wait.  n_sets == 0: LPSLAM_HIP_OK, nothing done.  n_sets < 0, offsets that start below 0 or do not ascend,
+ * iterations outside 1 .. LPSLAM_HIP_TWO_VIEW_MAX_ITERATIONS, a sigma that is no positive number or NULL where an array is needed:
+ * LPSLAM_HIP_ERR_INVALID with nothing written.
+ *
+ * lpslam_hip_two_view_check_poses: n_hyp <= LPSLAM_HIP_TWO_VIEW_MAX_POSES motion hypotheses (R 9 doubles row major, t 3 doubles:
+ * reference -> current), K4 = fx fy cx cy, the n matches, the chosen model's inlier flags and th2 (squared reprojection bound,
+ * pixels).  Per (hypothesis h, match i) at h n + i: code (0: no inlier or rejected, 1: a plausible point, 2: plausible and with
+ * enough parallax to become a landmark), X (3 doubles in the reference camera frame; NaN with code 0) and cosp (the cosine of its
+ * parallax; 0 with code 0).  Counting, sorting the cosines and the acceptance rules stay with the caller.  One upload, one launch,
+ * one wait.  n_hyp == 0 or n == 0: LPSLAM_HIP_OK, nothing done.  n_hyp outside 0 .. 8, n < 0 or NULL where an array is needed:
+ * LPSLAM_HIP_ERR_INVALID with nothing written. */
+#define LPSLAM_HIP_TWO_VIEW_MAX_ITERATIONS 1024
+#define LPSLAM_HIP_TWO_VIEW_MAX_POSES 8
+int lpslam_hip_two_view_ransac_batch(lpslam_hip_ctx* ctx, int32_t n_sets, const int32_t* offsets /* n_sets + 1 */, const double* p1, const double* p2,
+                                     double sigma, int32_t iterations, uint32_t seed, int32_t* best_iteration /* 2 per set */, double* score /* 2 per set */,
+                                     double* model /* 18 per set */, uint8_t* inlier_h /* per match */, uint8_t* inlier_f /* per match */);
+int lpslam_hip_two_view_check_poses(lpslam_hip_ctx* ctx, int32_t n_hyp, const double* R /* 9 per hypothesis */, const double* t /* 3 per hypothesis */,
+                                    const double* K4, int32_t n, const double* p1, const double* p2, const uint8_t* inlier /* per match */, double th2,
+                                    double* X /* 3 per (hypothesis, match) */, double* cosp, uint8_t* code);
+
 /* ---- Sim3 pose graph ---------------------------------------------------------------------------------------------
  * Replaces what openvslam::system runs on its global-optimisation thread after a loop closure while the loop detector
  * is enabled (reference: src/Trackers/OpenVSLAMTrackerBase.cpp:250-255): [UPSTREAM] optimize::graph_optimizer on

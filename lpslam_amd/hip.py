@@ -53,6 +53,7 @@ SYMBOLS = [
     "lpslam_hip_set_keypoint_camera_radtan", "lpslam_hip_undistort_points_radtan",
     "lpslam_hip_triangulate_neighbours", "lpslam_hip_triangulate_pairs",
     "lpslam_hip_pnp_ransac_batch",
+    "lpslam_hip_two_view_ransac_batch", "lpslam_hip_two_view_check_poses",
 ]
 
 
@@ -1003,6 +1004,97 @@ def epnp4_host(p4, u4, cam4):
     assert p4.size == 12 and u4.size == 8 and cam.size == 4
     R = np.zeros(9); t = np.zeros(3)
     return (R.reshape(3, 3), t) if f(_p(p4), _p(u4), _p(cam), _p(R), _p(t)) else None
+
+
+TWO_VIEW_MAX_ITERATIONS = 1024     # LPSLAM_HIP_TWO_VIEW_MAX_ITERATIONS
+TWO_VIEW_MAX_POSES = 8             # LPSLAM_HIP_TWO_VIEW_MAX_POSES
+_TV_RANSAC_ARGS = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_TV_POSES_ARGS = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def _tv_ransac_arrays(offsets, p1, p2):
+    off = np.ascontiguousarray(offsets, np.int32)
+    n_sets = len(off) - 1
+    total = int(off[-1]) if n_sets >= 0 else 0
+    out = (np.full((max(n_sets, 1), 2), -1, np.int32), np.zeros((max(n_sets, 1), 2)), np.zeros((max(n_sets, 1), 2, 3, 3)),
+           np.zeros(max(total, 1), np.uint8), np.zeros(max(total, 1), np.uint8))
+    return off, n_sets, total, np.ascontiguousarray(p1, np.float64), np.ascontiguousarray(p2, np.float64), out
+
+
+def _tv_ransac_result(n_sets, total, out):
+    best, score, model, fh, ff = out
+    return best[:n_sets], score[:n_sets], model[:n_sets], fh[:total], ff[:total]
+
+
+def two_view_ransac_batch(ctx, offsets, p1, p2, sigma=1.0, iterations=100, seed=0x9E3779B9):
+    """lpslam_hip_two_view_ransac_batch: the sets are matches offsets[s] .. offsets[s + 1] of p1, p2 (n, 2) pixels; returns per set and
+    model (0 = H, 1 = F) the winning iteration (S, 2; -1: none), its score (S, 2), the matrix (S, 2, 3, 3) and the inlier flags of
+    the H and of the F winner (n each)"""
+    off, n_sets, total, p1, p2, out = _tv_ransac_arrays(offsets, p1, p2)
+    f = ctx.lib.lpslam_hip_two_view_ransac_batch
+    f.argtypes = [C.c_void_p] + _TV_RANSAC_ARGS
+    _check(f(ctx.h, n_sets, _p(off), _p(p1), _p(p2), float(sigma), int(iterations), int(seed) & 0xffffffff, *[_p(a) for a in out]))
+    return _tv_ransac_result(n_sets, total, out)
+
+
+def two_view_ransac_batch_host(offsets, p1, p2, sigma=1.0, iterations=100, seed=0x9E3779B9):
+    """lpslam_two_view_ransac_batch_host: step 1 of LpSlam::two_view_initialize on each set, the CPU definition of two_view_ransac_batch"""
+    off, n_sets, total, p1, p2, out = _tv_ransac_arrays(offsets, p1, p2)
+    f = host_lib().lpslam_two_view_ransac_batch_host
+    f.argtypes = _TV_RANSAC_ARGS; f.restype = C.c_int
+    if f(n_sets, _p(off), _p(p1), _p(p2), float(sigma), int(iterations), int(seed) & 0xffffffff, *[_p(a) for a in out]):
+        raise LpslamHipError("lpslam_two_view_ransac_batch_host refused its arguments")
+    return _tv_ransac_result(n_sets, total, out)
+
+
+def _tv_poses_arrays(R, t, K4, p1, p2, inlier):
+    R = np.ascontiguousarray(R, np.float64).reshape(-1, 9); t = np.ascontiguousarray(t, np.float64).reshape(-1, 3)
+    p1 = np.ascontiguousarray(p1, np.float64).reshape(-1, 2); p2 = np.ascontiguousarray(p2, np.float64).reshape(-1, 2)
+    fl = np.ascontiguousarray(inlier, np.uint8)
+    P, n = len(R), len(p1)
+    assert len(t) == P and len(p2) == n and len(fl) == n
+    out = (np.zeros((P, n, 3)), np.zeros((P, n)), np.zeros((P, n), np.uint8))      # (nothing is written when P or n is 0)
+    return P, n, R, t, np.ascontiguousarray(K4, np.float64), p1, p2, fl, out
+
+
+def two_view_check_poses(ctx, R, t, K4, p1, p2, inlier, th2):
+    """lpslam_hip_two_view_check_poses: P motion hypotheses (R (P, 3, 3), t (P, 3)) over n matches; X (P, n, 3), cosp (P, n), code (P, n)"""
+    P, n, R, t, K, p1, p2, fl, (X, cosp, code) = _tv_poses_arrays(R, t, K4, p1, p2, inlier)
+    f = ctx.lib.lpslam_hip_two_view_check_poses
+    f.argtypes = [C.c_void_p] + _TV_POSES_ARGS
+    _check(f(ctx.h, P, _p(R), _p(t), _p(K), n, _p(p1), _p(p2), _p(fl), float(th2), _p(X), _p(cosp), _p(code)))
+    return X[:P, :n], cosp[:P, :n], code[:P, :n]
+
+
+def two_view_check_poses_host(R, t, K4, p1, p2, inlier, th2):
+    """lpslam_two_view_check_poses_host: the per-match part of two_view_initialize's pose check, the CPU definition of two_view_check_poses"""
+    P, n, R, t, K, p1, p2, fl, (X, cosp, code) = _tv_poses_arrays(R, t, K4, p1, p2, inlier)
+    f = host_lib().lpslam_two_view_check_poses_host
+    f.argtypes = _TV_POSES_ARGS; f.restype = C.c_int
+    if f(P, _p(R), _p(t), _p(K), n, _p(p1), _p(p2), _p(fl), float(th2), _p(X), _p(cosp), _p(code)):
+        raise LpslamHipError("lpslam_two_view_check_poses_host refused its arguments")
+    return X[:P, :n], cosp[:P, :n], code[:P, :n]
+
+
+def two_view_sample_table(n, iterations, seed):
+    """lpslam_two_view_sample_table: the (iterations, 8) match indices two_view_initialize draws for a set of n >= 8 matches"""
+    f = host_lib().lpslam_two_view_sample_table
+    f.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p]; f.restype = C.c_int
+    table = np.full((max(int(iterations), 1), 8), -1, np.int32)
+    if not f(int(n), int(iterations), int(seed) & 0xffffffff, _p(table)):
+        raise LpslamHipError("lpslam_two_view_sample_table: n < 8 or iterations < 1")
+    return table
+
+
+def two_view_models8_host(x1, x2):
+    """lpslam_two_view_models8_host: the header's estimators (csrc/two_view_math.h) at eight matches; (H (3, 3), F (3, 3))"""
+    f = host_lib().lpslam_two_view_models8_host
+    f.argtypes = [C.c_void_p] * 4; f.restype = None
+    x1 = np.ascontiguousarray(x1, np.float64); x2 = np.ascontiguousarray(x2, np.float64)
+    assert x1.size == 16 and x2.size == 16
+    H = np.zeros(9); F = np.zeros(9)
+    f(_p(x1), _p(x2), _p(H), _p(F))
+    return H.reshape(3, 3), F.reshape(3, 3)
 
 
 class RcclComm:

@@ -38,6 +38,7 @@ HipVslamTrackerBase::HipVslamTrackerBase()
     o.optional("triangulateNeighbours", 0);
     // relocalisation: the candidates' PnP RANSAC in one call on the device; false: one host solve per candidate
     o.optional("relocaliseOnDevice", false);
+    o.optional("initialiseOnDevice", false);
 }
 
 HipVslamTrackerBase::~HipVslamTrackerBase() { stop(); }
@@ -65,6 +66,7 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_fisheyeMaxAngleDeg = o.getDouble("fisheyeMaxAngleDeg");
     m_triangulateNeighbours = o.getInteger("triangulateNeighbours");
     m_relocaliseOnDevice = o.getBool("relocaliseOnDevice");
+    m_initialiseOnDevice = o.getBool("initialiseOnDevice");
 }
 
 // The keypoint camera of a monocular session: the fisheye model from the camera configuration (f_x, f_y, c_x, c_y, dist[0..3]) with
@@ -1210,7 +1212,27 @@ bool HipVslamTrackerBase::monoInitialize(FrameData& cur)
     prm.min_triangulated = m_initMinTriangulated;       // the reference's Initializer.* values (src/Trackers/OpenVSLAMTrackerBase.cpp:181-182)
     prm.parallax_deg_thr = m_initParallaxDeg;
     TwoViewResult tv;
-    if (!two_view_initialize(K, kr.data(), kc.data(), matches.data(), (int)(matches.size() / 2), prm, tv)) return false;
+    // initialiseOnDevice: the RANSAC loop and the pose check of two_view_initialize through the device calls (the same arithmetic, the
+    // same result); a call that fails is logged and that step of this frame's attempt runs on the host
+    TwoViewSteps steps;
+    if (m_initialiseOnDevice) {
+        steps.ctx = m_ctx;
+        steps.ransac = [](void* ctx, int32_t n_sets, const int32_t* offsets, const double* p1, const double* p2, double sigma, int32_t iterations, uint32_t seed,
+                          int32_t* best_iteration, double* score, double* model, uint8_t* inlier_h, uint8_t* inlier_f) -> int {
+            return lpslam_hip_two_view_ransac_batch((lpslam_hip_ctx*)ctx, n_sets, offsets, p1, p2, sigma, iterations, seed, best_iteration, score, model, inlier_h, inlier_f);
+        };
+        steps.check_poses = [](void* ctx, int32_t n_hyp, const double* R, const double* t, const double* K4, int32_t n, const double* p1, const double* p2,
+                               const uint8_t* inlier, double th2, double* X, double* cosp, uint8_t* code) -> int {
+            return lpslam_hip_two_view_check_poses((lpslam_hip_ctx*)ctx, n_hyp, R, t, K4, n, p1, p2, inlier, th2, X, cosp, code);
+        };
+    }
+    const auto t_init = std::chrono::steady_clock::now();
+    const bool tv_ok = two_view_initialize(K, kr.data(), kc.data(), matches.data(), (int)(matches.size() / 2), prm, tv, m_initialiseOnDevice ? &steps : nullptr);
+    m_stats.t_init_attempt += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_init).count();
+    ++m_stats.init_attempts;
+    m_stats.init_device_calls += steps.calls - steps.failed;
+    if (steps.failed) logMessage(LpSlamLogLevel_Error, std::string("VSLAM initialisation: a device step failed (") + lpslam_hip_last_error() + "); it ran on the host for this frame");
+    if (!tv_ok) return false;
 
     // ---- the initial map: reference keyframe at the last good pose (the origin for the first segment), current keyframe at (R, t)
     // relative to it, scale: median depth in the reference = 1
@@ -2108,7 +2130,7 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld pnp_batches=%ld reloc_frames=%ld ms_reloc_frame=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld pnp_batches=%ld reloc_frames=%ld ms_reloc_frame=%.4f init_attempts=%ld init_device_calls=%ld ms_init_attempt=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
@@ -2117,7 +2139,8 @@ void HipVslamTrackerBase::logStatistics()
                   s.t_total * per, s.t_front * per, s.t_track * per, s.t_local * per, s.t_keyframe * per,
                   s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per,
                   s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per, s.perspective_dropped,
-                  s.pnp_batches, s.reloc_frames, s.reloc_frames > 0 ? 1e3 * s.t_relocalise / (double)s.reloc_frames : 0.0);
+                  s.pnp_batches, s.reloc_frames, s.reloc_frames > 0 ? 1e3 * s.t_relocalise / (double)s.reloc_frames : 0.0,
+                  s.init_attempts, s.init_device_calls, s.init_attempts > 0 ? 1e3 * s.t_init_attempt / (double)s.init_attempts : 0.0);
     m_lastStatistics = buf;
     logMessage(LpSlamLogLevel_Info, buf);
 }

@@ -3,8 +3,10 @@
 #include "pose_math.h"
 #include "../csrc/epnp_math.h"
 #include "../csrc/triangulate_math.h"
+#include "../csrc/two_view_math.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <complex>
 #include <cstring>
@@ -14,28 +16,7 @@ namespace LpSlam {
 
 namespace {
 
-struct M3 { double m[9]; };
-
-inline M3 mul(const M3& a, const M3& b)
-{
-    M3 r;
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) r.m[i * 3 + j] = a.m[i * 3] * b.m[j] + a.m[i * 3 + 1] * b.m[3 + j] + a.m[i * 3 + 2] * b.m[6 + j];
-    return r;
-}
-inline M3 transpose(const M3& a) { M3 r; for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) r.m[i * 3 + j] = a.m[j * 3 + i]; return r; }
-inline double det(const M3& a)
-{
-    return a.m[0] * (a.m[4] * a.m[8] - a.m[5] * a.m[7]) - a.m[1] * (a.m[3] * a.m[8] - a.m[5] * a.m[6]) + a.m[2] * (a.m[3] * a.m[7] - a.m[4] * a.m[6]);
-}
-inline M3 inverse(const M3& a)
-{
-    const double d = det(a), id = 1.0 / d;
-    M3 r;
-    r.m[0] = (a.m[4] * a.m[8] - a.m[5] * a.m[7]) * id; r.m[1] = (a.m[2] * a.m[7] - a.m[1] * a.m[8]) * id; r.m[2] = (a.m[1] * a.m[5] - a.m[2] * a.m[4]) * id;
-    r.m[3] = (a.m[5] * a.m[6] - a.m[3] * a.m[8]) * id; r.m[4] = (a.m[0] * a.m[8] - a.m[2] * a.m[6]) * id; r.m[5] = (a.m[2] * a.m[3] - a.m[0] * a.m[5]) * id;
-    r.m[6] = (a.m[3] * a.m[7] - a.m[4] * a.m[6]) * id; r.m[7] = (a.m[1] * a.m[6] - a.m[0] * a.m[7]) * id; r.m[8] = (a.m[0] * a.m[4] - a.m[1] * a.m[3]) * id;
-    return r;
-}
+using lpslam_tv::M3; using lpslam_tv::mul; using lpslam_tv::transpose; using lpslam_tv::det; using lpslam_tv::inverse;      // csrc/two_view_math.h
 
 // M = U diag(s) V^T, s descending; U, V proper or improper as they come (callers fix signs)
 void svd3(const M3& M, M3& U, double* s, M3& V)
@@ -68,20 +49,10 @@ void svd3(const M3& M, M3& U, double* s, M3& V)
     if (mv[0] * U.m[2] + mv[1] * U.m[5] + mv[2] * U.m[8] < 0) for (int r = 0; r < 3; ++r) U.m[r * 3 + 2] = -U.m[r * 3 + 2];
 }
 
-// Hartley normalisation as ORB-SLAM / OpenVSLAM do it: centroid to the origin, mean absolute deviation 1 per axis
 void normalize_points(const std::vector<double>& in, std::vector<double>& out, M3& T)
 {
-    const size_t n = in.size() / 2;
-    double mx = 0, my = 0;
-    for (size_t i = 0; i < n; ++i) { mx += in[2 * i]; my += in[2 * i + 1]; }
-    mx /= (double)n; my /= (double)n;
-    double dx = 0, dy = 0;
     out.resize(in.size());
-    for (size_t i = 0; i < n; ++i) { out[2 * i] = in[2 * i] - mx; out[2 * i + 1] = in[2 * i + 1] - my; dx += std::fabs(out[2 * i]); dy += std::fabs(out[2 * i + 1]); }
-    dx /= (double)n; dy /= (double)n;
-    const double sx = 1.0 / dx, sy = 1.0 / dy;
-    for (size_t i = 0; i < n; ++i) { out[2 * i] *= sx; out[2 * i + 1] *= sy; }
-    T = M3{{sx, 0, -mx * sx, 0, sy, -my * sy, 0, 0, 1}};
+    lpslam_tv::normalize_points(in.data(), in.size() / 2, out.data(), T);
 }
 
 struct Rng {
@@ -89,98 +60,51 @@ struct Rng {
     uint32_t next() { s ^= s << 13; s ^= s >> 17; s ^= s << 5; return s; }
 };
 
-double check_homography(const M3& H21, const M3& H12, const std::vector<double>& p1, const std::vector<double>& p2, double sigma, std::vector<uint8_t>& inl)
+// the score of a model over all matches: the terms of csrc/two_view_math.h added in index order, first direction then second
+double check_homography(const M3& H21, const M3& H12, const double* p1, const double* p2, size_t n, double sigma, std::vector<uint8_t>& inl)
 {
-    const size_t n = p1.size() / 2;
-    const double th = 5.991, inv_s2 = 1.0 / (sigma * sigma);
+    const double inv_s2 = 1.0 / (sigma * sigma);
     double score = 0;
     inl.assign(n, 0);
     for (size_t i = 0; i < n; ++i) {
-        const double u1 = p1[2 * i], v1 = p1[2 * i + 1], u2 = p2[2 * i], v2 = p2[2 * i + 1];
-        bool in = true;
-        {   // second image point into the first
-            const double w = 1.0 / (H12.m[6] * u2 + H12.m[7] * v2 + H12.m[8]);
-            const double x = (H12.m[0] * u2 + H12.m[1] * v2 + H12.m[2]) * w, y = (H12.m[3] * u2 + H12.m[4] * v2 + H12.m[5]) * w;
-            const double c = ((u1 - x) * (u1 - x) + (v1 - y) * (v1 - y)) * inv_s2;
-            if (c > th) in = false; else score += th - c;
-        }
-        {   // first image point into the second
-            const double w = 1.0 / (H21.m[6] * u1 + H21.m[7] * v1 + H21.m[8]);
-            const double x = (H21.m[0] * u1 + H21.m[1] * v1 + H21.m[2]) * w, y = (H21.m[3] * u1 + H21.m[4] * v1 + H21.m[5]) * w;
-            const double c = ((u2 - x) * (u2 - x) + (v2 - y) * (v2 - y)) * inv_s2;
-            if (c > th) in = false; else score += th - c;
-        }
-        inl[i] = in ? 1 : 0;
+        const lpslam_tv::MatchTerms m = lpslam_tv::homography_terms(H21.m, H12.m, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1], inv_s2);
+        if (m.add1) score += m.t1;
+        if (m.add2) score += m.t2;
+        inl[i] = (uint8_t)m.inlier;
     }
     return score;
 }
 
-double check_fundamental(const M3& F21, const std::vector<double>& p1, const std::vector<double>& p2, double sigma, std::vector<uint8_t>& inl)
+double check_fundamental(const M3& F21, const double* p1, const double* p2, size_t n, double sigma, std::vector<uint8_t>& inl)
 {
-    const size_t n = p1.size() / 2;
-    const double th = 3.841, th_score = 5.991, inv_s2 = 1.0 / (sigma * sigma);
+    const double inv_s2 = 1.0 / (sigma * sigma);
     double score = 0;
     inl.assign(n, 0);
     for (size_t i = 0; i < n; ++i) {
-        const double u1 = p1[2 * i], v1 = p1[2 * i + 1], u2 = p2[2 * i], v2 = p2[2 * i + 1];
-        bool in = true;
-        {   // epipolar line of x1 in the second image: l2 = F21 x1
-            const double a = F21.m[0] * u1 + F21.m[1] * v1 + F21.m[2], b = F21.m[3] * u1 + F21.m[4] * v1 + F21.m[5], c = F21.m[6] * u1 + F21.m[7] * v1 + F21.m[8];
-            const double num = a * u2 + b * v2 + c;
-            const double chi = num * num / (a * a + b * b) * inv_s2;
-            if (chi > th) in = false; else score += th_score - chi;
-        }
-        {   // epipolar line of x2 in the first image: l1 = F21^T x2
-            const double a = F21.m[0] * u2 + F21.m[3] * v2 + F21.m[6], b = F21.m[1] * u2 + F21.m[4] * v2 + F21.m[7], c = F21.m[2] * u2 + F21.m[5] * v2 + F21.m[8];
-            const double num = a * u1 + b * v1 + c;
-            const double chi = num * num / (a * a + b * b) * inv_s2;
-            if (chi > th) in = false; else score += th_score - chi;
-        }
-        inl[i] = in ? 1 : 0;
+        const lpslam_tv::MatchTerms m = lpslam_tv::fundamental_terms(F21.m, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1], inv_s2);
+        if (m.add1) score += m.t1;
+        if (m.add2) score += m.t2;
+        inl[i] = (uint8_t)m.inlier;
     }
     return score;
 }
 
 struct Hypothesis { M3 R; double t[3]; };
 
-// triangulates the inlier matches under (R, t), counts the plausible ones (ORB-SLAM CheckRT / OpenVSLAM check_triangulated_pts)
-int check_pose(const Hypothesis& h, const double* K, const std::vector<double>& p1, const std::vector<double>& p2, const std::vector<uint8_t>& inl,
-               double th2, std::vector<double>& pts, std::vector<uint8_t>& good, double& parallax_deg)
+// what check_pose does after its loop over the matches (ORB-SLAM CheckRT / OpenVSLAM check_triangulated_pts): the plausible points
+// counted, their cosines in match order sorted, the parallax from the 51st
+int pose_tally(const double* X, const double* cosp, const uint8_t* code, size_t n, std::vector<double>& pts, std::vector<uint8_t>& good, double& parallax_deg)
 {
-    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3];
-    const size_t n = p1.size() / 2;
-    double P1[12] = {fx, 0, cx, 0, 0, fy, cy, 0, 0, 0, 1, 0}, P2[12];
-    for (int c = 0; c < 3; ++c) {
-        P2[c] = fx * h.R.m[c] + cx * h.R.m[6 + c]; P2[4 + c] = fy * h.R.m[3 + c] + cy * h.R.m[6 + c]; P2[8 + c] = h.R.m[6 + c];
-    }
-    P2[3] = fx * h.t[0] + cx * h.t[2]; P2[7] = fy * h.t[1] + cy * h.t[2]; P2[11] = h.t[2];
-    const double O2[3] = {-(h.R.m[0] * h.t[0] + h.R.m[3] * h.t[1] + h.R.m[6] * h.t[2]), -(h.R.m[1] * h.t[0] + h.R.m[4] * h.t[1] + h.R.m[7] * h.t[2]),
-                          -(h.R.m[2] * h.t[0] + h.R.m[5] * h.t[1] + h.R.m[8] * h.t[2])};
     pts.assign(3 * n, std::numeric_limits<double>::quiet_NaN());
     good.assign(n, 0);
     std::vector<double> cosines;
     int n_good = 0;
     for (size_t i = 0; i < n; ++i) {
-        if (!inl[i]) continue;
-        double X[3];
-        if (!triangulate_point(P1, P2, &p1[2 * i], &p2[2 * i], X)) continue;
-        if (!std::isfinite(X[0]) || !std::isfinite(X[1]) || !std::isfinite(X[2])) continue;
-        const double n1 = std::sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
-        const double d2[3] = {X[0] - O2[0], X[1] - O2[1], X[2] - O2[2]};
-        const double n2 = std::sqrt(d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2]);
-        const double cosp = (X[0] * d2[0] + X[1] * d2[1] + X[2] * d2[2]) / (n1 * n2);
-        if (X[2] <= 0 && cosp < 0.99998) continue;
-        const double X2[3] = {h.R.m[0] * X[0] + h.R.m[1] * X[1] + h.R.m[2] * X[2] + h.t[0], h.R.m[3] * X[0] + h.R.m[4] * X[1] + h.R.m[5] * X[2] + h.t[1],
-                              h.R.m[6] * X[0] + h.R.m[7] * X[1] + h.R.m[8] * X[2] + h.t[2]};
-        if (X2[2] <= 0 && cosp < 0.99998) continue;
-        const double e1x = fx * X[0] / X[2] + cx - p1[2 * i], e1y = fy * X[1] / X[2] + cy - p1[2 * i + 1];
-        if (e1x * e1x + e1y * e1y > th2) continue;
-        const double e2x = fx * X2[0] / X2[2] + cx - p2[2 * i], e2y = fy * X2[1] / X2[2] + cy - p2[2 * i + 1];
-        if (e2x * e2x + e2y * e2y > th2) continue;
-        cosines.push_back(cosp);
-        pts[3 * i] = X[0]; pts[3 * i + 1] = X[1]; pts[3 * i + 2] = X[2];
+        if (code[i] == lpslam_tv::kPoseRejected) continue;
+        cosines.push_back(cosp[i]);
+        pts[3 * i] = X[3 * i]; pts[3 * i + 1] = X[3 * i + 1]; pts[3 * i + 2] = X[3 * i + 2];
         ++n_good;
-        if (cosp < 0.99998) good[i] = 1;
+        if (code[i] == lpslam_tv::kPoseGood) good[i] = 1;
     }
     parallax_deg = 0;
     if (!cosines.empty()) {
@@ -278,39 +202,14 @@ void sym_eigen_jacobi(const double* A, int n, double* eigval, double* eigvec)
 
 void homography_from_matches(const double* x1, const double* x2, int n, double* H)
 {
-    double AtA[81] = {0};
-    for (int i = 0; i < n; ++i) {
-        const double u1 = x1[2 * i], v1 = x1[2 * i + 1], u2 = x2[2 * i], v2 = x2[2 * i + 1];
-        const double r1[9] = {0, 0, 0, -u1, -v1, -1, v2 * u1, v2 * v1, v2};
-        const double r2[9] = {u1, v1, 1, 0, 0, 0, -u2 * u1, -u2 * v1, -u2};
-        for (int a = 0; a < 9; ++a) for (int b = 0; b < 9; ++b) AtA[a * 9 + b] += r1[a] * r1[b] + r2[a] * r2[b];
-    }
-    double ev[9], evec[81];
-    sym_eigen_jacobi(AtA, 9, ev, evec);
-    for (int k = 0; k < 9; ++k) H[k] = evec[k * 9];
+    double ws[lpslam_tv::kWorkspace];
+    lpslam_tv::homography_from_matches<0>(x1, x2, n, ws, 1, H);
 }
 
 void fundamental_from_matches(const double* x1, const double* x2, int n, double* F)
 {
-    double AtA[81] = {0};
-    for (int i = 0; i < n; ++i) {
-        const double u1 = x1[2 * i], v1 = x1[2 * i + 1], u2 = x2[2 * i], v2 = x2[2 * i + 1];
-        const double r[9] = {u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1};
-        for (int a = 0; a < 9; ++a) for (int b = 0; b < 9; ++b) AtA[a * 9 + b] += r[a] * r[b];
-    }
-    double ev[9], evec[81];
-    sym_eigen_jacobi(AtA, 9, ev, evec);
-    M3 Fp;
-    for (int k = 0; k < 9; ++k) Fp.m[k] = evec[k * 9];
-    // rank 2: F <- F (I - v3 v3^T), v3 the right singular vector of the smallest singular value
-    const M3 FtF = mul(transpose(Fp), Fp);
-    double e3[3], v3[9];
-    sym_eigen_jacobi(FtF.m, 3, e3, v3);
-    const double v[3] = {v3[0], v3[3], v3[6]};
-    for (int r = 0; r < 3; ++r) {
-        const double fv = Fp.m[r * 3] * v[0] + Fp.m[r * 3 + 1] * v[1] + Fp.m[r * 3 + 2] * v[2];
-        for (int c = 0; c < 3; ++c) F[r * 3 + c] = Fp.m[r * 3 + c] - fv * v[c];
-    }
+    double ws[lpslam_tv::kWorkspace];
+    lpslam_tv::fundamental_from_matches<0>(x1, x2, n, ws, 1, F);
 }
 
 bool triangulate_point(const double* P1, const double* P2, const double* x1, const double* x2, double* X)
@@ -318,8 +217,135 @@ bool triangulate_point(const double* P1, const double* P2, const double* x1, con
     return lpslam_tri::triangulate_linear(P1, P2, x1[0], x1[1], x2[0], x2[1], X);
 }
 
+namespace {
+
+// the matches of one pair of views, Hartley-normalised: what steps 1 and 2 work on
+struct Normalised { std::vector<double> n1, n2; M3 T1, T2inv, T2t; };
+
+void normalise_pair(const std::vector<double>& p1, const std::vector<double>& p2, Normalised& nm)
+{
+    M3 T2;
+    normalize_points(p1, nm.n1, nm.T1);
+    normalize_points(p2, nm.n2, T2);
+    nm.T2inv = inverse(T2); nm.T2t = transpose(T2);
+}
+
+// ---- step 1: the RANSAC loop.  The same 8-match samples serve both models (ORB-SLAM draws them once); sampling without replacement
+void ransac_loop(const Normalised& nm, const double* p1, const double* p2, size_t n, double sigma, int iterations, uint32_t seed, TwoViewModels& out)
+{
+    out = TwoViewModels();
+    out.inl_h.assign(n, 0); out.inl_f.assign(n, 0);
+    if (n < 8 || iterations < 1) return;
+    std::vector<int> avail(n);
+    std::vector<int32_t> table((size_t)lpslam_tv::kSample * (size_t)iterations);
+    lpslam_tv::sample_table((int)n, iterations, seed, table.data(), avail.data());
+    std::vector<uint8_t> inl;
+    double best_h = -1, best_f = -1;
+    for (int it = 0; it < iterations; ++it) {
+        double s1[16], s2[16], ws[lpslam_tv::kWorkspace];
+        for (int k = 0; k < 8; ++k) {
+            const size_t idx = (size_t)table[(size_t)8 * it + k];
+            s1[2 * k] = nm.n1[2 * idx]; s1[2 * k + 1] = nm.n1[2 * idx + 1]; s2[2 * k] = nm.n2[2 * idx]; s2[2 * k + 1] = nm.n2[2 * idx + 1];
+        }
+        M3 Hn, Fn;
+        lpslam_tv::homography_from_matches<8>(s1, s2, 8, ws, 1, Hn.m);
+        lpslam_tv::fundamental_from_matches<8>(s1, s2, 8, ws, 1, Fn.m);
+        const M3 H21 = mul(mul(nm.T2inv, Hn), nm.T1);
+        const M3 F21 = mul(mul(nm.T2t, Fn), nm.T1);
+        if (std::fabs(det(H21)) > 1e-300) {
+            const double sh = check_homography(H21, inverse(H21), p1, p2, n, sigma, inl);
+            if (sh > best_h) { best_h = sh; out.it_h = it; std::memcpy(out.H, H21.m, sizeof(out.H)); out.inl_h = inl; }
+        }
+        const double sf = check_fundamental(F21, p1, p2, n, sigma, inl);
+        if (sf > best_f) { best_f = sf; out.it_f = it; std::memcpy(out.F, F21.m, sizeof(out.F)); out.inl_f = inl; }
+    }
+    out.score_h = out.it_h >= 0 ? best_h : 0.0; out.score_f = out.it_f >= 0 ? best_f : 0.0;
+}
+
+// step 1 through the caller's function; false: it failed (nothing of `out` is to be used)
+bool ransac_step(TwoViewSteps& st, const double* p1, const double* p2, size_t n, double sigma, int iterations, uint32_t seed, TwoViewModels& out)
+{
+    const int32_t offsets[2] = {0, (int32_t)n};
+    int32_t best[2] = {-1, -1};
+    double score[2] = {0, 0}, model[18] = {0};
+    out = TwoViewModels();
+    out.inl_h.assign(n, 0); out.inl_f.assign(n, 0);
+    ++st.calls;
+    if (st.ransac(st.ctx, 1, offsets, p1, p2, sigma, iterations, seed, best, score, model, out.inl_h.data(), out.inl_f.data()) != 0) { ++st.failed; return false; }
+    out.it_h = best[0]; out.it_f = best[1]; out.score_h = score[0]; out.score_f = score[1];
+    std::memcpy(out.H, model, sizeof(out.H)); std::memcpy(out.F, model + 9, sizeof(out.F));
+    return true;
+}
+
+// ---- step 2: [UPSTREAM] find_via_ransac(..., recompute = true): the best model of each kind is estimated again from all its inliers
+// (normalised coordinates) and its inliers and score are taken from that estimate; then the model choice by the score ratio.
+// false: neither model has a score.  best_H / best_F / the flags of `w` are updated in place.
+bool refit_and_choose(const Normalised& nm, const double* p1, const double* p2, size_t n, double sigma, TwoViewModels& w, TwoViewResult& out, bool& use_h)
+{
+    double best_h = w.it_h >= 0 ? w.score_h : -1, best_f = w.it_f >= 0 ? w.score_f : -1;
+    M3 best_H, best_F;
+    std::memcpy(best_H.m, w.H, sizeof(w.H)); std::memcpy(best_F.m, w.F, sizeof(w.F));
+    std::vector<uint8_t> inl;
+    auto gather = [&](const std::vector<uint8_t>& mask, std::vector<double>& a, std::vector<double>& b) {
+        a.clear(); b.clear();
+        for (size_t i = 0; i < n; ++i) if (mask[i]) { a.push_back(nm.n1[2 * i]); a.push_back(nm.n1[2 * i + 1]); b.push_back(nm.n2[2 * i]); b.push_back(nm.n2[2 * i + 1]); }
+    };
+    std::vector<double> ga, gb;
+    if (best_h >= 0) {
+        gather(w.inl_h, ga, gb);
+        if (ga.size() >= 16) {
+            M3 Hn; homography_from_matches(ga.data(), gb.data(), (int)(ga.size() / 2), Hn.m);
+            const M3 H21 = mul(mul(nm.T2inv, Hn), nm.T1);
+            if (std::fabs(det(H21)) > 1e-300) { best_h = check_homography(H21, inverse(H21), p1, p2, n, sigma, inl); best_H = H21; w.inl_h = inl; }
+        }
+    }
+    if (best_f >= 0) {
+        gather(w.inl_f, ga, gb);
+        if (ga.size() >= 16) {
+            M3 Fn; fundamental_from_matches(ga.data(), gb.data(), (int)(ga.size() / 2), Fn.m);
+            const M3 F21 = mul(mul(nm.T2t, Fn), nm.T1);
+            best_f = check_fundamental(F21, p1, p2, n, sigma, inl); best_F = F21; w.inl_f = inl;
+        }
+    }
+    out.score_h = std::max(best_h, 0.0); out.score_f = std::max(best_f, 0.0);
+    std::memcpy(out.H, best_H.m, sizeof(out.H)); std::memcpy(out.F, best_F.m, sizeof(out.F));
+    std::memcpy(w.H, best_H.m, sizeof(w.H)); std::memcpy(w.F, best_F.m, sizeof(w.F));
+    if (out.score_h + out.score_f <= 0) return false;
+    use_h = out.score_h / (out.score_h + out.score_f) > 0.40;
+    return true;
+}
+
+}  // namespace
+
+void two_view_ransac(const double* p1, const double* p2, int n, double sigma, int iterations, uint32_t seed, TwoViewModels& out)
+{
+    const size_t m = (size_t)std::max(n, 0);
+    if (m < 8) { out = TwoViewModels(); out.inl_h.assign(m, 0); out.inl_f.assign(m, 0); return; }
+    const std::vector<double> a(p1, p1 + 2 * m), b(p2, p2 + 2 * m);
+    Normalised nm;
+    normalise_pair(a, b, nm);
+    ransac_loop(nm, p1, p2, m, sigma, iterations, seed, out);
+}
+
+void two_view_check_poses(int n_hyp, const double* R, const double* t, const double* K4, int n, const double* p1, const double* p2,
+                          const uint8_t* inlier, double th2, double* X, double* cosp, uint8_t* code)
+{
+    for (int h = 0; h < n_hyp; ++h) {
+        lpslam_tv::PoseSetup ps;
+        lpslam_tv::pose_setup(R + 9 * h, t + 3 * h, K4, ps);
+        for (int i = 0; i < n; ++i) {
+            const size_t o = (size_t)h * (size_t)n + (size_t)i;
+            double x[3] = {0, 0, 0}, c = 0;
+            const int k = inlier[i] ? lpslam_tv::pose_point(ps, R + 9 * h, t + 3 * h, K4, p1 + 2 * i, p2 + 2 * i, th2, x, &c) : lpslam_tv::kPoseRejected;
+            code[o] = (uint8_t)k;
+            cosp[o] = k ? c : 0.0;
+            for (int a = 0; a < 3; ++a) X[3 * o + a] = k ? x[a] : std::numeric_limits<double>::quiet_NaN();
+        }
+    }
+}
+
 bool two_view_initialize(const double* K, const float* kp_ref, const float* kp_cur, const int32_t* matches, int n_matches,
-                         const TwoViewParams& prm, TwoViewResult& out)
+                         const TwoViewParams& prm, TwoViewResult& out, TwoViewSteps* steps)
 {
     out = TwoViewResult();
     out.inlier.assign((size_t)std::max(n_matches, 0), 0);
@@ -332,88 +358,64 @@ bool two_view_initialize(const double* K, const float* kp_ref, const float* kp_c
         p1[2 * i] = kp_ref[2 * matches[2 * i]]; p1[2 * i + 1] = kp_ref[2 * matches[2 * i] + 1];
         p2[2 * i] = kp_cur[2 * matches[2 * i + 1]]; p2[2 * i + 1] = kp_cur[2 * matches[2 * i + 1] + 1];
     }
-    std::vector<double> n1, n2;
-    M3 T1, T2;
-    normalize_points(p1, n1, T1);
-    normalize_points(p2, n2, T2);
-    const M3 T2inv = inverse(T2), T2t = transpose(T2);
+    Normalised nm;
+    normalise_pair(p1, p2, nm);
 
-    // the same 8-match samples serve both models (ORB-SLAM draws them once); sampling without replacement
-    Rng rng{prm.seed ? prm.seed : 1u};
-    std::vector<uint8_t> inl, best_inl_h(n, 0), best_inl_f(n, 0);
-    double best_h = -1, best_f = -1;
-    M3 best_H{}, best_F{};
-    std::vector<int> avail(n);
-    for (int it = 0; it < prm.ransac_iters; ++it) {
-        for (size_t i = 0; i < n; ++i) avail[i] = (int)i;
-        double s1[16], s2[16];
-        size_t left = n;
-        for (int k = 0; k < 8; ++k) {
-            const size_t r = rng.next() % left;
-            const int idx = avail[r];
-            avail[r] = avail[left - 1]; --left;
-            s1[2 * k] = n1[2 * idx]; s1[2 * k + 1] = n1[2 * idx + 1]; s2[2 * k] = n2[2 * idx]; s2[2 * k + 1] = n2[2 * idx + 1];
-        }
-        M3 Hn, Fn;
-        homography_from_matches(s1, s2, 8, Hn.m);
-        fundamental_from_matches(s1, s2, 8, Fn.m);
-        const M3 H21 = mul(mul(T2inv, Hn), T1);
-        const M3 F21 = mul(mul(T2t, Fn), T1);
-        if (std::fabs(det(H21)) > 1e-300) {
-            const double sh = check_homography(H21, inverse(H21), p1, p2, prm.sigma, inl);
-            if (sh > best_h) { best_h = sh; best_H = H21; best_inl_h = inl; }
-        }
-        const double sf = check_fundamental(F21, p1, p2, prm.sigma, inl);
-        if (sf > best_f) { best_f = sf; best_F = F21; best_inl_f = inl; }
-    }
-    // [UPSTREAM] find_via_ransac(..., recompute = true): the best model of each kind is estimated again from all its inliers
-    // (normalised coordinates) and its inliers and score are taken from that estimate
-    auto gather = [&](const std::vector<uint8_t>& mask, std::vector<double>& a, std::vector<double>& b) {
-        a.clear(); b.clear();
-        for (size_t i = 0; i < n; ++i) if (mask[i]) { a.push_back(n1[2 * i]); a.push_back(n1[2 * i + 1]); b.push_back(n2[2 * i]); b.push_back(n2[2 * i + 1]); }
+    // (a caller with steps also gets the seconds each step took)
+    auto t_last = std::chrono::steady_clock::now();
+    auto lap = [&](double TwoViewSteps::*field) {
+        if (!steps) return;
+        const auto t = std::chrono::steady_clock::now();
+        steps->*field += std::chrono::duration<double>(t - t_last).count();
+        t_last = t;
     };
-    std::vector<double> ga, gb;
-    if (best_h >= 0) {
-        gather(best_inl_h, ga, gb);
-        if (ga.size() >= 16) {
-            M3 Hn; homography_from_matches(ga.data(), gb.data(), (int)(ga.size() / 2), Hn.m);
-            const M3 H21 = mul(mul(T2inv, Hn), T1);
-            if (std::fabs(det(H21)) > 1e-300) { best_h = check_homography(H21, inverse(H21), p1, p2, prm.sigma, inl); best_H = H21; best_inl_h = inl; }
-        }
-    }
-    if (best_f >= 0) {
-        gather(best_inl_f, ga, gb);
-        if (ga.size() >= 16) {
-            M3 Fn; fundamental_from_matches(ga.data(), gb.data(), (int)(ga.size() / 2), Fn.m);
-            const M3 F21 = mul(mul(T2t, Fn), T1);
-            best_f = check_fundamental(F21, p1, p2, prm.sigma, inl); best_F = F21; best_inl_f = inl;
-        }
-    }
-    out.score_h = std::max(best_h, 0.0); out.score_f = std::max(best_f, 0.0);
-    std::memcpy(out.H, best_H.m, sizeof(out.H)); std::memcpy(out.F, best_F.m, sizeof(out.F));
-    if (out.score_h + out.score_f <= 0) return false;
-    const bool use_h = out.score_h / (out.score_h + out.score_f) > 0.40;
+    // 1. the RANSAC loop, 2. refit and model choice
+    TwoViewModels w;
+    if (!(steps && steps->ransac && ransac_step(*steps, p1.data(), p2.data(), n, prm.sigma, prm.ransac_iters, prm.seed, w)))
+        ransac_loop(nm, p1.data(), p2.data(), n, prm.sigma, prm.ransac_iters, prm.seed, w);
+    lap(&TwoViewSteps::t_ransac);
+    bool use_h = false;
+    const bool chosen = refit_and_choose(nm, p1.data(), p2.data(), n, prm.sigma, w, out, use_h);
+    lap(&TwoViewSteps::t_refit);
+    if (!chosen) return false;
     out.model = use_h ? 0 : 1;
-    const std::vector<uint8_t>& model_inl = use_h ? best_inl_h : best_inl_f;
+    const std::vector<uint8_t>& model_inl = use_h ? w.inl_h : w.inl_f;
     out.inlier = model_inl;
     out.n_inliers = (int)std::count(model_inl.begin(), model_inl.end(), (uint8_t)1);
 
+    // 3. the decomposition
+    M3 best_H, best_F;
+    std::memcpy(best_H.m, w.H, sizeof(w.H)); std::memcpy(best_F.m, w.F, sizeof(w.F));
     std::vector<Hypothesis> hyps;
     if (use_h) { if (!hypotheses_from_homography(best_H, K, hyps)) return false; }
     else hypotheses_from_fundamental(best_F, K, hyps);
 
+    lap(&TwoViewSteps::t_decompose);
+    // 4. the pose check of every hypothesis, then the acceptance rules
     const double th2 = prm.reproj_err_thr * prm.sigma * prm.sigma;       // ORB-SLAM: 4 sigma^2
+    const size_t np = hyps.size();
+    std::vector<double> Rs(9 * np), ts(3 * np), X(3 * np * n), cosp(np * n);
+    std::vector<uint8_t> code(np * n);
+    for (size_t i = 0; i < np; ++i) { std::memcpy(&Rs[9 * i], hyps[i].R.m, 9 * sizeof(double)); std::memcpy(&ts[3 * i], hyps[i].t, 3 * sizeof(double)); }
+    bool checked = false;
+    if (steps && steps->check_poses && np > 0) {
+        ++steps->calls;
+        checked = steps->check_poses(steps->ctx, (int32_t)np, Rs.data(), ts.data(), K, (int32_t)n, p1.data(), p2.data(), model_inl.data(), th2, X.data(), cosp.data(), code.data()) == 0;
+        if (!checked) ++steps->failed;
+    }
+    if (!checked) two_view_check_poses((int)np, Rs.data(), ts.data(), K, (int)n, p1.data(), p2.data(), model_inl.data(), th2, X.data(), cosp.data(), code.data());
     int best_good = 0, second_good = 0, best_i = -1;
     double best_parallax = 0;
     std::vector<double> pts, best_pts;
     std::vector<uint8_t> good, best_goodmask;
-    for (size_t i = 0; i < hyps.size(); ++i) {
+    for (size_t i = 0; i < np; ++i) {
         double parallax = 0;
-        const int ng = check_pose(hyps[i], K, p1, p2, model_inl, th2, pts, good, parallax);
+        const int ng = pose_tally(&X[3 * i * n], &cosp[i * n], &code[i * n], n, pts, good, parallax);
         if (ng > best_good) { second_good = best_good; best_good = ng; best_i = (int)i; best_parallax = parallax; best_pts = pts; best_goodmask = good; }
         else if (ng > second_good) second_good = ng;
     }
     out.n_valid = best_good; out.parallax_deg = best_parallax;
+    lap(&TwoViewSteps::t_pose);
     // one clear winner with enough plausible points and enough parallax ([UPSTREAM] initialize::base::find_most_plausible_pose)
     const int min_valid = std::max(prm.min_triangulated, (int)(0.9 * out.n_inliers));
     if (best_i < 0 || best_good < min_valid) return false;

@@ -36,9 +36,40 @@ struct TwoViewResult {
     std::vector<double> points;          // per match: X Y Z in the reference camera frame (valid where triangulated)
 };
 
+// The function is four steps: 1 the RANSAC loop over 8-match samples, 2 the refit of both winners and the
+// model choice, 3 the decomposition into motion hypotheses, 4 the pose check of every hypothesis and the acceptance rules.  Steps 1
+// and 4 exist on the device too (lpslam_hip_two_view_ransac_batch, lpslam_hip_two_view_check_poses: the same arithmetic,
+// csrc/two_view_math.h, the same bits); a caller hands them in through TwoViewSteps.
+// The winners of step 1 for one set of matches: per model the winning iteration (-1: none; then score 0, a zero matrix, flags cleared),
+// its score, the matrix in pixel coordinates (reference -> current) and the per-match inlier flags.
+struct TwoViewModels {
+    int it_h = -1, it_f = -1;
+    double score_h = 0, score_f = 0;
+    double H[9] = {0}, F[9] = {0};
+    std::vector<uint8_t> inl_h, inl_f;
+};
+// Steps 1 and 4 as a caller provides them (arguments of the two device entry points without the context, see include/lpslam_hip.h;
+// 0 = done).  A step that is null or fails runs on the host; `calls` and `failed` count what happened.
+struct TwoViewSteps {
+    void* ctx = nullptr;
+    int (*ransac)(void* ctx, int32_t n_sets, const int32_t* offsets, const double* p1, const double* p2, double sigma, int32_t iterations, uint32_t seed,
+                  int32_t* best_iteration, double* score, double* model, uint8_t* inlier_h, uint8_t* inlier_f) = nullptr;
+    int (*check_poses)(void* ctx, int32_t n_hyp, const double* R, const double* t, const double* K4, int32_t n, const double* p1, const double* p2,
+                       const uint8_t* inlier, double th2, double* X, double* cosp, uint8_t* code) = nullptr;
+    int calls = 0, failed = 0;
+    double t_ransac = 0, t_refit = 0, t_decompose = 0, t_pose = 0;      // seconds of steps 1 .. 4 (the normalisation counts to none)
+};
+
 // K = (fx, fy, cx, cy), shared by both views; keypoints (x, y) in pixels; matches = (index in ref, index in cur) pairs
 bool two_view_initialize(const double* K, const float* kp_ref, const float* kp_cur, const int32_t* matches, int n_matches,
-                         const TwoViewParams& prm, TwoViewResult& out);
+                         const TwoViewParams& prm, TwoViewResult& out, TwoViewSteps* steps = nullptr);
+
+// step 1 on the host: p1, p2 are n x 2 pixel coordinates (reference, current)
+void two_view_ransac(const double* p1, const double* p2, int n, double sigma, int iterations, uint32_t seed, TwoViewModels& out);
+// step 4's per-match part on the host, for n_hyp hypotheses (R: n_hyp x 9, t: n_hyp x 3): X (n_hyp x n x 3; NaN where the code is 0),
+// cosp (n_hyp x n; 0 where the code is 0), code (n_hyp x n: 0 rejected or no inlier, 1 counted, 2 counted and good)
+void two_view_check_poses(int n_hyp, const double* R, const double* t, const double* K4, int n, const double* p1, const double* p2,
+                          const uint8_t* inlier, double th2, double* X, double* cosp, uint8_t* code);
 
 // building blocks (exposed for the tests)
 void sym_eigen_jacobi(const double* A, int n, double* eigval, double* eigvec);        // A symmetric n x n; eigvec columns, ascending eigval

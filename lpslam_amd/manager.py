@@ -155,7 +155,7 @@ class Manager:
 
     def add_tracker(self, name, cfg=""):
         """cfg: the tracker's JSON object as text; every key goes to the plugin as written (INTEGRATION.md lists them, e.g.
-        "triangulateNeighbours": 10, "relocaliseOnDevice": true)"""
+        "triangulateNeighbours": 10, "relocaliseOnDevice": true, "initialiseOnDevice": true)"""
         return bool(self.lib.lpslam_manager_add_tracker(self.h, name.encode(), cfg.encode()))
 
     def add_processor(self, name, cfg=""):
