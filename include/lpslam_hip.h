@@ -466,14 +466,23 @@ int lpslam_hip_ba_counters(lpslam_hip_ctx* ctx, int64_t* out, int32_t n);
 /* How many launches of the one-workgroup factorisation (k_chol_wg: batches of LPSLAM_HIP_CW_MIN_BATCH = 40 problems and more) this
  * context has enqueued.  Test hook: proves which of the two factorisations a batch went through.  No reference counterpart. */
 int64_t lpslam_hip_ba_wg_factorisations(lpslam_hip_ctx* ctx);
-/* Test hook like lpslam_hip_debug_occupy_unreserved (no reference counterpart, no product path calls it): the dense factor-and-solve
- * on the caller's systems.  `problems`: n built problems with the dense solver selected, on one device; their observations do not
- * matter, they fix dim_i = 6 x free keyframes.  A[i]: full symmetric dim_i x dim_i matrix, row major; it stands for S + lambda I and
- * nothing is added to it.  b[i]: dim_i values.  Each reduced buffer is written as the product leaves it in front of a solve and the
- * batch takes the launches an optimize of these n problems takes (alone: the panel-pair chain; 40 problems and more: k_chol_wg for the
- * systems that fit it, the chain for the others).  x[i] receives dim_i values, pivot_flag[i] (may be NULL) 1 where the factorisation
- * met a pivot <= 0; x[i] is the zero step then, on both kernels (what the replaced pivot left in the factor need not be finite, and
- * none of it reaches x_p).  Finite inputs only.
+/* Test hook like lpslam_hip_debug_occupy_unreserved (no reference counterpart, no product path calls it): the factor-and-solve of a
+ * window on the caller's systems.  `problems`: n built problems on one device; their observations do not matter, they fix
+ * dim_i = 6 x free keyframes and the solver.  A[i]: dim_i x dim_i matrix, row major; it stands for S + lambda I and nothing is added to
+ * it.  b[i]: dim_i values.  Each reduced buffer is written as the product leaves it in front of a solve and the batch takes the
+ * launches an optimize of these n problems takes.
+ *   Problems with the dense solver: A[i] full symmetric; alone: the panel-pair chain; 40 problems and more: k_chol_wg for the systems
+ *   that fit it, the chain for the others.
+ *   Problems on the band solver (lpslam_hip_ba_get_solver: BAND, block half-bandwidth hbw): k_chol_band, launched as a solve launches
+ *   it, on what the fused reduction leaves in front of it.  A[i] must be zero below the diagonal further than 6 hbw + 5 from it
+ *   (LPSLAM_HIP_ERR_INVALID otherwise: the kernel reads 79 columns left of the diagonal whatever hbw says).  Only the lower triangle is
+ *   read; the strict upper triangle is copied as given and may hold anything.  The two hand-over words of the twisted factorisation
+ *   (systems of 12 strips of 16 and more) are cleared in front of the launch and must be zero again behind it:
+ *   LPSLAM_HIP_ERR_DEVICE otherwise.
+ *   A batch may mix the two kinds: both launch families run and each kernel skips the other's problems.
+ * x[i] receives dim_i values, pivot_flag[i] (may be NULL) 1 where the factorisation met a pivot <= 0; x[i] is the zero step then, on
+ * every kernel (what the replaced pivot left in the factor need not be finite, and none of it reaches x_p).  Finite inputs only (the
+ * band kernel's unread upper triangle excepted).
  * The call overwrites the problems' reduced systems and control blocks: lpslam_hip_ba_reset (or reset_batch) each of them before it
  * optimises again. */
 int lpslam_hip_ba_debug_solve(lpslam_hip_ba* const* problems, int32_t n, const double* const* A, const double* const* b,

@@ -425,7 +425,8 @@ __global__ __launch_bounds__(BC_THREADS) void k_chol_band(const BaView* __restri
             }
             const double sr = tid < 64 ? S[(size_t)dim * n + (dimA - 1 - tid)] : 0.0;
             // (bounded: should the helper never report -- it always does -- the factorisation is flagged as failed instead of the grid hanging)
-            if (tid == 0) { int spins = 0; while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2); if (spins >= (1 << 22)) { s_fail = 1; scal[5] = 1.0; __hip_atomic_fetch_add(ba_sync_words(vw), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } }
+            // (the flag's value carries the helper's pivot flag, 2 = failed: it arrives with the hand-over itself, whatever the placement)
+            if (tid == 0) { int spins = 0, got; while ((got = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2); if (got == 2) s_fail = 1; if (spins >= (1 << 22)) { s_fail = 1; scal[5] = 1.0; __hip_atomic_fetch_add(ba_sync_words(vw), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } }
             __syncthreads();
 #pragma unroll
             for (int q = 0; q < 8; ++q) { const int idx = tid + BC_THREADS * q; dv[q] = (idx & 63) <= (idx >> 6) ? ld_sc1(Dg + idx) : 0.0; }
@@ -516,7 +517,7 @@ __global__ __launch_bounds__(BC_THREADS) void k_chol_band(const BaView* __restri
         if (tid < 64) st_sc1(Dg + 64 * 64 + tid, rhsv[u0 + tid]);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wavefront's write-through stores (M blocks so far, the block above) have left
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) __hip_atomic_store(flag, s_fail ? 2 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (wave >= 4) bc_back_operands(ns - 1, wave - 4, 4, lane, LxL, Tinv, Mg);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -531,12 +532,14 @@ __global__ __launch_bounds__(BC_THREADS) void k_chol_band(const BaView* __restri
     //      memory round trip sits on the chain.  Lane = (row i of the strip, quarter q of its 64 columns): sixteen products in four
     //      independent sums, the quarters added by a quad butterfly -- a fixed tree.  Then the helper's strips the same way, in its
     //      order (flipped coordinates u = n - 1 - p), seeded with the 64 unknowns in front of them.
+    //      A flagged factorisation (s_fail: this chain's pivots, the helper's, a hand-over that timed out) went on with pivots replaced by
+    //      1.0: what the substitution makes of it is not a step.  x_p is then the zero step, as k_chol_xsolve and k_chol_wg write it.
     {
         const int bi = lane >> 2, bq = lane & 3;
         GPTR(double) MgB = vw.Minv + (size_t)BC_MAXS * 1024;
         double* const xB = rhsv;                             // the helper's unknowns, flipped order (rhsv is free after the forward pass)
         if (sB) {
-            if (tid == 0) { int spins = 0; while (__hip_atomic_load(flag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2); if (spins >= (1 << 22)) { scal[5] = 1.0; __hip_atomic_fetch_add(ba_sync_words(vw), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } }
+            if (tid == 0) { int spins = 0; while (__hip_atomic_load(flag + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 && ++spins < (1 << 22)) __builtin_amdgcn_s_sleep(2); if (spins >= (1 << 22)) { s_fail = 1; scal[5] = 1.0; __hip_atomic_fetch_add(ba_sync_words(vw), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } }
             __syncthreads();
             if (tid == 0) __hip_atomic_store(flag + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -604,11 +607,11 @@ __global__ __launch_bounds__(BC_THREADS) void k_chol_band(const BaView* __restri
                 }
                 BC_BARRIER();
             }
-            for (int u = tid; u < 16 * sB && u < dim; u += BC_THREADS) xp[dim - 1 - u] = xB[u];
+            for (int u = tid; u < 16 * sB && u < dim; u += BC_THREADS) xp[dim - 1 - u] = s_fail ? 0.0 : xB[u];
         }
     }
     BC_STAMPX(3);
-    for (int i = tid; i < dimA; i += BC_THREADS) xp[i] = xv[i];
+    for (int i = tid; i < dimA; i += BC_THREADS) xp[i] = s_fail ? 0.0 : xv[i];
 }
 
 // dynamic LDS beyond 64 KB: the attribute belongs to the (function, device) pair.  A refusal is reported HERE, with its reason -- left

@@ -1097,11 +1097,16 @@ int lpslam_hip_ba_reset_batch(lpslam_hip_ba* const* ps, int32_t n)
     return LPSLAM_HIP_OK;
 }
 
-// Test entry into the dense factor-and-solve: the caller's systems A x = b through the launches a solve of these problems takes
-// (tests/test_ba_solve_gpu.py; no product path calls it).  Every problem's reduced buffer is written as the product leaves it in front
-// of a non-fused solve -- A (it stands for S + lambda I, nothing is added) in the dim_pad layout, b in rhs and in row `dim`, 1e200 on
-// that row's diagonal, identity padding, pivot flag cleared -- the control blocks are armed so that no kernel idles, and
-// lp_enqueue_factor_solve gets what enqueue_solve computes for the batch (wg, any_small / any_large, nb, dim, spread).
+// Test entry into the factor-and-solve: the caller's systems A x = b through the launches a solve of these problems takes
+// (tests/test_ba_solve_gpu.py, tests/test_ba_band_solve_gpu.py; no product path calls it).  Every problem's reduced buffer is written as
+// the product leaves it in front of its solve -- A (it stands for S + lambda I, nothing is added) in the dim_pad layout, b in rhs and in
+// row `dim`, 1e200 on that row's diagonal, identity padding, pivot flag cleared -- the control blocks are armed so that no kernel idles.
+// Dense problems: lp_enqueue_factor_solve gets what enqueue_solve computes for the batch (wg, any_small / any_large, nb, dim, spread).
+// Band problems (band_hbw >= 0): what the fused reduction leaves in front of k_chol_band, the two hand-over words of the twisted form
+// cleared, then k_chol_band as enqueue_solve launches it.  A must be zero below the diagonal further than 6 band_hbw + 5 from it (the
+// product zeroes that region in set_solver and the kernel reads 79 columns left of the diagonal whatever band_hbw says); the strict
+// upper triangle is copied as given and never read.  The hand-over words must be back at zero behind the solve: LPSLAM_HIP_ERR_DEVICE
+// otherwise.  A batch may mix both kinds: both launch families run, each kernel skips the other's views.
 // It overwrites the reduced system and the control block: lpslam_hip_ba_reset (or reset_batch) the problems before they optimise again.
 int lpslam_hip_ba_debug_solve(lpslam_hip_ba* const* ps, int32_t n, const double* const* A, const double* const* rhs, double* const* x, int32_t* pivot_flag)
 {
@@ -1109,8 +1114,13 @@ int lpslam_hip_ba_debug_solve(lpslam_hip_ba* const* ps, int32_t n, const double*
     if (!A || !rhs || !x) { set_error("debug_solve: null matrix / right-hand side / solution array"); return LPSLAM_HIP_ERR_INVALID; }
     for (int i = 0; i < n; ++i) {
         if (!A[i] || !rhs[i] || !x[i]) { set_error("debug_solve: null matrix / right-hand side / solution (entry %d)", i); return LPSLAM_HIP_ERR_INVALID; }
-        if (ps[i]->h_view.band_hbw >= 0) { set_error("debug_solve: entry %d takes the band solver (lpslam_hip_ba_set_solver DENSE first)", i); return LPSLAM_HIP_ERR_INVALID; }
         if (ps[i]->dim < 1) { set_error("debug_solve: entry %d has no free keyframe", i); return LPSLAM_HIP_ERR_INVALID; }
+        if (ps[i]->h_view.band_hbw >= 0) {
+            const long dim = ps[i]->dim, w = 6L * ps[i]->h_view.band_hbw + 5;
+            for (long r = w + 1; r < dim; ++r)
+                for (long c = 0; c < r - w; ++c)
+                    if (!(A[i][r * dim + c] == 0.0)) { set_error("debug_solve: entry %d is a band problem of scalar half-bandwidth %ld, A(%ld, %ld) is not zero", i, w, r, c); return LPSLAM_HIP_ERR_INVALID; }
+        }
     }
     LP_HIP(hipSetDevice(ps[0]->ctx->cfg.device));
     BatchViews bv;
@@ -1137,18 +1147,29 @@ int lpslam_hip_ba_debug_solve(lpslam_hip_ba* const* ps, int32_t n, const double*
         for (size_t r = dim + 1; r < np; ++r) h[r * np + r] = 1.0;
         LP_HIP(hipMemcpyAsync(b->d_red, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, L.s));
         LP_HIP(hipMemsetAsync(b->d_scal + 5, 0, sizeof(double), L.s));
+        if (b->h_view.band_hbw >= 0) LP_HIP(hipMemsetAsync((void*)b->h_view.blk_ticket, 0, 2 * sizeof(int), L.s));
     }
     hipLaunchKernelGGL(k_ba_arm, dim3(1, n), dim3(64), 0, L.s, L.d_views, 1);
-    const bool wg = L.count >= cw_min_batch();
-    if (wg && L.any_small && L.ctx) L.ctx->ba_wg_launches.fetch_add(1);
-    lp_enqueue_factor_solve(L.s, L.d_views, L.count, L.nb, L.dim, wg, L.any_small, L.any_large, L.spread);
+    if (L.any_band) {
+        if (bd_set_attributes() != hipSuccess) return LPSLAM_HIP_ERR_DEVICE;
+        hipLaunchKernelGGL(k_chol_band, dim3(2, L.count), dim3(BC_THREADS), BC_LDS_BYTES, L.s, L.d_views);
+    }
+    if (L.dim > 0) {
+        const bool wg = L.count >= cw_min_batch();
+        if (wg && L.any_small && L.ctx) L.ctx->ba_wg_launches.fetch_add(1);
+        lp_enqueue_factor_solve(L.s, L.d_views, L.count, L.nb, L.dim, wg, L.any_small, L.any_large, L.spread);
+    }
     LP_HIP(hipGetLastError());
+    std::vector<int> handover(2 * (size_t)n, 0);
     for (int i = 0; i < n; ++i) {
         LP_HIP(hipMemcpyAsync(x[i], (const double*)ps[i]->h_view.xp, (size_t)ps[i]->dim * sizeof(double), hipMemcpyDeviceToHost, L.s));
         LP_HIP(hipMemcpyAsync(&flags[i], ps[i]->d_scal + 5, sizeof(double), hipMemcpyDeviceToHost, L.s));
+        if (ps[i]->h_view.band_hbw >= 0) LP_HIP(hipMemcpyAsync(&handover[2 * (size_t)i], (const void*)ps[i]->h_view.blk_ticket, 2 * sizeof(int), hipMemcpyDeviceToHost, L.s));
     }
     LP_HIP(hipStreamSynchronize(L.s));          // the staging blocks and the view array are released on return
     for (int i = 0; i < n; ++i) { release_stage(ps[i]); if (pivot_flag) pivot_flag[i] = flags[i] != 0.0 ? 1 : 0; }
+    for (int i = 0; i < n; ++i)
+        if (handover[2 * (size_t)i] || handover[2 * (size_t)i + 1]) { set_error("debug_solve: entry %d: k_chol_band left its hand-over words at %d, %d", i, handover[2 * (size_t)i], handover[2 * (size_t)i + 1]); return LPSLAM_HIP_ERR_DEVICE; }
     return LPSLAM_HIP_OK;
 }
 

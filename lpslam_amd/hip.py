@@ -1198,15 +1198,19 @@ def ba_reset_batch(problems):
 
 
 def ba_debug_solve(problems, As, bs):
-    """lpslam_hip_ba_debug_solve (test hook): the dense factor-and-solve of the caller's systems As[i] x = bs[i] through the launches a
-    solve of these problems takes; As[i] is the full symmetric matrix of 6 x (free keyframes of problems[i]) rows.  Returns
-    ([x_i], pivot flags).  The problems need a reset() before they optimise again."""
+    """lpslam_hip_ba_debug_solve (test hook): the factor-and-solve of the caller's systems As[i] x = bs[i] through the launches a solve
+    of these problems takes; As[i] is the matrix of 6 x (free keyframes of problems[i]) rows.  A problem with the dense solver takes a
+    full symmetric matrix (panel-pair chain or k_chol_wg); a problem on the band solver, ("band", hbw), takes one that is zero below the
+    diagonal further than 6 hbw + 5 from it, through k_chol_band, which reads the lower triangle only (the strict upper triangle may
+    hold anything, NaN included).  A batch may mix the two.  Returns ([x_i], pivot flags); x_i of a flagged solve is the zero step.
+    The problems need a reset() before they optimise again."""
     n = len(problems)
     As = [np.ascontiguousarray(a, np.float64) for a in As]; bs = [np.ascontiguousarray(b, np.float64) for b in bs]
     assert len(As) == n and len(bs) == n
-    for a, b in zip(As, bs):
+    for p, a, b in zip(problems, As, bs):
         assert a.ndim == 2 and a.shape[0] == a.shape[1] and b.shape == (a.shape[0],)
-        assert np.isfinite(a).all() and np.isfinite(b).all(), "finite inputs only"
+        read = np.tril(a) if p.solver()[0] == "band" else a
+        assert np.isfinite(read).all() and np.isfinite(b).all(), "finite inputs only"
     xs = [np.zeros(len(b)) for b in bs]
     flags = np.zeros(n, np.int32)
     hs = (C.c_void_p * n)(*[p.h for p in problems])

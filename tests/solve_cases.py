@@ -250,3 +250,185 @@ def synthetic_cases(n):
     if n in WIDE_DIMS:
         out += [ladder(n, 6), ladder(n, 12), graded(n, +1), graded(n, -1)]
     return out
+
+
+# ---- band systems (k_chol_band) ------------------------------------------------------------------------------------------------
+# A is symmetric with scalar half-bandwidth w = 6 hbw + 5 (hbw: the block half-bandwidth of the window) at most; the kernel takes it in
+# strips of 16 columns through a ring of 96 rows, from 12 strips on from both ends (a helper workgroup eliminates the last sB strips
+# bottom-up and hands a 64 x 64 block over in front of strip sM of the main chain), and substitutes backwards in runs of three strips.
+#   known-band    A = L L^T, integer lower-banded L: diagonal 24, the band's edge (i, i - w) +-1 in every row, two more +-1 per row inside
+#                 the band, BAND_FULL_COLS full to the band's edge.  Integer x, b = A x in int64: exact.
+#   ladder-band k A = B + 10^-k I, B = G G^T / ||G G^T||_2 with a lower-banded normal G whose every third column is zero (B is singular,
+#                 kappa_2(A) = 1 + 10^k); graded: D A D on k = 2.
+#   notpd-band    A = L D L^T with the integer L, D = I except D_pp = -1: the first failing pivot of a top-down elimination is exactly p.
+#                 Flipped (A[::-1, ::-1]) it fails at q counted from the bottom: the helper's strips.  Partner: D = I.
+#   zero pivot    row and column p of a ladder-band k = 2 matrix are zero.
+BAND_FREE = (1, 2, 3, 5, 8, 9, 11, 14, 16, 17, 19, 22, 27, 29, 30, 32, 33, 37, 38, 43, 46, 49, 50)
+BAND_DIMS = tuple(6 * f for f in BAND_FREE)
+BAND_MAX_W = 59                      # 6 BD_MAXHBW + 5
+BAND_TWIST_MIN = 12                  # strips from which on the factorisation runs from both ends
+BAND_WIDE_DIMS = (18, 54, 96, 132, 174, 180, 300)      # ladder-band k = 6, 12 and graded
+BAND_NARROW = tuple((w, n) for w in (5, 23) for n in (54, 102, 180, 300))       # block half-bandwidth 0 and 3
+BAND_FULL_COLS = (0, 15, 16, 31, 32, 63, 64, 79, 80, 95, 96)                    # and dim - 17, dim - 16
+# (dim, first failing pivot p of the top-down elimination, where that is)
+BAND_NOTPD_TOP = ((54, 5, "first strip"), (54, 20, "second strip"), (54, 50, "last strip, padding beside it"),
+                  (102, 97, "behind the ring's first wrap"), (174, 170, "last strip of the largest untwisted system"),
+                  (180, 40, "main chain, before the hand-over"), (180, 70, "the hand-over strip"), (180, 125, "main chain, after the hand-over"),
+                  (300, 100, "main chain"))
+# (dim, q: first failing pivot of the bottom-up elimination, counted from the end)
+BAND_NOTPD_BOTTOM = ((180, 3, "helper's first strip"), (180, 47, "helper's last strip"), (300, 60, "helper"), (300, 111, "helper's last strip"))
+BAND_ZERO_PIVOT = ((54, 20), (180, 70), (300, 290))
+
+
+def band_width(n):
+    return min(BAND_MAX_W, n - 1)
+
+
+def band_layout(n):
+    """(strips, sB, dimA, sM) as k_chol_band computes them"""
+    strips = (n + 15) // 16
+    sB = (strips - 5) // 2 if strips >= BAND_TWIST_MIN else 0
+    dimA = n - 16 * sB
+    return strips, sB, dimA, ((dimA - 64) // 16 if sB else -1)
+
+
+def half_bandwidth(A):
+    """the largest |i - j| with A_ij != 0"""
+    i, j = np.nonzero(A)
+    return int(np.abs(i - j).max()) if len(i) else 0
+
+
+def band_mask(n, w):
+    i = np.arange(n)
+    return np.abs(i[:, None] - i[None, :]) <= w
+
+
+def band_cholesky_solve(A, b, w=None):
+    """float64 right-looking Cholesky and two column-oriented substitutions that touch nothing beyond row j + w of column j (w=None: no
+    limit, the same operations on the whole matrix).  Every operation is elementwise -- no sum whose grouping could depend on a length --
+    so the two forms agree to the byte exactly when nothing outside the band matters.  Returns (L, x)."""
+    n = len(b)
+    w = n if w is None else w
+    L = np.tril(np.array(A, np.float64)); y = np.array(b, np.float64)
+    for j in range(n):
+        hi = min(n, j + w + 1)
+        L[j, j] = np.sqrt(L[j, j])
+        L[j + 1:hi, j] /= L[j, j]
+        L[j + 1:hi, j + 1:hi] -= np.tril(np.outer(L[j + 1:hi, j], L[j + 1:hi, j]))
+        y[j] /= L[j, j]
+        y[j + 1:hi] -= L[j + 1:hi, j] * y[j]
+    x = y
+    for j in range(n - 1, -1, -1):
+        lo = max(0, j - w)
+        x[j] /= L[j, j]
+        x[lo:j] -= L[j, lo:j] * x[j]
+    return L, x
+
+
+def known_band_factor(n, w):
+    rng = _rng(11, n, w)
+    L = np.zeros((n, n), np.int64)
+    for i in range(1, n):
+        lo = max(0, i - w)
+        for j in rng.integers(lo, i, 2):
+            L[i, j] = rng.choice((-1, 1))
+        if i - w >= 0:
+            L[i, i - w] = rng.choice((-1, 1))
+    for c in BAND_FULL_COLS + (n - 17, n - 16):
+        if 0 <= c < n - 1:
+            hi = min(n, c + w + 1)
+            L[c + 1:hi, c] = rng.choice((-1, 1), hi - c - 1)
+    L[np.arange(n), np.arange(n)] = KNOWN_DIAG
+    return L
+
+
+def _int_case(Ai, xi, family, tag=""):
+    bi = Ai @ xi
+    assert np.abs(Ai).max() < 2 ** 30 and np.abs(bi).max() < 2 ** 53      # exact in int64 and in float64
+    c = case_from(Ai.astype(np.float64), bi.astype(np.float64), family, x=xi.astype(LD), tag=tag)
+    c["A_int"], c["x_int"], c["b_int"] = Ai, xi, bi
+    return c
+
+
+def _int_x(n, *key):
+    xi = _rng(*key).integers(-9, 10, n)
+    xi[xi == 0] = 7
+    return xi
+
+
+@functools.lru_cache(maxsize=None)
+def known_band(n, w=None):
+    w = band_width(n) if w is None else w
+    L = known_band_factor(n, w)
+    c = _int_case(L @ L.T, _int_x(n, 12, n, w), "known-band")
+    c["L_int"], c["w"] = L, w
+    return c
+
+
+def _banded_normal(n, w, *key):
+    G = np.tril(_rng(*key).normal(size=(n, n))) * band_mask(n, w)
+    G[:, 2::3] = 0.0
+    return G
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_band(n, k, w=None):
+    w = band_width(n) if w is None else w
+    G = _banded_normal(n, w, 13, n, w)
+    B = G @ G.T
+    B = 0.5 * (B + B.T)
+    A = B / np.linalg.norm(B, 2)
+    A[np.arange(n), np.arange(n)] += 10.0 ** -k
+    c = _with_rhs(A, "ladder-band%d" % k, "", 14, n, k, w)
+    c["w"] = w
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def graded_band(n, sign):
+    A = ladder_band(n, 2)["A"]
+    d = np.where((np.arange(n) // 3) % 2 == 1, 10.0 ** (3 * sign), 1.0)
+    c = _with_rhs(A * np.outer(d, d), "graded-band%+d" % (3 * sign), "", 15, n, sign + 1)
+    c["w"] = band_width(n)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def notpd_band(n, p, bottom=False):
+    """(positive definite partner, case that fails at pivot p): top-down, or with bottom=True both flipped, so that the bottom-up
+    elimination fails at p counted from the end"""
+    w = band_width(n)
+    L = known_band_factor(n, w)
+    D = np.ones(n, np.int64); D[p] = -1
+    good_i, bad_i = L @ L.T, (L * D) @ L.T
+    if bottom:
+        good_i, bad_i = good_i[::-1, ::-1].copy(), bad_i[::-1, ::-1].copy()
+    tag = ("q=%d" if bottom else "p=%d") % p
+    xi = _int_x(n, 16, n, p)
+    good = _int_case(good_i, xi, "notpd-band-base", tag)
+    bad = _int_case(bad_i, xi, "notpd-band", tag)
+    for c in (good, bad):
+        c["w"], c["p"], c["bottom"] = w, p, bottom
+    return good, bad
+
+
+@functools.lru_cache(maxsize=None)
+def zero_pivot_band(n, p):
+    base = ladder_band(n, 2)
+    A = base["A"].copy()
+    A[p, :] = 0.0; A[:, p] = 0.0
+    c = case_from(A, base["b"], "zero-pivot-band", tag="p=%d" % p)
+    c["p"], c["w"] = p, band_width(n)
+    return c
+
+
+def band_cases(n):
+    """the positive definite synthetic band cases at dimension n and the full width min(59, n - 1)"""
+    out = [known_band(n), ladder_band(n, 2), ladder_band(n, 10)]
+    if n in BAND_WIDE_DIMS:
+        out += [ladder_band(n, 6), ladder_band(n, 12), graded_band(n, +1), graded_band(n, -1)]
+    return out
+
+
+def narrow_band_cases(n, w):
+    return [known_band(n, w), ladder_band(n, 2, w), ladder_band(n, 10, w)]

@@ -69,6 +69,111 @@ class Holders:
         return xs[:keep], flags[:keep], self.ctx.ba_wg_factorisations() - before
 
 
+# ---- band windows -------------------------------------------------------------------------------------------------------------
+BAND = "k_chol_band"
+
+
+def free_span(pr):
+    """the widest span of free slots a landmark covers: the block half-bandwidth lpslam_hip_ba_create finds"""
+    slot = np.cumsum(pr["fixed"] == 0) - 1
+    sl = np.where(pr["fixed"][pr["obs_pose"]] == 0, slot[pr["obs_pose"]], -1)
+    free = sl >= 0
+    lo = np.full(len(pr["points"]), 1 << 30); hi = np.full(len(pr["points"]), -1)
+    np.minimum.at(lo, pr["obs_point"][free], sl[free]); np.maximum.at(hi, pr["obs_point"][free], sl[free])
+    return int((hi - lo)[hi >= 0].max())
+
+
+def band_window(free, hbw, n_pts=None, seq=0):
+    """a synth.ba_problem window of `free` free keyframes with contiguous tracks whose landmarks span exactly `hbw` free slots at most:
+    the track cap is hbw + 2 keyframes (the fixed first keyframe may be one of them), and what a landmark has beyond hbw slots behind
+    its first free one is dropped"""
+    assert 0 <= hbw <= min(9, free - 1)
+    n_kf = free + 1
+    n_pts = n_pts or max(60, 6 * n_kf)
+    pr = synth.ba_problem(n_kf, n_pts, max(3, hbw + 2) * n_pts, 640, 480, seq_id=800 + free + 100 * hbw + seq, tracks="contiguous")
+    slot = np.cumsum(pr["fixed"] == 0) - 1
+    sl = np.where(pr["fixed"][pr["obs_pose"]] == 0, slot[pr["obs_pose"]], -1)
+    lo = np.full(n_pts, 1 << 30)
+    np.minimum.at(lo, pr["obs_point"][sl >= 0], sl[sl >= 0])
+    keep = (sl < 0) | (sl <= lo[pr["obs_point"]] + hbw)
+    for k in ("obs_pose", "obs_point", "obs_uvr", "obs_inv_sigma2"):
+        pr[k] = pr[k][keep]
+    assert free_span(pr) == hbw, (free, hbw, free_span(pr))
+    return pr
+
+
+class BandHolders:
+    """Built problems that stay on the band solver, by (dimension, block half-bandwidth).  They are never optimised."""
+
+    def __init__(self, hiplib, ctx):
+        self.hip, self.ctx, self.pool = hiplib, ctx, {}
+
+    def take(self, dim, k=1, hbw=None):
+        assert dim % 6 == 0
+        free = dim // 6
+        hbw = min(9, free - 1) if hbw is None else hbw
+        have = self.pool.setdefault((dim, hbw), [])
+        if len(have) < k:
+            pr = band_window(free, hbw)
+            obs = self.hip.ba_obs_array(pr)
+            while len(have) < k:
+                ba = self.hip.BundleAdjuster(self.ctx, pr["poses"], pr["fixed"], pr["points"], obs, pr["cam"])
+                assert ba.solver() == ("band", hbw), (dim, ba.solver())
+                have.append(ba)
+        return have[:k]
+
+    def close(self):
+        for key in list(self.pool):
+            for ba in self.pool.pop(key):
+                ba.close()
+
+    def holder_for(self, case, which=0):
+        """a holder whose band takes the case: 6 hbw + 5 >= w"""
+        hbw = -(-(case["w"] - 5) // 6)
+        assert 6 * hbw + 5 >= case["w"]
+        return self.take(case["n"], which + 1, hbw)[which]
+
+    def solve(self, problems, cases):
+        xs, flags = self.hip.ba_debug_solve(problems, [c["A"] for c in cases], [c["b"] for c in cases])
+        return xs, [int(f) for f in flags]
+
+    def alone(self, case, which=0):
+        xs, flags = self.solve([self.holder_for(case, which)], [case])
+        return xs[0], flags[0]
+
+    def batch(self, cases):
+        """every case on a holder of its own, in one call"""
+        used, probs = {}, []
+        for c in cases:
+            i = used.get(c["n"], 0); used[c["n"]] = i + 1
+            probs.append(self.holder_for(c, i))
+        return self.solve(probs, cases)
+
+
+def real_band_case(hiplib, ctx, free, hbw):
+    """S + lambda_0 I and rhs of the first LM trial of a contiguous-track window, read as real_case reads them (dense solver, step API);
+    the dense kernel's S is exactly zero outside the block band: the pair lists have no list there"""
+    n_kf = free + 1
+    pr = band_window(free, hbw, n_pts=max(150, 8 * n_kf), seq=50)
+    ba = hiplib.BundleAdjuster(ctx, pr["poses"], pr["fixed"], pr["points"], hiplib.ba_obs_array(pr), pr["cam"])
+    assert ba.solver() == ("band", hbw)
+    ba.set_solver("dense")
+    S, rhs, lam0, _ = first_trial_system(ba, 6 * free)
+    ba.close()
+    blk = np.arange(6 * free) // 6
+    outside = np.abs(blk[:, None] - blk[None, :]) > hbw
+    assert not S[outside].any(), "the dense Schur complement of a band window has entries outside the block band"
+    A = np.tril(S) + np.tril(S, -1).T
+    A[np.arange(len(A)), np.arange(len(A))] += lam0
+    c = sc.case_from(A, rhs, "real-band%d" % hbw)
+    c["w"] = 6 * hbw + 5
+    assert sc.half_bandwidth(A) <= c["w"]
+    return c
+
+
+REAL_BAND = ((9, 3), (30, 9), (50, 9))          # (free keyframes, block half-bandwidth)
+
+
 # ---- real windows -----------------------------------------------------------------------------------------------------------
 def real_window(kind, free):
     """a synth.ba_problem window with `free` free keyframes: random tracks; the same kind with monocular observations only; one
