@@ -29,8 +29,8 @@ UNIT_DEPS = {
     "intensity.hip": [],
     "ingest.hip": ["ingest_math.h"],
     "triangulate.hip": ["desc_wave.h", "triangulate_math.h", "jacobi_math.h"],
-    "pnp.hip": ["epnp_math.h", "jacobi_math.h", os.path.join(_HOST, "pose_math.h")],
-    "two_view.hip": ["two_view_math.h", "triangulate_math.h", "jacobi_math.h"],
+    "pnp.hip": ["epnp_math.h", "jacobi_math.h", "ransac_sample.h", os.path.join(_HOST, "pose_math.h")],
+    "two_view.hip": ["two_view_math.h", "triangulate_math.h", "jacobi_math.h", "ransac_sample.h"],
     "jpeg.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_tables.h")],
     "jpeg_dec.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_header.h"), os.path.join(_HOST, "jpeg_tables.h")],
 }
@@ -86,7 +86,7 @@ def host_library(force=False, verbose=False):
     """C++ host mirror of the reference interface (g++), linked against the HIP C-ABI library next to it."""
     hdir = os.path.join(HERE, "host")
     srcs = [os.path.join(hdir, s) for s in HOST_SOURCES]
-    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "radtan_math.h"), os.path.join("..", "csrc", "triangulate_math.h"), os.path.join("..", "csrc", "epnp_math.h"), os.path.join("..", "csrc", "jacobi_math.h"), os.path.join("..", "csrc", "two_view_math.h"))] + \
+    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "radtan_math.h"), os.path.join("..", "csrc", "triangulate_math.h"), os.path.join("..", "csrc", "epnp_math.h"), os.path.join("..", "csrc", "jacobi_math.h"), os.path.join("..", "csrc", "two_view_math.h"), os.path.join("..", "csrc", "ransac_sample.h"))] + \
         [os.path.join(HERE, "..", "include", h) for h in ("lpslam_types.h", "lpslam_manager.h", "lpslam_hip.h")] + [LIB]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps if os.path.exists(d)):
         return HOST_LIB

@@ -1364,13 +1364,16 @@ int lpslam_hip_get_keypoints(lpslam_hip_ctx* c, int image, lpslam_hip_keypoint* 
 
 unsigned* lp_done_counter(lpslam_hip_ctx* c, int which)
 {
+    if (which < 0 || which >= LP_DONE_COUNTERS) { set_error("arrival counter %d outside 0 .. %d", which, LP_DONE_COUNTERS - 1); return nullptr; }
     std::lock_guard<std::mutex> lock(c->pool_mutex);       // (a tracking thread and its prefetch thread may both arrive here first)
     if (!c->d_done) {
-        if (hipMalloc((void**)&c->d_done, 8 * 32 * sizeof(unsigned)) != hipSuccess) { c->d_done = nullptr; return nullptr; }
+        const size_t bytes = LP_DONE_COUNTERS * 32 * sizeof(unsigned);
+        if (hipMalloc((void**)&c->d_done, bytes) != hipSuccess) c->d_done = nullptr;
         // (the context's streams do not synchronise with the null stream: the zeroes must be there before any of them runs a kernel)
-        if (hipMemset(c->d_done, 0, 8 * 32 * sizeof(unsigned)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(c->d_done); c->d_done = nullptr; return nullptr; }
+        else if (hipMemset(c->d_done, 0, bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipFree(c->d_done); c->d_done = nullptr; }
     }
-    return c->d_done + 32 * (which & 7);
+    if (!c->d_done) { set_error("device memory for the completion counters"); return nullptr; }
+    return c->d_done + 32 * which;
 }
 
 uint8_t* lp_match_staging(lpslam_hip_ctx* c, size_t need, size_t grow_to, hipStream_t s)
@@ -1404,7 +1407,7 @@ bool lp_wait_recover(lpslam_hip_ctx* c, int which, hipStream_t s)
 int lp_done_arm(lpslam_hip_ctx* c, int which, int* flag, int& seq_counter, LpDone* d)
 {
     unsigned* counter = which < 0 ? nullptr : lp_done_counter(c, which);
-    if (which >= 0 && !counter) { set_error("device memory for the completion counters"); return LPSLAM_HIP_ERR_DEVICE; }
+    if (which >= 0 && !counter) return LPSLAM_HIP_ERR_DEVICE;      // (the text is lp_done_counter's)
     *d = LpDone{counter, flag, lp_next_seq(seq_counter), which};
     __atomic_store_n(flag, 0, __ATOMIC_RELAXED);
     return LPSLAM_HIP_OK;
@@ -1414,6 +1417,25 @@ int lp_done_wait(lpslam_hip_ctx* c, const LpDone& d, hipStream_t s)
 {
     if (lp_wait_done(d.flag, d.seq, s)) return LP_DONE_ARRIVED;
     return lp_wait_recover(c, d.which, s) ? LP_DONE_LATE : LP_DONE_DEAD;
+}
+
+int LpStagedCall::open(size_t host_bytes, size_t dev_bytes, int counter, size_t host_grow_to)
+{
+    if (dev_bytes >= (size_t)0xffffffffu) { set_error("%s: the sets do not fit one block", who); return LPSLAM_HIP_ERR_CAPACITY; }
+    host = lp_match_staging(ctx, host_bytes, host_grow_to ? host_grow_to : host_bytes + host_bytes / 2, stream);
+    if (!host) return LPSLAM_HIP_ERR_DEVICE;
+    if (int rc = blk.alloc(dev_bytes)) return rc;
+    return lp_done_arm(ctx, counter, (int*)host, ctx->done_seq, &done);
+}
+
+int LpStagedCall::finish()
+{
+    LP_HIP(hipGetLastError());
+    const int w = lp_done_wait(ctx, done, stream);
+    if (w == LP_DONE_ARRIVED) return LPSLAM_HIP_OK;
+    if (w == LP_DONE_DEAD) blk.leak();
+    set_error("%s: the kernels did not complete", who);
+    return LPSLAM_HIP_ERR_DEVICE;
 }
 
 namespace {
@@ -1516,7 +1538,7 @@ int lpslam_hip_prefetch_frame(lpslam_hip_ctx* c, int image, int32_t with_stereo)
     hipStream_t s = lp_fe_stream(c);
     if ((rc = pf_block_ready(c, f, "lpslam_hip_prefetch_frame"))) return rc;
     const int fields = FRAME_KPTS | FRAME_DESC | (with_stereo ? (FRAME_XR | FRAME_DEPTH) : 0);
-    if ((rc = frame_deliver(c, image, fields, c->h_stage_pf, 3, s, c->pf_seq_next, &c->pf_done))) return rc;
+    if ((rc = frame_deliver(c, image, fields, c->h_stage_pf, LP_DONE_PREFETCH, s, c->pf_seq_next, &c->pf_done))) return rc;
     c->pf_fields = fields; c->pf_stream = s; c->pf_in_flight = true;
     c->pf_image = image;
     return LPSLAM_HIP_OK;
@@ -1530,7 +1552,7 @@ int lp_prepare_delivery(lpslam_hip_ctx* c, int image, int with_stereo, LpDeliver
     const FrameStage f = frame_stage(c);
     int rc = pf_block_ready(c, f, "front end"); if (rc) return rc;
     LpDone d{};
-    if ((rc = lp_done_arm(c, 3, (int*)(c->h_stage_pf + 32), c->pf_seq_next, &d))) return rc;
+    if ((rc = lp_done_arm(c, LP_DONE_PREFETCH, (int*)(c->h_stage_pf + 32), c->pf_seq_next, &d))) return rc;
     const size_t S = (size_t)c->slots_per_image, o = (size_t)image * S;
     const float* fs = c->d_stereo + o * 2;
     const int words = (int)S * (7 + 8 + (with_stereo ? 2 : 0));
@@ -1650,7 +1672,7 @@ static int frame_collect(lpslam_hip_ctx* c, int image, int fields, uint8_t** blo
         }
         st = c->h_stage;
         LpDone done{};
-        if ((rc = frame_deliver(c, image, fields, st, 0, c->stream, c->done_seq, &done))) return rc;
+        if ((rc = frame_deliver(c, image, fields, st, LP_DONE_FRAME, c->stream, c->done_seq, &done))) return rc;
         if (lp_done_wait(c, done, c->stream)) { set_error("lpslam_hip_get_frame: the read-back kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
     }
     int32_t n = 0;

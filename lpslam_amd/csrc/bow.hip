@@ -206,7 +206,7 @@ static int bow_transform_device(lpslam_hip_ctx* c, lpslam_hip_vocab* v, const ui
     uint8_t* hb = lp_match_staging(c, total, total + total / 2, s);
     if (!hb) return LPSLAM_HIP_ERR_DEVICE;
     LpDone done{};
-    { const int rc = lp_done_arm(c, 4, (int*)hb, c->done_seq, &done); if (rc) return rc; }
+    { const int rc = lp_done_arm(c, LP_DONE_BOW, (int*)hb, c->done_seq, &done); if (rc) return rc; }
     hipLaunchKernelGGL(k_bow_transform16, dim3((unsigned)((nm * 16 + 255) / 256)), dim3(256), 0, s, d_desc, d_count, n_max, v->d_child_start, v->d_child_list, v->d_desc, v->d_weight,
                        v->d_word, v->L, levels_up, n_max, (int32_t*)(hb + 32), (int32_t*)(hb + o_word), (float*)(hb + o_w), (int32_t*)(hb + o_node), done.counter, done.flag, done.seq);
     LP_HIP(hipGetLastError());

@@ -5,8 +5,8 @@
 //   horn           Horn's absolute orientation of n >= 3 matched points, with or without a free scale
 //   lsq_small      the small least-squares solves of EPnP's betas
 //   pnp_inlier     the scoring rule of the RANSAC around EPnP, pnp_score its count over a set
-//   host only:     sample_table (the 4-match samples of LpSlam::pnp_solve_ransac; the draw is sequential by definition),
-//                  pnp_solve_sample (one sample's hypothesis) and pnp_refit (EPnP once more over the winner's inliers)
+//   host only:     pnp_solve_sample (one sample's hypothesis) and pnp_refit (EPnP once more over the winner's inliers); the 4-match
+//                  samples of LpSlam::pnp_solve_ransac are sample_table<4> of ransac_sample.h
 // No heap: every array is of fixed size or the caller's.  The 12 x 12 matrix M^T M and its eigenvectors (288 doubles) live in a
 // workspace of the caller: element e of it is ws[e * stride].  On the device sixteen lanes of a wave solve one hypothesis together:
 // they share the workspace (LDS) and divide the independent elements of each Jacobi rotation of the 12 x 12 matrix among them
@@ -286,23 +286,6 @@ LP_EPNP_FN bool pnp_inlier(const double* R, const double* t, const double* cam, 
 }
 
 // ---- host only from here on (plain inline functions) ---------------------------------------------------------------------------
-// The samples of LpSlam::pnp_solve_ransac for a set of n >= 4 matches: xorshift32 from seed ? seed : 1, four draws per iteration (whether
-// or not the solve succeeds), each a step of a partial Fisher-Yates over avail[0 .. n) that is rebuilt every iteration.  table
-// receives iterations x 4 match indices; avail is n ints of scratch.
-inline void sample_table(int n, int iterations, uint32_t seed, int32_t* table, int* avail)
-{
-    uint32_t s = seed ? seed : 1u;
-    for (int it = 0; it < iterations; ++it) {
-        for (int i = 0; i < n; ++i) avail[i] = i;
-        int left = n;
-        for (int k = 0; k < 4; ++k) {
-            s ^= s << 13; s ^= s >> 17; s ^= s << 5;
-            const int r = (int)(s % (uint32_t)left);
-            table[4 * it + k] = avail[r]; avail[r] = avail[left - 1]; --left;
-        }
-    }
-}
-
 // The hypothesis of one sample: EPnP on the four matches idx names
 inline bool pnp_solve_sample(const double* pw, const double* obs, const int32_t* idx, const double* cam, double* R, double* t)
 {

@@ -356,7 +356,11 @@ __device__ __forceinline__ void lp_signal_done_of(unsigned* counter, int* flag, 
 __device__ __forceinline__ void lp_signal_done(unsigned* counter, int* flag, int seq) { lp_signal_done_of(counter, flag, seq, gridDim.x * gridDim.y * gridDim.z); }
 #endif
 inline void lp_pf_invalidate(lpslam_hip_ctx* c, int first, int n) { const int p = c->pf_image.load(std::memory_order_relaxed); if (p >= first && p < first + n) c->pf_image.store(-1, std::memory_order_relaxed); }      // the slot's results are being rewritten
-unsigned* lp_done_counter(lpslam_hip_ctx* c, int which);      // arrival counter number `which` (0 .. 7) of the context, nullptr on failure
+// The context's arrival counters, one per kind of delivery: two deliveries that may be in flight together never count on the same one.
+// A new kind takes a new name in front of LP_DONE_COUNTERS.
+enum { LP_DONE_FRAME = 0, LP_DONE_WINDOW = 1, LP_DONE_STORED = 2, LP_DONE_PREFETCH = 3, LP_DONE_BOW = 4, LP_DONE_TRIANGULATE = 5, LP_DONE_PNP = 6, LP_DONE_TWO_VIEW = 7,
+       LP_DONE_COUNTERS = 8 };
+unsigned* lp_done_counter(lpslam_hip_ctx* c, int which);      // arrival counter `which` of the context; nullptr, error set: no such counter or no memory for them
 bool lp_wait_recover(lpslam_hip_ctx* c, int which, hipStream_t s);      // after a failed lp_wait_done: counter re-zeroed (which < 0: none); false = the stream is dead, leak what its kernels touch
 // the next sequence number of a completion flag: positive, never 0 (0 is what the flag is reset to before a launch)
 inline int lp_next_seq(int& s) { s = s >= 0x7ffffff0 ? 1 : s + 1; return s; }
@@ -391,6 +395,23 @@ int lp_done_arm(lpslam_hip_ctx* c, int which, int* flag, int& seq_counter, LpDon
 // kernels touched may be released; LP_DONE_DEAD: leak it.  (The error text is the caller's.)
 enum { LP_DONE_ARRIVED = 0, LP_DONE_LATE = 1, LP_DONE_DEAD = 2 };
 int lp_done_wait(lpslam_hip_ctx* c, const LpDone& d, hipStream_t s);
+// Offsets into a block, 64 bytes apart at least: take() hands out the next one.
+struct LpLayout { size_t at = 0; size_t take(size_t bytes) { const size_t o = at; at += (bytes + 63) & ~(size_t)63; return o; } };
+// One call that stages its input in the context's page-locked block (flag at 0 | input from byte 64 | results), runs kernels on a block
+// of the cache (input | scratch) and has the last of them deliver into the page-locked block: open, fill `host`,
+// upload, launch with `done`, finish, read.  Whichever way the caller returns, the device block goes back to the cache -- unless
+// finish() found the stream dead: its kernels may still write the block, it is leaked.
+struct LpStagedCall {
+    lpslam_hip_ctx* ctx; hipStream_t stream; const char* who;
+    LpPoolBlock blk{ctx}; uint8_t* host = nullptr; LpDone done{};
+    uint8_t* dev() const { return (uint8_t*)blk.ptr; }
+    // host_bytes page-locked (a block that has to grow: to host_grow_to, 0 = half as much again, after the stream is synchronised),
+    // dev_bytes on the device -- 4 GiB or more are refused in front of any allocation --, the flag armed on arrival counter `counter`
+    int open(size_t host_bytes, size_t dev_bytes, int counter, size_t host_grow_to = 0);
+    // host + host_offset .. to the start of the device block, one copy on the stream
+    int upload(size_t host_offset, size_t bytes) { LP_HIP(hipMemcpyAsync(blk.ptr, host + host_offset, bytes, hipMemcpyHostToDevice, stream)); return LPSLAM_HIP_OK; }
+    int finish();      // after the launches: their launch error, then the wait for the flag
+};
 // LPSLAM_HIP_MATCH_TRACE: the matchers print where a call's microseconds went
 struct LpMatchTrace {
     const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();

@@ -609,7 +609,7 @@ int lpslam_hip_match_bf_descriptors(lpslam_hip_ctx* c, int query, int scratch, c
     uint32_t* st = (uint32_t*)lp_match_staging(c, words * 4, words * 8, s);
     if (!st) return LPSLAM_HIP_ERR_DEVICE;
     LpDone done{};
-    if ((rc = lp_done_arm(c, 2, (int*)st, c->done_seq, &done))) return rc;
+    if ((rc = lp_done_arm(c, LP_DONE_STORED, (int*)st, c->done_seq, &done))) return rc;
     const uint32_t* fq = (const uint32_t*)(c->d_bf + (size_t)query * 3 * S);
     const uint32_t* ft = (const uint32_t*)(c->d_bf + (size_t)scratch * 3 * S);
     WordRuns r{{fq, fq + S, fq + 2 * S, ft}, {nq, nq, nq, cross_check ? n_train : 0}, {(int)o_bi, (int)o_bd, (int)o_sd, (int)o_rbi}};
@@ -696,14 +696,13 @@ int lpslam_hip_match_bf_stored(lpslam_hip_ctx* c, int query, const int32_t* keys
     // when it grows, sized at once for a search over 48 full sets (a tracker's candidate list grows one keyframe at a time: growing the
     // block with it cost a page-locked reallocation -- 1 ms -- on every frame that crossed the previous size)
     const size_t roomy = std::max(host_bytes * 2, (size_t)4096 + 96 * (sizeof(BfPair) + sizeof(WordRun)) + (size_t)48 * 4 * S * 4);
-    uint8_t* hb = lp_match_staging(c, host_bytes, roomy, s);
-    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
-    LpPoolBlock blk(c);
-    // (always the size of a 48-set search: the context's block cache then serves every call from the same block -- a request that
-    // grows by one keyframe per call would miss it every time, 1 ms of hipMalloc)
-    if ((rc = blk.alloc(std::max(dev_words * 4, (size_t)48 * 6 * S * 4)))) return rc;
+    // (the device block always the size of a 48-set search: the context's block cache then serves every call from the same block -- a
+    // request that grows by one keyframe per call would miss it every time, 1 ms of hipMalloc)
+    LpStagedCall call{c, s, "lpslam_hip_match_bf_stored"};
+    if ((rc = call.open(host_bytes, std::max(dev_words * 4, (size_t)48 * 6 * S * 4), LP_DONE_STORED, roomy))) return rc;
+    uint8_t* hb = call.host;
     BfPair* pairs = (BfPair*)(hb + o_pairs); WordRun* runs = (WordRun*)(hb + o_runs);
-    int32_t* d_res = (int32_t*)blk.ptr;
+    int32_t* d_res = (int32_t*)call.dev();
     const uint8_t* qdesc = c->d_desc + (size_t)query * S * 32;
     size_t w = 0;
     std::vector<size_t> h_fwd((size_t)n_keys), h_rev((size_t)n_keys);
@@ -720,15 +719,10 @@ int lpslam_hip_match_bf_stored(lpslam_hip_ctx* c, int query, const int32_t* keys
     // a set without descriptors leaves its forward arrays unwritten by the kernel (no train descriptor: best index -1): preset them
     for (int k = 0; k < n_keys; ++k)
         if (c->desc_store[keys[k]].n == 0) LP_HIP(hipMemsetAsync(d_res + o_fwd[(size_t)k], 0xff, (size_t)nq * 4, s));
-    LpDone done{};
-    if ((rc = lp_done_arm(c, 2, (int*)hb, c->done_seq, &done))) return rc;
     const int q_blocks = (std::max(nq, nt_max) + BF_QPW - 1) / BF_QPW;
     hipLaunchKernelGGL(k_bf_knn2_pairs, dim3(q_blocks, n_pairs), dim3(256), 0, s, (const BfPair*)pairs);
-    hipLaunchKernelGGL(k_runs_to_host, dim3(4, n_runs), dim3(256), 0, s, (const WordRun*)runs, (uint32_t*)hb, done.counter, done.flag, done.seq);
-    LP_HIP(hipGetLastError());
-    // (a failed wait: the block goes back to the pool only when the stream still synchronises -- its kernels are then complete --, and the
-    // arrival counter they left part-way is zeroed; on a dead stream the block is leaked rather than handed to the next caller)
-    if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("lpslam_hip_match_bf_stored: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+    hipLaunchKernelGGL(k_runs_to_host, dim3(4, n_runs), dim3(256), 0, s, (const WordRun*)runs, (uint32_t*)hb, call.done.counter, call.done.flag, call.done.seq);
+    if ((rc = call.finish())) return rc;
     const int32_t* hw = (const int32_t*)hb;
     for (int k = 0; k < n_keys; ++k) {
         const int nt = c->desc_store[keys[k]].n;
@@ -835,7 +829,7 @@ static int window_match(lpslam_hip_ctx* c, int image, const lpslam_hip_proj_quer
     // the candidate lists and counts are written by the kernel straight into the page-locked mirror, and its last store releases a
     // sequence number there (internal.h, lp_signal_done): no copy-engine packet on the way back
     LpDone done{};
-    if ((rc = lp_done_arm(c, 1, (int*)(hb + o_ids + 32), c->done_seq, &done))) return rc;
+    if ((rc = lp_done_arm(c, LP_DONE_WINDOW, (int*)(hb + o_ids + 32), c->done_seq, &done))) return rc;
     const int16_t* first_bsf = taken_in ? (const int16_t*)(hb + o_bsf) : (const int16_t*)nullptr;
     // several sessions tracking at once: the first scan joins the other sessions' pending scans in one launch (share.hip)
     int shared = LP_SHARE_DIRECT;
@@ -1232,7 +1226,7 @@ int lpslam_hip_rank_stored(lpslam_hip_ctx* c, int query, const int32_t* keys, in
     if (!hb) { set_error("page-locked memory for rank_stored"); return LPSLAM_HIP_ERR_DEVICE; }
     LpDone done{};
     int w = LP_DONE_ARRIVED;
-    if (!(rc = lp_done_arm(c, 2, (int*)hb, c->done_seq, &done))) {
+    if (!(rc = lp_done_arm(c, LP_DONE_STORED, (int*)hb, c->done_seq, &done))) {
         const uint8_t* qdesc = c->d_desc + (size_t)query * c->slots_per_image * 32;
         int32_t* d_votes = (int32_t*)blk.ptr;
         const int32_t* out = (const int32_t*)(hb + o_out);

@@ -1,6 +1,6 @@
 // pnp.hip -- the relocaliser's pose solver for a batch of match sets ([UPSTREAM] solve::pnp_solver, the host
 // form is LpSlam::pnp_solve_ransac in lpslam_amd/host/two_view.cpp).  One call takes S sets of landmark / keypoint matches:
-//   host            the sample table (the 4-match samples pnp_solve_ransac would draw, epnp_math.h) and ONE upload of it with the matches
+//   host            the sample table (the 4-match samples pnp_solve_ransac would draw, ransac_sample.h) and ONE upload of it with the matches
 //   k_pnp_hypotheses  sixteen lanes per (set, iteration): EPnP on the four sampled matches (epnp<4> of epnp_math.h, the function the host
 //                   solver calls); the 12 x 12 matrix and its eigenvectors live in LDS (2.3 KB a hypothesis, four a wave) and
 //                   the lanes divide each Jacobi rotation's elements among them
@@ -8,8 +8,11 @@
 //                   key count << 32 | ~iteration (the lowest iteration among equal counts, the host's `count > best`), its flags and
 //                   pose written to page-locked memory, then the done flag (internal.h)
 //   host            one wait; per set the refit of pnp_solve_ransac (pnp_refit of epnp_math.h): EPnP over the winner's inliers
+// The round trip -- page-locked block, device block, done flag, what becomes of them when a stream is late or dead -- is LpStagedCall
+// (internal.h).
 #include "internal.h"
 #include "epnp_math.h"
+#include "ransac_sample.h"
 #include "../host/pose_math.h"
 #include <cmath>
 
@@ -113,8 +116,6 @@ __global__ __launch_bounds__(256) void k_pnp_score(const uint8_t* __restrict__ b
     lp_signal_done(counter, flag, seq);
 }
 
-size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 }  // namespace
 
 extern "C" {
@@ -123,12 +124,10 @@ int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const int32_t
                                 const double* cam4, int32_t iterations, uint32_t seed, double* pose7, int32_t* n_inliers, uint8_t* inlier, int32_t* best_iteration)
 {
     if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
-    if (n_sets < 0) { set_error("pnp_ransac_batch: %d sets", n_sets); return LPSLAM_HIP_ERR_INVALID; }
+    int first = 0, total = 0;
+    if (const char* why = lpslam_ransac::check_offsets(n_sets, offsets, &first, &total)) { set_error("pnp_ransac_batch: %s", why); return LPSLAM_HIP_ERR_INVALID; }
     if (iterations < 1 || iterations > LPSLAM_HIP_PNP_MAX_ITERATIONS) { set_error("pnp_ransac_batch: %d iterations outside 1 .. %d", iterations, LPSLAM_HIP_PNP_MAX_ITERATIONS); return LPSLAM_HIP_ERR_INVALID; }
-    if (!offsets || !cam4 || (n_sets > 0 && (!pose7 || !n_inliers))) { set_error("pnp_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
-    if (offsets[0] < 0) { set_error("pnp_ransac_batch: offsets[0] = %d is negative", offsets[0]); return LPSLAM_HIP_ERR_INVALID; }
-    for (int s = 0; s < n_sets; ++s) if (offsets[s + 1] < offsets[s]) { set_error("pnp_ransac_batch: offsets do not ascend at set %d", s); return LPSLAM_HIP_ERR_INVALID; }
-    const int first = offsets[0], total = offsets[n_sets] - first;
+    if (!cam4 || (n_sets > 0 && (!pose7 || !n_inliers))) { set_error("pnp_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
     if (total > 0 && (!pw || !obs || !inv_sigma2 || !inlier)) { set_error("pnp_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
     for (int k = 0; k < 4; ++k) if (!std::isfinite(cam4[k])) { set_error("pnp_ransac_batch: the camera is no number"); return LPSLAM_HIP_ERR_INVALID; }
     if (n_sets == 0) return LPSLAM_HIP_OK;
@@ -139,26 +138,18 @@ int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const int32_t
     const LpMatchTrace tr;
     // page-locked block: flag | input (head, offsets rebased to 0, sample table, landmarks, keypoints, weights) | results (a record per
     // set, a flag per match); device block: the input, then the hypotheses (R, t) and their valid flags
-    const size_t o_in = 64;
-    size_t at = al64(sizeof(PnpHead));
-    const size_t o_offsets = at; at += al64((size_t)(n_sets + 1) * 4);
-    const size_t o_table = at; at += al64(n_hyp * 16);
-    const size_t o_pw = at; at += al64((size_t)std::max(total, 1) * 24);
-    const size_t o_obs = at; at += al64((size_t)std::max(total, 1) * 16);
-    const size_t o_w = at; at += al64((size_t)std::max(total, 1) * 8);
-    const size_t in_bytes = at;
-    const size_t d_hyp = at; at += al64(n_hyp * 96);
-    const size_t d_valid = at; at += al64(n_hyp * 4);
-    const size_t dev_bytes = at;
-    const size_t h_res = o_in + in_bytes, h_flags = h_res + al64((size_t)n_sets * sizeof(PnpResult));
-    const size_t host_bytes = h_flags + al64((size_t)std::max(total, 1));
-    if (dev_bytes >= (size_t)0xffffffffu) { set_error("pnp_ransac_batch: the sets do not fit one block"); return LPSLAM_HIP_ERR_CAPACITY; }
-    uint8_t* hb = lp_match_staging(c, host_bytes, host_bytes + host_bytes / 2, s);
-    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
-    LpPoolBlock blk(c);
-    if (int rc = blk.alloc(dev_bytes)) return rc;
-    uint8_t* base = (uint8_t*)blk.ptr;
-    uint8_t* in = hb + o_in;
+    const size_t o_in = 64, tot1 = (size_t)std::max(total, 1);
+    LpLayout dev;
+    dev.take(sizeof(PnpHead));
+    const size_t o_offsets = dev.take((size_t)(n_sets + 1) * 4), o_table = dev.take(n_hyp * 16);
+    const size_t o_pw = dev.take(tot1 * 24), o_obs = dev.take(tot1 * 16), o_w = dev.take(tot1 * 8);
+    const size_t in_bytes = dev.at;
+    const size_t d_hyp = dev.take(n_hyp * 96), d_valid = dev.take(n_hyp * 4);
+    LpLayout host{o_in + in_bytes};
+    const size_t h_res = host.take((size_t)n_sets * sizeof(PnpResult)), h_flags = host.take(tot1);
+    LpStagedCall call{c, s, "pnp_ransac_batch"};
+    if (int rc = call.open(host.at, dev.at, LP_DONE_PNP)) return rc;
+    uint8_t *hb = call.host, *base = call.dev(), *in = hb + o_in;
     PnpHead head{};
     for (int k = 0; k < 4; ++k) head.cam[k] = cam4[k];
     head.n_sets = n_sets; head.iterations = iterations;
@@ -166,33 +157,19 @@ int lpslam_hip_pnp_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const int32_t
     memcpy(in, &head, sizeof head);
     int32_t* off0 = (int32_t*)(in + o_offsets);
     for (int i = 0; i <= n_sets; ++i) off0[i] = offsets[i] - first;
-    int32_t* table = (int32_t*)(in + o_table);
-    {
-        int max_n = 0;
-        for (int i = 0; i < n_sets; ++i) max_n = std::max(max_n, off0[i + 1] - off0[i]);
-        std::vector<int> avail((size_t)std::max(max_n, 1));
-        for (int i = 0; i < n_sets; ++i) {
-            const int n = off0[i + 1] - off0[i];
-            int32_t* tb = table + 4 * (size_t)i * (size_t)iterations;
-            if (n >= 4) ep::sample_table(n, iterations, seed, tb, avail.data());
-            else memset(tb, 0, (size_t)iterations * 16);
-        }
-    }
+    lpslam_ransac::batch_tables<4>(n_sets, off0, iterations, seed, (int32_t*)(in + o_table));
     if (total > 0) {
         memcpy(in + o_pw, pw + 3 * (size_t)first, (size_t)total * 24);
         memcpy(in + o_obs, obs + 2 * (size_t)first, (size_t)total * 16);
         memcpy(in + o_w, inv_sigma2 + (size_t)first, (size_t)total * 8);
     }
     const double tr_staged = tr.us();
-    LpDone done{};
-    if (int rc = lp_done_arm(c, 6, (int*)hb, c->done_seq, &done)) return rc;
-    LP_HIP(hipMemcpyAsync(base, in, in_bytes, hipMemcpyHostToDevice, s));
+    if (int rc = call.upload(o_in, in_bytes)) return rc;
     double* hyp = (double*)(base + d_hyp); int* valid = (int*)(base + d_valid);
     hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)((n_hyp + kHypPerWg - 1) / kHypPerWg)), dim3(64), 0, s, (const uint8_t*)base, hyp, valid);
     hipLaunchKernelGGL(k_pnp_score, dim3((unsigned)n_sets), dim3(256), 0, s, (const uint8_t*)base, (const double*)hyp, (const int*)valid,
-                       (PnpResult*)(hb + h_res), hb + h_flags, done.counter, done.flag, done.seq);
-    LP_HIP(hipGetLastError());
-    if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("pnp_ransac_batch: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+                       (PnpResult*)(hb + h_res), hb + h_flags, call.done.counter, call.done.flag, call.done.seq);
+    if (int rc = call.finish()) return rc;
     const double tr_back = tr.us();
     // the refit of pnp_solve_ransac, per set (pnp_refit of epnp_math.h): EPnP over the winner's inliers, kept when it explains at least as many
     const PnpResult* res = (const PnpResult*)(hb + h_res);

@@ -4,8 +4,9 @@
 //                 by (distance, index) and the number that passed are kept
 //   k_tri_pairs   one thread per listed candidate: tri_pair in FP64, results straight into page-locked host memory, then the
 //                 completion flag (internal.h, lp_signal_done)
-// One upload, the two launches and one wait per keyframe.  The order-dependent part (a neighbour's keypoint taken by an earlier
-// query is invisible to later ones) is the caller's replay over these lists (lpslam_tri::replay_host).
+// One upload, the two launches and one wait per keyframe: an LpStagedCall (internal.h, DESIGN.md section 40 -- the two blocks, the
+// done flag and what becomes of them when a stream is late or dead).  The order-dependent part (a neighbour's keypoint taken by an
+// earlier query is invisible to later ones) is the caller's replay over these lists (lpslam_tri::replay_host).
 #include "internal.h"
 #include "desc_wave.h"
 #include "triangulate_math.h"
@@ -161,7 +162,6 @@ bool finite_all(const double* p, int n) { for (int i = 0; i < n; ++i) if (!std::
 bool pose_ok(const double* p) { return finite_all(p, 7) && p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3] > 0.0; }
 tri::Camera to_camera(const lpslam_hip_tri_camera* c) { return tri::Camera{c->fx, c->fy, c->cx, c->cy, c->focal_x_baseline, c->scale_factor}; }
 void fill_scale(float* dst, const float* scale, int n_levels) { for (int l = 0; l < LPSLAM_HIP_MAX_LEVELS; ++l) dst[l] = l < n_levels ? scale[l] : 1.0f; }
-size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 }  // namespace
 
@@ -200,31 +200,23 @@ int lpslam_hip_triangulate_neighbours(lpslam_hip_ctx* c, int image, const int32_
     // (counts, keys, codes, X); device block: the input, then the lists of k_epi_topk
     const size_t entries = (size_t)n_sets * (size_t)nq * tri::kListed, lists = (size_t)n_sets * (size_t)nq;
     const size_t o_in = 64;
-    size_t at = al64(sizeof(TriHead));
-    const size_t o_sets = at; at += al64((size_t)n_sets * sizeof(TriSetDev));
-    const size_t o_group1 = at; at += al64((size_t)nq * 4);
+    LpLayout dev;
+    dev.take(sizeof(TriHead));
+    const size_t o_sets = dev.take((size_t)n_sets * sizeof(TriSetDev)), o_group1 = dev.take((size_t)nq * 4);
     std::vector<TriSetDev> dev_sets((size_t)n_sets);
     for (int i = 0; i < n_sets; ++i) {
         TriSetDev& d = dev_sets[(size_t)i];
         const size_t n = (size_t)std::max(sets[i].n, 1);                 // (an empty set keeps one zeroed record: the clamped loads stay inside)
-        d.o_gate = (unsigned)at; at += al64(n * sizeof(GateRec));
-        d.o_desc = (unsigned)at; at += al64(n * 32);
-        d.o_xr = (unsigned)at; at += al64(n * 4);
-        d.o_depth = (unsigned)at; at += al64(n * 4);
+        d.o_gate = (unsigned)dev.take(n * sizeof(GateRec)); d.o_desc = (unsigned)dev.take(n * 32);
+        d.o_xr = (unsigned)dev.take(n * 4); d.o_depth = (unsigned)dev.take(n * 4);
     }
-    const size_t in_bytes = at;
-    const size_t d_keys_off = at; at += al64(entries * 8);
-    const size_t d_cnt_off = at; at += al64(lists * 4);
-    const size_t dev_bytes = at;
-    const size_t h_cnt_off = o_in + in_bytes, h_keys_off = h_cnt_off + al64(lists * 4), h_code_off = h_keys_off + al64(entries * 8), h_X_off = h_code_off + al64(entries * 4);
-    const size_t host_bytes = h_X_off + al64(entries * 24);
-    if (dev_bytes >= (size_t)0xffffffffu) { set_error("triangulate_neighbours: the sets do not fit one block"); return LPSLAM_HIP_ERR_CAPACITY; }
-    uint8_t* hb = lp_match_staging(c, host_bytes, host_bytes + host_bytes / 2, s);
-    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
-    LpPoolBlock blk(c);
-    if (int rc = blk.alloc(dev_bytes)) return rc;
-    uint8_t* base = (uint8_t*)blk.ptr;
-    uint8_t* in = hb + o_in;
+    const size_t in_bytes = dev.at;
+    const size_t d_keys_off = dev.take(entries * 8), d_cnt_off = dev.take(lists * 4);
+    LpLayout host{o_in + in_bytes};
+    const size_t h_cnt_off = host.take(lists * 4), h_keys_off = host.take(entries * 8), h_code_off = host.take(entries * 4), h_X_off = host.take(entries * 24);
+    LpStagedCall call{c, s, "triangulate_neighbours"};
+    if (int rc = call.open(host.at, dev.at, LP_DONE_TRIANGULATE)) return rc;
+    uint8_t *hb = call.host, *base = call.dev(), *in = hb + o_in;
     const tri::Camera camera = to_camera(cam);
     TriHead head{};
     head.cam = camera; head.v1 = tri::view_from_pose(pose1);
@@ -250,19 +242,16 @@ int lpslam_hip_triangulate_neighbours(lpslam_hip_ctx* c, int image, const int32_
         memcpy(in + o_sets + (size_t)i * sizeof(TriSetDev), &d, sizeof d);
     }
     const double tr_staged = tr.us();
-    LpDone done{};
-    if (int rc = lp_done_arm(c, 5, (int*)hb, c->done_seq, &done)) return rc;
     const size_t o = (size_t)image * c->slots_per_image;
     const lpslam_hip_keypoint* kp1 = c->d_kpts + o;
     const float* xr1 = camera.fxb > 0.0 ? c->d_stereo + o * 2 : nullptr;            // the slot's last stereo match
     const float* depth1 = xr1 ? xr1 + c->slots_per_image : nullptr;
-    LP_HIP(hipMemcpyAsync(base, in, in_bytes, hipMemcpyHostToDevice, s));
+    if (int rc = call.upload(o_in, in_bytes)) return rc;
     unsigned long long* d_keys = (unsigned long long*)(base + d_keys_off); int* d_cnt = (int*)(base + d_cnt_off);
     hipLaunchKernelGGL(k_epi_topk, dim3((unsigned)((nq + 3) / 4), (unsigned)n_sets), dim3(256), 0, s, (const uint8_t*)base, kp1, (const uint8_t*)(c->d_desc + o * 32), depth1, d_keys, d_cnt);
     hipLaunchKernelGGL(k_tri_pairs, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, (const uint8_t*)base, kp1, xr1, depth1, (const unsigned long long*)d_keys, (const int*)d_cnt,
-                       (int*)(hb + h_cnt_off), (unsigned long long*)(hb + h_keys_off), (int*)(hb + h_code_off), (double*)(hb + h_X_off), done.counter, done.flag, done.seq);
-    LP_HIP(hipGetLastError());
-    if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("triangulate_neighbours: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+                       (int*)(hb + h_cnt_off), (unsigned long long*)(hb + h_keys_off), (int*)(hb + h_code_off), (double*)(hb + h_X_off), call.done.counter, call.done.flag, call.done.seq);
+    if (int rc = call.finish()) return rc;
     const double tr_back = tr.us();
     const int* h_cnt = (const int*)(hb + h_cnt_off); const unsigned long long* h_keys = (const unsigned long long*)(hb + h_keys_off);
     const int* h_code = (const int*)(hb + h_code_off); const double* h_X = (const double*)(hb + h_X_off);
@@ -296,7 +285,9 @@ int lpslam_hip_triangulate_pairs(lpslam_hip_ctx* c, const lpslam_hip_tri_camera*
     LP_HIP(hipSetDevice(c->cfg.device));
     static_assert(sizeof(lpslam_hip_tri_keypoint) == sizeof(tri::Keypoint), "keypoint layout");
     // one block of the cache: keypoints of view 1 | of view 2 | scale table | X | codes
-    const size_t kb = al64((size_t)n * sizeof(tri::Keypoint)), o_scale = 2 * kb, o_X = o_scale + 64, o_code = o_X + al64((size_t)n * 24);
+    LpLayout lay;
+    lay.take((size_t)n * sizeof(tri::Keypoint));
+    const size_t kb = lay.take((size_t)n * sizeof(tri::Keypoint)), o_scale = lay.take(sizeof(PairsHead::scale)), o_X = lay.take((size_t)n * 24), o_code = lay.at;
     LpPoolBlock blk(c);
     if (int rc = blk.alloc(o_code + (size_t)n * 4)) return rc;
     uint8_t* base = (uint8_t*)blk.ptr;

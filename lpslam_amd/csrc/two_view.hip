@@ -14,8 +14,11 @@
 //   host          one wait
 // lpslam_hip_two_view_check_poses, P <= 8 motion hypotheses over n matches:
 //   k_tv_pose     one lane per (hypothesis, match): X, the cosine of the parallax and the code, to page-locked memory; one wait
+// The round trip of either call -- page-locked block, device block, done flag, what becomes of them when a stream is late or dead --
+// is LpStagedCall (internal.h).
 #include "internal.h"
 #include "two_view_math.h"
+#include "ransac_sample.h"
 #include <cmath>
 
 using namespace lpslam;
@@ -27,7 +30,6 @@ constexpr int kUnitLanes = 16;         // lanes that estimate one model together
 constexpr int kUnitsPerWg = 64 / kUnitLanes;   // one wave per workgroup
 constexpr int kUnitLds = tv::kWorkspace + 2;   // doubles of LDS per unit: the four workspaces of a wave start on different banks
 constexpr int kScoreWaves = 16;        // waves of a scoring workgroup: hypotheses in flight per (set, model)
-constexpr int kDoneCounter = 7;        // the arrival counter of both calls (0 .. 6 belong to the frame delivery, the matchers, the vocabulary walk, triangulation, PnP)
 
 struct TvHead { double inv_s2; int32_t n_sets, iterations; uint32_t o_offsets, o_table, o_norm, o_p1, o_p2, o_n1, o_n2, pad; };
 struct TvResult { int32_t best_iteration, pad; double score, M[9]; };
@@ -188,8 +190,6 @@ __global__ __launch_bounds__(256) void k_tv_pose(PoseHead head, const double* __
     lp_signal_done(counter, flag, seq);
 }
 
-size_t al64(size_t x) { return (x + 63) & ~(size_t)63; }
-
 }  // namespace
 
 extern "C" {
@@ -198,13 +198,11 @@ int lpslam_hip_two_view_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const in
                                      uint32_t seed, int32_t* best_iteration, double* score, double* model, uint8_t* inlier_h, uint8_t* inlier_f)
 {
     if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
-    if (n_sets < 0) { set_error("two_view_ransac_batch: %d sets", n_sets); return LPSLAM_HIP_ERR_INVALID; }
+    int first = 0, total = 0;
+    if (const char* why = lpslam_ransac::check_offsets(n_sets, offsets, &first, &total)) { set_error("two_view_ransac_batch: %s", why); return LPSLAM_HIP_ERR_INVALID; }
     if (iterations < 1 || iterations > LPSLAM_HIP_TWO_VIEW_MAX_ITERATIONS) { set_error("two_view_ransac_batch: %d iterations outside 1 .. %d", iterations, LPSLAM_HIP_TWO_VIEW_MAX_ITERATIONS); return LPSLAM_HIP_ERR_INVALID; }
     if (!(sigma > 0) || !std::isfinite(sigma)) { set_error("two_view_ransac_batch: sigma is no positive number"); return LPSLAM_HIP_ERR_INVALID; }
-    if (!offsets || (n_sets > 0 && (!best_iteration || !score || !model))) { set_error("two_view_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
-    if (offsets[0] < 0) { set_error("two_view_ransac_batch: offsets[0] = %d is negative", offsets[0]); return LPSLAM_HIP_ERR_INVALID; }
-    for (int s = 0; s < n_sets; ++s) if (offsets[s + 1] < offsets[s]) { set_error("two_view_ransac_batch: offsets do not ascend at set %d", s); return LPSLAM_HIP_ERR_INVALID; }
-    const int first = offsets[0], total = offsets[n_sets] - first;
+    if (n_sets > 0 && (!best_iteration || !score || !model)) { set_error("two_view_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
     if (total > 0 && (!p1 || !p2 || !inlier_h || !inlier_f)) { set_error("two_view_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
     if (n_sets == 0) return LPSLAM_HIP_OK;
     const size_t n_hyp = (size_t)n_sets * (size_t)iterations;
@@ -214,29 +212,18 @@ int lpslam_hip_two_view_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const in
     const LpMatchTrace tr;
     // page-locked block: flag | input (head, offsets rebased to 0, sample table, the sets' normalisations, the matches in pixels and
     // normalised) | results (two records per set, two flags per match); device block: the input, then the hypotheses and their valid flags
-    const size_t o_in = 64;
-    const size_t tot1 = (size_t)std::max(total, 1);
-    size_t at = al64(sizeof(TvHead));
-    const size_t o_offsets = at; at += al64((size_t)(n_sets + 1) * 4);
-    const size_t o_table = at; at += al64(n_hyp * 32);
-    const size_t o_norm = at; at += al64((size_t)n_sets * 27 * 8);
-    const size_t o_p1 = at; at += al64(tot1 * 16);
-    const size_t o_p2 = at; at += al64(tot1 * 16);
-    const size_t o_n1 = at; at += al64(tot1 * 16);
-    const size_t o_n2 = at; at += al64(tot1 * 16);
-    const size_t in_bytes = at;
-    const size_t d_hyp = at; at += al64(n_hyp * kHypDoubles * 8);
-    const size_t d_valid = at; at += al64(n_hyp * 2 * 4);
-    const size_t dev_bytes = at;
-    const size_t h_res = o_in + in_bytes, h_fh = h_res + al64((size_t)n_sets * 2 * sizeof(TvResult)), h_ff = h_fh + al64(tot1);
-    const size_t host_bytes = h_ff + al64(tot1);
-    if (dev_bytes >= (size_t)0xffffffffu) { set_error("two_view_ransac_batch: the sets do not fit one block"); return LPSLAM_HIP_ERR_CAPACITY; }
-    uint8_t* hb = lp_match_staging(c, host_bytes, host_bytes + host_bytes / 2, s);
-    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
-    LpPoolBlock blk(c);
-    if (int rc = blk.alloc(dev_bytes)) return rc;
-    uint8_t* base = (uint8_t*)blk.ptr;
-    uint8_t* in = hb + o_in;
+    const size_t o_in = 64, tot1 = (size_t)std::max(total, 1);
+    LpLayout dev;
+    dev.take(sizeof(TvHead));
+    const size_t o_offsets = dev.take((size_t)(n_sets + 1) * 4), o_table = dev.take(n_hyp * 32), o_norm = dev.take((size_t)n_sets * 27 * 8);
+    const size_t o_p1 = dev.take(tot1 * 16), o_p2 = dev.take(tot1 * 16), o_n1 = dev.take(tot1 * 16), o_n2 = dev.take(tot1 * 16);
+    const size_t in_bytes = dev.at;
+    const size_t d_hyp = dev.take(n_hyp * kHypDoubles * 8), d_valid = dev.take(n_hyp * 2 * 4);
+    LpLayout host{o_in + in_bytes};
+    const size_t h_res = host.take((size_t)n_sets * 2 * sizeof(TvResult)), h_fh = host.take(tot1), h_ff = host.take(tot1);
+    LpStagedCall call{c, s, "two_view_ransac_batch"};
+    if (int rc = call.open(host.at, dev.at, LP_DONE_TWO_VIEW)) return rc;
+    uint8_t *hb = call.host, *base = call.dev(), *in = hb + o_in;
     TvHead head{};
     head.inv_s2 = 1.0 / (sigma * sigma);
     head.n_sets = n_sets; head.iterations = iterations;
@@ -249,35 +236,25 @@ int lpslam_hip_two_view_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const in
         memcpy(in + o_p1, p1 + 2 * (size_t)first, (size_t)total * 16);
         memcpy(in + o_p2, p2 + 2 * (size_t)first, (size_t)total * 16);
     }
-    int32_t* table = (int32_t*)(in + o_table);
-    {
-        int max_n = 0;
-        for (int i = 0; i < n_sets; ++i) max_n = std::max(max_n, off0[i + 1] - off0[i]);
-        std::vector<int> avail((size_t)std::max(max_n, 1));
-        for (int i = 0; i < n_sets; ++i) {
-            const int o = off0[i], n = off0[i + 1] - o;
-            int32_t* tb = table + tv::kSample * (size_t)i * (size_t)iterations;
-            double* nm = (double*)(in + o_norm) + 27 * (size_t)i;
-            if (n < tv::kSample) { memset(tb, 0, (size_t)iterations * 32); memset(nm, 0, 27 * 8); continue; }
-            tv::sample_table(n, iterations, seed, tb, avail.data());
-            tv::M3 T1, T2;
-            tv::normalize_points((const double*)(in + o_p1) + 2 * (size_t)o, (size_t)n, (double*)(in + o_n1) + 2 * (size_t)o, T1);
-            tv::normalize_points((const double*)(in + o_p2) + 2 * (size_t)o, (size_t)n, (double*)(in + o_n2) + 2 * (size_t)o, T2);
-            const tv::M3 T2inv = tv::inverse(T2), T2t = tv::transpose(T2);
-            memcpy(nm, T1.m, 72); memcpy(nm + 9, T2inv.m, 72); memcpy(nm + 18, T2t.m, 72);
-        }
+    lpslam_ransac::batch_tables<tv::kSample>(n_sets, off0, iterations, seed, (int32_t*)(in + o_table));
+    for (int i = 0; i < n_sets; ++i) {
+        const int o = off0[i], n = off0[i + 1] - o;
+        double* nm = (double*)(in + o_norm) + 27 * (size_t)i;
+        if (n < tv::kSample) { memset(nm, 0, 27 * 8); continue; }
+        tv::M3 T1, T2;
+        tv::normalize_points((const double*)(in + o_p1) + 2 * (size_t)o, (size_t)n, (double*)(in + o_n1) + 2 * (size_t)o, T1);
+        tv::normalize_points((const double*)(in + o_p2) + 2 * (size_t)o, (size_t)n, (double*)(in + o_n2) + 2 * (size_t)o, T2);
+        const tv::M3 T2inv = tv::inverse(T2), T2t = tv::transpose(T2);
+        memcpy(nm, T1.m, 72); memcpy(nm + 9, T2inv.m, 72); memcpy(nm + 18, T2t.m, 72);
     }
     const double tr_staged = tr.us();
-    LpDone done{};
-    if (int rc = lp_done_arm(c, kDoneCounter, (int*)hb, c->done_seq, &done)) return rc;
-    LP_HIP(hipMemcpyAsync(base, in, in_bytes, hipMemcpyHostToDevice, s));
+    if (int rc = call.upload(o_in, in_bytes)) return rc;
     double* hyp = (double*)(base + d_hyp); int* valid = (int*)(base + d_valid);
     const size_t n_units = 2 * n_hyp;
     hipLaunchKernelGGL(k_tv_models, dim3((unsigned)((n_units + kUnitsPerWg - 1) / kUnitsPerWg)), dim3(64), 0, s, (const uint8_t*)base, hyp, valid);
     hipLaunchKernelGGL(k_tv_score, dim3((unsigned)(2 * n_sets)), dim3(64 * kScoreWaves), 0, s, (const uint8_t*)base, (const double*)hyp, (const int*)valid,
-                       (TvResult*)(hb + h_res), hb + h_fh, hb + h_ff, done.counter, done.flag, done.seq);
-    LP_HIP(hipGetLastError());
-    if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("two_view_ransac_batch: the kernels did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+                       (TvResult*)(hb + h_res), hb + h_fh, hb + h_ff, call.done.counter, call.done.flag, call.done.seq);
+    if (int rc = call.finish()) return rc;
     const TvResult* res = (const TvResult*)(hb + h_res);
     for (int i = 0; i < n_sets; ++i) {
         const int o = off0[i], n = off0[i + 1] - o;
@@ -306,30 +283,22 @@ int lpslam_hip_two_view_check_poses(lpslam_hip_ctx* c, int32_t n_hyp, const doub
     const size_t pn = (size_t)n_hyp * (size_t)n;
     // page-locked block: flag | input (the matches, their flags) | results (X, cosines, codes); device block: the input
     const size_t o_in = 64;
-    size_t at = 0;
-    const size_t o_p1 = at; at += al64((size_t)n * 16);
-    const size_t o_p2 = at; at += al64((size_t)n * 16);
-    const size_t o_fl = at; at += al64((size_t)n);
-    const size_t in_bytes = at;
-    const size_t h_x = o_in + in_bytes, h_cos = h_x + al64(pn * 24), h_code = h_cos + al64(pn * 8);
-    const size_t host_bytes = h_code + al64(pn);
-    uint8_t* hb = lp_match_staging(c, host_bytes, host_bytes + host_bytes / 2, s);
-    if (!hb) return LPSLAM_HIP_ERR_DEVICE;
-    LpPoolBlock blk(c);
-    if (int rc = blk.alloc(in_bytes)) return rc;
-    uint8_t* base = (uint8_t*)blk.ptr;
-    uint8_t* in = hb + o_in;
+    LpLayout dev;
+    const size_t o_p1 = dev.take((size_t)n * 16), o_p2 = dev.take((size_t)n * 16), o_fl = dev.take((size_t)n);
+    const size_t in_bytes = dev.at;
+    LpLayout host{o_in + in_bytes};
+    const size_t h_x = host.take(pn * 24), h_cos = host.take(pn * 8), h_code = host.take(pn);
+    LpStagedCall call{c, s, "two_view_check_poses"};
+    if (int rc = call.open(host.at, in_bytes, LP_DONE_TWO_VIEW)) return rc;
+    uint8_t *hb = call.host, *base = call.dev(), *in = hb + o_in;
     memcpy(in + o_p1, p1, (size_t)n * 16); memcpy(in + o_p2, p2, (size_t)n * 16); memcpy(in + o_fl, inlier, (size_t)n);
     PoseHead head{};
     memcpy(head.R, R, (size_t)n_hyp * 72); memcpy(head.t, t, (size_t)n_hyp * 24); memcpy(head.K, K4, 32);
     head.th2 = th2; head.n_hyp = n_hyp; head.n = n;
-    LpDone done{};
-    if (int rc = lp_done_arm(c, kDoneCounter, (int*)hb, c->done_seq, &done)) return rc;
-    LP_HIP(hipMemcpyAsync(base, in, in_bytes, hipMemcpyHostToDevice, s));
+    if (int rc = call.upload(o_in, in_bytes)) return rc;
     hipLaunchKernelGGL(k_tv_pose, dim3((unsigned)((pn + 255) / 256)), dim3(256), 0, s, head, (const double*)(base + o_p1), (const double*)(base + o_p2),
-                       (const uint8_t*)(base + o_fl), (double*)(hb + h_x), (double*)(hb + h_cos), hb + h_code, done.counter, done.flag, done.seq);
-    LP_HIP(hipGetLastError());
-    if (const int w = lp_done_wait(c, done, s)) { if (w == LP_DONE_DEAD) blk.leak(); set_error("two_view_check_poses: the kernel did not complete"); return LPSLAM_HIP_ERR_DEVICE; }
+                       (const uint8_t*)(base + o_fl), (double*)(hb + h_x), (double*)(hb + h_cos), hb + h_code, call.done.counter, call.done.flag, call.done.seq);
+    if (int rc = call.finish()) return rc;
     memcpy(X, hb + h_x, pn * 24); memcpy(cosp, hb + h_cos, pn * 8); memcpy(code, hb + h_code, pn);
     return LPSLAM_HIP_OK;
 }

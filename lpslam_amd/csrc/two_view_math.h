@@ -6,7 +6,7 @@
 //   fundamental_from_matches<N>             eight-point algorithm + rank 2
 //   homography_terms / fundamental_terms    one match's two score terms and its inlier flag
 //   pose_setup / pose_point                 one match under one motion hypothesis: X, the cosine of its parallax, a code
-//   host only: normalize_points (Hartley), sample_table (the 8-match samples; the draw is sequential by definition)
+//   host only: normalize_points (Hartley); the 8-match samples are sample_table<kSample> of ransac_sample.h
 // No heap: every array is of fixed size or the caller's.  The 9 x 9 matrix A^T A and its eigenvectors (162 doubles) live in a
 // workspace of the caller: element e of it is ws[e * stride].  On the device sixteen lanes of a wave estimate one model together:
 // they share the workspace (LDS), divide the 81 sums of A^T A and the independent elements of each Jacobi rotation among them
@@ -231,23 +231,6 @@ inline void normalize_points(const double* in, size_t n, double* out, M3& T)
     const double sx = 1.0 / dx, sy = 1.0 / dy;
     for (size_t i = 0; i < n; ++i) { out[2 * i] *= sx; out[2 * i + 1] *= sy; }
     T = M3{{sx, 0, -mx * sx, 0, sy, -my * sy, 0, 0, 1}};
-}
-
-// The samples of LpSlam::two_view_initialize for a set of n >= 8 matches: xorshift32 from seed ? seed : 1, eight draws per iteration,
-// each a step of a partial Fisher-Yates over avail[0 .. n) that is rebuilt every iteration.  table receives iterations x 8 match
-// indices; avail is n ints of scratch.
-inline void sample_table(int n, int iterations, uint32_t seed, int32_t* table, int* avail)
-{
-    uint32_t s = seed ? seed : 1u;
-    for (int it = 0; it < iterations; ++it) {
-        for (int i = 0; i < n; ++i) avail[i] = i;
-        int left = n;
-        for (int k = 0; k < kSample; ++k) {
-            s ^= s << 13; s ^= s >> 17; s ^= s << 5;
-            const int r = (int)(s % (uint32_t)left);
-            table[kSample * it + k] = avail[r]; avail[r] = avail[left - 1]; --left;
-        }
-    }
 }
 
 }  // namespace lpslam_tv

@@ -1,9 +1,10 @@
 // pnp_batch.cpp -- the CPU side of the batched PnP RANSAC: C shims for the tests and the timing tool.
-//   lpslam_pnp_sample_table        the 4-match samples pnp_solve_ransac draws for a set of n matches (csrc/epnp_math.h)
+//   lpslam_pnp_sample_table        the 4-match samples pnp_solve_ransac draws for a set of n matches (csrc/ransac_sample.h)
 //   lpslam_epnp4_host              the header's epnp<4> on the host (LpSlam::epnp_solve at n = 4 runs the same template at a run-time n)
 //   lpslam_pnp_ransac_batch_host   lpslam_hip_pnp_ransac_batch without the context: pnp_solve_ransac on each set -- the CPU definition
 #include "two_view.h"
 #include "../csrc/epnp_math.h"
+#include "../csrc/ransac_sample.h"
 #include <vector>
 
 #define LP_EXPORT extern "C" __attribute__((visibility("default")))
@@ -13,7 +14,7 @@ LP_EXPORT int lpslam_pnp_sample_table(int n, int iterations, uint32_t seed, int3
 {
     if (n < 4 || iterations < 1 || !table) return 0;
     std::vector<int> avail((size_t)n);
-    lpslam_epnp::sample_table(n, iterations, seed, table, avail.data());
+    lpslam_ransac::sample_table<4>(n, iterations, seed, table, avail.data());
     return 1;
 }
 
@@ -23,13 +24,13 @@ LP_EXPORT int lpslam_epnp4_host(const double* p4, const double* u4, const double
     return lpslam_epnp::epnp<4>(p4, u4, 4, cam, nullptr, nullptr, ws, 1, R9, t3) ? 1 : 0;
 }
 
-// 0: done; 1: refused (the argument rules of lpslam_hip_pnp_ransac_batch), nothing written
+// 0: done; 1: refused (the argument rules of lpslam_hip_pnp_ransac_batch, but for its cap on the iterations), nothing written
 LP_EXPORT int lpslam_pnp_ransac_batch_host(int32_t n_sets, const int32_t* offsets, const double* pw, const double* obs, const double* inv_sigma2, const double* cam4,
                                            int32_t iterations, uint32_t seed, double* pose7, int32_t* n_inliers, uint8_t* inlier, int32_t* best_iteration)
 {
-    if (n_sets < 0 || iterations < 1 || !offsets || !cam4 || (n_sets > 0 && (!pose7 || !n_inliers)) || offsets[0] < 0) return 1;
-    for (int s = 0; s < n_sets; ++s) if (offsets[s + 1] < offsets[s]) return 1;
-    if (offsets[n_sets] > offsets[0] && (!pw || !obs || !inv_sigma2 || !inlier)) return 1;
+    int first = 0, total = 0;
+    if (lpslam_ransac::check_offsets(n_sets, offsets, &first, &total) || iterations < 1 || !cam4 || (n_sets > 0 && (!pose7 || !n_inliers))) return 1;
+    if (total > 0 && (!pw || !obs || !inv_sigma2 || !inlier)) return 1;
     std::vector<int32_t> table;
     std::vector<uint8_t> cur;
     for (int s = 0; s < n_sets; ++s) {

@@ -2,6 +2,7 @@
 #include "two_view.h"
 #include "pose_math.h"
 #include "../csrc/epnp_math.h"
+#include "../csrc/ransac_sample.h"
 #include "../csrc/triangulate_math.h"
 #include "../csrc/two_view_math.h"
 
@@ -54,11 +55,6 @@ void normalize_points(const std::vector<double>& in, std::vector<double>& out, M
     out.resize(in.size());
     lpslam_tv::normalize_points(in.data(), in.size() / 2, out.data(), T);
 }
-
-struct Rng {
-    uint32_t s;
-    uint32_t next() { s ^= s << 13; s ^= s >> 17; s ^= s << 5; return s; }
-};
 
 // the score of a model over all matches: the terms of csrc/two_view_math.h added in index order, first direction then second
 double check_homography(const M3& H21, const M3& H12, const double* p1, const double* p2, size_t n, double sigma, std::vector<uint8_t>& inl)
@@ -238,7 +234,7 @@ void ransac_loop(const Normalised& nm, const double* p1, const double* p2, size_
     if (n < 8 || iterations < 1) return;
     std::vector<int> avail(n);
     std::vector<int32_t> table((size_t)lpslam_tv::kSample * (size_t)iterations);
-    lpslam_tv::sample_table((int)n, iterations, seed, table.data(), avail.data());
+    lpslam_ransac::sample_table<lpslam_tv::kSample>((int)n, iterations, seed, table.data(), avail.data());
     std::vector<uint8_t> inl;
     double best_h = -1, best_f = -1;
     for (int it = 0; it < iterations; ++it) {
@@ -438,14 +434,13 @@ int sim3_solve_ransac(const double* p1c, const double* p2c, const double* obs1, 
                       int n, const double* cam1, const double* cam2, bool fix_scale, int iterations, uint32_t seed, double* s12, uint8_t* inlier)
 {
     if (n < 3) return 0;
-    Rng rng{seed ? seed : 1u};
+    uint32_t rng = seed ? seed : 1u;
     std::vector<int> avail((size_t)n);
     std::vector<uint8_t> cur((size_t)n);
     int best = 0;
     for (int it = 0; it < iterations; ++it) {
-        for (int i = 0; i < n; ++i) avail[(size_t)i] = i;
-        int left = n, idx[3];
-        for (int k = 0; k < 3; ++k) { const int r = (int)(rng.next() % (uint32_t)left); idx[k] = avail[(size_t)r]; avail[(size_t)r] = avail[(size_t)left - 1]; --left; }
+        int32_t idx[3];
+        lpslam_ransac::draw<3>(rng, n, avail.data(), idx);
         double a1[9], a2[9], R[9], t[3], sc;
         for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) { a1[3 * k + a] = p1c[3 * idx[k] + a]; a2[3 * k + a] = p2c[3 * idx[k] + a]; }
         if (!lpslam_epnp::horn(a1, a2, 3, fix_scale, R, t, &sc)) continue;
@@ -490,7 +485,7 @@ int pnp_solve_ransac(const double* pw, const double* obs, const double* inv_sigm
     if (n < 4) return 0;
     std::vector<int> avail((size_t)n);
     std::vector<int32_t> table((size_t)4 * (size_t)std::max(iterations, 0));
-    ep::sample_table(n, iterations, seed, table.data(), avail.data());
+    lpslam_ransac::sample_table<4>(n, iterations, seed, table.data(), avail.data());
     std::vector<uint8_t> cur((size_t)n);
     int best = 0;
     double bestR[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, bestT[3] = {0, 0, 0};

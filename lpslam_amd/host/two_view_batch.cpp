@@ -1,5 +1,5 @@
 // two_view_batch.cpp -- the CPU side of the two-view initialiser's device steps: C shims for the tests and the timing tool.
-//   lpslam_two_view_sample_table        the 8-match samples two_view_initialize draws for a set of n matches (csrc/two_view_math.h)
+//   lpslam_two_view_sample_table        the 8-match samples two_view_initialize draws for a set of n matches (csrc/ransac_sample.h)
 //   lpslam_two_view_models8_host        the header's two estimators at 8 on the host (the instance the RANSAC loop and the kernel run)
 //   lpslam_two_view_ransac_batch_host   lpslam_hip_two_view_ransac_batch without the context: step 1 of two_view_initialize on each set
 //   lpslam_two_view_check_poses_host    lpslam_hip_two_view_check_poses without the context: the per-match part of step 4
@@ -7,6 +7,7 @@
 //   lpslam_two_view_initialize_with     ... or from the caller's functions (the device entry points), with the seconds each step took
 #include "two_view.h"
 #include "../csrc/two_view_math.h"
+#include "../csrc/ransac_sample.h"
 #include <cstring>
 #include <vector>
 
@@ -17,7 +18,7 @@ LP_EXPORT int lpslam_two_view_sample_table(int n, int iterations, uint32_t seed,
 {
     if (n < 8 || iterations < 1 || !table) return 0;
     std::vector<int> avail((size_t)n);
-    lpslam_tv::sample_table(n, iterations, seed, table, avail.data());
+    lpslam_ransac::sample_table<lpslam_tv::kSample>(n, iterations, seed, table, avail.data());
     return 1;
 }
 
@@ -40,9 +41,9 @@ LP_EXPORT void lpslam_two_view_models_host(const double* x1, const double* x2, i
 LP_EXPORT int lpslam_two_view_ransac_batch_host(int32_t n_sets, const int32_t* offsets, const double* p1, const double* p2, double sigma, int32_t iterations, uint32_t seed,
                                                 int32_t* best_iteration, double* score, double* model, uint8_t* inlier_h, uint8_t* inlier_f)
 {
-    if (n_sets < 0 || iterations < 1 || iterations > 1024 || !(sigma > 0) || !__builtin_isfinite(sigma) || !offsets || (n_sets > 0 && (!best_iteration || !score || !model)) || offsets[0] < 0) return 1;
-    for (int s = 0; s < n_sets; ++s) if (offsets[s + 1] < offsets[s]) return 1;
-    if (offsets[n_sets] > offsets[0] && (!p1 || !p2 || !inlier_h || !inlier_f)) return 1;
+    int first = 0, total = 0;
+    if (lpslam_ransac::check_offsets(n_sets, offsets, &first, &total) || iterations < 1 || iterations > 1024 || !(sigma > 0) || !__builtin_isfinite(sigma)) return 1;
+    if ((n_sets > 0 && (!best_iteration || !score || !model)) || (total > 0 && (!p1 || !p2 || !inlier_h || !inlier_f))) return 1;
     LpSlam::TwoViewModels w;
     for (int s = 0; s < n_sets; ++s) {
         const size_t o = (size_t)offsets[s];
