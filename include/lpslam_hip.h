@@ -823,6 +823,42 @@ int lpslam_hip_sim3_transform_optimize(lpslam_hip_ctx* ctx, int32_t n_problems, 
                                        const int32_t* pair_start, const double* cam1, const double* cam2, double chi_sq,
                                        int32_t fix_scale, uint8_t* inlier, int32_t* n_inliers);
 
+/* ---- Sim3 RANSAC and loop verification for a batch of candidates (loop closing) ---------------------------------------
+ * Replaces the loop of LpSlam::sim3_solve_ransac calls (lpslam_amd/host/two_view.h) the loop closer makes, one per candidate keyframe,
+ * and the transform-optimiser call behind them: [UPSTREAM] solve::sim3_solver -- the similarity camera 2 -> camera 1 from matched
+ * landmark pairs alone, Horn's absolute orientation on 3-pair samples inside a RANSAC over the reprojection error in both images
+ * (chi-square 9.210 at the keypoints' levels).  DESIGN.md section 41; the arithmetic is lpslam_amd/csrc/sim3_math.h and horn of
+ * lpslam_amd/csrc/epnp_math.h, the text the host solver runs: the same bits.
+ * Set i owns pairs [pair_start[i], pair_start[i+1]), the input format of lpslam_hip_sim3_transform_optimize; cam = fx fy cx cy;
+ * fix_scale != 0 holds the scale at 1 (stereo / RGBD); every set is sampled with the same seed (xorshift32 from seed ? seed : 1) and
+ * `iterations` samples.
+ *
+ * lpslam_hip_sim3_ransac_batch: per set s12 = qw qx qy qz tx ty tz s of the first sample with the largest count, n_inliers (that
+ * count), the per-pair flags in `inlier` (indexed like the pairs) and, where best_iteration is not NULL, the winning sample (-1: none).
+ * A set with fewer than three pairs, one whose every sample is refused (coincident points under a free scale) and one whose samples
+ * explain no pair answer n_inliers 0, flags cleared, best_iteration -1 and s12 = 1 0 0 0 0 0 0 1.  No refit.  The results are those of
+ * lpslam_sim3_ransac_batch_host (liblpslam.so), sim3_solve_ransac on each set.  One upload, two launches, one wait.
+ *
+ * lpslam_hip_sim3_verify_batch: the same RANSAC, then for every set whose count reaches min_seed_inliers the flow of
+ * lpslam_hip_sim3_transform_optimize from that seed at chi_sq, all on the device.  Per set seed_inliers (the RANSAC's count), s12 (the
+ * optimised similarity), n_inliers (the optimiser's: 0 when fewer than 10 pairs survive its first cut) and, where `inlier` is not NULL,
+ * the optimiser's per-pair flags.  A set below the gate answers n_inliers 0, flags cleared and the RANSAC's seed in s12.  Per set the
+ * results are those of the host solver followed by lpslam_hip_sim3_transform_optimize.  One upload, three launches, one wait.
+ *
+ * n_sets == 0: LPSLAM_HIP_OK, nothing done.  n_sets < 0, a pair_start that starts below 0 or does not ascend, iterations outside
+ * 1 .. LPSLAM_HIP_SIM3_RANSAC_MAX_ITERATIONS, a camera that is no number, a chi_sq that is no positive number, min_seed_inliers < 0 or
+ * NULL where an array is needed (best_iteration and the verify call's inlier alone may be NULL): LPSLAM_HIP_ERR_INVALID with nothing
+ * written. */
+#define LPSLAM_HIP_SIM3_RANSAC_MAX_ITERATIONS 1024
+int lpslam_hip_sim3_ransac_batch(lpslam_hip_ctx* ctx, int32_t n_sets, const lpslam_hip_sim3_pair* pairs, const int32_t* pair_start /* n_sets + 1 */,
+                                 const double* cam1, const double* cam2, int32_t fix_scale, int32_t iterations, uint32_t seed,
+                                 double* s12 /* 8 per set */, int32_t* n_inliers /* per set */, uint8_t* inlier /* per pair */,
+                                 int32_t* best_iteration /* per set, may be NULL */);
+int lpslam_hip_sim3_verify_batch(lpslam_hip_ctx* ctx, int32_t n_sets, const lpslam_hip_sim3_pair* pairs, const int32_t* pair_start /* n_sets + 1 */,
+                                 const double* cam1, const double* cam2, int32_t fix_scale, int32_t iterations, uint32_t seed,
+                                 int32_t min_seed_inliers, double chi_sq, int32_t* seed_inliers /* per set */, double* s12 /* 8 per set, optimised */,
+                                 int32_t* n_inliers /* per set */, uint8_t* inlier /* per pair, may be NULL */);
+
 /* ---- 2-D occupancy grid from laser scans (the reference's map_publisher occupancy_map_export, reached through
  * src/Trackers/OpenVSLAMStereoTracker.cpp:374-400; the grid itself is defined in INTEGRATION.md, "Occupancy grid") ----------
  * Beam directions are uploaded once per scan geometry (cos a, sin a per beam, computed by the caller in double); the ranges of each

@@ -22,14 +22,14 @@ UNIT_DEPS = {
     "match.hip": ["desc_wave.h"],
     "ba.hip": ["ba_common.h", "chol_panel.inl", "ba_build.inl", "ba_solve.inl", "ba_band.inl", "ba_update.inl", "ba_host.inl", "ba_partitioned.inl"],
     "pose_opt.hip": ["ba_common.h"],
-    "sim3.hip": ["ba_common.h"],
+    "sim3.hip": ["ba_common.h", "epnp_math.h", "jacobi_math.h", "ransac_sample.h", "sim3_math.h"],
     "bow.hip": ["desc_wave.h"],
     "share.hip": [],
     "occupancy.hip": [],
     "intensity.hip": [],
     "ingest.hip": ["ingest_math.h"],
     "triangulate.hip": ["desc_wave.h", "triangulate_math.h", "jacobi_math.h"],
-    "pnp.hip": ["epnp_math.h", "jacobi_math.h", "ransac_sample.h", os.path.join(_HOST, "pose_math.h")],
+    "pnp.hip": ["epnp_math.h", "jacobi_math.h", "ransac_sample.h", "sim3_math.h", os.path.join(_HOST, "pose_math.h")],
     "two_view.hip": ["two_view_math.h", "triangulate_math.h", "jacobi_math.h", "ransac_sample.h"],
     "jpeg.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_tables.h")],
     "jpeg_dec.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_header.h"), os.path.join(_HOST, "jpeg_tables.h")],
@@ -79,14 +79,14 @@ def hip_library(force=False, verbose=False):
 
 
 HOST_LIB = os.path.join(HERE, "liblpslam.so")
-HOST_SOURCES = ["slam_manager.cpp", "hip_tracker.cpp", "interface.cpp", "rectify.cpp", "replay.cpp", "two_view.cpp", "bow.cpp", "jpeg.cpp", "jpeg_device.cpp", "map_file.cpp", "record.cpp", "intensity.cpp", "ingest.cpp", "pnp_batch.cpp", "two_view_batch.cpp"]
+HOST_SOURCES = ["slam_manager.cpp", "hip_tracker.cpp", "interface.cpp", "rectify.cpp", "replay.cpp", "two_view.cpp", "bow.cpp", "jpeg.cpp", "jpeg_device.cpp", "map_file.cpp", "record.cpp", "intensity.cpp", "ingest.cpp", "pnp_batch.cpp", "two_view_batch.cpp", "sim3_batch.cpp"]
 
 
 def host_library(force=False, verbose=False):
     """C++ host mirror of the reference interface (g++), linked against the HIP C-ABI library next to it."""
     hdir = os.path.join(HERE, "host")
     srcs = [os.path.join(hdir, s) for s in HOST_SOURCES]
-    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "radtan_math.h"), os.path.join("..", "csrc", "triangulate_math.h"), os.path.join("..", "csrc", "epnp_math.h"), os.path.join("..", "csrc", "jacobi_math.h"), os.path.join("..", "csrc", "two_view_math.h"), os.path.join("..", "csrc", "ransac_sample.h"))] + \
+    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "radtan_math.h"), os.path.join("..", "csrc", "triangulate_math.h"), os.path.join("..", "csrc", "epnp_math.h"), os.path.join("..", "csrc", "jacobi_math.h"), os.path.join("..", "csrc", "two_view_math.h"), os.path.join("..", "csrc", "ransac_sample.h"), os.path.join("..", "csrc", "sim3_math.h"))] + \
         [os.path.join(HERE, "..", "include", h) for h in ("lpslam_types.h", "lpslam_manager.h", "lpslam_hip.h")] + [LIB]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps if os.path.exists(d)):
         return HOST_LIB

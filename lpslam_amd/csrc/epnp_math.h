@@ -95,12 +95,25 @@ LP_EPNP_FN bool horn(const double* x1, const double* x2, int n_points, bool fix_
                     M[6] - M[2], M[1] + M[3], -M[0] + M[4] - M[8], M[5] + M[7],
                     M[1] - M[3], M[6] + M[2], M[5] + M[7], -M[0] - M[4] + M[8]};
     double evec[16];
-    int order[4];
-    lpslam_jacobi::jacobi<4, 4>(N, evec, 1, order);                    // ascending: the last column belongs to the largest eigenvalue
+    int top;                                                           // the column of the largest eigenvalue
+    if constexpr (NFIX == 3) {
+        // a lane of the Sim3 kernel holds the 4 x 4 in registers: no index list with its variable indices (they put the matrix into
+        // scratch), the last column of the ascending order found directly -- the largest eigenvalue, the later one among equal ones
+        lpslam_jacobi::jacobi_sweeps<4, 4, false>(N, evec, 1);
+        top = 0;
+        double dtop = N[0];
+        if (!(N[5] < dtop)) { top = 1; dtop = N[5]; }
+        if (!(N[10] < dtop)) { top = 2; dtop = N[10]; }
+        if (!(N[15] < dtop)) { top = 3; dtop = N[15]; }
+    } else {
+        int order[4];
+        lpslam_jacobi::jacobi<4, 4>(N, evec, 1, order);                // ascending: the last column belongs to the largest eigenvalue
+        top = order[3];
+    }
     double q[4];
     q[0] = evec[0]; q[1] = evec[4]; q[2] = evec[8]; q[3] = evec[12];
     LP_EPNP_UNROLL(3)
-    for (int c = 1; c < 4; ++c) if (order[3] == c) { q[0] = evec[c]; q[1] = evec[4 + c]; q[2] = evec[8 + c]; q[3] = evec[12 + c]; }
+    for (int c = 1; c < 4; ++c) if (top == c) { q[0] = evec[c]; q[1] = evec[4 + c]; q[2] = evec[8 + c]; q[3] = evec[12 + c]; }
     const double qn = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     if (!(qn > 0)) return false;
     for (int k = 0; k < 4; ++k) q[k] /= qn;

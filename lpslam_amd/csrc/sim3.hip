@@ -20,9 +20,13 @@
 
 #include "internal.h"
 #include "ba_common.h"
+#include "epnp_math.h"
+#include "ransac_sample.h"
+#include "sim3_math.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #pragma clang fp contract(off)
@@ -652,18 +656,14 @@ __device__ void s3_t_levenberg(const S3Pair* pairs, const uint8_t* active, int n
     __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void k_sim3_transform(double* s12, const S3Pair* pairs_all, const int* pair_start, const double* cams,
-                                                        double chi_sq, int fix_scale, uint8_t* active_all, uint8_t* inlier_all, int* n_inliers)
+// One problem of the transform optimiser, run by the whole workgroup of 256: the n pairs, the seed s12_in (8 doubles), the result to s12_out
+// (it may be s12_in), the flags to inlier and the count to *n_inliers; active: n bytes of scratch on the device.
+__device__ __forceinline__ void s3_transform_problem(S3TShared& sh, const double* s12_in, double* s12_out, const S3Pair* pairs, int n, const double* c1, const double* c2,
+                                     double chi_sq, int fix_scale, uint8_t* active, uint8_t* inlier, int* n_inliers)
 {
-    __shared__ S3TShared sh;
-    const int pb = blockIdx.x, tid = threadIdx.x;
-    const S3Pair* pairs = pairs_all + pair_start[pb];
-    const int n = pair_start[pb + 1] - pair_start[pb];
-    uint8_t* active = active_all + pair_start[pb];
-    uint8_t* inlier = inlier_all + pair_start[pb];
-    const double* c1 = cams; const double* c2 = cams + 4;
+    const int tid = threadIdx.x;
     const double delta = sqrt(chi_sq);
-    if (tid == 0) { Sim3d S, Si; s3_load(s12 + 8 * (size_t)pb, S); s3_inv(S, Si); sh.S = S; sh.Si = Si; sh.n_bad = 0; sh.n_in = 0; }
+    if (tid == 0) { Sim3d S, Si; s3_load(s12_in, S); s3_inv(S, Si); sh.S = S; sh.Si = Si; sh.n_bad = 0; sh.n_in = 0; }
     for (int k = tid; k < n; k += 256) active[k] = 1;
     __syncthreads();
     s3_t_levenberg(pairs, active, n, c1, c2, delta, fix_scale, 5, sh);
@@ -692,7 +692,227 @@ __global__ __launch_bounds__(256) void k_sim3_transform(double* s12, const S3Pai
     } else {
         for (int k = tid; k < n; k += 256) inlier[k] = 0;
     }
-    if (tid == 0) { s3_store(sh.S, s12 + 8 * (size_t)pb); n_inliers[pb] = n_in; }
+    if (tid == 0) { s3_store(sh.S, s12_out); *n_inliers = n_in; }
+}
+
+__global__ __launch_bounds__(256) void k_sim3_transform(double* s12, const S3Pair* pairs_all, const int* pair_start, const double* cams,
+                                                        double chi_sq, int fix_scale, uint8_t* active_all, uint8_t* inlier_all, int* n_inliers)
+{
+    __shared__ S3TShared sh;
+    const int pb = blockIdx.x;
+    s3_transform_problem(sh, s12 + 8 * (size_t)pb, s12 + 8 * (size_t)pb, pairs_all + pair_start[pb], pair_start[pb + 1] - pair_start[pb], cams, cams + 4,
+                         chi_sq, fix_scale, active_all + pair_start[pb], inlier_all + pair_start[pb], n_inliers + pb);
+}
+
+// ---- loop verification for a batch of candidates ([UPSTREAM] solve::sim3_solver, the host form is
+// LpSlam::sim3_solve_ransac in lpslam_amd/host/two_view.cpp) -------------------------------------------------------------------
+//   host                     the sample table (the 3-pair samples sim3_solve_ransac would draw, ransac_sample.h) and ONE upload of it with the pairs
+//   k_s3r_hypotheses         a lane per (set, iteration): Horn on the three sampled pairs (horn<3> of epnp_math.h, the function the host calls)
+//   k_s3r_score              one workgroup per set, a wave per hypothesis in turn: inliers counted with the host's expression (sim3_inlier of
+//                            sim3_math.h), the winner by the key count << 32 | ~iteration (the lowest iteration among equal counts, the host's
+//                            `count > best`), its flags and record to page-locked memory, its seed and count to the device
+//   k_sim3_transform_gated   one workgroup per set: the transform optimiser above on the seed, for the sets whose count reaches the gate
+// The last kernel of a call releases the done flag (internal.h); the round trip is LpStagedCall.
+struct S3rHead { double cam1[4], cam2[4], chi_sq; int32_t n_sets, iterations, fix_scale, min_seed; uint32_t o_start, o_table, o_pairs, pad; };
+struct S3rResult { int32_t best_iteration, count; double s12[8]; };
+static_assert(sizeof(S3rResult) == 72, "result record");
+constexpr int kS3rHyp = 13;            // doubles per hypothesis: R (9, row major), t (3), s
+
+__global__ __launch_bounds__(64) void k_s3r_hypotheses(const uint8_t* __restrict__ base, double* __restrict__ hyp, int* __restrict__ valid)
+{
+    const S3rHead& head = *(const S3rHead*)base;
+    const int h = blockIdx.x * 64 + threadIdx.x;
+    if (h >= head.n_sets * head.iterations) return;           // (no barrier in this kernel)
+    const int s = h / head.iterations;
+    const int32_t* start = (const int32_t*)(base + head.o_start);
+    const int o = start[s], n = start[s + 1] - o;
+    if (n < 3) { valid[h] = 0; return; }
+    const int32_t* idx = (const int32_t*)(base + head.o_table) + 3 * (size_t)h;
+    const S3Pair* pairs = (const S3Pair*)(base + head.o_pairs) + (size_t)o;
+    double a1[9], a2[9], R[9], t[3], sc;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const S3Pair& pr = pairs[min(max(idx[k], 0), n - 1)];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { a1[3 * k + a] = pr.p1c[a]; a2[3 * k + a] = pr.p2c[a]; }
+    }
+    const bool ok = lpslam_epnp::horn<3>(a1, a2, 3, head.fix_scale != 0, R, t, &sc);
+    valid[h] = ok ? 1 : 0;
+    if (ok) {
+        double* out = hyp + kS3rHyp * (size_t)h;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out[k] = R[k];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[9 + k] = t[k];
+        out[12] = sc;
+    }
+}
+
+__device__ __forceinline__ bool s3r_pair_inlier(const double* Rts, const S3Pair& p, const double* c1, const double* c2)
+{
+    return lpslam_sim3::sim3_inlier(Rts, Rts + 9, Rts[12], p.p1c, p.p2c, p.obs1, p.obs2, p.w1, p.w2, c1, c2);
+}
+
+// flag == nullptr: another kernel follows on the stream and signals (the verify call); this one then only makes its stores to
+// page-locked memory visible to the host
+__global__ __launch_bounds__(256) void k_s3r_score(const uint8_t* __restrict__ base, const double* __restrict__ hyp, const int* __restrict__ valid,
+                                                   S3rResult* __restrict__ res, uint8_t* __restrict__ flags, double* __restrict__ d_s12, int* __restrict__ d_count,
+                                                   unsigned* counter, int* flag, int seq)
+{
+    __shared__ unsigned long long wkey[4];
+    const S3rHead& head = *(const S3rHead*)base;
+    const int s = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t* start = (const int32_t*)(base + head.o_start);
+    const int o = start[s], n = start[s + 1] - o;
+    const S3Pair* pairs = (const S3Pair*)(base + head.o_pairs) + (size_t)o;
+    double c1[4], c2[4];
+    for (int k = 0; k < 4; ++k) { c1[k] = head.cam1[k]; c2[k] = head.cam2[k]; }
+    unsigned long long best = 0;
+    if (n >= 3)
+        for (int it = wave; it < head.iterations; it += 4) {              // the same for every lane of a wave
+            const size_t h = (size_t)s * (size_t)head.iterations + (size_t)it;
+            if (!valid[h]) continue;
+            double Rts[kS3rHyp];
+            for (int k = 0; k < kS3rHyp; ++k) Rts[k] = hyp[kS3rHyp * h + k];
+            int count = 0;
+            for (int i0 = 0; i0 < n; i0 += 64) {
+                const int i = i0 + lane;
+                const bool in = i < n && s3r_pair_inlier(Rts, pairs[i], c1, c2);
+                count += __popcll(__ballot(in));
+            }
+            const unsigned long long key = (unsigned long long)count << 32 | (unsigned long long)(~(uint32_t)it);
+            if (count > 0 && key > best) best = key;
+        }
+    if (lane == 0) wkey[wave] = best;
+    __syncthreads();
+    best = wkey[0];
+    for (int k = 1; k < 4; ++k) if (wkey[k] > best) best = wkey[k];
+    const int count = (int)(best >> 32);
+    const int it = (int)(~(uint32_t)(best & 0xffffffffu));
+    uint8_t* fl = flags + o;
+    S3rResult r{};
+    if (count == 0) {                                                     // nothing found: no sample, or none that explains a pair
+        for (int i = threadIdx.x; i < n; i += 256) fl[i] = 0;
+        r.best_iteration = -1; r.count = 0; r.s12[0] = 1.0; r.s12[7] = 1.0;
+    } else {
+        const size_t h = (size_t)s * (size_t)head.iterations + (size_t)it;
+        double Rts[kS3rHyp];
+        for (int k = 0; k < kS3rHyp; ++k) Rts[k] = hyp[kS3rHyp * h + k];
+        for (int i = threadIdx.x; i < n; i += 256) fl[i] = s3r_pair_inlier(Rts, pairs[i], c1, c2) ? 1 : 0;
+        r.best_iteration = it; r.count = count;
+        lpslam_sim3::rot_to_quat(Rts, r.s12);
+        for (int k = 0; k < 3; ++k) r.s12[4 + k] = Rts[9 + k];
+        r.s12[7] = Rts[12];
+    }
+    if (threadIdx.x == 0) {
+        res[s] = r;
+        for (int k = 0; k < 8; ++k) d_s12[8 * (size_t)s + k] = r.s12[k];
+        d_count[s] = r.count;
+    }
+    if (flag) lp_signal_done(counter, flag, seq);
+    else __threadfence_system();
+}
+
+// The transform optimiser behind the gate.  A set whose RANSAC count is below head.min_seed runs nothing -- the branch is the whole
+// workgroup's, in front of every barrier of the optimiser -- and the host answers for it (n_inliers 0, flags cleared, the seed);
+// every workgroup arrives at the counter, the last one releases the flag.
+__global__ __launch_bounds__(256) void k_sim3_transform_gated(const uint8_t* __restrict__ base, const double* d_s12, const int* __restrict__ d_count, uint8_t* active_all,
+                                                              double* s12_out, uint8_t* inlier_all, int* n_inliers, unsigned* counter, int* flag, int seq)
+{
+    __shared__ S3TShared sh;
+    const S3rHead& head = *(const S3rHead*)base;
+    const int pb = blockIdx.x;
+    if (d_count[pb] >= head.min_seed) {
+        const int32_t* start = (const int32_t*)(base + head.o_start);
+        const int o = start[pb], n = start[pb + 1] - o;
+        s3_transform_problem(sh, d_s12 + 8 * (size_t)pb, s12_out + 8 * (size_t)pb, (const S3Pair*)(base + head.o_pairs) + (size_t)o, n, head.cam1, head.cam2,
+                             head.chi_sq, head.fix_scale, active_all + o, inlier_all + o, n_inliers + pb);
+    }
+    lp_signal_done(counter, flag, seq);
+}
+
+// Both entry points: the RANSAC alone (verify false: s12 / n_inliers / inlier / best_iteration are the RANSAC's) or RANSAC, gate and
+// optimiser (verify true: seed_inliers is the RANSAC's count, the rest the optimiser's).  The arguments are checked by the callers.
+int s3r_run(lpslam_hip_ctx* c, const char* who, bool verify, int32_t n_sets, const lpslam_hip_sim3_pair* pairs, const int32_t* pair_start, int first, int total,
+            const double* cam1, const double* cam2, int32_t fix_scale, int32_t iterations, uint32_t seed, int32_t min_seed, double chi_sq,
+            int32_t* seed_inliers, double* s12, int32_t* n_inliers, uint8_t* inlier, int32_t* best_iteration)
+{
+    static_assert(sizeof(lpslam_hip_sim3_pair) == sizeof(S3Pair), "pair layout");
+    const size_t n_hyp = (size_t)n_sets * (size_t)iterations;
+    if (n_hyp > (size_t)0x7fffffff / 4) { set_error("%s: %d sets x %d iterations do not fit one launch", who, n_sets, iterations); return LPSLAM_HIP_ERR_CAPACITY; }
+    LP_HIP(hipSetDevice(c->cfg.device));
+    hipStream_t s = c->stream;
+    const LpMatchTrace tr;
+    // page-locked block: flag | input (head, offsets rebased to 0, sample table, pairs) | results (a record per set, the RANSAC's flag per
+    // pair; verify: the optimised s12, its count per set, its flag per pair); device block: the input, then the hypotheses (R, t, s), their
+    // valid flags, the seeds and counts the optimiser reads and its active flags
+    const size_t o_in = 64, tot1 = (size_t)std::max(total, 1);
+    LpLayout dev;
+    dev.take(sizeof(S3rHead));
+    const size_t o_start = dev.take((size_t)(n_sets + 1) * 4), o_table = dev.take(n_hyp * 12), o_pairs = dev.take(tot1 * sizeof(S3Pair));
+    const size_t in_bytes = dev.at;
+    const size_t d_hyp = dev.take(n_hyp * kS3rHyp * 8), d_valid = dev.take(n_hyp * 4), d_seed = dev.take((size_t)n_sets * 64), d_cnt = dev.take((size_t)n_sets * 4), d_act = dev.take(tot1);
+    LpLayout host{o_in + in_bytes};
+    const size_t h_res = host.take((size_t)n_sets * sizeof(S3rResult)), h_flags = host.take(tot1);
+    const size_t h_s12 = host.take((size_t)n_sets * 64), h_cnt = host.take((size_t)n_sets * 4), h_inl = host.take(tot1);
+    LpStagedCall call{c, s, who};
+    if (int rc = call.open(host.at, dev.at, LP_DONE_SIM3_RANSAC)) return rc;
+    uint8_t *hb = call.host, *base = call.dev(), *in = hb + o_in;
+    S3rHead head{};
+    for (int k = 0; k < 4; ++k) { head.cam1[k] = cam1[k]; head.cam2[k] = cam2[k]; }
+    head.chi_sq = chi_sq; head.n_sets = n_sets; head.iterations = iterations; head.fix_scale = fix_scale ? 1 : 0; head.min_seed = min_seed;
+    head.o_start = (uint32_t)o_start; head.o_table = (uint32_t)o_table; head.o_pairs = (uint32_t)o_pairs;
+    memcpy(in, &head, sizeof head);
+    int32_t* off0 = (int32_t*)(in + o_start);
+    for (int i = 0; i <= n_sets; ++i) off0[i] = pair_start[i] - first;
+    lpslam_ransac::batch_tables<3>(n_sets, off0, iterations, seed, (int32_t*)(in + o_table));
+    if (total > 0) memcpy(in + o_pairs, pairs + (size_t)first, (size_t)total * sizeof(S3Pair));
+    const double tr_staged = tr.us();
+    if (int rc = call.upload(o_in, in_bytes)) return rc;
+    double* hyp = (double*)(base + d_hyp); int* valid = (int*)(base + d_valid);
+    hipLaunchKernelGGL(k_s3r_hypotheses, dim3((unsigned)((n_hyp + 63) / 64)), dim3(64), 0, s, (const uint8_t*)base, hyp, valid);
+    hipLaunchKernelGGL(k_s3r_score, dim3((unsigned)n_sets), dim3(256), 0, s, (const uint8_t*)base, (const double*)hyp, (const int*)valid,
+                       (S3rResult*)(hb + h_res), hb + h_flags, (double*)(base + d_seed), (int*)(base + d_cnt),
+                       call.done.counter, verify ? (int*)nullptr : call.done.flag, call.done.seq);
+    if (verify)
+        hipLaunchKernelGGL(k_sim3_transform_gated, dim3((unsigned)n_sets), dim3(256), 0, s, (const uint8_t*)base, (const double*)(base + d_seed), (const int*)(base + d_cnt),
+                           base + d_act, (double*)(hb + h_s12), hb + h_inl, (int*)(hb + h_cnt), call.done.counter, call.done.flag, call.done.seq);
+    if (int rc = call.finish()) return rc;
+    const S3rResult* res = (const S3rResult*)(hb + h_res);
+    for (int i = 0; i < n_sets; ++i) {
+        const int o = off0[i], n = off0[i + 1] - o;
+        uint8_t* out_fl = inlier ? inlier + (size_t)(first + o) : nullptr;
+        if (!verify) {
+            memcpy(s12 + 8 * (size_t)i, res[i].s12, 64);
+            n_inliers[i] = res[i].count;
+            if (best_iteration) best_iteration[i] = res[i].best_iteration;
+            if (n > 0) memcpy(out_fl, hb + h_flags + o, (size_t)n);
+            continue;
+        }
+        seed_inliers[i] = res[i].count;
+        if (res[i].count < min_seed) {                                     // gated out: the seed as the RANSAC left it
+            memcpy(s12 + 8 * (size_t)i, res[i].s12, 64);
+            n_inliers[i] = 0;
+            if (out_fl && n > 0) memset(out_fl, 0, (size_t)n);
+        } else {
+            memcpy(s12 + 8 * (size_t)i, hb + h_s12 + 64 * (size_t)i, 64);
+            n_inliers[i] = ((const int32_t*)(hb + h_cnt))[i];
+            if (out_fl && n > 0) memcpy(out_fl, hb + h_inl + o, (size_t)n);
+        }
+    }
+    if (tr.on()) fprintf(stderr, "%s: %d sets, %d pairs, %d iterations; us: staged %.1f, results back %.1f\n", who, n_sets, total, iterations, tr_staged, tr.us());
+    return LPSLAM_HIP_OK;
+}
+
+// the argument rules both calls share; nullptr: they hold
+const char* s3r_check(int32_t n_sets, const int32_t* pair_start, const double* cam1, const double* cam2, int32_t iterations, int* first, int* total)
+{
+    static thread_local char why[96];
+    if (const char* w = lpslam_ransac::check_offsets(n_sets, pair_start, first, total)) return w;
+    if (iterations < 1 || iterations > LPSLAM_HIP_SIM3_RANSAC_MAX_ITERATIONS) { snprintf(why, sizeof why, "%d iterations outside 1 .. %d", iterations, LPSLAM_HIP_SIM3_RANSAC_MAX_ITERATIONS); return why; }
+    if (!cam1 || !cam2) return "null argument";
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(cam1[k]) || !std::isfinite(cam2[k])) return "a camera is no number";
+    return nullptr;
 }
 
 }  // namespace
@@ -920,6 +1140,31 @@ int lpslam_hip_sim3_transform_optimize(lpslam_hip_ctx* ctx, int32_t n_problems, 
 #undef T_HIP
     release();
     return LPSLAM_HIP_OK;
+}
+
+int lpslam_hip_sim3_ransac_batch(lpslam_hip_ctx* c, int32_t n_sets, const lpslam_hip_sim3_pair* pairs, const int32_t* pair_start, const double* cam1, const double* cam2,
+                                 int32_t fix_scale, int32_t iterations, uint32_t seed, double* s12, int32_t* n_inliers, uint8_t* inlier, int32_t* best_iteration)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    int first = 0, total = 0;
+    if (const char* why = s3r_check(n_sets, pair_start, cam1, cam2, iterations, &first, &total)) { set_error("sim3_ransac_batch: %s", why); return LPSLAM_HIP_ERR_INVALID; }
+    if ((n_sets > 0 && (!s12 || !n_inliers)) || (total > 0 && (!pairs || !inlier))) { set_error("sim3_ransac_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    if (n_sets == 0) return LPSLAM_HIP_OK;
+    return s3r_run(c, "sim3_ransac_batch", false, n_sets, pairs, pair_start, first, total, cam1, cam2, fix_scale, iterations, seed, 0, 1.0, nullptr, s12, n_inliers, inlier, best_iteration);
+}
+
+int lpslam_hip_sim3_verify_batch(lpslam_hip_ctx* c, int32_t n_sets, const lpslam_hip_sim3_pair* pairs, const int32_t* pair_start, const double* cam1, const double* cam2,
+                                 int32_t fix_scale, int32_t iterations, uint32_t seed, int32_t min_seed_inliers, double chi_sq,
+                                 int32_t* seed_inliers, double* s12, int32_t* n_inliers, uint8_t* inlier)
+{
+    if (!c) { set_error("null context"); return LPSLAM_HIP_ERR_INVALID; }
+    int first = 0, total = 0;
+    if (const char* why = s3r_check(n_sets, pair_start, cam1, cam2, iterations, &first, &total)) { set_error("sim3_verify_batch: %s", why); return LPSLAM_HIP_ERR_INVALID; }
+    if (!(chi_sq > 0) || !std::isfinite(chi_sq)) { set_error("sim3_verify_batch: chi_sq is no positive number"); return LPSLAM_HIP_ERR_INVALID; }
+    if (min_seed_inliers < 0) { set_error("sim3_verify_batch: min_seed_inliers = %d is negative", min_seed_inliers); return LPSLAM_HIP_ERR_INVALID; }
+    if ((n_sets > 0 && (!seed_inliers || !s12 || !n_inliers)) || (total > 0 && !pairs)) { set_error("sim3_verify_batch: null argument"); return LPSLAM_HIP_ERR_INVALID; }
+    if (n_sets == 0) return LPSLAM_HIP_OK;
+    return s3r_run(c, "sim3_verify_batch", true, n_sets, pairs, pair_start, first, total, cam1, cam2, fix_scale, iterations, seed, min_seed_inliers, chi_sq, seed_inliers, s12, n_inliers, inlier, nullptr);
 }
 
 }  // extern "C"

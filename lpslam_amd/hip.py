@@ -43,6 +43,7 @@ SYMBOLS = [
     "lpslam_hip_ba_local", "lpslam_hip_ba_set_points_fixed", "lpslam_hip_ba_pose_optimize", "lpslam_hip_pose_optimize", "lpslam_hip_ba_reset", "lpslam_hip_ba_set_state", "lpslam_hip_prefetch_begin", "lpslam_hip_prefetch_end", "lpslam_hip_prefetch_join", "lpslam_hip_ba_get", "lpslam_hip_ba_chi2", "lpslam_hip_ba_reduced_buffer",
     "lpslam_hip_ba_step_begin", "lpslam_hip_ba_step_lambda0", "lpslam_hip_ba_step_solve", "lpslam_hip_ba_scalar_buffer", "lpslam_hip_ba_step_end", "lpslam_hip_ba_status",
     "lpslam_hip_sim3_create", "lpslam_hip_sim3_destroy", "lpslam_hip_sim3_optimize", "lpslam_hip_sim3_get", "lpslam_hip_sim3_chi2", "lpslam_hip_sim3_transform_optimize",
+    "lpslam_hip_sim3_ransac_batch", "lpslam_hip_sim3_verify_batch",
     "lpslam_hip_scan_geometry_put", "lpslam_hip_scan_store_put", "lpslam_hip_scan_store_drop", "lpslam_hip_occupancy_build",
     "lpslam_hip_jpeg_create", "lpslam_hip_jpeg_destroy", "lpslam_hip_jpeg_encode",
     "lpslam_hip_jpeg_dec_create", "lpslam_hip_jpeg_dec_create2", "lpslam_hip_jpeg_dec_destroy", "lpslam_hip_jpeg_decode", "lpslam_hip_jpeg_dec_last",
@@ -1307,6 +1308,69 @@ def sim3_transform_optimize(ctx, s12, pairs_list, cam1, cam2, chi_sq=10.0, fix_s
     f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]
     _check(f(ctx.h, n, _p(s), _p(pairs), _p(start), _p(c1), _p(c2), float(chi_sq), int(fix_scale), _p(inl), _p(cnt)))
     return s, [inl[start[i]:start[i + 1]].astype(bool) for i in range(n)], cnt[:n].copy()
+
+
+SIM3_RANSAC_MAX_ITERATIONS = 1024          # LPSLAM_HIP_SIM3_RANSAC_MAX_ITERATIONS
+
+
+def _sim3_batch_arrays(pairs_list, cam1, cam2, first=0):
+    """the pairs of all sets in one array behind `first` unused records, pair_start (from `first`), both cameras"""
+    n = len(pairs_list)
+    start = np.full(n + 1, int(first), np.int32); start[1:] += np.cumsum([len(p) for p in pairs_list], dtype=np.int64).astype(np.int32)
+    pairs = np.ascontiguousarray(np.concatenate([np.zeros(int(first), SIM3_PAIR_DTYPE)] + [np.ascontiguousarray(p, SIM3_PAIR_DTYPE) for p in pairs_list]), SIM3_PAIR_DTYPE)
+    return n, start, pairs, np.ascontiguousarray(cam1, np.float64), np.ascontiguousarray(cam2, np.float64)
+
+
+_SIM3_RANSAC_ARGS = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+def _sim3_ransac(f, head, pairs_list, cam1, cam2, fix_scale, iterations, seed, want_iteration, first):
+    n, start, pairs, c1, c2 = _sim3_batch_arrays(pairs_list, cam1, cam2, first)
+    s12 = np.zeros((max(n, 1), 8)); cnt = np.zeros(max(n, 1), np.int32); inl = np.zeros(max(len(pairs), 1), np.uint8); best = np.full(max(n, 1), -1, np.int32)
+    rc = f(*head, n, _p(pairs), _p(start), _p(c1), _p(c2), int(bool(fix_scale)), int(iterations), int(seed) & 0xffffffff, _p(s12), _p(cnt), _p(inl), _p(best) if want_iteration else None)
+    return rc, (s12[:n], cnt[:n], [inl[start[i]:start[i + 1]].copy() for i in range(n)], (best[:n] if want_iteration else None))
+
+
+def sim3_ransac_batch(ctx, pairs_list, cam1, cam2, fix_scale=True, iterations=200, seed=0x9E3779B9, want_iteration=True, first=0):
+    """lpslam_hip_sim3_ransac_batch: one SIM3_PAIR_DTYPE array per set (`first`: pair_start[0], that many unused records in front);
+    returns s12 (S, 8), n_inliers (S), a list of per-pair flags and the winning iteration per set (-1: none; None when not asked for)"""
+    f = ctx.lib.lpslam_hip_sim3_ransac_batch
+    f.argtypes = [C.c_void_p] + _SIM3_RANSAC_ARGS
+    rc, out = _sim3_ransac(f, (ctx.h,), pairs_list, cam1, cam2, fix_scale, iterations, seed, want_iteration, first)
+    _check(rc)
+    return out
+
+
+def sim3_ransac_batch_host(pairs_list, cam1, cam2, fix_scale=True, iterations=200, seed=0x9E3779B9, want_iteration=True, first=0):
+    """lpslam_sim3_ransac_batch_host: LpSlam::sim3_solve_ransac on each set, the CPU definition of sim3_ransac_batch (same results)"""
+    f = host_lib().lpslam_sim3_ransac_batch_host
+    f.argtypes = _SIM3_RANSAC_ARGS; f.restype = C.c_int
+    rc, out = _sim3_ransac(f, (), pairs_list, cam1, cam2, fix_scale, iterations, seed, want_iteration, first)
+    if rc:
+        raise LpslamHipError("lpslam_sim3_ransac_batch_host refused its arguments")
+    return out
+
+
+def sim3_sample_table(n, iterations, seed):
+    """lpslam_sim3_sample_table: the (iterations, 3) pair indices sim3_solve_ransac draws for a set of n >= 3 pairs"""
+    f = host_lib().lpslam_sim3_sample_table
+    f.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p]; f.restype = C.c_int
+    table = np.full((max(int(iterations), 1), 3), -1, np.int32)
+    if not f(int(n), int(iterations), int(seed) & 0xffffffff, _p(table)):
+        raise LpslamHipError("lpslam_sim3_sample_table: n < 3 or iterations < 1")
+    return table
+
+
+def sim3_verify_batch(ctx, pairs_list, cam1, cam2, fix_scale=True, iterations=200, seed=0x9E3779B9, min_seed_inliers=12, chi_sq=10.0, want_inlier=True):
+    """lpslam_hip_sim3_verify_batch: RANSAC, gate and transform optimiser for a batch of loop candidates in one call; returns
+    seed_inliers (S), s12 (S, 8), n_inliers (S) and a list of the optimiser's per-pair flags (None when not asked for)"""
+    n, start, pairs, c1, c2 = _sim3_batch_arrays(pairs_list, cam1, cam2)
+    seed_cnt = np.zeros(max(n, 1), np.int32); s12 = np.zeros((max(n, 1), 8)); cnt = np.zeros(max(n, 1), np.int32); inl = np.zeros(max(len(pairs), 1), np.uint8)
+    f = ctx.lib.lpslam_hip_sim3_verify_batch
+    f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    _check(f(ctx.h, n, _p(pairs), _p(start), _p(c1), _p(c2), int(bool(fix_scale)), int(iterations), int(seed) & 0xffffffff, int(min_seed_inliers), float(chi_sq),
+             _p(seed_cnt), _p(s12), _p(cnt), _p(inl) if want_inlier else None))
+    return seed_cnt[:n], s12[:n], cnt[:n], ([inl[start[i]:start[i + 1]].copy() for i in range(n)] if want_inlier else None)
 
 
 def match_orientation_filter(angle_q, angle_t, match_idx):

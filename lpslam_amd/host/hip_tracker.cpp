@@ -38,6 +38,7 @@ HipVslamTrackerBase::HipVslamTrackerBase()
     o.optional("triangulateNeighbours", 0);
     // relocalisation: the candidates' PnP RANSAC in one call on the device; false: one host solve per candidate
     o.optional("relocaliseOnDevice", false);
+    o.optional("verifyLoopsOnDevice", false);
     o.optional("initialiseOnDevice", false);
 }
 
@@ -66,6 +67,7 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_fisheyeMaxAngleDeg = o.getDouble("fisheyeMaxAngleDeg");
     m_triangulateNeighbours = o.getInteger("triangulateNeighbours");
     m_relocaliseOnDevice = o.getBool("relocaliseOnDevice");
+    m_verifyLoopsOnDevice = o.getBool("verifyLoopsOnDevice");
     m_initialiseOnDevice = o.getBool("initialiseOnDevice");
 }
 
@@ -1797,45 +1799,84 @@ bool HipVslamTrackerBase::detectAndCloseLoop(FrameData& cur, int c)
     // 3-match samples, RANSAC over the reprojection error in both images), independent of the drifted estimates; the Sim3 optimiser
     // on the device refines it.  Monocular maps drift in scale, so the scale is free there and fixed for stereo.
     const bool fix_scale = m_stereo;
+    const auto t_try = std::chrono::steady_clock::now();
+    ++m_stats.loop_tries;
     std::vector<lpslam_hip_sim3_pair> pairs;
     std::vector<int32_t> start{0};
     std::vector<double> s12;
     std::vector<int> vote_kf;
     const Mat3 Rc = quatToRot(kc.pose.q);
     const double cam[4] = {m_cam.f_x, m_cam.f_y, m_cam.c_x, m_cam.c_y};
-    for (auto& v : votes) {
+    // the pairs of one vote behind those already there: landmark of c in c's camera, landmark of the candidate in the candidate's, both
+    // keypoints and 1 / scale^2 of their levels (the optimiser's input format, which the solvers take too)
+    auto appendPairs = [&](const Vote& v) {
         const Keyframe& ka = m_kfs[(size_t)v.kf];
         const Mat3 Ra = quatToRot(ka.pose.q);
-        const size_t first = pairs.size(), np_ = v.pairs.size();
-        std::vector<double> p1((size_t)3 * np_), p2((size_t)3 * np_), o1((size_t)2 * np_), o2((size_t)2 * np_), w1(np_), w2(np_);
-        for (size_t n_ = 0; n_ < np_; ++n_) {
+        for (size_t n_ = 0; n_ < v.pairs.size(); ++n_) {
             const size_t ic = (size_t)v.pairs[n_].first, ia = (size_t)v.pairs[n_].second;
             const Landmark& lc = m_landmarks.at(resolve(kc.landmark[ic]));
             const Landmark& la = m_landmarks.at(resolve(ka.landmark[ia]));
             lpslam_hip_sim3_pair pr{};
             transform(Rc, kc.pose.t, lc.p, pr.p1c); transform(Ra, ka.pose.t, la.p, pr.p2c);
-            std::copy(pr.p1c, pr.p1c + 3, &p1[3 * n_]); std::copy(pr.p2c, pr.p2c + 3, &p2[3 * n_]);
             pr.obs1[0] = kc.kpts[ic].x; pr.obs1[1] = kc.kpts[ic].y; pr.obs2[0] = ka.kpts[ia].x; pr.obs2[1] = ka.kpts[ia].y;
             const double s1 = m_scales[kc.kpts[ic].octave], s2 = m_scales[ka.kpts[ia].octave];
             pr.inv_sigma2_1 = 1.0 / (s1 * s1); pr.inv_sigma2_2 = 1.0 / (s2 * s2);
-            o1[2 * n_] = pr.obs1[0]; o1[2 * n_ + 1] = pr.obs1[1]; o2[2 * n_] = pr.obs2[0]; o2[2 * n_ + 1] = pr.obs2[1];
-            w1[n_] = pr.inv_sigma2_1; w2[n_] = pr.inv_sigma2_2;
             pairs.push_back(pr);
         }
-        double seed12[8];
-        std::vector<uint8_t> seed_inl(np_);
-        const int found = sim3_solve_ransac(p1.data(), p2.data(), o1.data(), o2.data(), w1.data(), w2.data(), (int)np_, cam, cam, fix_scale, 200, 0x9E3779B9u, seed12, seed_inl.data());
-        // a seed needs 12 inliers ([UPSTREAM] asks the solver for 20 of its several hundred bag-of-words matches); the count that
-        // decides stays the optimiser's: 20
-        if (found < 12) { pairs.resize(first); continue; }
-        start.push_back((int32_t)pairs.size());
-        s12.insert(s12.end(), seed12, seed12 + 8);
-        vote_kf.push_back(v.kf);
+    };
+    // a seed needs 12 inliers ([UPSTREAM] asks the solver for 20 of its several hundred bag-of-words matches); the count that
+    // decides stays the optimiser's: 20
+    const int kSeedInliers = 12;
+    std::vector<int32_t> n_inl;
+    // the host path: the solver per vote, the votes whose seed passes the gate kept, then the optimiser for those
+    auto verifyOnHost = [&]() -> bool {
+        pairs.clear(); start.assign(1, 0); s12.clear(); vote_kf.clear();
+        for (auto& v : votes) {
+            const size_t first = pairs.size(), np_ = v.pairs.size();
+            appendPairs(v);
+            std::vector<double> p1((size_t)3 * np_), p2((size_t)3 * np_), o1((size_t)2 * np_), o2((size_t)2 * np_), w1(np_), w2(np_);
+            for (size_t n_ = 0; n_ < np_; ++n_) {
+                const lpslam_hip_sim3_pair& pr = pairs[first + n_];
+                std::copy(pr.p1c, pr.p1c + 3, &p1[3 * n_]); std::copy(pr.p2c, pr.p2c + 3, &p2[3 * n_]);
+                o1[2 * n_] = pr.obs1[0]; o1[2 * n_ + 1] = pr.obs1[1]; o2[2 * n_] = pr.obs2[0]; o2[2 * n_ + 1] = pr.obs2[1];
+                w1[n_] = pr.inv_sigma2_1; w2[n_] = pr.inv_sigma2_2;
+            }
+            double seed12[8];
+            std::vector<uint8_t> seed_inl(np_);
+            const int found = sim3_solve_ransac(p1.data(), p2.data(), o1.data(), o2.data(), w1.data(), w2.data(), (int)np_, cam, cam, fix_scale, 200, 0x9E3779B9u, seed12, seed_inl.data());
+            if (found < kSeedInliers) { pairs.resize(first); continue; }
+            start.push_back((int32_t)pairs.size());
+            s12.insert(s12.end(), seed12, seed12 + 8);
+            vote_kf.push_back(v.kf);
+        }
+        if (vote_kf.empty()) return false;
+        std::vector<uint8_t> inl(pairs.size());
+        n_inl.assign(vote_kf.size(), 0);
+        return lpslam_hip_sim3_transform_optimize(m_ctx, (int32_t)vote_kf.size(), s12.data(), pairs.data(), start.data(), cam, cam, 10.0, fix_scale ? 1 : 0, inl.data(), n_inl.data()) == LPSLAM_HIP_OK;
+    };
+    // verifyLoopsOnDevice: the pairs of all votes first, ONE call for solver, gate and optimiser (lpslam_hip_sim3_verify_batch, per set
+    // the results of the host path); the sets below the gate come back with n_inliers 0 and never win.  -1: the call failed
+    auto verifyOnDevice = [&]() -> int {
+        pairs.clear(); start.assign(1, 0); vote_kf.clear();
+        for (auto& v : votes) { appendPairs(v); start.push_back((int32_t)pairs.size()); vote_kf.push_back(v.kf); }
+        s12.assign(8 * vote_kf.size(), 0.0);
+        n_inl.assign(vote_kf.size(), 0);
+        std::vector<int32_t> seed_cnt(vote_kf.size(), 0);
+        if (lpslam_hip_sim3_verify_batch(m_ctx, (int32_t)vote_kf.size(), pairs.data(), start.data(), cam, cam, fix_scale ? 1 : 0, 200, 0x9E3779B9u, kSeedInliers, 10.0,
+                                         seed_cnt.data(), s12.data(), n_inl.data(), nullptr) != LPSLAM_HIP_OK) return -1;
+        ++m_stats.sim3_batches;
+        bool any = false;
+        for (size_t i = 0; i < vote_kf.size(); ++i) { if (seed_cnt[i] >= kSeedInliers) any = true; else n_inl[i] = 0; }
+        return any ? 1 : 0;
+    };
+    int verified = -1;
+    if (m_verifyLoopsOnDevice) {
+        verified = verifyOnDevice();
+        if (verified < 0) logMessage(LpSlamLogLevel_Error, std::string("loop verification on the device: ") + lpslam_hip_last_error() + "; this keyframe's candidates are verified on the host");
     }
-    if (vote_kf.empty()) return false;
-    std::vector<uint8_t> inl(pairs.size());
-    std::vector<int32_t> n_inl(vote_kf.size(), 0);
-    if (lpslam_hip_sim3_transform_optimize(m_ctx, (int32_t)vote_kf.size(), s12.data(), pairs.data(), start.data(), cam, cam, 10.0, fix_scale ? 1 : 0, inl.data(), n_inl.data()) != LPSLAM_HIP_OK) return false;
+    if (verified < 0) verified = verifyOnHost() ? 1 : 0;
+    m_stats.t_loop_try += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_try).count();
+    if (!verified) return false;
     int best = -1;
     for (size_t i = 0; i < vote_kf.size(); ++i) if (n_inl[i] >= 20 && (best < 0 || n_inl[i] > n_inl[(size_t)best])) best = (int)i;
     if (best < 0) return false;
@@ -2124,13 +2165,13 @@ void HipVslamTrackerBase::storeDescriptors(int key, Keyframe& kf)
 void HipVslamTrackerBase::logStatistics()
 {
     const Statistics& s = m_stats;
-    char buf[2048];
+    char buf[3072];
     const double per = s.frames > 0 ? 1e3 / (double)s.frames : 0.0;
     int64_t dev[LPSLAM_HIP_BA_COUNTERS] = {0};        // what happened to the windows on the device: graph cache, replays, timed-out hand-overs
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld pnp_batches=%ld reloc_frames=%ld ms_reloc_frame=%.4f init_attempts=%ld init_device_calls=%ld ms_init_attempt=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld pnp_batches=%ld reloc_frames=%ld ms_reloc_frame=%.4f init_attempts=%ld init_device_calls=%ld ms_init_attempt=%.4f sim3_batches=%ld loop_tries=%ld ms_loop_try=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
@@ -2140,7 +2181,8 @@ void HipVslamTrackerBase::logStatistics()
                   s.t_dev_upload * per, s.t_dev_extract * per, s.t_dev_get * per, s.t_dev_match * per, s.t_dev_pose * per, s.t_prefetch_wait * per, s.t_prefetch_busy * per, s.t_kf_wait * per, s.t_kf_apply * per, s.t_kf_insert * per, s.t_kf_loop * per, s.t_kf_prepare * per, s.t_map_solve * per,
                   s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per, s.perspective_dropped,
                   s.pnp_batches, s.reloc_frames, s.reloc_frames > 0 ? 1e3 * s.t_relocalise / (double)s.reloc_frames : 0.0,
-                  s.init_attempts, s.init_device_calls, s.init_attempts > 0 ? 1e3 * s.t_init_attempt / (double)s.init_attempts : 0.0);
+                  s.init_attempts, s.init_device_calls, s.init_attempts > 0 ? 1e3 * s.t_init_attempt / (double)s.init_attempts : 0.0,
+                  s.sim3_batches, s.loop_tries, s.loop_tries > 0 ? 1e3 * s.t_loop_try / (double)s.loop_tries : 0.0);
     m_lastStatistics = buf;
     logMessage(LpSlamLogLevel_Info, buf);
 }

@@ -101,6 +101,7 @@ protected:
         long local_ba = 0, loops_closed = 0, loop_fused = 0, global_ba = 0, lost = 0, relocalised = 0, reinitialised = 0, nav_priors = 0, prefetched = 0;
         long color_converted = 0;                     // frames whose colour / YUV source was converted to grey on the device
         long pnp_batches = 0, reloc_frames = 0; double t_relocalise = 0;      // relocalisation: solver batches on the device (relocaliseOnDevice), Lost frames that tried, seconds they took
+        long sim3_batches = 0, loop_tries = 0; double t_loop_try = 0;      // loop closing: verification batches on the device (verifyLoopsOnDevice), keyframes whose candidates were verified, seconds that took
         long init_attempts = 0, init_device_calls = 0; double t_init_attempt = 0;      // monocular initialisation: two_view_initialize calls, their steps that ran on the device (initialiseOnDevice), seconds the calls took
         long triangulated = 0, tri_pairs = 0, tri_exhausted = 0;      // triangulateNeighbours: landmarks made, (keyframe, neighbour) pairs served, queries whose eight candidates were all taken while more had passed
         long fisheye_dropped = 0;                     // fisheye session: keypoints the undistort stage removed (beyond the angle limit or 90 degrees, not converged), summed
@@ -237,6 +238,7 @@ protected:
     int m_slamKeypoints = 1200, m_viewerFps = 10;
     double m_baselineDistThresh = 0.1, m_maxLaserAge = 1.0;      // baselineDistThresh: read by the triangulateNeighbours step only
     bool m_initialiseOnDevice = false;                // monoInitialize(): the RANSAC loop and the pose check of two_view_initialize on the device (lpslam_hip_two_view_*)
+    bool m_verifyLoopsOnDevice = false;               // closeLoop(): solver, gate and optimiser of all candidates in one device call (lpslam_hip_sim3_verify_batch)
     bool m_relocaliseOnDevice = false;                // relocalise(): the candidates' pose solver in one device call (lpslam_hip_pnp_ransac_batch)
     int m_triangulateNeighbours = 0;                  // 0: as before (monocular: the previous keyframe by brute force; stereo: nothing); 1 .. 32: that many covisible keyframes
     // MI355X additions: the generated reference config hard-codes these

@@ -5,6 +5,7 @@
 // po_quat_to_rot, s3_q_to_R) differ on purpose in contraction and normalisation and are not these.
 #pragma once
 #include <cmath>
+#include "../csrc/sim3_math.h"
 
 namespace LpSlam {
 
@@ -28,24 +29,8 @@ inline void quatMul(const double* a, const double* b, double* o)
     for (int i = 0; i < 4; ++i) o[i] = r[i] / n;
 }
 
-// Eigen::Quaterniond(R) for a rotation matrix (row major)
-inline void rotToQuat(const double* m, double* q)
-{
-    const double tr = m[0] + m[4] + m[8];
-    if (tr > 0) {
-        const double s = std::sqrt(tr + 1.0) * 2;
-        q[0] = 0.25 * s; q[1] = (m[7] - m[5]) / s; q[2] = (m[2] - m[6]) / s; q[3] = (m[3] - m[1]) / s;
-    } else if (m[0] > m[4] && m[0] > m[8]) {
-        const double s = std::sqrt(1.0 + m[0] - m[4] - m[8]) * 2;
-        q[0] = (m[7] - m[5]) / s; q[1] = 0.25 * s; q[2] = (m[1] + m[3]) / s; q[3] = (m[2] + m[6]) / s;
-    } else if (m[4] > m[8]) {
-        const double s = std::sqrt(1.0 + m[4] - m[0] - m[8]) * 2;
-        q[0] = (m[2] - m[6]) / s; q[1] = (m[1] + m[3]) / s; q[2] = 0.25 * s; q[3] = (m[5] + m[7]) / s;
-    } else {
-        const double s = std::sqrt(1.0 + m[8] - m[0] - m[4]) * 2;
-        q[0] = (m[3] - m[1]) / s; q[1] = (m[2] + m[6]) / s; q[2] = (m[5] + m[7]) / s; q[3] = 0.25 * s;
-    }
-}
+// Eigen::Quaterniond(R) for a rotation matrix (row major): the one definition is csrc/sim3_math.h (the device calls it too)
+inline void rotToQuat(const double* m, double* q) { lpslam_sim3::rot_to_quat(m, q); }
 inline void rotToQuat(const Mat3& R, double* q) { rotToQuat(R.m, q); }
 
 // out = R X + t (out must not be X)

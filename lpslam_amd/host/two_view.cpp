@@ -3,6 +3,7 @@
 #include "pose_math.h"
 #include "../csrc/epnp_math.h"
 #include "../csrc/ransac_sample.h"
+#include "../csrc/sim3_math.h"
 #include "../csrc/triangulate_math.h"
 #include "../csrc/two_view_math.h"
 
@@ -443,20 +444,9 @@ int sim3_solve_ransac(const double* p1c, const double* p2c, const double* obs1, 
         lpslam_ransac::draw<3>(rng, n, avail.data(), idx);
         double a1[9], a2[9], R[9], t[3], sc;
         for (int k = 0; k < 3; ++k) for (int a = 0; a < 3; ++a) { a1[3 * k + a] = p1c[3 * idx[k] + a]; a2[3 * k + a] = p2c[3 * idx[k] + a]; }
-        if (!lpslam_epnp::horn(a1, a2, 3, fix_scale, R, t, &sc)) continue;
-        int count = 0;
-        for (int i = 0; i < n; ++i) {
-            cur[(size_t)i] = 0;
-            // 2 -> 1: x1 = s R x2 + t;  1 -> 2: x2 = R^T (x1 - t) / s
-            double q1[3], q2[3];
-            for (int r = 0; r < 3; ++r) q1[r] = sc * (R[r * 3] * p2c[3 * i] + R[r * 3 + 1] * p2c[3 * i + 1] + R[r * 3 + 2] * p2c[3 * i + 2]) + t[r];
-            const double d[3] = {p1c[3 * i] - t[0], p1c[3 * i + 1] - t[1], p1c[3 * i + 2] - t[2]};
-            for (int r = 0; r < 3; ++r) q2[r] = (R[r] * d[0] + R[3 + r] * d[1] + R[6 + r] * d[2]) / sc;
-            if (!(q1[2] > 0) || !(q2[2] > 0)) continue;
-            const double e1x = cam1[0] * q1[0] / q1[2] + cam1[2] - obs1[2 * i], e1y = cam1[1] * q1[1] / q1[2] + cam1[3] - obs1[2 * i + 1];
-            const double e2x = cam2[0] * q2[0] / q2[2] + cam2[2] - obs2[2 * i], e2y = cam2[1] * q2[1] / q2[2] + cam2[3] - obs2[2 * i + 1];
-            if ((e1x * e1x + e1y * e1y) * inv_sigma2_1[i] < 9.210 && (e2x * e2x + e2y * e2y) * inv_sigma2_2[i] < 9.210) { cur[(size_t)i] = 1; ++count; }
-        }
+        if (!lpslam_epnp::horn<3>(a1, a2, 3, fix_scale, R, t, &sc)) continue;                 // (the instance the device kernel runs)
+        // the rule per pair (2 -> 1: x1 = s R x2 + t;  1 -> 2: x2 = R^T (x1 - t) / s) is csrc/sim3_math.h, the text the device kernels run
+        const int count = lpslam_sim3::sim3_score(R, t, sc, p1c, p2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, n, cam1, cam2, cur.data());
         if (count > best) {
             best = count;
             double q[4];

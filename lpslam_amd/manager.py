@@ -143,8 +143,8 @@ class Manager:
         """this manager's own "VSLAM statistics" line of its last stop() as a dict (the log file is process-wide)"""
         f = self.lib.lpslam_manager_tracker_statistics
         f.restype = C.c_size_t; f.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-        buf = C.create_string_buffer(4096)
-        f(self.h, buf, 4096)
+        buf = C.create_string_buffer(8192)          # (the line has grown past 2 KB of keys and values)
+        f(self.h, buf, 8192)
         line = buf.value.decode(errors="replace")
         if "VSLAM statistics:" not in line:
             return {}
@@ -155,7 +155,7 @@ class Manager:
 
     def add_tracker(self, name, cfg=""):
         """cfg: the tracker's JSON object as text; every key goes to the plugin as written (INTEGRATION.md lists them, e.g.
-        "triangulateNeighbours": 10, "relocaliseOnDevice": true, "initialiseOnDevice": true)"""
+        "triangulateNeighbours": 10, "relocaliseOnDevice": true, "initialiseOnDevice": true, "verifyLoopsOnDevice": true)"""
         return bool(self.lib.lpslam_manager_add_tracker(self.h, name.encode(), cfg.encode()))
 
     def add_processor(self, name, cfg=""):
