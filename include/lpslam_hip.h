@@ -556,6 +556,26 @@ int lpslam_hip_pose_optimize(lpslam_hip_ctx* ctx, double* pose7, const double* p
 /* Diagnostic: passes over the observations the last lpslam_hip_pose_optimize on this context made (one per round + one per
  * Levenberg trial; the call's duration is this number times the latency of a trial). */
 int32_t lpslam_hip_pose_optimize_passes(lpslam_hip_ctx* ctx);
+/* ---- The covariance of poses the motion-only optimiser returned ---------------------------------------
+ * Set i owns observations [set_start[i], set_start[i+1]) of `obs` (7 doubles each: u v ur inv_sigma2 X Y Z, ur < 0 = monocular) and of
+ * `active` (1 = use: the optimiser's !outlier), and the pose pose7 + 7 i (qw qx qy qz tx ty tz, world -> camera); cam = fx fy cx cy fxb.
+ * Per set: info21 = the upper triangle (row by row) of H = sum w B^T B over the active observations in front of the camera, B the pose
+ * Jacobian of the optimiser (rotation first), w = inv_sigma2, no Huber; chi2 = sum w |e|^2; n_used = their number; cov21 = H^-1 in the
+ * tangent space of T <- exp(d) T, through the Cholesky factor of D H D, D = diag(H)^-1/2; min_pivot = the smallest pivot of that
+ * factorisation; status 0 = a covariance, 1 = fewer than 3 observations used, 2 = refused (a diagonal entry of H not positive or not
+ * finite, or a pivot at or below 1e-8) -- on 1 and 2 cov21 is 21 zeros; min_pivot is 0 where the diagonal let no factorisation begin.
+ * The arithmetic and the order of every sum are lpslam_amd/csrc/pose_cov_math.h; the results are those of
+ * lpslam_pose_covariance_batch_host (liblpslam.so) bit for bit.  lpslam_pose_sigmas_host there turns cov21 into the interface's sigmas.
+ * One upload, one launch (one workgroup per set), one wait.
+ * A NULL argument, n_sets < 1, a set_start that starts below 0 or does not ascend: LPSLAM_HIP_ERR_INVALID; n_sets above
+ * LPSLAM_HIP_POSE_COV_MAX_SETS or more than LPSLAM_HIP_POSE_COV_MAX_OBS observations in all: LPSLAM_HIP_ERR_CAPACITY.  Nothing is
+ * allocated or written then. */
+#define LPSLAM_HIP_POSE_COV_MAX_SETS 4096
+#define LPSLAM_HIP_POSE_COV_MAX_OBS (1 << 18)
+int lpslam_hip_pose_covariance_batch(lpslam_hip_ctx* ctx, int32_t n_sets, const int32_t* set_start /* n_sets + 1 */, const double* pose7 /* 7 per set */,
+                                     const double* obs /* 7 per observation */, const uint8_t* active /* per observation */, const double* cam /* 5 */,
+                                     double* info21 /* 21 per set */, double* cov21 /* 21 per set */, double* chi2, double* min_pivot, int32_t* n_used,
+                                     int32_t* status /* each per set */);
 /* local_bundle_adjuster flow: first_iters robust, outlier classification, second_iters plain. */
 int lpslam_hip_ba_local(lpslam_hip_ba* ba, int32_t first_iters, int32_t second_iters, uint8_t* outlier);
 /* A keyframe's local bundle adjustment in ONE call ([UPSTREAM] mapping_module -> optimize::local_bundle_adjuster::optimize, started per

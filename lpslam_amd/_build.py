@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "liblpslam_hip.so")
-HIP_SOURCES = ["api.hip", "frontend.hip", "match.hip", "ba.hip", "pose_opt.hip", "sim3.hip", "bow.hip", "share.hip", "occupancy.hip", "jpeg.hip", "jpeg_dec.hip", "intensity.hip", "ingest.hip", "triangulate.hip", "pnp.hip", "two_view.hip"]
+HIP_SOURCES = ["api.hip", "frontend.hip", "match.hip", "ba.hip", "pose_opt.hip", "sim3.hip", "bow.hip", "share.hip", "occupancy.hip", "jpeg.hip", "jpeg_dec.hip", "intensity.hip", "ingest.hip", "triangulate.hip", "pnp.hip", "two_view.hip", "pose_cov.hip"]
 # -ffp-contract=off: parity with the CPU definition forbids FMA contraction ("Numerics").
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
@@ -31,6 +31,7 @@ UNIT_DEPS = {
     "triangulate.hip": ["desc_wave.h", "triangulate_math.h", "jacobi_math.h"],
     "pnp.hip": ["epnp_math.h", "jacobi_math.h", "ransac_sample.h", "sim3_math.h", os.path.join(_HOST, "pose_math.h")],
     "two_view.hip": ["two_view_math.h", "triangulate_math.h", "jacobi_math.h", "ransac_sample.h"],
+    "pose_cov.hip": ["pose_cov_math.h", "jacobi_math.h"],
     "jpeg.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_tables.h")],
     "jpeg_dec.hip": ["jpeg_scan.inl", os.path.join(_HOST, "jpeg_header.h"), os.path.join(_HOST, "jpeg_tables.h")],
 }
@@ -79,14 +80,14 @@ def hip_library(force=False, verbose=False):
 
 
 HOST_LIB = os.path.join(HERE, "liblpslam.so")
-HOST_SOURCES = ["slam_manager.cpp", "hip_tracker.cpp", "interface.cpp", "rectify.cpp", "replay.cpp", "two_view.cpp", "bow.cpp", "jpeg.cpp", "jpeg_device.cpp", "map_file.cpp", "record.cpp", "intensity.cpp", "ingest.cpp", "pnp_batch.cpp", "two_view_batch.cpp", "sim3_batch.cpp"]
+HOST_SOURCES = ["slam_manager.cpp", "hip_tracker.cpp", "interface.cpp", "rectify.cpp", "replay.cpp", "two_view.cpp", "bow.cpp", "jpeg.cpp", "jpeg_device.cpp", "map_file.cpp", "record.cpp", "intensity.cpp", "ingest.cpp", "pnp_batch.cpp", "two_view_batch.cpp", "sim3_batch.cpp", "pose_cov_batch.cpp"]
 
 
 def host_library(force=False, verbose=False):
     """C++ host mirror of the reference interface (g++), linked against the HIP C-ABI library next to it."""
     hdir = os.path.join(HERE, "host")
     srcs = [os.path.join(hdir, s) for s in HOST_SOURCES]
-    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "radtan_math.h"), os.path.join("..", "csrc", "triangulate_math.h"), os.path.join("..", "csrc", "epnp_math.h"), os.path.join("..", "csrc", "jacobi_math.h"), os.path.join("..", "csrc", "two_view_math.h"), os.path.join("..", "csrc", "ransac_sample.h"), os.path.join("..", "csrc", "sim3_math.h"))] + \
+    deps = srcs + [os.path.join(hdir, h) for h in ("core.h", "json_min.h", "hip_tracker.h", "slam_manager.h", "rectify.h", "replay.h", "two_view.h", "pose_math.h", "bow.h", "jpeg.h", "jpeg_header.h", "jpeg_device.h", "jpeg_tables.h", "map_file.h", "occupancy.h", "record.h", "intensity.h", "ingest.h", os.path.join("..", "csrc", "ingest_math.h"), os.path.join("..", "csrc", "fisheye_math.h"), os.path.join("..", "csrc", "radtan_math.h"), os.path.join("..", "csrc", "triangulate_math.h"), os.path.join("..", "csrc", "epnp_math.h"), os.path.join("..", "csrc", "jacobi_math.h"), os.path.join("..", "csrc", "two_view_math.h"), os.path.join("..", "csrc", "ransac_sample.h"), os.path.join("..", "csrc", "sim3_math.h"), os.path.join("..", "csrc", "pose_cov_math.h"))] + \
         [os.path.join(HERE, "..", "include", h) for h in ("lpslam_types.h", "lpslam_manager.h", "lpslam_hip.h")] + [LIB]
     if not force and os.path.exists(HOST_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(HOST_LIB) for d in deps if os.path.exists(d)):
         return HOST_LIB

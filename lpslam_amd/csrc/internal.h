@@ -359,7 +359,7 @@ inline void lp_pf_invalidate(lpslam_hip_ctx* c, int first, int n) { const int p 
 // The context's arrival counters, one per kind of delivery: two deliveries that may be in flight together never count on the same one.
 // A new kind takes a new name in front of LP_DONE_COUNTERS.
 enum { LP_DONE_FRAME = 0, LP_DONE_WINDOW = 1, LP_DONE_STORED = 2, LP_DONE_PREFETCH = 3, LP_DONE_BOW = 4, LP_DONE_TRIANGULATE = 5, LP_DONE_PNP = 6, LP_DONE_TWO_VIEW = 7,
-       LP_DONE_SIM3_RANSAC = 8, LP_DONE_COUNTERS = 9 };
+       LP_DONE_SIM3_RANSAC = 8, LP_DONE_POSE_COV = 9, LP_DONE_COUNTERS = 10 };
 unsigned* lp_done_counter(lpslam_hip_ctx* c, int which);      // arrival counter `which` of the context; nullptr, error set: no such counter or no memory for them
 bool lp_wait_recover(lpslam_hip_ctx* c, int which, hipStream_t s);      // after a failed lp_wait_done: counter re-zeroed (which < 0: none); false = the stream is dead, leak what its kernels touch
 // the next sequence number of a completion flag: positive, never 0 (0 is what the flag is reset to before a launch)

@@ -55,6 +55,7 @@ SYMBOLS = [
     "lpslam_hip_triangulate_neighbours", "lpslam_hip_triangulate_pairs",
     "lpslam_hip_pnp_ransac_batch",
     "lpslam_hip_two_view_ransac_batch", "lpslam_hip_two_view_check_poses",
+    "lpslam_hip_pose_covariance_batch",
 ]
 
 
@@ -1371,6 +1372,56 @@ def sim3_verify_batch(ctx, pairs_list, cam1, cam2, fix_scale=True, iterations=20
     _check(f(ctx.h, n, _p(pairs), _p(start), _p(c1), _p(c2), int(bool(fix_scale)), int(iterations), int(seed) & 0xffffffff, int(min_seed_inliers), float(chi_sq),
              _p(seed_cnt), _p(s12), _p(cnt), _p(inl) if want_inlier else None))
     return seed_cnt[:n], s12[:n], cnt[:n], ([inl[start[i]:start[i + 1]].copy() for i in range(n)] if want_inlier else None)
+
+
+POSE_COV_MAX_SETS, POSE_COV_MAX_OBS = 4096, 1 << 18          # LPSLAM_HIP_POSE_COV_MAX_SETS, LPSLAM_HIP_POSE_COV_MAX_OBS
+_POSE_COV_ARGS = [C.c_int32] + [C.c_void_p] * 11
+
+
+def _pose_cov(f, head, set_start, pose7, obs, active, cam):
+    start = np.ascontiguousarray(set_start, np.int32)
+    n = len(start) - 1
+    pose = np.ascontiguousarray(pose7, np.float64).reshape(-1); ob = np.ascontiguousarray(obs, np.float64).reshape(-1)
+    act = np.ascontiguousarray(active, np.uint8).reshape(-1); cm = np.ascontiguousarray(cam, np.float64).reshape(-1)
+    m = max(n, 1)
+    assert len(pose) >= 7 * n and len(cm) == 5 and (n < 1 or (len(ob) >= 7 * int(start[-1]) and len(act) >= int(start[-1])))
+    info = np.zeros((m, 21)); cov = np.zeros((m, 21)); chi2 = np.zeros(m); piv = np.zeros(m); used = np.zeros(m, np.int32); status = np.zeros(m, np.int32)
+    rc = f(*head, n, _p(start), _p(pose), _p(ob) if len(ob) else None, _p(act) if len(act) else None, _p(cm), _p(info), _p(cov), _p(chi2), _p(piv), _p(used), _p(status))
+    return rc, dict(info21=info[:n], cov21=cov[:n], chi2=chi2[:n], min_pivot=piv[:n], n_used=used[:n], status=status[:n])
+
+
+def pose_covariance_batch(ctx, set_start, pose7, obs, active, cam):
+    """lpslam_hip_pose_covariance_batch: set i owns observations [set_start[i], set_start[i + 1]) of obs (rows u v ur inv_sigma2 X Y Z) and
+    of active (1 = use) and the pose pose7[i]; cam = fx fy cx cy fxb.  Returns a dictionary of info21 (S, 21), cov21 (S, 21), chi2,
+    min_pivot, n_used and status (S each; 0 = a covariance, 1 = fewer than 3 observations, 2 = refused)."""
+    f = ctx.lib.lpslam_hip_pose_covariance_batch
+    f.argtypes = [C.c_void_p] + _POSE_COV_ARGS
+    rc, out = _pose_cov(f, (ctx.h,), set_start, pose7, obs, active, cam)
+    _check(rc)
+    return out
+
+
+def pose_covariance_batch_host(set_start, pose7, obs, active, cam):
+    """lpslam_pose_covariance_batch_host: the CPU definition of pose_covariance_batch (csrc/pose_cov_math.h; the same bits).  A refusal
+    raises with the code the device call answers (1 invalid, 3 capacity) in the exception's `code`."""
+    f = host_lib().lpslam_pose_covariance_batch_host
+    f.argtypes = _POSE_COV_ARGS; f.restype = C.c_int
+    rc, out = _pose_cov(f, (), set_start, pose7, obs, active, cam)
+    if rc:
+        e = LpslamHipError("lpslam_pose_covariance_batch_host refused its arguments (%d)" % rc)
+        e.code = rc
+        raise e
+    return out
+
+
+def pose_sigmas_host(pose7, cov21):
+    """lpslam_pose_sigmas_host: x_sigma, y_sigma, z_sigma (lpslam axes) and the orientation sigma (radians) of a pose's covariance"""
+    f = host_lib().lpslam_pose_sigmas_host
+    f.argtypes = [C.c_void_p] * 3; f.restype = C.c_int
+    pose = np.ascontiguousarray(pose7, np.float64).reshape(7); cov = np.ascontiguousarray(cov21, np.float64).reshape(21); out = np.zeros(4)
+    if f(_p(pose), _p(cov), _p(out)):
+        raise LpslamHipError("lpslam_pose_sigmas_host refused its arguments")
+    return out
 
 
 def match_orientation_filter(angle_q, angle_t, match_idx):

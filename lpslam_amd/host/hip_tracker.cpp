@@ -6,6 +6,7 @@
 #include <future>
 #include "rectify.h"
 #include "two_view.h"
+#include "../csrc/pose_cov_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,6 +41,8 @@ HipVslamTrackerBase::HipVslamTrackerBase()
     o.optional("relocaliseOnDevice", false);
     o.optional("verifyLoopsOnDevice", false);
     o.optional("initialiseOnDevice", false);
+    // the covariance of every pose the motion-only optimiser returns, as the result's sigmas; false: sigmas 0
+    o.optional("poseSigma", false);
 }
 
 HipVslamTrackerBase::~HipVslamTrackerBase() { stop(); }
@@ -69,6 +72,7 @@ void HipVslamTrackerBase::OnConfigurationUpdate()
     m_relocaliseOnDevice = o.getBool("relocaliseOnDevice");
     m_verifyLoopsOnDevice = o.getBool("verifyLoopsOnDevice");
     m_initialiseOnDevice = o.getBool("initialiseOnDevice");
+    m_poseSigma = o.getBool("poseSigma");
 }
 
 // The keypoint camera of a monocular session: the fisheye model from the camera configuration (f_x, f_y, c_x, c_y, dist[0..3]) with
@@ -389,6 +393,16 @@ void HipVslamTrackerBase::warmUpContext(bool stereo)
         std::vector<uint8_t> outl(32);
         int32_t inl = 0;
         ok = lpslam_hip_pose_optimize(m_ctx, pose7, pts.data(), 16, obs.data(), 16, &cam, outl.data(), &inl) == LPSLAM_HIP_OK;
+        if (ok && m_poseSigma) {      // poseSigma: the covariance call that follows every optimiser call of a session (its first launch, its staging block)
+            std::vector<double> packed;
+            for (int i = 0; i < 16; ++i) { const lpslam_hip_ba_obs& o = obs[(size_t)i]; packed.insert(packed.end(), {o.u, o.v, o.ur, o.inv_sigma2, pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]}); }
+            const std::vector<uint8_t> active(16, 1);
+            const double cam5[5] = {cam.fx, cam.fy, cam.cx, cam.cy, cam.focal_x_baseline};
+            const int32_t set_start[2] = {0, 16};
+            double info[21], cov[21], chi2 = 0, pivot = 0;
+            int32_t used = 0, status = 0;
+            ok = lpslam_hip_pose_covariance_batch(m_ctx, 1, set_start, pose7, packed.data(), active.data(), cam5, info, cov, &chi2, &pivot, &used, &status) == LPSLAM_HIP_OK;
+        }
         const uint8_t fixed[2] = {1, 0};
         lpslam_hip_ba* ba = nullptr;
         if (ok && lpslam_hip_ba_create(m_ctx, poses.data(), fixed, 2, pts.data(), 16, obs.data(), 32, &cam, &ba) == LPSLAM_HIP_OK) {
@@ -425,7 +439,7 @@ std::array<double, 16> HipVslamTrackerBase::currentCamPose()
 
 // T_cw -> camera centre, optical axes (x right, y down, z forward) -> lpslam axes: p_lp = (-y, x, z), q_lp = (w, -y, x, z)
 // (src/Trackers/OpenVSLAMTrackerBase.cpp:307-329)
-TrackerResult HipVslamTrackerBase::createTrackerResult(const Pose& p, TimeStamp timestamp) const
+TrackerResult HipVslamTrackerBase::createTrackerResult(const Pose& p, TimeStamp timestamp, const double* sigma) const
 {
     double C[3], q[4];
     centre(p, C);
@@ -435,6 +449,8 @@ TrackerResult HipVslamTrackerBase::createTrackerResult(const Pose& p, TimeStamp 
     t.id = 0;
     t.position.value = {-C[1], C[0], C[2]};
     t.orientation.value = {q[0], -q[2], q[1], q[3]};
+    t.position.sigma = {sigma[0], sigma[1], sigma[2]};       // (lpslam axes already: pose_sigmas of csrc/pose_cov_math.h)
+    t.orientation.sigma = sigma[3];
     t.timestamp.system_time = timestamp;
     return t;
 }
@@ -774,7 +790,44 @@ bool HipVslamTrackerBase::poseFromMatches(FrameData& cur, const std::vector<int>
     for (int k = 0; k < 3; ++k) cur.pose.t[k] = pose7[4 + k];
     std::fill(cur.landmark.begin(), cur.landmark.end(), -1);
     for (size_t k = 0; k < kept_idx.size(); ++k) cur.landmark[(size_t)kept_idx[k]] = outlier[k] ? -1 : kept_lm[k];   // inliers keep their landmark
+    ++m_stats.pose_fits;
+    if (m_poseSigma) {      // (timed on its own: what it takes is taken off t_dev_pose, whose scope is the whole of this function's tail as before)
+        const double before = m_stats.t_dev_pose_sigma;
+        poseSigmas(cur, pose7, pts, obs, outlier);
+        m_stats.t_dev_pose -= m_stats.t_dev_pose_sigma - before;
+    }
     return true;
+}
+
+// poseSigma: the covariance of the pose poseFromMatches just found, over its inliers (lpslam_hip_pose_covariance_batch with one set),
+// as the frame's four sigmas.  A refused set (status 1 or 2) or a failed call leaves them 0; the pose stands either way.
+void HipVslamTrackerBase::poseSigmas(FrameData& cur, const double* pose7, const std::vector<double>& pts, const std::vector<lpslam_hip_ba_obs>& obs, const std::vector<uint8_t>& outlier)
+{
+    ScopedSeconds timed(m_stats.t_dev_pose_sigma);
+    for (double& s : cur.sigma) s = 0.0;
+    const size_t n = obs.size();
+    std::vector<double> packed(7 * n);
+    std::vector<uint8_t> active(n);
+    for (size_t k = 0; k < n; ++k) {
+        const lpslam_hip_ba_obs& o = obs[k];
+        const double* X = pts.data() + 3 * (size_t)o.point;
+        double* d = packed.data() + 7 * k;
+        d[0] = o.u; d[1] = o.v; d[2] = o.ur; d[3] = o.inv_sigma2; d[4] = X[0]; d[5] = X[1]; d[6] = X[2];
+        active[k] = outlier[k] ? 0 : 1;
+    }
+    const lpslam_hip_ba_camera bc = baCamera(true);
+    const double cam[5] = {bc.fx, bc.fy, bc.cx, bc.cy, bc.focal_x_baseline};
+    const int32_t set_start[2] = {0, (int32_t)n};
+    double info[21], cov[21], chi2 = 0, pivot = 0;
+    int32_t used = 0, status = 0;
+    if (lpslam_hip_pose_covariance_batch(m_ctx, 1, set_start, pose7, packed.data(), active.data(), cam, info, cov, &chi2, &pivot, &used, &status) != LPSLAM_HIP_OK) {
+        ++m_stats.pose_sigma_refused;
+        if (!m_poseSigmaFailureLogged) { m_poseSigmaFailureLogged = true; logMessage(LpSlamLogLevel_Error, std::string("pose covariance call failed: ") + lpslam_hip_last_error() + "; sigmas are 0 where it fails"); }
+        return;
+    }
+    if (status != 0) { ++m_stats.pose_sigma_refused; return; }
+    lpslam_pose_cov::pose_sigmas(pose7, cov, cur.sigma);
+    ++m_stats.pose_sigmas;
 }
 
 // prediction of the current pose: constant velocity from the last two tracked frames; when that is unknown (first frame of a
@@ -1571,6 +1624,7 @@ bool HipVslamTrackerBase::relocalise(FrameData& cur)
         FrameData trial = cur;
         if (!poseFromMatches(trial, cur_idx, lm_ids, seed, inl, 30)) return false;
         cur.pose = trial.pose; cur.landmark = trial.landmark;
+        for (int a = 0; a < 4; ++a) cur.sigma[a] = trial.sigma[a];
         logMessage(LpSlamLogLevel_Info, "VSLAM relocalised against keyframe " + std::to_string(kf_index) + " with " + std::to_string(inl) + " inliers");
         return true;
     };
@@ -2171,7 +2225,7 @@ void HipVslamTrackerBase::logStatistics()
     if (m_ctx) (void)lpslam_hip_ba_counters(m_ctx, dev, LPSLAM_HIP_BA_COUNTERS);
     std::snprintf(buf, sizeof(buf), "VSLAM statistics: frames=%ld motion_tracked=%ld bf_tracked=%ld local_map_joined=%ld keyframes=%ld fused_added=%ld fused_merged=%ld "
                   "local_ba=%ld loops_closed=%ld loop_fused=%ld global_ba=%ld lost=%ld relocalised=%ld reinitialised=%ld nav_priors=%ld landmarks=%zu "
-                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld pnp_batches=%ld reloc_frames=%ld ms_reloc_frame=%.4f init_attempts=%ld init_device_calls=%ld ms_init_attempt=%.4f sim3_batches=%ld loop_tries=%ld ms_loop_try=%.4f",
+                  "culled_landmarks=%ld culled_keyframes=%ld live_keyframes=%ld prefetched=%ld ba_failed=%ld ba_signatures=%ld ba_graphs=%ld ba_replays=%ld ba_timeouts=%ld intensity_adjusted=%ld color_converted=%ld fisheye_dropped=%ld ms_per_frame=%.4f ms_front_end=%.4f ms_track=%.4f ms_local_map=%.4f ms_keyframe=%.4f ms_dev_upload=%.4f ms_dev_extract=%.4f ms_dev_get=%.4f ms_dev_match=%.4f ms_dev_pose=%.4f ms_prefetch_wait=%.4f ms_prefetch_busy=%.4f ms_kf_wait=%.4f ms_kf_apply=%.4f ms_kf_insert=%.4f ms_kf_loop=%.4f ms_kf_prepare=%.4f ms_map_solve=%.4f triangulated=%ld tri_pairs=%ld tri_exhausted=%ld ms_kf_triangulate=%.4f perspective_dropped=%ld pnp_batches=%ld reloc_frames=%ld ms_reloc_frame=%.4f init_attempts=%ld init_device_calls=%ld ms_init_attempt=%.4f sim3_batches=%ld loop_tries=%ld ms_loop_try=%.4f pose_fits=%ld pose_sigmas=%ld pose_sigma_refused=%ld ms_dev_pose_sigma=%.4f",
                   s.frames, s.motion_tracked, s.bf_tracked, s.local_map_joined, s.keyframes, s.fused_added, s.fused_merged, s.local_ba, s.loops_closed, s.loop_fused,
                   s.global_ba, s.lost, s.relocalised, s.reinitialised, s.nav_priors, m_landmarks.size(), s.culled_landmarks, s.culled_keyframes,
                   (long)std::count_if(m_kfs.begin(), m_kfs.end(), [](const Keyframe& k) { return !k.erased; }), s.prefetched,
@@ -2182,7 +2236,8 @@ void HipVslamTrackerBase::logStatistics()
                   s.triangulated, s.tri_pairs, s.tri_exhausted, s.t_kf_triangulate * per, s.perspective_dropped,
                   s.pnp_batches, s.reloc_frames, s.reloc_frames > 0 ? 1e3 * s.t_relocalise / (double)s.reloc_frames : 0.0,
                   s.init_attempts, s.init_device_calls, s.init_attempts > 0 ? 1e3 * s.t_init_attempt / (double)s.init_attempts : 0.0,
-                  s.sim3_batches, s.loop_tries, s.loop_tries > 0 ? 1e3 * s.t_loop_try / (double)s.loop_tries : 0.0);
+                  s.sim3_batches, s.loop_tries, s.loop_tries > 0 ? 1e3 * s.t_loop_try / (double)s.loop_tries : 0.0,
+                  s.pose_fits, s.pose_sigmas, s.pose_sigma_refused, s.t_dev_pose_sigma * per);
     m_lastStatistics = buf;
     logMessage(LpSlamLogLevel_Info, buf);
 }
@@ -2459,7 +2514,7 @@ TrackerBase::ProcessImageResult HipVslamTrackerBase::trackFrame(CameraQueueEntry
     m_lastFrameSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     m_stats.t_total += m_lastFrameSeconds;
     if (m_state == TrackerState::Tracking) {
-        TrackerResult tres = createTrackerResult(m_prev.pose, cam.timestamp);
+        TrackerResult tres = createTrackerResult(m_prev.pose, cam.timestamp, m_prev.sigma);
         tres.timestamp.ros_timestamp = cam.ros_timestamp;
         res.push_back(tres);
     }

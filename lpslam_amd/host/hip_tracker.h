@@ -63,6 +63,7 @@ protected:
         std::vector<float> x_right, depth;
         std::vector<int> landmark;                    // landmark id per keypoint or -1
         Pose pose;
+        double sigma[4] = {0, 0, 0, 0};               // poseSigma: x y z (lpslam axes) and orientation sigma of `pose` where poseFromMatches found it, else 0
         int slot = 0;
     };
     // The map ([UPSTREAM] data::map_database): every keyframe ever inserted with its keypoints, descriptors, stereo columns and
@@ -102,6 +103,7 @@ protected:
         long color_converted = 0;                     // frames whose colour / YUV source was converted to grey on the device
         long pnp_batches = 0, reloc_frames = 0; double t_relocalise = 0;      // relocalisation: solver batches on the device (relocaliseOnDevice), Lost frames that tried, seconds they took
         long sim3_batches = 0, loop_tries = 0; double t_loop_try = 0;      // loop closing: verification batches on the device (verifyLoopsOnDevice), keyframes whose candidates were verified, seconds that took
+        long pose_fits = 0, pose_sigmas = 0, pose_sigma_refused = 0; double t_dev_pose_sigma = 0;      // poseFromMatches calls that returned a pose; poseSigma: those whose covariance gave sigmas, those refused (status 1, 2 or a failed call), seconds in the call
         long init_attempts = 0, init_device_calls = 0; double t_init_attempt = 0;      // monocular initialisation: two_view_initialize calls, their steps that ran on the device (initialiseOnDevice), seconds the calls took
         long triangulated = 0, tri_pairs = 0, tri_exhausted = 0;      // triangulateNeighbours: landmarks made, (keyframe, neighbour) pairs served, queries whose eight candidates were all taken while more had passed
         long fisheye_dropped = 0;                     // fisheye session: keypoints the undistort stage removed (beyond the angle limit or 90 degrees, not converged), summed
@@ -120,9 +122,10 @@ protected:
     void warmUpContext(bool stereo);                  // one frame's worth of every per-frame call on blank images: lazily created resources exist before the first frame
     ProcessImageResult trackFrame(CameraQueueEntry& cam, bool stereo, const std::optional<GlobalStateInTime>& navOdom,
                                   std::optional<ScanAttach> scan = std::nullopt);
-    TrackerResult createTrackerResult(const Pose& pose_cw, TimeStamp timestamp) const;
+    TrackerResult createTrackerResult(const Pose& pose_cw, TimeStamp timestamp, const double* sigma4) const;
     bool initializeMap(FrameData& f, const Pose& at);
     bool poseFromMatches(FrameData& cur, const std::vector<int>& cur_idx, const std::vector<int>& lm_ids, const Pose& init, int& n_inliers, int min_inliers = 10);
+    void poseSigmas(FrameData& cur, const double* pose7, const std::vector<double>& pts, const std::vector<lpslam_hip_ba_obs>& obs, const std::vector<uint8_t>& outlier);
     // pc = R X + t and its pinhole image (u, v): false when the point is not in front of the camera or falls outside the image
     // (the ONE visibility test of the tracker: nothing else compares against the resolution)
     // (defined here, as projQuery is, so that the per-landmark loops of the query builders keep them inline)
@@ -237,6 +240,8 @@ protected:
     std::string m_configFromFile, m_cameraSetup = "monocular", m_vocabFile = "orb_vocab.dbow2", m_mapFilename = "map.db";
     int m_slamKeypoints = 1200, m_viewerFps = 10;
     double m_baselineDistThresh = 0.1, m_maxLaserAge = 1.0;      // baselineDistThresh: read by the triangulateNeighbours step only
+    bool m_poseSigma = false;                         // poseFromMatches(): the pose's covariance from the device (lpslam_hip_pose_covariance_batch) into the result's sigmas
+    bool m_poseSigmaFailureLogged = false;
     bool m_initialiseOnDevice = false;                // monoInitialize(): the RANSAC loop and the pose check of two_view_initialize on the device (lpslam_hip_two_view_*)
     bool m_verifyLoopsOnDevice = false;               // closeLoop(): solver, gate and optimiser of all candidates in one device call (lpslam_hip_sim3_verify_batch)
     bool m_relocaliseOnDevice = false;                // relocalise(): the candidates' pose solver in one device call (lpslam_hip_pnp_ransac_batch)

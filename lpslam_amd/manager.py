@@ -155,7 +155,8 @@ class Manager:
 
     def add_tracker(self, name, cfg=""):
         """cfg: the tracker's JSON object as text; every key goes to the plugin as written (INTEGRATION.md lists them, e.g.
-        "triangulateNeighbours": 10, "relocaliseOnDevice": true, "initialiseOnDevice": true, "verifyLoopsOnDevice": true)"""
+        "triangulateNeighbours": 10, "relocaliseOnDevice": true, "initialiseOnDevice": true, "verifyLoopsOnDevice": true,
+        "poseSigma": true -- the results' x_sigma, y_sigma, z_sigma and orientation sigma from the pose covariance call, `sigma` of collect_results)"""
         return bool(self.lib.lpslam_manager_add_tracker(self.h, name.encode(), cfg.encode()))
 
     def add_processor(self, name, cfg=""):
@@ -175,7 +176,8 @@ class Manager:
             s = state.contents
             self.results.append(dict(timestamp=s.timestamp, valid=bool(s.state.valid),
                                      p=(s.state.position.x, s.state.position.y, s.state.position.z),
-                                     q=(s.state.orientation.w, s.state.orientation.x, s.state.orientation.y, s.state.orientation.z)))
+                                     q=(s.state.orientation.w, s.state.orientation.x, s.state.orientation.y, s.state.orientation.z),
+                                     sigma=(s.state.position.x_sigma, s.state.position.y_sigma, s.state.position.z_sigma, s.state.orientation.sigma)))
             if on_result is not None:
                 on_result()
         f = RECON_CB(cb); self._keep.append(f)
